@@ -8,6 +8,12 @@ encode + decode of the frame with the 9/7 irreversible path (grk_compress -I)
 and encode + decode with the 5/3 lossless path; 8 such pairs (16 frames) are in
 flight per GPU, each on its own codec context, HIP stream and host thread.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the line with `value` and `ms_per_step`; `--full` adds every
+other leg below (pcie_inclusive, t1, roofline, cpu_baseline), each a run of its
+own after the timed region.  `--dump-outputs DIR` writes what the last timed
+step computed (see dump_outputs).
+
   value            whole-job throughput with each frame's int32 planes
                    already resident in HBM when the timed region starts.  The
                    task's bench contract fixes this: "`value` is whole-job
@@ -17,18 +23,18 @@ flight per GPU, each on its own codec context, HIP stream and host thread.
                    never `value`)".  The codestream crosses PCIe once each way
                    per frame (host Tier-2 / headers), the decoded frame stays
                    in HBM.
-  pcie_inclusive   SURVEY 8(d)'s end-to-end variant, reported beside it:
+  pcie_inclusive   (--full) SURVEY 8(d)'s end-to-end variant, reported beside it:
                    every frame starts in pinned host memory at its file's
                    sample width (12-bit -> uint16, 2 B/sample) and is copied
                    H2D inside the timed region (grkgpu_compress_ex widens it
                    on the GPU).
-  t1               MQ symbols/s and code-blocks/s (batch and lone frame).
-  e2e_frac         value / (8e12 / B_e2e), B_e2e = C (ceil(prec/8) + 4 * 4/3 + 4).
-  roofline         the forward 9/7 DWT (dominant HBM kernel): B_DWT over the
+  t1               (--full) MQ symbols/s and code-blocks/s (batch and lone frame).
+  e2e_frac         (--full) value / (8e12 / B_e2e), B_e2e = C (ceil(prec/8) + 4 * 4/3 + 4).
+  roofline         (--full) the forward 9/7 DWT (dominant HBM kernel): B_DWT over the
                    sum of its launches' device times; roofline.inverse the
                    same for the decode's inverse 9/7 DWT; roofline.r53 the
                    forward and inverse 5/3 DWT (8K workload).
-  cpu_baseline     the REFERENCE (Grok 5.1.0 libgrok compiled from source,
+  cpu_baseline     (--full) the REFERENCE (Grok 5.1.0 libgrok compiled from source,
                    oracle/_ref) on every host core of the process's affinity
                    mask, one frame pair.
 
@@ -161,11 +167,44 @@ def cpu_reference(img, bits, args_list, threads, label):
     return tot
 
 
+DUMP_SAMPLES = 1 << 18  # values kept of each dumped array (1 MiB as float32)
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write what the last timed step handed back, one
+    DIR/<name>.npy per array, float32 (codestream bytes and decoded samples of
+    up to 16 bits are exact in it).  An array of more than DUMP_SAMPLES values
+    is cut to a fixed sample: the values at DUMP_SAMPLES sorted indices drawn
+    from a generator seeded with DUMP_SEED and the array's length, so two
+    builds that return arrays of the same length are compared at the same
+    positions; a codestream's length is written beside it as <name>_len.
+    arrays: name -> numpy array or torch tensor (any device)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        flat = a.reshape(-1)
+        n = int(flat.shape[0])
+        if n > DUMP_SAMPLES:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, n]).integers(0, n, DUMP_SAMPLES))
+            flat = flat[torch.from_numpy(idx).to(flat.device)] if isinstance(flat, torch.Tensor) else flat[idx]
+        if isinstance(flat, torch.Tensor):
+            flat = flat.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(flat, dtype=np.float32))
+        if "codestream" in name:
+            np.save(os.path.join(dirname, name + "_len.npy"), np.array([n], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg of the line: pcie_inclusive, t1, roofline, "
+                         "cpu_baseline (each a run of its own; --no-pcie / --no-cpu-baseline still drop theirs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (every frame's codestream and decoded frame) as "
+                         "DIR/<name>.npy, float32, a fixed seeded sample of the large ones")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive (input H2D timed) leg")
     ap.add_argument("--concurrency", type=int, default=16, help="frames in flight per GPU: 1, or an even number (half 9/7, half 5/3)")
@@ -224,7 +263,9 @@ def main():
         wl = "8K 7680x4320 12-bit RGB frame per GPU; 9/7 (-I) + 5/3 lossless, enc+dec; 6 resolutions, 64x64 code-blocks, 1 layer LRCP"
     frame = torch.from_numpy(img).to("cuda:%d" % local)
     # the frame as its file holds it (12-bit samples in 16-bit words), pinned
-    host_frame = torch.from_numpy(img.astype(np.uint16)).pin_memory()
+    # (the PCIe-inclusive leg's input)
+    want_pcie = args.full and not args.no_pcie
+    host_frame = torch.from_numpy(img.astype(np.uint16)).pin_memory() if want_pcie else None
     ncodec = max(1, args.concurrency)
     assert ncodec == 1 or ncodec % 2 == 0, "--concurrency must be 1 or even"
     codecs = [grk.Codec(local) for _ in range(ncodec)]
@@ -238,8 +279,10 @@ def main():
     # (stage_ms in the line: their means, so one frame's outlier does not
     # stand for the step)
     acc = {"on": False}
+    # --dump-outputs: the codestream views of the last timed step, by job
+    last = {}
 
-    def pipe(codec, p, out, tag, src):
+    def pipe(codec, p, out, tag, src, keep=None):
         with torch.cuda.stream(streams[codecs.index(codec)]):
             b = codec.compress(src, BITS, p, view=True)
             st["enc" + tag] = codec.stats()
@@ -250,6 +293,8 @@ def main():
             if acc["on"]:
                 acc.setdefault("enc" + tag, []).append(st["enc" + tag])
                 acc.setdefault("dec" + tag, []).append(st["dec" + tag])
+            if keep is not None:
+                last[keep] = b
 
     from concurrent.futures import ThreadPoolExecutor
     pool = ThreadPoolExecutor(max_workers=ncodec) if ncodec > 1 else None
@@ -257,18 +302,21 @@ def main():
         [j for i in range(npairs) for j in ((codecs[2 * i], pa, outs[i][0], tags[0]),
                                             (codecs[2 * i + 1], pb, outs[i][1], tags[1]))]
 
-    def run_steps(n, src):
+    def run_steps(n, src, keep_last=False):
         """n steps; each frame's pipeline runs its n iterations back to back on
-        its own thread/stream (no barrier between steps)."""
+        its own thread/stream (no barrier between steps).  keep_last: every
+        job's last iteration leaves its codestream view in `last`."""
+        def keep(k, i):
+            return k if keep_last and i == n - 1 else None
         if pool is None:
-            for _ in range(n):
-                for j in jobs:
-                    pipe(*j, src)
+            for i in range(n):
+                for k, j in enumerate(jobs):
+                    pipe(*j, src, keep(k, i))
         else:
-            def loop(j):
-                for _ in range(n):
-                    pipe(*j, src)
-            for x in [pool.submit(loop, j) for j in jobs]:
+            def loop(k, j):
+                for i in range(n):
+                    pipe(*j, src, keep(k, i))
+            for x in [pool.submit(loop, k, j) for k, j in enumerate(jobs)]:
                 x.result()
 
     def barrier():
@@ -276,10 +324,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(n, src):
+    def timed(n, src, keep_last=False):
         barrier()
         t0 = time.perf_counter()
-        run_steps(n, src)
+        run_steps(n, src, keep_last)
         barrier()
         el = time.perf_counter() - t0
         return max_over_ranks(dist, el)
@@ -287,13 +335,69 @@ def main():
     pix_per_step = 2 * npairs * H * W
     # value: the frames already resident in HBM when the timed region starts
     run_steps(args.warmup, frame)
-    if args.workload == "8k":
+    if args.workload == "8k" and args.warmup > 0:
         assert torch.equal(outs[0][1], frame), "5/3 round trip is not lossless"
     acc["on"] = True
-    elapsed = timed(args.steps, frame)
+    elapsed = timed(args.steps, frame, keep_last=bool(args.dump_outputs))
     acc["on"] = False
+    if args.dump_outputs:
+        # every job's codestream and decoded frame of the last timed step
+        pre = "rank%d_" % rank if world > 1 else ""
+        arrays = {}
+        for k, j in enumerate(jobs):
+            arrays["%scodestream_%02d_%s" % (pre, k, j[3])] = last[k]
+            arrays["%sdecoded_%02d_%s" % (pre, k, j[3])] = j[2]
+        dump_outputs(args.dump_outputs, arrays)
+        last.clear()
+        del arrays
+
+    def finish(legs):
+        """Print the result line (rank 0; `legs`: the --full legs' objects)
+        and close the contexts."""
+        def r(d):
+            return {k: (round(v, 3) if isinstance(v, float) else v) for k, v in d.items()}
+
+        def mean_stats(k):
+            """Stage times of tag k: the mean over every frame of the timed
+            steps (counts from the last frame), and the frames averaged."""
+            runs = acc.get(k) or [st[k]]
+            out = dict(st[k])
+            for f in out:
+                if f.endswith("_ms"):
+                    out[f] = sum(x[f] for x in runs) / len(runs)
+            out["frames"] = len(runs)
+            return r(out)
+        if rank == 0:
+            metric = "Mpixels/sec encode+decode, 8K RGB 5/3 lossless & 9/7 lossy" if args.workload == "8k" else \
+                "Mpixels/sec encode+decode, DCI 4K cinema frames"
+            line = {
+                "metric": metric,
+                "value": round(value, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "int32/f32 (integer encode, f32 9/7 decode)",
+                "data": "synthetic (tests/golden/synth.py %s, seed %d+rank)" % (
+                    {"smooth": "smooth+2% noise", "uniform": "uniform full-range noise",
+                     "const": "constant mid-grey"}[args.data], 5 if args.workload == "c5" else 3),
+                "config": {"workload": wl, "input": args.data, "frames_per_step_per_gpu": 2 * npairs,
+                           "frames_in_flight": ncodec, "parallelism": "frame-batch x%d (no collectives)" % world},
+                "full": args.full,
+            }
+            line.update(legs)
+            line["codestream_bytes"] = {tags[0]: st["bytes" + tags[0]], tags[1]: st["bytes" + tags[1]]}
+            line["stage_ms"] = {k: mean_stats(k)
+                                for k in ("enc" + tags[0], "dec" + tags[0], "enc" + tags[1], "dec" + tags[1])}
+            if args.opt:
+                line["config"]["plan_options"] = args.opt
+            print(json.dumps(line), flush=True)
+        for c in codecs:
+            c.close()
+        if dist is not None:
+            dist.destroy_process_group()
+
     value = world * pix_per_step * args.steps / elapsed / 1e6
     ms_per_step = 1e3 * elapsed / args.steps
+    if not args.full:  # a plain run: the timed steps' figures only
+        return finish({})
     nsym_step = npairs * (st["enc" + tags[0]]["mq_symbols"] + st["enc" + tags[1]]["mq_symbols"])
     ncb_step = npairs * (st["enc" + tags[0]]["num_cblks"] + st["enc" + tags[1]]["num_cblks"])
 
@@ -301,7 +405,7 @@ def main():
     # starting in pinned host memory (2 B/sample) and copied H2D inside the
     # timed region
     pcie = None
-    if not args.no_pcie:
+    if want_pcie:
         psteps = args.steps
         run_steps(1, host_frame)
         if args.workload == "8k":
@@ -479,47 +583,7 @@ def main():
                    "sample": "1 step through the C oracle (oracle/grk_oracle.c), %d threads" % ncpu,
                    "seconds": round(ct, 2)}
 
-    if rank == 0:
-        def r(d):
-            return {k: (round(v, 3) if isinstance(v, float) else v) for k, v in d.items()}
-
-        def mean_stats(k):
-            """Stage times of tag k: the mean over every frame of the timed
-            steps (counts from the last frame), and the frames averaged."""
-            runs = acc.get(k) or [st[k]]
-            out = dict(st[k])
-            for f in out:
-                if f.endswith("_ms"):
-                    out[f] = sum(x[f] for x in runs) / len(runs)
-            out["frames"] = len(runs)
-            return r(out)
-        metric = "Mpixels/sec encode+decode, 8K RGB 5/3 lossless & 9/7 lossy" if args.workload == "8k" else \
-            "Mpixels/sec encode+decode, DCI 4K cinema frames"
-        line = {
-            "metric": metric,
-            "value": round(value, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "int32/f32 (integer encode, f32 9/7 decode)",
-            "data": "synthetic (tests/golden/synth.py %s, seed %d+rank)" % (
-                {"smooth": "smooth+2% noise", "uniform": "uniform full-range noise", "const": "constant mid-grey"}[args.data],
-                5 if args.workload == "c5" else 3),
-            "config": {"workload": wl, "input": args.data, "frames_per_step_per_gpu": 2 * npairs, "frames_in_flight": ncodec,
-                       "parallelism": "frame-batch x%d (no collectives)" % world},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "pcie_inclusive": pcie,
-            "t1": t1,
-            "e2e_frac": e2e,
-            "codestream_bytes": {tags[0]: st["bytes" + tags[0]], tags[1]: st["bytes" + tags[1]]},
-            "stage_ms": {k: mean_stats(k) for k in ("enc" + tags[0], "dec" + tags[0], "enc" + tags[1], "dec" + tags[1])},
-        }
-        if args.opt:
-            line["config"]["plan_options"] = args.opt
-        print(json.dumps(line), flush=True)
-    for c in codecs:
-        c.close()
-    if dist is not None:
-        dist.destroy_process_group()
+    finish({"roofline": roofline, "cpu_baseline": cpu, "pcie_inclusive": pcie, "t1": t1, "e2e_frac": e2e})
 
 
 def bench_c4(args, grk, synth, dist, world, rank, local):
@@ -539,7 +603,7 @@ def bench_c4(args, grk, synth, dist, world, rank, local):
     slab = synth.synth_plane(H, W, BITS, 4, 0, "smooth", rows=(r0, r1))[None]
     frame = torch.from_numpy(slab).to("cuda:%d" % local)
     del slab
-    out = torch.empty((1, H, W), dtype=torch.int32, device="cuda:%d" % local)
+    out = torch.zeros((1, H, W), dtype=torch.int32, device="cuda:%d" % local)
     codec = grk.Codec(local)
 
     def step():
@@ -558,6 +622,11 @@ def bench_c4(args, grk, synth, dist, world, rank, local):
     if dist is not None:
         dist.barrier()
     el = max_over_ranks(dist, time.perf_counter() - t0)
+    if args.dump_outputs:
+        # this rank's codestream and the image rows of its tiles (zero where
+        # a tile of those rows is another rank's)
+        pre = "rank%d_" % rank if world > 1 else ""
+        dump_outputs(args.dump_outputs, {pre + "codestream_tiles": cs, pre + "decoded_rows": out[:, r0:r1]})
     if rank == 0:
         print(json.dumps({"metric": "Mpixels/sec encode+decode, 16K tiled, tile shards",
                           "value": round(H * W * args.steps / el / 1e6, 2), "unit": "Mpixels/s", "n_gpus": world,

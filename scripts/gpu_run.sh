@@ -39,9 +39,10 @@ print(s)
 PY
 }
 
-# bench.py under a timeout; $1 = output name, the rest = bench.py arguments
+# bench.py --full (every leg of the line) under a timeout; $1 = output name,
+# the rest = bench.py arguments
 bench() { local n=$1; shift
-  timeout -k 10 500 python3 -u bench.py "$@" > $OUT/$n.json 2> $OUT/$n.err || { echo "bench $n failed"; tail -30 $OUT/$n.err; exit 1; }
+  timeout -k 10 500 python3 -u bench.py --full "$@" > $OUT/$n.json 2> $OUT/$n.err || { echo "bench $n failed"; tail -30 $OUT/$n.err; exit 1; }
   summ $OUT/$n.json $n
 }
 
@@ -74,7 +75,7 @@ case $MODE in
     for w in $WLS; do i=$((i+1)); line $w $i; done
     ;;
   prof)
-    GPU_MAX_HW_QUEUES=20 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python3 -u bench.py --no-cpu-baseline --no-pcie --steps 2 --warmup 1 --concurrency 2 > $OUT/bench.json 2> $OUT/prof.err || { echo "rocprof failed"; tail -20 $OUT/prof.err; exit 1; }
+    GPU_MAX_HW_QUEUES=20 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python3 -u bench.py --full --no-cpu-baseline --no-pcie --steps 2 --warmup 1 --concurrency 2 > $OUT/bench.json 2> $OUT/prof.err || { echo "rocprof failed"; tail -20 $OUT/prof.err; exit 1; }
     python3 scripts/prof_summary.py $OUT/prof $OUT/kernel_stats.csv > /dev/null
     python3 scripts/roofline_check.py $OUT/prof $OUT/bench.json | tee $OUT/roofline_check.txt
     bash scripts/pmc_bench.sh ${TAG}_pmc
