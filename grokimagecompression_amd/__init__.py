@@ -190,6 +190,17 @@ class Planes(ctypes.Structure):
                 ("ncols", ctypes.c_uint32)]
 
 
+LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
+_LAYOUTS = {"chw": LAYOUT_PLANAR, "hwc": LAYOUT_INTERLEAVED}
+
+
+class OutPlanes(ctypes.Structure):
+    """grkgpu_out_planes: where grkgpu_decompress_to / grkgpu_mct_inv_dcshift_to
+    store their samples (format GRKGPU_SAMPLE_*, layout GRKGPU_LAYOUT_*)."""
+    _fields_ = [("planes", ctypes.c_void_p * MAXC), ("sample_fmt", ctypes.c_uint32), ("layout", ctypes.c_uint32),
+                ("on_device", ctypes.c_int32), ("pad_", ctypes.c_uint32)]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("h2d_ms", ctypes.c_float), ("dcshift_mct_ms", ctypes.c_float), ("dwt_ms", ctypes.c_float),
                 ("t1_ms", ctypes.c_float), ("gather_ms", ctypes.c_float), ("d2h_ms", ctypes.c_float),
@@ -295,6 +306,9 @@ def lib():
         L.grkgpu_decompress_window.argtypes = [VP, VP, ctypes.c_size_t, U32, U32, U32, U32, P(ImageDesc), P(VP),
                                                ctypes.c_int]
         L.grkgpu_decompress_ex.argtypes = [VP, VP, ctypes.c_size_t, P(DParams), P(ImageDesc), P(VP), ctypes.c_int]
+        L.grkgpu_decompress_to.argtypes = [VP, VP, ctypes.c_size_t, P(DParams), U32, U32, P(ImageDesc), P(OutPlanes)]
+        L.grkgpu_mct_inv_dcshift_to.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), I32, I32, P(OutPlanes), U32,
+                                                VP]
         L.grkgpu_dcshift_mct_fwd.argtypes = [P(VP), U32, U32, U32, U32, P(I32), I32, I32, VP]
         L.grkgpu_mct_inv_dcshift.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), I32, I32, VP]
         L.grkgpu_dwt_fwd.argtypes = [VP, VP, U32, U32, U32, U32, U32, I32, VP]
@@ -400,20 +414,60 @@ def _torch():
     return torch
 
 
-def _check_out(out, shape, device):
-    """Validate a caller-supplied output (shape, int32, contiguous, device)
-    before raw pointers to it cross the C ABI."""
+def _out_format(dtype):
+    """(numpy dtype, GRKGPU_SAMPLE_*) of a decode output dtype (None: int32)."""
+    try:
+        dt = np.dtype(np.int32 if dtype is None else dtype)
+    except TypeError:
+        dt = None
+    if dt not in _NP_FMT:
+        raise GrkGpuError("dtype must be int32, uint8, int8, uint16 or int16 (got %s)" % (dtype,))
+    return dt, _NP_FMT[dt]
+
+
+def _torch_dtype(dt):
+    """The torch dtype of a decode output dtype; torch.uint16 only where this
+    torch build has it."""
+    torch = _torch()
+    name = np.dtype(dt).name
+    if not isinstance(getattr(torch, name, None), torch.dtype):
+        raise GrkGpuError("this torch build has no %s tensors" % name)
+    return getattr(torch, name)
+
+
+def _out_dtype(out):
+    """numpy dtype of a caller-supplied output's samples (None: not one a
+    decode writes, or not an array / tensor at all)."""
     if isinstance(out, np.ndarray):
-        if out.shape != tuple(shape) or out.dtype != np.int32 or not out.flags.c_contiguous:
-            raise GrkGpuError("out must be a C-contiguous int32 array of shape %s (got %s %s)"
-                              % (tuple(shape), out.shape, out.dtype))
+        return out.dtype if out.dtype in _NP_FMT else None
+    name = str(getattr(out, "dtype", "")).replace("torch.", "")
+    return np.dtype(name) if name in [d.name for d in _NP_FMT] else None
+
+
+def _layout_shape(shape, layout):
+    if layout not in _LAYOUTS:
+        raise GrkGpuError("layout must be 'chw' or 'hwc' (got %r)" % (layout,))
+    c, h, w = shape
+    return (c, h, w) if layout == "chw" else (h, w, c)
+
+
+def _check_out(out, shape, device, dtype=np.int32, layout="chw"):
+    """Validate a caller-supplied output (the layout's shape of the (c,h,w)
+    `shape`, dtype, contiguous, device) before raw pointers to it cross the C
+    ABI."""
+    dt, _ = _out_format(dtype)
+    shape = _layout_shape(shape, layout)
+    if isinstance(out, np.ndarray):
+        if out.shape != tuple(shape) or out.dtype != dt or not out.flags.c_contiguous:
+            raise GrkGpuError("out must be a C-contiguous %s array of shape %s (got %s %s)"
+                              % (dt.name, tuple(shape), out.shape, out.dtype))
         return False
     torch = _torch()
     if not isinstance(out, torch.Tensor):
         raise GrkGpuError("out must be a numpy array or a torch tensor")
-    if tuple(out.shape) != tuple(shape) or out.dtype != torch.int32 or not out.is_contiguous():
-        raise GrkGpuError("out must be a contiguous int32 tensor of shape %s (got %s %s)"
-                          % (tuple(shape), tuple(out.shape), out.dtype))
+    if tuple(out.shape) != tuple(shape) or out.dtype != _torch_dtype(dt) or not out.is_contiguous():
+        raise GrkGpuError("out must be a contiguous %s tensor of shape %s (got %s %s)"
+                          % (dt.name, tuple(shape), tuple(out.shape), out.dtype))
     if not out.is_cuda or out.device.index != device:
         raise GrkGpuError("out must live on cuda:%d (got %s)" % (device, out.device))
     return True
@@ -583,12 +637,34 @@ class Codec:
             return np.asarray(_CtxView(self, out, n.value)) if n.value else np.empty(0, np.uint8)
         return ctypes.string_at(out, n.value)
 
-    def decompress_tiles(self, buf, tile_begin, tile_end, out):
+    def _out_planes(self, out, c, fmt, layout, on_dev):
+        """grkgpu_out_planes of a checked output: a (c,h,w) / (h,w,c) array or
+        tensor, or a list of host planes."""
+        op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout], on_device=1 if on_dev else 0)
+        ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.ctypes.data)
+        if layout == "hwc":
+            op.planes[0] = ptr(out)
+        else:
+            for k in range(c):
+                op.planes[k] = ptr(out[k])
+        return op
+
+    def decompress_tiles(self, buf, tile_begin, tile_end, out, layout="chw"):
         """Decode tiles [tile_begin, tile_end) of a codestream into `out`
-        ((c,h,w) int32 numpy array or cuda tensor); other tiles untouched."""
+        ((c,h,w) numpy array or cuda tensor, or (h,w,c) with layout="hwc", of
+        int32 or -- where they hold the precision -- uint8 / int8 / uint16 /
+        int16 samples); other tiles untouched."""
         d = read_header(buf)
         c = d.numcomps
-        on_dev = _check_out(out, (c, d.y1 - d.y0, d.x1 - d.x0), self.device)
+        dt, fmt = _out_format(_out_dtype(out))
+        on_dev = _check_out(out, (c, d.y1 - d.y0, d.x1 - d.x0), self.device, dt, layout)
+        if fmt != SAMPLE_I32 or layout != "chw":
+            if on_dev:
+                lib().grkgpu_set_stream(self._ctx, _stream_handle(out.device))
+            op = self._out_planes(out, c, fmt, layout, on_dev)
+            bp, bn, keep = _buf_ptr(buf)
+            _check(lib().grkgpu_decompress_to(self._ctx, bp, bn, None, tile_begin, tile_end, None, ctypes.byref(op)))
+            return out
         if on_dev:
             lib().grkgpu_set_stream(self._ctx, _stream_handle(out.device))
             ptrs = (ctypes.c_void_p * c)(*[out[k].data_ptr() for k in range(c)])
@@ -598,9 +674,13 @@ class Codec:
         _check(lib().grkgpu_decompress_tiles(self._ctx, bp, bn, tile_begin, tile_end, ptrs, 1 if on_dev else 0))
         return out
 
-    def decompress(self, buf, device_out=False, out=None, reduce=0, window=None, layers=0):
+    def decompress(self, buf, device_out=False, out=None, reduce=0, window=None, layers=0, dtype=None, layout="chw"):
         """Decode a .j2k codestream -> (c,h,w) int32 (numpy, or torch.cuda when
-        device_out / out is a cuda tensor).  reduce > 0: the image at
+        device_out / out is a cuda tensor).  dtype = uint8 / int8 / uint16 /
+        int16: samples of that type, stored by the last decode kernel (the
+        type must hold the stream's precision and signedness; the values are
+        the int32 decode's); an `out` of one of those dtypes selects it too.
+        layout="hwc": pixel-interleaved (h,w,c).  reduce > 0: the image at
         resolution numres-1-reduce (grk_decompress -r), ceil(size / 2^reduce)
         samples a side (a window: ceil(x1 / 2^reduce) - ceil(x0 / 2^reduce)).  window = (x0, y0, x1, y1) in image coordinates:
         only that region (grk_set_decode_area), clipped to the image.
@@ -624,23 +704,59 @@ class Codec:
             return cd(cd(a1, s) - cd(a0, s), R)
         c = d.numcomps
         h, w = extent(d.y0, d.y1, 1), extent(d.x0, d.x1, 1)
+        # the sample format: dtype, or the dtype of `out` (an `out` no decode
+        # writes is refused below as "not int32")
+        dt, fmt = _out_format(dtype)
+        if out is not None and _out_dtype(out) is not None:
+            if dtype is not None and _out_dtype(out) != dt:
+                raise GrkGpuError("out holds %s samples, dtype asks for %s" % (_out_dtype(out).name, dt.name))
+            dt, fmt = _out_format(_out_dtype(out))
+        shape = _layout_shape((c, h, w), layout)
+        narrow = fmt != SAMPLE_I32 or layout != "chw"  # grkgpu_decompress_to; else today's entry points
         if any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)):
             # subsampled components: a list of host planes, each on its grid
             if out is not None or device_out:
                 raise GrkGpuError("subsampled components decode to host planes only")
-            outs = [np.empty((extent(d.y0, d.y1, d.dy[k]), extent(d.x0, d.x1, d.dx[k])), dtype=np.int32)
+            if layout != "chw" and all(d.dx[k] == d.dx[0] and d.dy[k] == d.dy[0] for k in range(c)):
+                raise GrkGpuError("subsampled components decode to host planes only")
+            outs = [np.empty((extent(d.y0, d.y1, d.dy[k]), extent(d.x0, d.x1, d.dx[k])), dtype=dt)
                     for k in range(c)]
             ptrs = (ctypes.c_void_p * c)(*[a.ctypes.data for a in outs])
             bp, bn, keep = _buf_ptr(buf)
             dp = DParams(cp_reduce=reduce, cp_layer=layers)
             if window is not None:
                 dp.DA_x0, dp.DA_y0, dp.DA_x1, dp.DA_y1 = [int(v) for v in window]
+            if narrow:
+                # interleaved: components on different grids have no pixels
+                # (the library refuses before it touches the planes)
+                op = self._out_planes(outs, c, fmt, "chw", False)
+                op.layout = _LAYOUTS[layout]
+                _check(lib().grkgpu_decompress_to(self._ctx, bp, bn, ctypes.byref(dp), 0, 0xFFFFFFFF, None,
+                                                  ctypes.byref(op)))
+                return outs
             _check(lib().grkgpu_decompress_ex(self._ctx, bp, bn, ctypes.byref(dp), None, ptrs, 0))
             return outs
         if out is not None:
-            on_dev = _check_out(out, (c, h, w), self.device)
+            on_dev = _check_out(out, (c, h, w), self.device, dt, layout)
         else:
             on_dev = bool(device_out)
+        if narrow:
+            if layers < 0:
+                raise GrkGpuError("layers must be >= 0")
+            if on_dev:
+                if out is None:
+                    out = _torch().empty(shape, dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
+                lib().grkgpu_set_stream(self._ctx, _stream_handle(out.device))
+            elif out is None:
+                out = np.empty(shape, dtype=dt)
+            op = self._out_planes(out, c, fmt, layout, on_dev)
+            bp, bn, keep = _buf_ptr(buf)
+            dp = DParams(cp_reduce=reduce, cp_layer=layers)
+            if window is not None:
+                dp.DA_x0, dp.DA_y0, dp.DA_x1, dp.DA_y1 = [int(v) for v in window]
+            _check(lib().grkgpu_decompress_to(self._ctx, bp, bn, ctypes.byref(dp), 0, 0xFFFFFFFF, None,
+                                              ctypes.byref(op)))
+            return out
         if on_dev:
             torch = _torch()
             if out is None:
@@ -813,3 +929,35 @@ def mct_inv_dcshift(planes, prec, sgnd, mct, irreversible):
     _check(lib().grkgpu_mct_inv_dcshift(ptrs, c, w, h, w, pr, sg, mct, 1 if irreversible else 0,
                                         _stream_handle(planes.device)))
     return planes
+
+
+def mct_inv_dcshift_to(src, dst, w, prec, sgnd, mct, irreversible, layout="chw", dst_stride=None):
+    """grkgpu_mct_inv_dcshift_to.  src: (c,h,src_stride) int32 cuda tensor
+    whose rows hold the w samples first (9/7: float bit patterns).  dst: a 1-D
+    cuda tensor of the output dtype -- any view, so it may start at any
+    sample -- filled from its first sample, rows dst_stride samples apart
+    (default: tight): "chw" plane k from k * h * dst_stride, "hwc" pixels of c
+    samples.  Returns dst."""
+    c, h, sstride = src.shape
+    dt, fmt = _out_format(_out_dtype(dst))
+    _layout_shape((c, h, w), layout)  # refuses an unknown layout
+    il = layout == "hwc"
+    row = w * c if il else w
+    stride = row if dst_stride is None else dst_stride
+    need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
+    if (src.dtype != _torch_dtype(np.int32) or not src.is_contiguous() or not src.is_cuda or dst.dim() != 1
+            or not dst.is_contiguous() or dst.device != src.device or w > sstride or stride < row
+            or dst.numel() < need):
+        raise GrkGpuError("mct_inv_dcshift_to: src (c,h,stride >= w) int32, dst flat, %d samples, on src's device"
+                          % need)
+    op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout], on_device=1)
+    for k in range(1 if il else c):
+        op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
+    ptrs = (ctypes.c_void_p * c)(*[src[k].data_ptr() for k in range(c)])
+    pr = (ctypes.c_uint32 * c)(*([prec] * c))
+    sg = (ctypes.c_int32 * c)(*([1 if sgnd else 0] * c))
+    _check(lib().grkgpu_mct_inv_dcshift_to(ptrs, c, w, h, sstride, pr, sg, mct, 1 if irreversible else 0,
+                                           ctypes.byref(op), stride, _stream_handle(src.device)))
+    return dst
+
+

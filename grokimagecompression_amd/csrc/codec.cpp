@@ -2276,6 +2276,18 @@ static bool walk_tile_parts(const uint8_t *cs, size_t len, size_t sot0, uint32_t
     return true;
 }
 
+// Where a decode stores its samples: the caller's planes, their sample format
+// (SampleFmt) and layout.
+struct DecodeOut {
+    void *const *planes;  // planar: one per component; interleaved: planes[0]
+    int32_t fmt;          // SampleFmt
+    int32_t interleaved;
+    int on_device;
+};
+static DecodeOut i32_planes(int32_t *const *planes, int on_device) {
+    return {(void *const *)planes, SMP_I32, 0, on_device};
+}
+
 // reduce > 0 (whole-image decode only): the image at resolution
 // numres - 1 - reduce (grk_decompress -r, cp_reduce, grok.h:698-702): every
 // packet is still parsed, code-blocks of the dropped resolutions are not
@@ -2298,11 +2310,24 @@ static bool walk_tile_parts(const uint8_t *cs, size_t len, size_t sot0, uint32_t
 // host_only: stop after the host Tier-2 (tile-part walk, packet headers, the
 // code-block table) -- no device call; *decoded_out (when given) receives the
 // tiles decoded (grkgpu_walk_tiles)
+//
+// od: where the samples go (DecodeOut) -- the caller's planes, their sample
+// format and layout.  k_mct_inv_dcshift's clamp leaves every sample inside its
+// component's range, and the format must hold that range (compress_impl's
+// rule), so a narrow format is exact: the last kernel stores the samples at
+// that width, and the staging image, the zero fills and the copies to the host
+// are sized by it.  Interleaved: one destination of ncomp-sample pixels, every
+// component on one grid.
 static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu_image_desc *img,
-                           int32_t *const *planes, int planes_on_device, uint32_t tb, uint32_t te,
+                           const DecodeOut &od, uint32_t tb, uint32_t te,
                            uint32_t reduce = 0, const Rect *win = nullptr, uint32_t max_layers = 0,
                            bool host_only = false, std::vector<uint8_t> *decoded_out = nullptr) {
+    void *const *const planes = od.planes;
+    const int planes_on_device = od.on_device;
     if ((!c && !host_only) || !csb || (!planes && !host_only)) return set_err(GRKGPU_EINVAL, "null argument");
+    if (od.fmt < SMP_I32 || od.fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    const uint32_t sb = sample_bytes(od.fmt);  // bytes per output sample
+    const bool il = od.interleaved != 0;
     ActiveCall active;
     double t_start = now_ms();
     CodingParams cp;
@@ -2352,6 +2377,18 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         mixed = mixed || cp.dx[k] != cp.dx[0] || cp.dy[k] != cp.dy[0];
     }
     if (subs && !whole) return set_err(GRKGPU_EUNSUPPORTED, "tile-range decode of subsampled images is not supported");
+    if (win && !whole) return set_err(GRKGPU_EINVAL, "window decode of a tile range is not supported");
+    for (uint32_t k = 0; od.fmt != SMP_I32 && k < nc; ++k) {
+        const bool sg = od.fmt == SMP_I8 || od.fmt == SMP_I16;
+        if ((cp.sgnd[k] != 0) != sg || cp.prec[k] > 8 * sb)
+            return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
+    }
+    if (il && mixed)
+        return set_err(GRKGPU_EUNSUPPORTED, "interleaved output needs every component on one grid");
+    if (il && (uint64_t)iw * nc > 0xffffffffull)  // the kernel's row stride is 32 bits of samples
+        return set_err(GRKGPU_EUNSUPPORTED, "image too wide for interleaved output");
+    for (uint32_t k = 0; !host_only && k < (il ? 1u : nc); ++k)
+        if (!planes[k] || (uintptr_t)planes[k] % sb) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
     Rect orect[GRKGPU_MAX_COMPS];
     uint64_t ooff[GRKGPU_MAX_COMPS + 1];
     ooff[0] = 0;
@@ -2776,29 +2813,40 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     HIPCHK(dwt_launch(dplan[1], c->dwtjobs, 1, true, s, c->launch_timing ? &llog : nullptr));
     HIPCHK(dwt_launch(dplan[0], c->dwtjobs53, 0, true, s, c->launch_timing ? &llog : nullptr));
     HIPCHK(hipEventRecord(c->ev[3], s));
-    PlanePtrs dst{};
+    // the output as the copies and fills see it: `nout` regions (the planes,
+    // or the one interleaved image) of elements `eb` bytes wide (a sample, or
+    // a pixel of nc samples); region k holds ooff[k + 1] - ooff[k] samples
+    // (interleaved: all ooff[nc] of them)
+    const uint32_t nout = il ? 1 : nc;
+    const size_t eb = il ? (size_t)nc * sb : sb;
+    auto region_bytes = [&](uint32_t k) { return (size_t)(il ? ooff[nc] : ooff[k + 1] - ooff[k]) * sb; };
+    DstPlanes dst{};
     if (planes_on_device) {
-        for (uint32_t k = 0; k < nc; ++k) dst.p[k] = planes[k];
+        for (uint32_t k = 0; k < nout; ++k) dst.p[k] = planes[k];
     } else {
-        HIPCHK(c->img.ensure(ooff[nc] * 4 + 256));
-        for (uint32_t k = 0; k < nc; ++k) dst.p[k] = c->img.as<int32_t>() + ooff[k];
+        // staging image: every region on a 16-byte boundary, so that the
+        // kernel's packed stores stay aligned whatever the sample width
+        size_t off[GRKGPU_MAX_COMPS + 1] = {0};
+        for (uint32_t k = 0; k < nout; ++k) off[k + 1] = (off[k] + region_bytes(k) + 15) & ~(size_t)15;
+        HIPCHK(c->img.ensure(off[nout] + 256));
+        for (uint32_t k = 0; k < nout; ++k) dst.p[k] = c->img.as<uint8_t>() + off[k];
     }
+    auto at = [&](uint32_t k, uint64_t elem) { return (void *)((uint8_t *)dst.p[k] + elem * eb); };
     if (opad)
-        for (uint32_t k = 0; k < nc; ++k)
-            HIPCHK(hipMemsetAsync(dst.p[k], 0, (ooff[k + 1] - ooff[k]) * 4, s));
+        for (uint32_t k = 0; k < nout; ++k) HIPCHK(hipMemsetAsync(dst.p[k], 0, region_bytes(k), s));
     else if (missing)  // tiles the tile-part walk never reached: zero (their regions only -- a shard's
                        // device planes hold other tiles)
         for (uint32_t t = tb; t < te; ++t) {
             if (walk.decoded[t] || wskip[t]) continue;
-            for (uint32_t k = 0; k < nc; ++k) {
+            for (uint32_t k = 0; k < nout; ++k) {
                 const Rect cr = comp_rect(tile_rect(cp, t), cp.dx[k], cp.dy[k]);
                 const Rect rr{ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
                               ceil_pow2(cr.y1, reduce)};
                 const Rect o = intersect(rr, orect[k]);
                 if (o.empty()) continue;
                 const uint32_t ow = orect[k].w();
-                HIPCHK(hipMemset2DAsync(dst.p[k] + (uint64_t)(o.y0 - orect[k].y0) * ow + (o.x0 - orect[k].x0),
-                                        (size_t)ow * 4, 0, (size_t)o.w() * 4, o.h(), s));
+                HIPCHK(hipMemset2DAsync(at(k, (uint64_t)(o.y0 - orect[k].y0) * ow + (o.x0 - orect[k].x0)),
+                                        (size_t)ow * eb, 0, (size_t)o.w() * eb, o.h(), s));
             }
         }
     ShiftArr sh{}, mn{}, mx{};
@@ -2815,46 +2863,50 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                 const Rect tr = tc.res[tc.numres - 1 - reduce].r;
                 const Rect out = intersect(tr, orect[k]);
                 if (out.empty()) continue;
-                PlanePtrs tsrc{}, tdst{};
+                PlanePtrs tsrc{};
+                DstPlanes tdst{};
                 ShiftArr sk{}, mnk{}, mxk{};
                 tsrc.p[0] = c->work.as<int32_t>() + tc.arena_off + (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0);
-                tdst.p[0] = dst.p[k] + (uint64_t)(out.y0 - orect[k].y0) * orect[k].w() + (out.x0 - orect[k].x0);
+                tdst.p[0] = at(k, (uint64_t)(out.y0 - orect[k].y0) * orect[k].w() + (out.x0 - orect[k].x0));
                 sk.v[0] = sh.v[k];
                 mnk.v[0] = mn.v[k];
                 mxk.v[0] = mx.v[k];
-                HIPCHK(launch_mct_inv_dcshift(tsrc, tr.w(), out.w(), out.h(), tdst, orect[k].w(), 1, sk, mnk, mxk, 0,
-                                              tc.irrev, s));
+                HIPCHK(launch_mct_inv_dcshift_to(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, false, orect[k].w(), 1,
+                                                 sk, mnk, mxk, 0, tc.irrev, s));
             }
             continue;
         }
         // every component on one grid: one launch, MCT included (orect[k]
         // is the output on that grid -- the image itself without subsampling)
-        PlanePtrs tsrc{}, tdst{};
+        PlanePtrs tsrc{};
+        DstPlanes tdst{};
         const Rect tr = tile.comps[0].res[tile.comps[0].numres - 1 - reduce].r;  // the tile at the decoded resolution
         const Rect out = intersect(tr, orect[0]);             // its part of the output
         if (out.empty()) continue;
         const uint32_t ow = orect[0].w();
-        for (uint32_t k = 0; k < nc; ++k) {
+        for (uint32_t k = 0; k < nc; ++k)
             tsrc.p[k] = c->work.as<int32_t>() + tile.comps[k].arena_off + (uint64_t)(out.y0 - tr.y0) * tr.w() +
                         (out.x0 - tr.x0);
-            tdst.p[k] = dst.p[k] + (uint64_t)(out.y0 - orect[0].y0) * ow + (out.x0 - orect[0].x0);
-        }
+        for (uint32_t k = 0; k < nout; ++k)
+            tdst.p[k] = at(k, (uint64_t)(out.y0 - orect[0].y0) * ow + (out.x0 - orect[0].x0));
         int32_t wmask = 0;  // components holding 9/7 (float) samples
         for (uint32_t k = 0; k < nc; ++k) wmask |= tile.comps[k].irrev << k;
-        HIPCHK(launch_mct_inv_dcshift(tsrc, tr.w(), out.w(), out.h(), tdst, ow, nc, sh, mn, mx,
-                                      tmct[tile.index - tb], wmask, s));
+        // row stride in samples: a row of an interleaved image holds ow pixels of nc samples
+        HIPCHK(launch_mct_inv_dcshift_to(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * nc : ow, nc, sh,
+                                         mn, mx, tmct[tile.index - tb], wmask, s));
     }
     HIPCHK(hipEventRecord(c->ev[4], s));
     if (!planes_on_device) {
         if (whole) {
-            for (uint32_t k = 0; k < nc; ++k)
-                HIPCHK(hipMemcpyAsync(planes[k], dst.p[k], (ooff[k + 1] - ooff[k]) * 4, hipMemcpyDeviceToHost, s));
+            for (uint32_t k = 0; k < nout; ++k)
+                HIPCHK(hipMemcpyAsync(planes[k], dst.p[k], region_bytes(k), hipMemcpyDeviceToHost, s));
         } else {  // only the shard's tiles
             for (auto &tile : tiles)
-                for (uint32_t k = 0; k < nc; ++k) {
-                    const uint64_t o = (uint64_t)(tile.r.y0 - cp.image.y0) * iw + (tile.r.x0 - cp.image.x0);
-                    HIPCHK(hipMemcpy2DAsync(planes[k] + o, (size_t)iw * 4, dst.p[k] + o, (size_t)iw * 4,
-                                            (size_t)tile.r.w() * 4, tile.r.h(), hipMemcpyDeviceToHost, s));
+                for (uint32_t k = 0; k < nout; ++k) {
+                    const uint64_t o = ((uint64_t)(tile.r.y0 - cp.image.y0) * iw + (tile.r.x0 - cp.image.x0)) * eb;
+                    HIPCHK(hipMemcpy2DAsync((uint8_t *)planes[k] + o, (size_t)iw * eb, (uint8_t *)dst.p[k] + o,
+                                            (size_t)iw * eb, (size_t)tile.r.w() * eb, tile.r.h(),
+                                            hipMemcpyDeviceToHost, s));
                 }
         }
     }
@@ -2878,28 +2930,28 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
 
 extern "C" int grkgpu_decompress(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu_image_desc *img,
                                  int32_t *const *planes, int planes_on_device) {
-    return decompress_impl(c, csb, len, img, planes, planes_on_device, 0, 0xffffffffu);
+    return decompress_impl(c, csb, len, img, i32_planes(planes, planes_on_device), 0, 0xffffffffu);
 }
 
 extern "C" int grkgpu_decompress_reduced(grkgpu_ctx *c, const uint8_t *csb, size_t len, uint32_t reduce,
                                          grkgpu_image_desc *img, int32_t *const *planes, int planes_on_device) {
-    return decompress_impl(c, csb, len, img, planes, planes_on_device, 0, 0xffffffffu, reduce);
+    return decompress_impl(c, csb, len, img, i32_planes(planes, planes_on_device), 0, 0xffffffffu, reduce);
 }
 
 extern "C" int grkgpu_decompress_window(grkgpu_ctx *c, const uint8_t *csb, size_t len, uint32_t x0, uint32_t y0,
                                         uint32_t x1, uint32_t y1, grkgpu_image_desc *img, int32_t *const *planes,
                                         int planes_on_device) {
     const Rect w{x0, y0, x1, y1};
-    return decompress_impl(c, csb, len, img, planes, planes_on_device, 0, 0xffffffffu, 0, &w);
+    return decompress_impl(c, csb, len, img, i32_planes(planes, planes_on_device), 0, 0xffffffffu, 0, &w);
 }
 
 extern "C" int grkgpu_decompress_ex(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
                                     grkgpu_image_desc *img, int32_t *const *planes, int planes_on_device) {
-    if (!dp) return decompress_impl(c, csb, len, img, planes, planes_on_device, 0, 0xffffffffu);
+    if (!dp) return decompress_impl(c, csb, len, img, i32_planes(planes, planes_on_device), 0, 0xffffffffu);
     const bool win = dp->DA_x0 || dp->DA_y0 || dp->DA_x1 || dp->DA_y1;
     const Rect w{dp->DA_x0, dp->DA_y0, dp->DA_x1, dp->DA_y1};
     if (win && (dp->DA_x1 <= dp->DA_x0 || dp->DA_y1 <= dp->DA_y0)) return set_err(GRKGPU_EINVAL, "empty decode area");
-    return decompress_impl(c, csb, len, img, planes, planes_on_device, 0, 0xffffffffu, dp->cp_reduce,
+    return decompress_impl(c, csb, len, img, i32_planes(planes, planes_on_device), 0, 0xffffffffu, dp->cp_reduce,
                            win ? &w : nullptr, dp->cp_layer);
 }
 
@@ -2909,7 +2961,7 @@ extern "C" int grkgpu_walk_tiles(const uint8_t *csb, size_t len, uint8_t *decode
     int rc = grkgpu_read_header(csb, len, &d);
     if (rc) return rc;
     std::vector<uint8_t> dec;
-    rc = decompress_impl(nullptr, csb, len, nullptr, nullptr, 0, 0, 0xffffffffu, 0, nullptr, 0, true, &dec);
+    rc = decompress_impl(nullptr, csb, len, nullptr, i32_planes(nullptr, 0), 0, 0xffffffffu, 0, nullptr, 0, true, &dec);
     if (rc) return rc;
     *ntiles = (uint32_t)dec.size();
     if (decoded)
@@ -2919,7 +2971,30 @@ extern "C" int grkgpu_walk_tiles(const uint8_t *csb, size_t len, uint8_t *decode
 
 extern "C" int grkgpu_decompress_tiles(grkgpu_ctx *c, const uint8_t *csb, size_t len, uint32_t tile_begin,
                                        uint32_t tile_end, int32_t *const *planes, int planes_on_device) {
-    return decompress_impl(c, csb, len, nullptr, planes, planes_on_device, tile_begin, tile_end);
+    return decompress_impl(c, csb, len, nullptr, i32_planes(planes, planes_on_device), tile_begin, tile_end);
+}
+
+// grkgpu_out_planes' own rules, checked before anything touches a device
+static int check_out_planes(const grkgpu_out_planes *out) {
+    if (!out) return set_err(GRKGPU_EINVAL, "null argument");
+    if (out->sample_fmt > GRKGPU_SAMPLE_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if (out->layout > GRKGPU_LAYOUT_INTERLEAVED) return set_err(GRKGPU_EINVAL, "unknown layout");
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_decompress_to(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
+                                    uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                                    const grkgpu_out_planes *out) {
+    int rc = check_out_planes(out);
+    if (rc) return rc;
+    const DecodeOut od{out->planes, (int32_t)out->sample_fmt, out->layout == GRKGPU_LAYOUT_INTERLEAVED,
+                       out->on_device};
+    if (!dp) return decompress_impl(c, csb, len, img, od, tile_begin, tile_end);
+    const bool win = dp->DA_x0 || dp->DA_y0 || dp->DA_x1 || dp->DA_y1;
+    const Rect w{dp->DA_x0, dp->DA_y0, dp->DA_x1, dp->DA_y1};
+    if (win && (dp->DA_x1 <= dp->DA_x0 || dp->DA_y1 <= dp->DA_y0)) return set_err(GRKGPU_EINVAL, "empty decode area");
+    return decompress_impl(c, csb, len, img, od, tile_begin, tile_end, dp->cp_reduce, win ? &w : nullptr,
+                           dp->cp_layer);
 }
 
 // ---------------------------------------------------------------------------
@@ -2956,6 +3031,43 @@ extern "C" int grkgpu_mct_inv_dcshift(int32_t *const *planes, uint32_t numcomps,
     }
     HIPCHK(launch_mct_inv_dcshift(p, stride, w, h, p, stride, numcomps, sh, mn, mx, mct, irreversible ? 0xFFFF : 0,
                                   (hipStream_t)stream));
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t numcomps, uint32_t w, uint32_t h,
+                                         uint32_t src_stride, const uint32_t *prec, const int32_t *sgnd, int32_t mct,
+                                         int32_t irreversible, const grkgpu_out_planes *dst, uint32_t dst_stride,
+                                         void *stream) {
+    int rc = check_out_planes(dst);
+    if (rc) return rc;
+    const bool il = dst->layout == GRKGPU_LAYOUT_INTERLEAVED;
+    const int32_t fmt = (int32_t)dst->sample_fmt;
+    const uint32_t sb = sample_bytes(fmt);
+    if (!src || !prec || !sgnd || numcomps < 1 || numcomps > 16 || src_stride < w ||
+        (uint64_t)dst_stride < (uint64_t)w * (il ? numcomps : 1))
+        return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
+    PlanePtrs p{};
+    DstPlanes d{};
+    ShiftArr sh{}, mn{}, mx{};
+    for (uint32_t k = 0; k < numcomps; ++k) {
+        if (prec[k] < 1 || prec[k] > 31 || !src[k]) return set_err(GRKGPU_EINVAL, "bad arguments");
+        const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
+        if (fmt != SMP_I32 && ((sgnd[k] != 0) != sg || prec[k] > 8 * sb))
+            return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
+        p.p[k] = const_cast<int32_t *>(src[k]);
+        sh.v[k] = sgnd[k] ? 0 : (1 << (prec[k] - 1));
+        if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
+        else { mn.v[k] = 0; mx.v[k] = (int32_t)((1u << prec[k]) - 1); }
+    }
+    for (uint32_t k = 0; k < (il ? 1u : numcomps); ++k) {
+        if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
+            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+        d.p[k] = dst->planes[k];
+    }
+    rc = check_device(-1);
+    if (rc) return rc;
+    HIPCHK(launch_mct_inv_dcshift_to(p, src_stride, w, h, d, fmt, il, dst_stride, numcomps, sh, mn, mx, mct,
+                                     irreversible ? 0xFFFF : 0, (hipStream_t)stream));
     return GRKGPU_OK;
 }
 

@@ -71,6 +71,16 @@ hipError_t launch_dcshift_mct_custom(const SrcPlanes &src, int32_t fmt, uint32_t
 hipError_t launch_mct_inv_dcshift(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th,
                                   const PlanePtrs &dst, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift,
                                   const ShiftArr &mn, const ShiftArr &mx, int32_t mct, int32_t irrev, hipStream_t s);
+// The same pass, storing the clamped samples in the caller's format `fmt`
+// (SampleFmt; the clamp range must fit it, so the narrowing is exact) and
+// layout: planar -- dst.p[c] = plane c, rows dstride samples apart -- or
+// interleaved -- sample (y, x, c) at dst.p[0][y * dstride + x * ncomp + c].
+// Destinations may start at any sample; int32 planar runs launch_mct_inv_dcshift.
+struct DstPlanes { void *p[GRK_MAX_COMPS]; };
+hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th,
+                                     const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
+                                     uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn, const ShiftArr &mx,
+                                     int32_t mct, int32_t irrev, hipStream_t s);
 // One DWT level of one tile-component (dwt.hip).  A launch runs one level of
 // every job in a table (grid.y = job).
 struct DwtJob {

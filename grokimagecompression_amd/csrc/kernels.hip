@@ -128,6 +128,219 @@ __global__ void k_mct_inv_dcshift(PlanePtrs src, uint32_t sstride, uint32_t tw, 
     }
 }
 
+// Inverse MCT + DC shift + clamp straight to the caller's sample type T
+// (uint8 / int8 / uint16 / int16, or int32 for the interleaved layout) and
+// layout -- k_mct_inv_dcshift's arithmetic, statement for statement; only the
+// store differs.  The clamp to the component's [min, max] comes first and the
+// format holds that range (checked by the callers), so the narrowing is exact.
+//
+// A thread owns a run of RUN = 16 / sizeof(T) adjacent pixels of one row: it
+// reads each component's coefficients as dwordx4 where the source is 16-byte
+// aligned and writes the run as packed words -- one dwordx4 per component
+// (planar), ncomp dwordx4 (interleaved, 16 * ncomp bytes).  Runs are laid on
+// the destination's 16-byte grid: thread 0 of a row takes the `lead` pixels
+// before the first aligned address (scalar stores), thread t > 0 the run from
+// lead + (t - 1) * RUN, and the row's last run is cut at tw (scalar stores).
+// Where a full run's address still is not 16-byte aligned (another plane's
+// base, a row pitch that moves it) it goes out as dwords if 4-byte aligned
+// and as single samples otherwise: every byte offset is correct, the aligned
+// interior is fast.  Stores are non-temporal: nothing on the device reads the
+// image again.
+template <typename T>
+struct NarrowRun { static constexpr int N = 16 / (int)sizeof(T); };
+
+// one word of a run: samples [j * 4 / sizeof(T), ...) of v, low address first
+template <typename T>
+__device__ __forceinline__ uint32_t pack_word(const int32_t *v, int j) {
+    if constexpr (sizeof(T) == 1)
+        return ((uint32_t)v[4 * j] & 0xffu) | (((uint32_t)v[4 * j + 1] & 0xffu) << 8) |
+               (((uint32_t)v[4 * j + 2] & 0xffu) << 16) | ((uint32_t)v[4 * j + 3] << 24);
+    else if constexpr (sizeof(T) == 2)
+        return ((uint32_t)v[2 * j] & 0xffffu) | ((uint32_t)v[2 * j + 1] << 16);
+    else
+        return (uint32_t)v[j];
+}
+
+// NS samples (a multiple of a 16-byte group; static indices only, so v stays
+// in registers), of which the first n are stored
+template <typename T, int NS>
+__device__ __forceinline__ void store_samples(T *p, const int32_t (&v)[NS], int n) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr int G = NarrowRun<T>::N;  // samples per 16 bytes
+    const uintptr_t a = (uintptr_t)p;
+    if (n == NS && !(a & 15)) {
+#pragma unroll
+        for (int g = 0; g < NS / G; ++g) {
+            const u32x4 w = {pack_word<T>(v + g * G, 0), pack_word<T>(v + g * G, 1), pack_word<T>(v + g * G, 2),
+                             pack_word<T>(v + g * G, 3)};
+            __builtin_nontemporal_store(w, (u32x4 *)p + g);
+        }
+    } else if (n == NS && !(a & 3)) {
+#pragma unroll
+        for (int j = 0; j < NS / G * 4; ++j)
+            __builtin_nontemporal_store(pack_word<T>(v + (j / 4) * G, j % 4), (uint32_t *)p + j);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NS; ++i)
+            if (i < n) __builtin_nontemporal_store((T)v[i], p + i);
+    }
+}
+
+// n <= N coefficients of one component's row
+template <int N>
+__device__ __forceinline__ void load_run(const int32_t *p, int n, int32_t (&v)[N]) {
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    if (n == N && !((uintptr_t)p & 15)) {
+#pragma unroll
+        for (int g = 0; g < N / 4; ++g) {
+            const i32x4 q = ((const i32x4 *)p)[g];
+            v[4 * g] = q.x; v[4 * g + 1] = q.y; v[4 * g + 2] = q.z; v[4 * g + 3] = q.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = i < n ? p[i] : 0;
+    }
+}
+
+// the run of thread t of a row whose first sample lies at byte address a and
+// whose pixels are pxb bytes: first pixel and pixel count (0: none)
+template <int N>
+__device__ __forceinline__ int run_of(uintptr_t a, uint32_t pxb, uint32_t t, uint32_t tw, uint32_t &x0) {
+    uint32_t lead = 0;  // pixels before the first 16-byte boundary a run can start on (none: runs from 0)
+    for (uint32_t l = 0; l < (uint32_t)N; ++l)
+        if (!((a + (uintptr_t)l * pxb) & 15)) { lead = l; break; }
+    const uint64_t first = t ? (uint64_t)lead + (uint64_t)(t - 1) * N : 0;
+    const uint64_t end = t ? first + N : lead;
+    x0 = (uint32_t)(first < tw ? first : tw);
+    return (int)((end < tw ? end : tw) - x0);
+}
+
+// the three MCT components of n pixels: k_mct_inv_dcshift's first branch
+template <int N>
+__device__ __forceinline__ void inv_mct_run(int32_t (&a)[N], int32_t (&b)[N], int32_t (&c)[N], int32_t irrev,
+                                            const ShiftArr &shift, const ShiftArr &minv, const ShiftArr &maxv) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        int32_t o[3];
+        if (!(irrev & 1)) {
+            int32_t yv = a[i], u = b[i], v = c[i];
+            int32_t g = yv - ((u + v) >> 2);
+            o[0] = v + g; o[1] = g; o[2] = u + g;
+        } else {
+            float yv = __int_as_float(a[i]), u = __int_as_float(b[i]), v = __int_as_float(c[i]);
+            // mct::decode_irrev (mct.cpp:352-408): separate mul/add, no FMA
+            float r = __fadd_rn(yv, __fmul_rn(v, 1.402f));
+            float g = __fsub_rn(__fsub_rn(yv, __fmul_rn(u, 0.34413f)), __fmul_rn(v, 0.71414f));
+            float bl = __fadd_rn(yv, __fmul_rn(u, 1.772f));
+            o[0] = (int32_t)rintf(r); o[1] = (int32_t)rintf(g); o[2] = (int32_t)rintf(bl);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            int32_t v = o[k] + shift.v[k];
+            o[k] = v < minv.v[k] ? minv.v[k] : (v > maxv.v[k] ? maxv.v[k] : v);
+        }
+        a[i] = o[0]; b[i] = o[1]; c[i] = o[2];
+    }
+}
+
+// a component outside the MCT: k_mct_inv_dcshift's second loop
+template <int N>
+__device__ __forceinline__ void inv_plain_run(int32_t (&a)[N], int32_t irrev_c, int32_t shift, int32_t mn, int32_t mx) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        int32_t v = a[i];
+        if (irrev_c) v = (int32_t)rintf(__int_as_float(v));
+        v += shift;
+        a[i] = v < mn ? mn : (v > mx ? mx : v);
+    }
+}
+
+// planar: dst.p[c] = plane c (samples T), rows dstride samples apart
+template <typename T>
+__global__ void k_mct_inv_dcshift_planar(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
+                                         uint32_t dstride, uint32_t ncomp, ShiftArr shift, ShiftArr minv,
+                                         ShiftArr maxv, int32_t mct, int32_t irrev) {
+    constexpr int N = NarrowRun<T>::N;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (y >= th) return;
+    const size_t drow = (size_t)y * dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)((T *)dst.p[0] + drow), sizeof(T), t, tw, x0);
+    if (n <= 0) return;
+    const size_t si = (size_t)y * sstride + x0, di = drow + x0;
+    uint32_t c0 = 0;
+    if (mct && ncomp >= 3) {
+        int32_t a[N], b[N], c[N];
+        load_run<N>(src.p[0] + si, n, a);
+        load_run<N>(src.p[1] + si, n, b);
+        load_run<N>(src.p[2] + si, n, c);
+        inv_mct_run<N>(a, b, c, irrev, shift, minv, maxv);
+        store_samples<T, N>((T *)dst.p[0] + di, a, n);
+        store_samples<T, N>((T *)dst.p[1] + di, b, n);
+        store_samples<T, N>((T *)dst.p[2] + di, c, n);
+        c0 = 3;
+    }
+    for (uint32_t k = c0; k < ncomp; ++k) {
+        int32_t a[N];
+        load_run<N>(src.p[k] + si, n, a);
+        inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        store_samples<T, N>((T *)dst.p[k] + di, a, n);
+    }
+}
+
+// interleaved, NC = 3 or 4 components: sample (y, x, c) at dst.p[0][y * dstride + x * NC + c]
+template <typename T, int NC>
+__global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
+                                         uint32_t dstride, ShiftArr shift, ShiftArr minv, ShiftArr maxv, int32_t mct,
+                                         int32_t irrev) {
+    constexpr int N = NarrowRun<T>::N;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (y >= th) return;
+    T *const drow = (T *)dst.p[0] + (size_t)y * dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)drow, NC * sizeof(T), t, tw, x0);
+    if (n <= 0) return;
+    const size_t si = (size_t)y * sstride + x0;
+    int32_t v[NC][N];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) load_run<N>(src.p[k] + si, n, v[k]);
+    if (mct) inv_mct_run<N>(v[0], v[1], v[2], irrev, shift, minv, maxv);
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+        if (!mct || k >= 3) inv_plain_run<N>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+    int32_t px[N * NC];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int k = 0; k < NC; ++k) px[i * NC + k] = v[k][i];
+    store_samples<T, N * NC>(drow + (size_t)x0 * NC, px, n * NC);
+}
+
+// interleaved, any other component count: one thread per pixel, one store per sample
+template <typename T>
+__global__ void k_mct_inv_dcshift_pixels_any(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
+                                             uint32_t dstride, uint32_t ncomp, ShiftArr shift, ShiftArr minv,
+                                             ShiftArr maxv, int32_t mct, int32_t irrev) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= tw || y >= th) return;
+    const size_t si = (size_t)y * sstride + x;
+    T *const d = (T *)dst.p[0] + (size_t)y * dstride + (size_t)x * ncomp;
+    uint32_t c0 = 0;
+    if (mct && ncomp >= 3) {
+        int32_t a[1] = {src.p[0][si]}, b[1] = {src.p[1][si]}, c[1] = {src.p[2][si]};
+        inv_mct_run<1>(a, b, c, irrev, shift, minv, maxv);
+        __builtin_nontemporal_store((T)a[0], d);
+        __builtin_nontemporal_store((T)b[0], d + 1);
+        __builtin_nontemporal_store((T)c[0], d + 2);
+        c0 = 3;
+    }
+    for (uint32_t k = c0; k < ncomp; ++k) {
+        int32_t a[1] = {src.p[k][si]};
+        inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        __builtin_nontemporal_store((T)a[0], d + k);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // T1 (t1_lane.h).  Encode = prep (wave per block: quantise, sign rows, numbps,
 // magnitude bit-planes via ballots) + lane coder (one lane per block).
@@ -822,6 +1035,52 @@ hipError_t launch_mct_inv_dcshift(const PlanePtrs &src, uint32_t sstride, uint32
     dim3 grid((tw + 255) / 256, th);
     hipLaunchKernelGGL(k_mct_inv_dcshift, grid, dim3(256), 0, s, src, sstride, tw, th, dst, dstride, ncomp, shift, mn,
                        mx, mct, irrev);
+    return hipGetLastError();
+}
+
+template <typename T>
+static void launch_inv_to(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
+                          bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift,
+                          const ShiftArr &mn, const ShiftArr &mx, int32_t mct, int32_t irrev, hipStream_t s) {
+    // threads of a row: the lead run + the runs of RUN pixels
+    const uint32_t runs = (uint32_t)(((uint64_t)tw + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
+    const dim3 grid((runs + 255) / 256, th);
+    mct = mct && ncomp >= 3;
+    if (!interleaved || ncomp == 1)
+        hipLaunchKernelGGL(k_mct_inv_dcshift_planar<T>, grid, dim3(256), 0, s, src, sstride, tw, th, dst, dstride,
+                           ncomp, shift, mn, mx, mct, irrev);
+    else if (ncomp == 3)
+        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 3>), grid, dim3(256), 0, s, src, sstride, tw, th, dst, dstride,
+                           shift, mn, mx, mct, irrev);
+    else if (ncomp == 4)
+        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 4>), grid, dim3(256), 0, s, src, sstride, tw, th, dst, dstride,
+                           shift, mn, mx, mct, irrev);
+    else
+        hipLaunchKernelGGL(k_mct_inv_dcshift_pixels_any<T>, dim3((tw + 255) / 256, th), dim3(256), 0, s, src, sstride,
+                           tw, th, dst, dstride, ncomp, shift, mn, mx, mct, irrev);
+}
+
+hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th,
+                                     const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
+                                     uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn, const ShiftArr &mx,
+                                     int32_t mct, int32_t irrev, hipStream_t s) {
+    if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS) return hipErrorInvalidValue;
+    if (!tw || !th) return hipSuccess;
+    if (fmt == SMP_I32 && !interleaved) {  // int32 planes: the kernel every int32 decode has always run
+        PlanePtrs d{};
+        for (uint32_t k = 0; k < ncomp; ++k) d.p[k] = (int32_t *)dst.p[k];
+        return launch_mct_inv_dcshift(src, sstride, tw, th, d, dstride, ncomp, shift, mn, mx, mct, irrev, s);
+    }
+#define GRK_INV(T) launch_inv_to<T>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev, s)
+    switch (fmt) {
+        case SMP_I32: GRK_INV(int32_t); break;
+        case SMP_U8: GRK_INV(uint8_t); break;
+        case SMP_I8: GRK_INV(int8_t); break;
+        case SMP_U16: GRK_INV(uint16_t); break;
+        case SMP_I16: GRK_INV(int16_t); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_INV
     return hipGetLastError();
 }
 

@@ -27,6 +27,11 @@
  *                          (mct/mct.cpp:85, :195; TileProcessor.cpp:1449).
  *   grkgpu_mct_inv_dcshift mct::decode_rev / decode_irrev + DC shift + clamp
  *                          (mct/mct.cpp:143, :352; TileProcessor.cpp:1377).
+ *   grkgpu_decompress_to / grkgpu_mct_inv_dcshift_to
+ *                          the same decode, its samples stored as the 8 / 16-bit
+ *                          planar or interleaved samples the reference's image
+ *                          writers produce from the int32 planes
+ *                          (bin/jp2/PNMFormat.cpp, RAWFormat.cpp).
  *   grkgpu_t1_encode_blocks  Tier1::encodeCodeblocks -> T1Encoder::encode ->
  *                          T1Part1::preEncode/encode (t1/Tier1.cpp:24,
  *                          T1Encoder.cpp:40-85, t1_part1/T1Part1.cpp:58-127,
@@ -489,6 +494,37 @@ int grkgpu_decompress_ex(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, const g
  * for the shard's tiles only. */
 int grkgpu_decompress_tiles(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, uint32_t tile_begin,
                             uint32_t tile_end, int32_t *const *planes, int planes_on_device);
+/* Decode straight to the samples a consumer holds: 8 / 16-bit (or int32)
+ * samples, planar or pixel-interleaved -- the decode-side counterpart of
+ * grkgpu_planes.  The reference decodes to grk_image's int32 planes and leaves
+ * the narrowing to whoever writes the file: its PNM / raw writers walk the
+ * planes and emit 1 or 2 bytes per sample, interleaving the components as
+ * they go (PNMFormat.cpp, RAWFormat.cpp encode paths).  Here the last decode
+ * kernel (inverse MCT + DC shift + clamp) stores the samples in that form, so
+ * a 12-bit frame leaves the GPU at 2 B/sample.  The clamp to the component's
+ * [min, max] comes first and sample_fmt must hold every component's
+ * precision and signedness (grkgpu_compress_ex's rule, else GRKGPU_EINVAL),
+ * so the narrowing is exact -- the values are those of the int32 decode.
+ * Rows are tight: w samples (planar), w * numcomps samples (interleaved:
+ * sample (y, x, c) at planes[0][(y * w + x) * numcomps + c]).  Interleaved
+ * output needs every component on one grid (subsampled components on
+ * different grids: GRKGPU_EUNSUPPORTED; planar output takes them, each plane
+ * on its own grid).  Geometry as grkgpu_decompress_ex, the reduced whole
+ * image's zero margin included.
+ * p = NULL: whole image, all layers.  tile_begin / tile_end = 0, 0xffffffff:
+ * every tile; a proper range has grkgpu_decompress_tiles' rules (no reduce /
+ * window, the other tiles' samples untouched). */
+enum { GRKGPU_LAYOUT_PLANAR = 0, GRKGPU_LAYOUT_INTERLEAVED = 1 };
+typedef struct {
+    void *planes[GRKGPU_MAX_COMPS]; /* planar: one per component; interleaved: planes[0] */
+    uint32_t sample_fmt;            /* GRKGPU_SAMPLE_* */
+    uint32_t layout;                /* GRKGPU_LAYOUT_* */
+    int32_t on_device;
+    uint32_t pad_;
+} grkgpu_out_planes;
+int grkgpu_decompress_to(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, const grkgpu_dparams *p,
+                         uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                         const grkgpu_out_planes *out);
 /* (multi-device decode into host planes: see grkgpu_device_set above) */
 int grkgpu_decompress_multi(const grkgpu_device_set *devs, const uint8_t *cs, size_t len, grkgpu_image_desc *img,
                             int32_t *const *planes);
@@ -511,6 +547,17 @@ int grkgpu_dcshift_mct_fwd(int32_t *const *planes, uint32_t numcomps, uint32_t w
 int grkgpu_mct_inv_dcshift(int32_t *const *planes, uint32_t numcomps, uint32_t w, uint32_t h,
                            uint32_t stride, const uint32_t *prec, const int32_t *sgnd, int32_t mct,
                            int32_t irreversible, void *stream);
+/* grkgpu_mct_inv_dcshift out of place, to the sample format and layout of dst
+ * (the last kernel of grkgpu_decompress_to on its own; in the reference the
+ * caller's own narrowing when it writes a PNM or raw file): src[c] = the
+ * int32 (9/7: float bit pattern) planes, rows src_stride apart; dst->planes
+ * are device pointers (on_device is not read), rows dst_stride samples apart
+ * (>= w, interleaved >= w * numcomps), starting at any sample.  The format
+ * must hold every component's precision and signedness (GRKGPU_EINVAL). */
+int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t numcomps, uint32_t w, uint32_t h,
+                              uint32_t src_stride, const uint32_t *prec, const int32_t *sgnd, int32_t mct,
+                              int32_t irreversible, const grkgpu_out_planes *dst, uint32_t dst_stride,
+                              void *stream);
 /* In-place (Mallat layout) forward / inverse DWT of one tile-component with
  * origin (x0,y0), size (x1-x0) x (y1-y0), row stride x1-x0.  scratch must
  * hold grkgpu_dwt_scratch_bytes(...) device bytes.  For 9/7 inverse the buffer
