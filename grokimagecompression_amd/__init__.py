@@ -222,7 +222,8 @@ class DwtOptions(ctypes.Structure):
                 ("inv01_min_samples", ctypes.c_uint64), ("f64_lift", ctypes.c_int32), ("t1_dec_sort", ctypes.c_int32),
                 ("t1_dec_bpw", ctypes.c_int32), ("mid_th", ctypes.c_int32),
                 ("t1_enc_bpw", ctypes.c_int32), ("t1_enc_sort", ctypes.c_int32), ("pair_kernel", ctypes.c_int32),
-                ("pair_rows", ctypes.c_int32), ("pair_waves", ctypes.c_int32), ("pair_min_samples", ctypes.c_uint64)]
+                ("pair_rows", ctypes.c_int32), ("pair_waves", ctypes.c_int32), ("pair_min_samples", ctypes.c_uint64),
+                ("t1_lone", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
 class DeviceSet(ctypes.Structure):

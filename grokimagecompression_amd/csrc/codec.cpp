@@ -234,7 +234,8 @@ struct ActiveCall {
     ActiveCall() { g_active_calls.fetch_add(1); }
     ~ActiveCall() { g_active_calls.fetch_sub(1); }
 };
-static bool lone_call() { return g_active_calls.load() <= 1; }
+// t1_lone forces the choice either way (the parity suite's handle on the batch kernels).
+static bool lone_call() { return g_dwt_opts.t1_lone ? g_dwt_opts.t1_lone > 0 : g_active_calls.load() <= 1; }
 }  // namespace grkgpu
 
 extern "C" {
@@ -258,6 +259,8 @@ void grkgpu_get_dwt_options(grkgpu_dwt_options *out) {
     out->pair_rows = g_dwt_opts.pair_rows;
     out->pair_waves = g_dwt_opts.pair_waves;
     out->pair_min_samples = g_dwt_opts.pair_min_samples;
+    out->t1_lone = g_dwt_opts.t1_lone;
+    out->pad_ = 0;
 }
 
 int grkgpu_set_dwt_options(const grkgpu_dwt_options *o) {
@@ -284,6 +287,8 @@ int grkgpu_set_dwt_options(const grkgpu_dwt_options *o) {
         return set_err(GRKGPU_EINVAL, "pair_rows must be 0 or an even count <= 65536");
     if (o->pair_waves != 0 && o->pair_waves != 3 && o->pair_waves != 4)
         return set_err(GRKGPU_EINVAL, "pair_waves must be 0, 3 or 4");
+    if (o->t1_lone < -1 || o->t1_lone > 1) return set_err(GRKGPU_EINVAL, "t1_lone must be -1, 0 or 1");
+    g_dwt_opts.t1_lone = o->t1_lone;
     g_dwt_opts.pair_kernel = o->pair_kernel;
     g_dwt_opts.pair_rows = o->pair_rows;
     g_dwt_opts.pair_waves = o->pair_waves;

@@ -132,6 +132,7 @@ struct DwtOptions {
     int32_t pair_rows = 0;    // k_dwt_fwd_pair: level-(l+1) rows per segment (even; 0 = by size)
     int32_t pair_waves = 0;   // k_dwt_fwd_pair: level-l waves per workgroup (3 / 4; 0 = by width)
     uint64_t pair_min_samples = (uint64_t)1 << 20;  // k_dwt_fwd_pair: fuse pairs from this many level-l samples
+    int32_t t1_lone = 0;      // T1 plan: 0 = by the calls in progress, 1 = always the lone plan, -1 = always the batch plan
 };
 const DwtOptions &dwt_options();
 // level geometry code (window rows) for a level of that many samples whose

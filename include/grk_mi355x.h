@@ -249,7 +249,15 @@ int grkgpu_set_launch_timing(grkgpu_ctx *ctx, int on);
  *   pair_rows        k_dwt_fwd_pair: level-(l+1) rows per segment (even); 0
  *                    (default) = sized for one resident wave of workgroups.
  *   pair_waves       k_dwt_fwd_pair: level-l wavefronts per workgroup, 3 or 4;
- *                    0 (default) = whichever wastes fewer columns. */
+ *                    0 (default) = whichever wastes fewer columns.
+ *   t1_lone          which T1 plan a call takes: 0 (default) = by the calls in
+ *                    progress in the process (a call that is alone spreads
+ *                    its code-blocks over the chip, concurrent calls pack
+ *                    full wavefronts); 1 = every call takes the lone plan;
+ *                    -1 = every call takes the batch plan (the wide MQ coder
+ *                    and the lane-per-block unstuff from 4096 blocks), so
+ *                    the parity suite reaches the batch kernels without
+ *                    overlapping calls.  Same output. */
 typedef struct {
     int32_t fuse_level0;
     int32_t f01_rows;
@@ -268,6 +276,8 @@ typedef struct {
     int32_t pair_rows;
     int32_t pair_waves;
     uint64_t pair_min_samples;
+    int32_t t1_lone;
+    int32_t pad_;
 } grkgpu_dwt_options;
 void grkgpu_get_dwt_options(grkgpu_dwt_options *out);  /* current values */
 int grkgpu_set_dwt_options(const grkgpu_dwt_options *opts);  /* NULL: the defaults */

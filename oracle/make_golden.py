@@ -14,8 +14,12 @@ Stores:
                                  sha256 of input image / j2k / decoded image
   tests/golden/manifest_large.json  same hashes for the BASELINE.json configs
                                  (full-size streams are too big to commit)
+  tests/golden/manifest_many.json   same hashes, plus one per 64 KiB of the
+                                 codestream, for the MANY list: code-block
+                                 mode switches (-M) on images of more than
+                                 4,096 code-blocks (tests/test_gpu_t1_many.py)
 
-Usage:  python oracle/make_golden.py [--large] [--check] [--only NAME ...]
+Usage:  python oracle/make_golden.py [--large | --many] [--check] [--only NAME ...]
   --check  regenerate into a temporary directory and compare with the
            committed files instead of overwriting them (exit 1 on a mismatch)
 """
@@ -205,6 +209,41 @@ LARGE = [
     ("C3_8k_rgb12_const", (4320, 7680, 3, 12), "const", 3, []),
 ]
 
+# Code-block mode switches (-M) on images of more than 4,096 code-blocks of
+# one style in one call: the T1 kernels picked by block count
+# (tests/test_gpu_t1_many.py; hash-only, regenerated in seconds).  Not uniform
+# noise in 4x4 / 8x8 blocks with TERMALL or BYPASS: the reference refuses
+# those itself ("Code block layer size ... exceeds number of available bytes").
+def _many():
+    out = []
+
+    def add(base, shape, kind, seed, args, modes):
+        for m in modes:
+            out.append(("%s_M%d" % (base, m), shape, kind, seed, list(args) + ["-M", str(m)]))
+
+    rgb = ((640, 640, 3, 12), "uniform", 3)
+    add("m_rgb12u_640_b16", *rgb, ["-b", "16,16"], (2, 4, 8, 16, 32, 17))
+    add("m_rgb12u_640_b16_I_r", *rgb, ["-b", "16,16", "-I", "-r", "20,5"], (1, 62))
+    add("m_rgb12u_640_b16_r", *rgb, ["-b", "16,16", "-r", "20,5"], (5,))
+    # every combination of the six switches
+    add("m_g12_544_b8", (544, 544, 1, 12), "smooth", 1, ["-b", "8,8"], range(1, 64))
+    # 76-sample edge tiles: partial blocks
+    add("m_g8_1100_b16_t256", (1100, 1100, 1, 8), "smooth", 5, ["-b", "16,16", "-t", "256,256"], (1, 4, 46, 63))
+    # partial 20-sample edge blocks, heights not a multiple of 4
+    add("m_g12u_2100_b32", (2100, 2100, 1, 12), "uniform", 6, ["-b", "32,32"], (1, 63))
+    # odd image origin
+    add("m_g16_1300_b16_d53", (1300, 1300, 1, 16), "smooth", 7, ["-b", "16,16", "-d", "5,3"], (1, 21, 63))
+    return out
+
+
+MANY = _many()
+# one rate-controlled case by layers, one 5/3 case by resolutions (as DEC_VARIANTS)
+MANY_DEC_VARIANTS = {
+    "m_rgb12u_640_b16_I_r_M62": [["-l", "1"]],
+    "m_g12_544_b8_M63": [["-r", "1"]],
+}
+CHUNK = 64 * 1024  # chunk_sha256: one hash per successive 64 KiB of the codestream
+
 
 def sha(b):
     return hashlib.sha256(b).hexdigest()
@@ -257,7 +296,7 @@ def ref_decode_planes(j2k, tmp, extra=()):
     return planes, subs
 
 
-def run_case(name, shape, kind, seed, args, tmp, keep_dir=None):
+def run_case(name, shape, kind, seed, args, tmp, keep_dir=None, variants_of=None, chunks=False):
     h, w, c, bits = shape
     img = synth.synth_image(h, w, c, bits, seed, kind)
     jb = ref_encode(img, bits, args, tmp)
@@ -269,12 +308,14 @@ def run_case(name, shape, kind, seed, args, tmp, keep_dir=None):
                dec_sha256=synth.image_sha256(dec),
                dec_vs_src_maxabs=int(np.abs(diff).max()) if diff.size else 0,
                dec_vs_src_mse=mse)
+    if chunks:
+        rec["chunk_sha256"] = [sha(jb[o:o + CHUNK]) for o in range(0, len(jb), CHUNK)]
     if keep_dir:
         with open(os.path.join(keep_dir, f"{name}.j2k"), "wb") as f:
             f.write(jb)
         np.save(os.path.join(keep_dir, f"{name}.dec.npy"), dec)
     variants = {}
-    for vargs in DEC_VARIANTS.get(name, []):
+    for vargs in (DEC_VARIANTS if variants_of is None else variants_of).get(name, []):
         vdec, hdr = ref_decode(jb, tmp, vargs)
         tag = variant_tag(vargs)
         variants[tag] = dict(args=vargs, dec_sha256=synth.image_sha256(vdec), header=list(hdr))
@@ -288,14 +329,18 @@ def run_case(name, shape, kind, seed, args, tmp, keep_dir=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--large", action="store_true")
+    ap.add_argument("--many", action="store_true")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--only", nargs="*")
     a = ap.parse_args()
     build_ref()
-    cases = LARGE if a.large else CASES
+    if a.large and a.many:
+        ap.error("--large and --many are separate lists")
+    cases = LARGE if a.large else MANY if a.many else CASES
     if a.only:
         cases = [cs for cs in cases if cs[0] in a.only]
-    mname = "manifest_large.json" if a.large else "manifest.json"
+    mname = "manifest_large.json" if a.large else "manifest_many.json" if a.many else "manifest.json"
+    hash_only = a.large or a.many
     committed = {}
     if os.path.exists(os.path.join(GOLD, mname)):
         with open(os.path.join(GOLD, mname)) as f:
@@ -303,14 +348,17 @@ def main():
     bad = 0
     man = dict(committed)
     with tempfile.TemporaryDirectory() as tmp:
-        keep = None if (a.large or a.check) else GOLD
+        keep = None if (hash_only or a.check) else GOLD
         for case in cases:
-            rec = run_case(*case, tmp, keep_dir=keep)
+            # a case the reference refuses ends the run (check=True in ref_encode / ref_decode): never dropped
+            rec = run_case(*case, tmp, keep_dir=keep, variants_of=MANY_DEC_VARIANTS if a.many else None,
+                           chunks=a.many)
             if a.check:
                 ref = committed.get(case[0])
                 same = ref is not None and all(ref.get(k) == rec.get(k)
-                                               for k in ("j2k_sha256", "dec_sha256", "image_sha256", "variants"))
-                if not a.large and same:
+                                               for k in ("j2k_sha256", "dec_sha256", "image_sha256", "variants",
+                                                         "j2k_len", "chunk_sha256", "args", "shape", "kind", "seed"))
+                if not hash_only and same:
                     with open(os.path.join(GOLD, f"{case[0]}.j2k"), "rb") as f:
                         same = sha(f.read()) == rec["j2k_sha256"]
                     same = same and synth.image_sha256(np.load(os.path.join(GOLD, f"{case[0]}.dec.npy"))) == rec["dec_sha256"]
@@ -323,8 +371,15 @@ def main():
                 man[case[0]] = rec
                 print(case[0], rec["j2k_len"], flush=True)
     if a.check:
+        if a.many and not a.only:  # the committed list is exactly this one
+            stale = sorted(set(committed) - {cs[0] for cs in cases})
+            for n in stale:
+                print(n, "MISMATCH (not in MANY)", flush=True)
+            bad += len(stale)
         print("mismatches", bad)
         sys.exit(1 if bad else 0)
+    if a.many and not a.only:
+        man = {cs[0]: man[cs[0]] for cs in cases}
     with open(os.path.join(GOLD, mname), "w") as f:
         json.dump(man, f, indent=1)
     print("ok", len(cases))

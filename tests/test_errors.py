@@ -219,7 +219,15 @@ def test_dwt_options_checks():
         assert (cur.f01_rows, cur.fuse_level0, cur.f01_min_samples) == (6, 0, 1 << 23)
     grk.lib().grkgpu_get_dwt_options(ctypes.byref(cur))
     assert (cur.f01_rows, cur.fuse_level0) == (4, -1)
-    for kw in (dict(f01_rows=3), dict(f01_rows=8), dict(fuse_level0=2), dict(inv01=1), dict(inv01=3), dict(inv01=-1)):
+    assert ctypes.sizeof(cur) == 96 and cur.t1_lone == 0
+    for lone in (1, -1):
+        with grk.dwt_options(t1_lone=lone):
+            grk.lib().grkgpu_get_dwt_options(ctypes.byref(cur))
+            assert cur.t1_lone == lone
+    grk.lib().grkgpu_get_dwt_options(ctypes.byref(cur))
+    assert cur.t1_lone == 0
+    for kw in (dict(f01_rows=3), dict(f01_rows=8), dict(fuse_level0=2), dict(inv01=1), dict(inv01=3), dict(inv01=-1),
+               dict(t1_lone=2), dict(t1_lone=-2)):
         with pytest.raises(grk.GrkGpuError):
             with grk.dwt_options(**kw):
                 pass

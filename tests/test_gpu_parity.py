@@ -709,8 +709,10 @@ def test_mid_size_blocks_per_wave(codec, oracle, hw, irrev):
     """Images of 1,000-4,000 code-blocks: the T1 lane coders run 2-32 blocks
     per wavefront there (kernels.hip t1_blocks_per_wave; the goldens have
     fewer than 1,024 blocks -- one per wavefront -- and the full-size configs
-    more than 4,096 -- 64).  Codestream == the oracle's, decode == the
-    oracle's decode."""
+    more than 4,096 -- 64; all without mode switches.  The block-count ranges
+    and the kernels each picks are listed in tests/test_gpu_t1_many.py, which
+    runs the mode switches above 4,096 blocks).  Codestream == the oracle's,
+    decode == the oracle's decode."""
     import grokimagecompression_amd as grk
     h, w = hw
     img = synth.synth_image(h, w, 3, 10, h + w)

@@ -54,6 +54,39 @@ def test_t1_core_host_matches_oracle(oracle, tmp_path):
     assert r.returncode == 0, r.stdout[-2000:]
 
 
+def _build_t1_modes(exe, flags):
+    ob = os.path.join(ROOT, "oracle", "build")
+    subprocess.run(["g++", *flags, "-std=c++17", "-Wno-unknown-pragmas", "-o", str(exe),
+                    os.path.join(ROOT, "tests/cpp/test_t1_modes.cpp"), "-L" + ob, "-lgrk_oracle", "-Wl,-rpath," + ob],
+                   check=True)
+
+
+def test_t1_mode_switches_host_match_oracle(oracle, tmp_path):
+    """tests/cpp/test_t1_modes.cpp: random blocks under every code-block style
+    1..63 through the host build of the coders -- styled encode, codeword
+    segments, per-segment unstuff, decode over the segment cursor -- against
+    the oracle's decode of its style-0 encode, all passes and a truncated
+    count."""
+    exe = tmp_path / "test_t1_modes"
+    _build_t1_modes(exe, ["-O2"])
+    r = subprocess.run([str(exe), "1500"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "OK: 0 failures / 1500 blocks" in r.stdout
+
+
+def test_t1_mode_switches_host_sanitized(oracle, tmp_path):
+    """The same stand-alone program under AddressSanitizer and UBSan, its
+    buffers sized as the GPU path sizes them: no report, exit status 0."""
+    exe = tmp_path / "test_t1_modes_san"
+    # the runtimes linked into the program itself: nothing depends on the order libraries load in
+    _build_t1_modes(exe, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                          "-static-libasan", "-static-libubsan"])
+    r = subprocess.run([str(exe), "300"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "OK: 0 failures / 300 blocks" in r.stdout
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
 def test_ict_term_identity():
     """grk_device.h ict_term: the forward ICT's int_fix_mul(r << 11, c)
     (mct.cpp:195-350, 64-bit product) equals floor((r c + 2) / 4) in 32-bit

@@ -110,6 +110,14 @@ def test_c1_config_hash_regenerates():
     assert "C1_512_gray8 ok" in out
 
 
+def test_many_block_fixtures_regenerate():
+    """tests/golden/manifest_many.json: the mode-switch matrix on images of
+    more than 4,096 code-blocks (oracle/make_golden.py MANY; hashes only),
+    regenerated by the reference."""
+    out = _check("--many")
+    assert "mismatches 0" in out
+
+
 def test_plugin_abi_layout_matches_reference_headers():
     """include/grk_plugin_abi.h re-declares grok.h's plugin-boundary structs;
     oracle/abi/ compiles one offset/size table over the reference's headers
