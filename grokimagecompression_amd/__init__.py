@@ -179,12 +179,15 @@ class CParams(ctypes.Structure):
 
 
 SAMPLE_I32, SAMPLE_U8, SAMPLE_I8, SAMPLE_U16, SAMPLE_I16 = 0, 1, 2, 3, 4
+# flags on a grkgpu_planes sample_fmt: pixels in planes[0]; 16-bit samples most-significant byte first
+SAMPLE_INTERLEAVED, SAMPLE_BIG_ENDIAN = 0x100, 0x200
 _NP_FMT = {np.dtype(np.int32): SAMPLE_I32, np.dtype(np.uint8): SAMPLE_U8, np.dtype(np.int8): SAMPLE_I8,
            np.dtype(np.uint16): SAMPLE_U16, np.dtype(np.int16): SAMPLE_I16}
 
 
 class Planes(ctypes.Structure):
-    """grkgpu_planes: the image planes of grkgpu_compress_ex."""
+    """grkgpu_planes: the image planes of grkgpu_compress_ex (sample_fmt = a
+    SAMPLE_* width | SAMPLE_INTERLEAVED | SAMPLE_BIG_ENDIAN)."""
     _fields_ = [("planes", ctypes.c_void_p * MAXC), ("sample_fmt", ctypes.c_uint32), ("on_device", ctypes.c_int32),
                 ("row0", ctypes.c_uint32), ("nrows", ctypes.c_uint32), ("col0", ctypes.c_uint32),
                 ("ncols", ctypes.c_uint32)]
@@ -289,6 +292,8 @@ def lib():
                                            P(P(ctypes.c_uint8)), P(ctypes.c_size_t)]
         L.grkgpu_compress_ex.argtypes = [VP, P(ImageDesc), P(CParams), P(Planes), U32, U32, U32, P(P(ctypes.c_uint8)),
                                          P(ctypes.c_size_t)]
+        L.grkgpu_encode_blocks_ex.argtypes = [VP, P(ImageDesc), P(CParams), P(Planes), ctypes.c_int, P(VP), P(U32)]
+        L.grkgpu_dcshift_mct_fwd_from.argtypes = [P(Planes), U32, U32, U32, U32, P(I32), I32, I32, P(VP), U32, VP]
         L.grkgpu_read_header.argtypes = [VP, ctypes.c_size_t, P(ImageDesc)]
         L.grkgpu_decompress.argtypes = [VP, VP, ctypes.c_size_t, P(ImageDesc), P(VP), ctypes.c_int]
         L.grkgpu_free.argtypes = [VP]
@@ -356,6 +361,69 @@ def _fmt_fits(fmt, prec, sgnd):
     bits = 8 if fmt in (SAMPLE_U8, SAMPLE_I8) else 16
     signed = fmt in (SAMPLE_I8, SAMPLE_I16)
     return bool(sgnd) == signed and prec <= bits
+
+
+def _np_in_format(dt):
+    """sample_fmt (width | SAMPLE_BIG_ENDIAN) of a numpy dtype an encode reads
+    as it is, None for any other: the five native widths, and 16-bit samples
+    stored most-significant byte first ('>u2' / '>i2')."""
+    if dt in _NP_FMT:
+        return _NP_FMT[dt]
+    if dt.byteorder == ">" and dt.itemsize == 2 and dt.newbyteorder("=") in _NP_FMT:
+        return _NP_FMT[dt.newbyteorder("=")] | SAMPLE_BIG_ENDIAN
+    return None
+
+
+def _in_samples(img, prec, sgnd, layout="chw"):
+    """Check an encode's input -- a (c,h,w) array / tensor, or (h,w,c) with
+    layout="hwc" -- and return (img, (c, h, w), sample_fmt, is_tensor): img as
+    the library reads it (widened to int32 where its dtype does not hold the
+    precision) and the sample_fmt with its interleaved / big-endian flags.
+    "hwc" input must be contiguous: it is read in place, never copied."""
+    if layout not in _LAYOUTS:
+        raise GrkGpuError("layout must be 'chw' or 'hwc' (got %r)" % (layout,))
+    hwc = layout == "hwc"
+    if len(img.shape) != 3:
+        raise GrkGpuError("image must have 3 dimensions, %s (got shape %s)"
+                          % ("(h,w,c)" if hwc else "(c,h,w)", tuple(img.shape)))
+    c, h, w = (img.shape[2], img.shape[0], img.shape[1]) if hwc else img.shape
+    if not 1 <= c <= MAXC:
+        raise GrkGpuError("1 .. %d components (shape %s read as %s)" % (MAXC, tuple(img.shape), layout))
+    if isinstance(img, np.ndarray):
+        if hwc and not img.flags.c_contiguous:
+            raise GrkGpuError("an (h,w,c) image must be C-contiguous")
+        fmt = _np_in_format(img.dtype)
+        if fmt is None or not _fmt_fits(fmt & 0xFF, prec, sgnd):
+            img, fmt = img.astype(np.int32), SAMPLE_I32
+        img = np.ascontiguousarray(img)
+        is_tensor = False
+    else:
+        torch = _torch()
+        tf = {torch.int32: SAMPLE_I32, torch.uint8: SAMPLE_U8, torch.int8: SAMPLE_I8, torch.int16: SAMPLE_I16}
+        if hasattr(torch, "uint16"):
+            tf[torch.uint16] = SAMPLE_U16
+        if not isinstance(img, torch.Tensor) or img.dtype not in tf or not img.is_contiguous():
+            raise GrkGpuError("image tensor must be contiguous int32 / uint16 / int16 / uint8 / int8")
+        if not _fmt_fits(tf[img.dtype], prec, sgnd):
+            img = img.to(torch.int32)  # e.g. 12-bit unsigned samples held in int16
+        fmt = tf[img.dtype]
+        is_tensor = True
+    if hwc:
+        fmt |= SAMPLE_INTERLEAVED
+    return img, (c, h, w), fmt, is_tensor
+
+
+def _in_planes(img, shape, fmt, is_tensor):
+    """grkgpu_planes of _in_samples' image (on_device left 0)."""
+    pl = Planes()
+    ptr = (lambda a: a.data_ptr()) if is_tensor else (lambda a: a.ctypes.data)
+    if fmt & SAMPLE_INTERLEAVED:
+        pl.planes[0] = ptr(img)
+    else:
+        for k in range(shape[0]):
+            pl.planes[k] = ptr(img[k])
+    pl.sample_fmt = fmt
+    return pl
 
 
 class _CtxView:
@@ -517,11 +585,12 @@ class Codec:
         return [{"kernel": t.kernel.decode(), "level0": t.level0, "levels": t.levels, "ms": t.ms, "bytes": t.bytes}
                 for t in arr[:n.value]]
 
-    def _image(self, img, prec, offset, sgnd):
-        """Image descriptor + grkgpu_planes of a (c,h,w) numpy array or torch
-        tensor of int32, uint16, int16, uint8 or int8 samples (host, pinned
-        host, or on this codec's device)."""
-        c, h, w = img.shape
+    def _image(self, img, prec, offset, sgnd, layout="chw"):
+        """Image descriptor + grkgpu_planes of a (c,h,w) -- layout "hwc":
+        (h,w,c) -- numpy array or torch tensor of int32, uint16, int16, uint8
+        or int8 samples (host, pinned host, or on this codec's device; numpy
+        '>u2' / '>i2' arrays are read as they are, big-endian)."""
+        img, (c, h, w), fmt, is_tensor = _in_samples(img, prec, sgnd, layout)
         d = ImageDesc()
         d.x0, d.y0 = offset
         d.x1, d.y1 = offset[0] + w, offset[1] + h
@@ -529,25 +598,9 @@ class Codec:
         for k in range(c):
             d.prec[k] = prec
             d.sgnd[k] = 1 if sgnd else 0
-        pl = Planes()
-        if isinstance(img, np.ndarray):
-            if img.dtype not in _NP_FMT or not _fmt_fits(_NP_FMT[img.dtype], prec, sgnd):
-                img = img.astype(np.int32)
-            img = np.ascontiguousarray(img)
-            fmt = _NP_FMT[img.dtype]
-            for k in range(c):
-                pl.planes[k] = img[k].ctypes.data
-            on_dev = False
-        else:
+        on_dev = False
+        if is_tensor:
             torch = _torch()
-            tf = {torch.int32: SAMPLE_I32, torch.uint8: SAMPLE_U8, torch.int8: SAMPLE_I8, torch.int16: SAMPLE_I16}
-            if hasattr(torch, "uint16"):
-                tf[torch.uint16] = SAMPLE_U16
-            if img.dtype not in tf or not img.is_contiguous():
-                raise GrkGpuError("image tensor must be contiguous int32 / uint16 / int16 / uint8 / int8")
-            if not _fmt_fits(tf[img.dtype], prec, sgnd):
-                img = img.to(torch.int32)  # e.g. 12-bit unsigned samples held in int16
-            fmt = tf[img.dtype]
             on_dev = img.is_cuda
             if on_dev:
                 if img.device.index != self.device:
@@ -557,21 +610,24 @@ class Codec:
                 # host tensor (pinned or not): the library copies it H2D on the
                 # caller's current stream
                 lib().grkgpu_set_stream(self._ctx, _stream_handle(torch.device("cuda", self.device)))
-            for k in range(c):
-                pl.planes[k] = img[k].data_ptr()
-        pl.sample_fmt = fmt
+        pl = _in_planes(img, (c, h, w), fmt, is_tensor)
         pl.on_device = 1 if on_dev else 0
         return d, pl, img
 
-    def compress(self, img, prec, params=None, offset=(0, 0), sgnd=False, view=False):
+    def compress(self, img, prec, params=None, offset=(0, 0), sgnd=False, view=False, layout="chw"):
         """img: (c,h,w) numpy array or torch tensor (host, pinned host or
         cuda:<device>) of int32 samples, or of the 8 / 16-bit samples of the
         image file (uint8 / int8 / uint16 / int16: widened on the GPU, so a host
-        frame crosses PCIe at its own width).  Returns the .j2k codestream as
+        frame crosses PCIe at its own width).  layout="hwc": img is (h,w,c),
+        pixel-interleaved as image loaders, capture and torch pipelines hold
+        frames -- contiguous, read in place by the first kernel (no permute,
+        no host copy).  numpy '>u2' / '>i2' arrays are read big-endian as they
+        are.  The codestream does not depend on the dtype or layout the
+        samples arrive in.  Returns the .j2k codestream as
         bytes, or (view=True) as a zero-copy numpy uint8 view of the context's
         pinned output buffer, valid for as long as the view lives (_CtxView)."""
         return self.compress_tiles(img, prec, params or CParams.make(), 0, 0xFFFFFFFF, PART_ALL, offset, sgnd,
-                                   view=view)
+                                   view=view, layout=layout)
 
     def compress_subsampled(self, planes, prec, size, subsampling, params=None, offset=(0, 0), sgnd=False):
         """Subsampled components (SIZ XRsiz / YRsiz): planes[k] is component
@@ -617,19 +673,19 @@ class Codec:
         return ctypes.string_at(out, n.value)
 
     def compress_tiles(self, img, prec, params, tile_begin, tile_end, parts=PART_TILES, offset=(0, 0), sgnd=False,
-                       row0=None, height=None, view=False):
+                       row0=None, height=None, view=False, layout="chw"):
         """Encode tiles [tile_begin, tile_end) of img; returns their tile-parts
         (plus the main header / EOC when `parts` asks for them) as bytes, or
         (view=True) as a numpy uint8 view of the context's pinned output
         buffer (no copy), valid for as long as the view lives (_CtxView).
         row0 / height: img holds only image rows [row0, row0 + img rows) of an
-        image `height` rows tall (a tile-row shard)."""
-        d, pl, keep = self._image(img, prec, offset, sgnd)
+        image `height` rows tall (a tile-row shard).  layout: as compress."""
+        d, pl, keep = self._image(img, prec, offset, sgnd, layout)
         if row0 is not None:
             if height is None:
                 raise GrkGpuError("height (the full image height) is required with row0")
             d.y1 = offset[1] + height
-            pl.row0, pl.nrows = row0, img.shape[1]
+            pl.row0, pl.nrows = row0, img.shape[0 if layout == "hwc" else 1]
         out = ctypes.POINTER(ctypes.c_uint8)()
         n = ctypes.c_size_t()
         _check(lib().grkgpu_compress_ex(self._ctx, ctypes.byref(d), ctypes.byref(params), ctypes.byref(pl), tile_begin,
@@ -804,14 +860,17 @@ def _devset(devices):
     return ds
 
 
-def compress_multi(img, prec, params=None, devices=None, offset=(0, 0), sgnd=False):
+def compress_multi(img, prec, params=None, devices=None, offset=(0, 0), sgnd=False, layout="chw"):
     """One encode over several device workers (grkgpu_compress_multi: the
     tiles sharded in contiguous ranges, each worker uploading only its tiles'
     rows; the pieces concatenated in tile order, TLM patched).  img: (c,h,w)
-    host numpy array (int32 or the file's 8 / 16-bit samples).  devices: the
+    host numpy array (int32 or the file's 8 / 16-bit samples), or (h,w,c)
+    with layout="hwc" (Codec.compress's rules).  devices: the
     workers' devices (a device may repeat), default device_set(-1).  Returns
     the codestream bytes -- the same bytes as Codec.compress."""
-    c, h, w = img.shape
+    if not isinstance(img, np.ndarray):
+        raise GrkGpuError("compress_multi reads a host numpy array")
+    img, (c, h, w), fmt, _ = _in_samples(img, prec, sgnd, layout)
     d = ImageDesc()
     d.x0, d.y0 = offset
     d.x1, d.y1 = offset[0] + w, offset[1] + h
@@ -819,13 +878,7 @@ def compress_multi(img, prec, params=None, devices=None, offset=(0, 0), sgnd=Fal
     for k in range(c):
         d.prec[k] = prec
         d.sgnd[k] = 1 if sgnd else 0
-    if img.dtype not in _NP_FMT or not _fmt_fits(_NP_FMT[img.dtype], prec, sgnd):
-        img = img.astype(np.int32)
-    img = np.ascontiguousarray(img)
-    pl = Planes()
-    for k in range(c):
-        pl.planes[k] = img[k].ctypes.data
-    pl.sample_fmt = _NP_FMT[img.dtype]
+    pl = _in_planes(img, (c, h, w), fmt, False)
     pl.on_device = 0
     out = ctypes.POINTER(ctypes.c_uint8)()
     n = ctypes.c_size_t()
@@ -920,6 +973,37 @@ def dcshift_mct_fwd(planes, shifts, mct, irreversible):
     _check(lib().grkgpu_dcshift_mct_fwd(ptrs, c, w, h, w, sh, mct, 1 if irreversible else 0,
                                         _stream_handle(planes.device)))
     return planes
+
+
+def dcshift_mct_fwd_from(src, fmt, byte_offset, dst, w, h, shifts, mct, irreversible, src_stride=None):
+    """grkgpu_dcshift_mct_fwd_from.  src: a flat uint8 cuda tensor holding the
+    samples from byte `byte_offset` on (any byte), in format fmt (a SAMPLE_*
+    width | SAMPLE_INTERLEAVED | SAMPLE_BIG_ENDIAN), rows src_stride samples
+    apart (default: tight); planar: plane k from sample k * h * src_stride.
+    dst: (c, h, dst_stride) int32 cuda tensor (or a view of rows of one: its
+    planes' rows dst_stride apart) whose rows receive the w results first.
+    Returns dst."""
+    c = dst.shape[0]
+    il = bool(fmt & SAMPLE_INTERLEAVED)
+    sb = 4 if fmt & 0xFF == SAMPLE_I32 else (1 if fmt & 0xFF in (SAMPLE_U8, SAMPLE_I8) else 2)
+    row = w * c if il else w
+    stride = row if src_stride is None else src_stride
+    dstride = dst.shape[2]
+    need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
+    if (src.dtype != _torch_dtype(np.uint8) or src.dim() != 1 or not src.is_contiguous() or not src.is_cuda
+            or dst.dtype != _torch_dtype(np.int32) or dst.dim() != 3 or tuple(dst.stride()[1:]) != (dstride, 1)
+            or dst.device != src.device or dst.shape[1] != h or w > dstride or stride < row or byte_offset < 0
+            or src.numel() < byte_offset + need * sb):
+        raise GrkGpuError("dcshift_mct_fwd_from: src flat uint8 holding %d samples from byte_offset, dst (c,h,"
+                          "stride >= w) int32 on src's device" % need)
+    pl = Planes(sample_fmt=fmt, on_device=1)
+    for k in range(1 if il else c):
+        pl.planes[k] = src.data_ptr() + byte_offset + k * h * stride * sb
+    ptrs = (ctypes.c_void_p * c)(*[dst[k].data_ptr() for k in range(c)])
+    sh = (ctypes.c_int32 * c)(*shifts)
+    _check(lib().grkgpu_dcshift_mct_fwd_from(ctypes.byref(pl), c, w, h, stride, sh, mct, 1 if irreversible else 0,
+                                             ptrs, dstride, _stream_handle(src.device)))
+    return dst
 
 
 def mct_inv_dcshift(planes, prec, sgnd, mct, irreversible):

@@ -639,6 +639,7 @@ struct DwtPlan {
     bool fused0 = false;  // forward level 0 reads the image planes (DC shift + MCT fused, dwt.hip)
     bool mct3 = false;    // ... and its jobs are MCT component triples (tile-major, component-minor)
     int32_t fmt = SMP_I32;  // ... reading image samples of this format
+    bool pixels = false;    // ... from interleaved pixels (MCT triples)
     bool inverse = false;
     std::vector<uint32_t> f01;  // per level: workgroups per job if levels l, l+1 run fused (k_dwt_fwd01), else 0
     std::vector<uint8_t> f01ny; // ... and its level-0 row windows per workgroup (k_dwt_fwd01)
@@ -1016,7 +1017,9 @@ static hipError_t dwt_run_levels(const DwtPlan &P, DwtJob *djobs, int irrev, boo
         uint32_t maxt = 0;
         for (auto &j : l) maxt = std::max<uint32_t>(maxt, (uint32_t)j.ntiles);
         const bool f0 = li == 0 && P.fused0 && !inverse;
-        const int code = P.th[li] | (f0 ? (P.mct3 ? DWT_FUSED_MCT3 : DWT_FUSED) | (P.fmt << DWT_FMT_SHIFT) : 0);
+        const int code = P.th[li] | (f0 ? (P.mct3 ? DWT_FUSED_MCT3 : DWT_FUSED) | (P.fmt << DWT_FMT_SHIFT) |
+                                       (P.mct3 && P.pixels ? DWT_FUSED_PIXELS : 0)
+                                 : 0);
         snprintf(name, sizeof(name), "%s<%s,%d>", inverse ? "k_dwt_inv" : f0 && P.mct3 ? "k_dwt_fwd_mct3" : "k_dwt_fwd", wl,
                  P.th[li] & 0xff);
         if ((e = log_begin(log, s, name, (uint32_t)li, 1, level_bytes(l), li > 0))) return e;
@@ -1126,13 +1129,28 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
     CodingParams cp;
     int rc = setup_params(img, p, cp);
     if (rc) return rc;
+    // sample_fmt = width | flags (GRKGPU_SAMPLE_INTERLEAVED / _BIG_ENDIAN), all
+    // checked before the context or a device is touched
+    const int32_t fflags = fmt & ~0xff;
+    fmt &= 0xff;
+    if (fflags & ~(SMP_INTERLEAVED | SMP_BIG_ENDIAN)) return set_err(GRKGPU_EINVAL, "unknown sample format flags");
     if (fmt < SMP_I32 || fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if ((fflags & SMP_BIG_ENDIAN) && fmt != SMP_U16 && fmt != SMP_I16)
+        return set_err(GRKGPU_EINVAL, "big-endian samples are 16-bit (U16 / I16)");
     for (uint32_t k = 0; fmt != SMP_I32 && k < img->numcomps; ++k) {
         const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
         if ((img->sgnd[k] != 0) != sg || img->prec[k] > 8 * sample_bytes(fmt))
             return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
     }
     const uint32_t sb = sample_bytes(fmt);  // bytes per input sample
+    for (uint32_t k = 1; (fflags & SMP_INTERLEAVED) && k < cp.numcomps; ++k)
+        if (cp.dx[k] != cp.dx[0] || cp.dy[k] != cp.dy[0])
+            return set_err(GRKGPU_EUNSUPPORTED, "interleaved samples need every component on one grid");
+    // pixels in planes[0] (one component's pixels are its plane), and the
+    // format as the loader kernels take it
+    const bool il = (fflags & SMP_INTERLEAVED) && cp.numcomps > 1;
+    const bool big = (fflags & SMP_BIG_ENDIAN) != 0;
+    const int32_t lfmt = fmt | (il ? SMP_INTERLEAVED : 0) | (big ? SMP_BIG_ENDIAN : 0);
     {
         const uint32_t nt = cp.tw * cp.th;
         if (te > nt) te = nt;
@@ -1282,7 +1300,11 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
     // by the first kernel that reads them)
     SrcPlanes src{};
     if (planes_on_device) {
-        for (uint32_t k = 0; k < nc; ++k) src.p[k] = planes[k];
+        for (uint32_t k = 0; k < (il ? 1u : nc); ++k) src.p[k] = planes[k];
+    } else if (il) {  // one copy of the pixels held: rows * columns * components samples
+        HIPCHK(c->img.ensure(poff[nc] * sb + 256));
+        src.p[0] = c->img.as<uint8_t>();
+        HIPCHK(hipMemcpyAsync((void *)src.p[0], planes[0], poff[nc] * sb, hipMemcpyHostToDevice, s));
     } else {
         HIPCHK(c->img.ensure(poff[nc] * sb + 256));
         for (uint32_t k = 0; k < nc; ++k) {
@@ -1291,7 +1313,11 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
                                   s));
         }
     }
-    auto src_at = [&](uint32_t k, uint64_t off) { return (const void *)((const uint8_t *)src.p[k] + off * sb); };
+    // sample `off` (an element offset in the component's plane: a pixel offset) of component k
+    auto src_at = [&](uint32_t k, uint64_t off) {
+        return il ? (const void *)((const uint8_t *)src.p[0] + (off * nc + k) * sb)
+                  : (const void *)((const uint8_t *)src.p[k] + off * sb);
+    };
     HIPCHK(hipEventRecord(c->ev[1], s));
     ShiftArr sh{};
     for (uint32_t k = 0; k < nc; ++k) sh.v[k] = cp.shift[k];
@@ -1313,6 +1339,10 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
         }
     if ((cp.mct && nc != 3) || cp.mct == 2) fuse = false;  // MCT over more than 3 components, custom MCT: separate pass
     if (fmt == SMP_I8 || fmt == SMP_I16) fuse = false;  // the fused loads read int32, u16 or u8 samples
+    if (big) fuse = false;                               // ... in host byte order
+    // ... and interleaved pixels only as an MCT triple (k_dwt_fwd_mct3); the
+    // single-component fused loads stay planar: other pixels take the separate pass
+    if (il && !(cp.mct == 1 && nc == 3 && (uintptr_t)src.p[0] % sb == 0)) fuse = false;
     DwtPlan dplan;
     dplan.fused0 = fuse;
     dplan.mct3 = fuse && cp.mct == 1 && nc == 3;
@@ -1331,16 +1361,18 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
                 j.src[i] = src_at(pk, org);
                 j.shift[i] = cp.shift[pk];
             }
-            j.src_stride = pw;
-            j.src_bytes = (uint32_t)std::min<uint64_t>((plane - org) * sb, 0xffffffffu);
+            j.src_stride = il ? pw * nc : pw;
+            j.src_pitch = il ? (int32_t)nc : 1;
+            j.src_bytes = (uint32_t)std::min<uint64_t>((plane - org) * (il ? nc : 1) * sb, 0xffffffffu);
             j.src_fmt = fmt;
             j.mct_mode = mct3 ? (cp.irrev ? 3 : 2) : 1;
             j.comp = (int32_t)k;
-            bool al = (pw & 1) == 0;
-            for (uint32_t i = 0; i < 3; ++i) al = al && ((uintptr_t)j.src[i] & (2 * sb - 1)) == 0;
+            bool al = (j.src_stride & 1) == 0;
+            for (uint32_t i = 0; i < (il ? 1u : 3u); ++i) al = al && ((uintptr_t)j.src[i] & (2 * sb - 1)) == 0;
             j.src_vec = al ? 1 : 0;
         }
     dplan.fmt = fmt;
+    dplan.pixels = il && fuse;
     HIPCHK(dwt_upload(dplan, c->dwtjobs, c->h_dwtjobs, cp.irrev, s));
     for (auto &tile : tiles) {
         if (fuse) break;
@@ -1353,8 +1385,8 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
                 tsrc.p[0] = src_at(k, plane_org(k, tc));
                 tdst.p[0] = c->work.as<int32_t>() + tc.arena_off;
                 sk.v[0] = sh.v[k];
-                HIPCHK(launch_dcshift_mct_fwd(tsrc, fmt, prect[k].w(), tdst, tc.r.w(), tc.r.h(), 1, sk, 0, cp.irrev,
-                                              s));
+                HIPCHK(launch_dcshift_mct_fwd(tsrc, fmt | (big ? SMP_BIG_ENDIAN : 0), prect[k].w(), tdst, tc.r.w(),
+                                              tc.r.h(), 1, sk, 0, cp.irrev, s));
             }
             continue;
         }
@@ -1367,13 +1399,13 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
             tdst.p[k] = c->work.as<int32_t>() + tile.comps[k].arena_off;
         }
         const Rect &tcr = tile.comps[0].r;
-        const uint32_t spw = prect[0].w();
+        const uint32_t spw = prect[0].w() * (il ? nc : 1);  // interleaved: tsrc.p[0] = the tile's first pixel
         if (cp.mct == 2) {
             MctMatrix mm{};
             memcpy(mm.c, cp.mct_coding, sizeof(int32_t) * nc * nc);
-            HIPCHK(launch_dcshift_mct_custom(tsrc, fmt, spw, tdst, tcr.w(), tcr.h(), nc, sh, mm, s));
+            HIPCHK(launch_dcshift_mct_custom(tsrc, lfmt, spw, tdst, tcr.w(), tcr.h(), nc, sh, mm, s));
         } else {
-            HIPCHK(launch_dcshift_mct_fwd(tsrc, fmt, spw, tdst, tcr.w(), tcr.h(), nc, sh, cp.mct, cp.irrev, s));
+            HIPCHK(launch_dcshift_mct_fwd(tsrc, lfmt, spw, tdst, tcr.w(), tcr.h(), nc, sh, cp.mct, cp.irrev, s));
         }
     }
     HIPCHK(hipEventRecord(c->ev[2], s));
@@ -1927,9 +1959,24 @@ extern "C" int grkgpu_compress_ex(grkgpu_ctx *c, const grkgpu_image_desc *img, c
 extern "C" int grkgpu_encode_blocks(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkgpu_cparams *p,
                                     const int32_t *const *planes, int planes_on_device, int with_distortion,
                                     const grkgpu_block_info **blocks, uint32_t *nblocks) {
-    if (!blocks || !nblocks) return set_err(GRKGPU_EINVAL, "null argument");
-    int rc = compress_impl(c, img, p, (const void *const *)planes, planes_on_device, SMP_I32, nullptr, nullptr, 0,
-                           0xffffffffu, GRKGPU_PART_ALL, true, with_distortion);
+    if (!planes || !img) return set_err(GRKGPU_EINVAL, "null argument");
+    grkgpu_planes pl;
+    memset(&pl, 0, sizeof(pl));
+    for (uint32_t k = 0; k < img->numcomps && k < GRKGPU_MAX_COMPS; ++k) pl.planes[k] = planes[k];
+    pl.sample_fmt = GRKGPU_SAMPLE_I32;
+    pl.on_device = planes_on_device;
+    return grkgpu_encode_blocks_ex(c, img, p, &pl, with_distortion, blocks, nblocks);
+}
+
+extern "C" int grkgpu_encode_blocks_ex(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkgpu_cparams *p,
+                                       const grkgpu_planes *in, int with_distortion,
+                                       const grkgpu_block_info **blocks, uint32_t *nblocks) {
+    if (!in || !blocks || !nblocks) return set_err(GRKGPU_EINVAL, "null argument");
+    if (in->nrows == 0 && in->row0) return set_err(GRKGPU_EINVAL, "row0 without nrows");
+    if (in->ncols == 0 && in->col0) return set_err(GRKGPU_EINVAL, "col0 without ncols");
+    int rc = compress_impl(c, img, p, in->planes, in->on_device, (int32_t)in->sample_fmt, nullptr, nullptr, 0,
+                           0xffffffffu, GRKGPU_PART_ALL, true, with_distortion, in->row0, in->nrows, in->col0,
+                           in->ncols);
     if (rc) return rc;
     *blocks = c->bexp.data();
     *nblocks = (uint32_t)c->bexp.size();
@@ -3016,6 +3063,36 @@ extern "C" int grkgpu_dcshift_mct_fwd(int32_t *const *planes, uint32_t numcomps,
     ShiftArr sh{};
     for (uint32_t k = 0; k < numcomps; ++k) { p.p[k] = planes[k]; ps.p[k] = planes[k]; sh.v[k] = shift[k]; }
     HIPCHK(launch_dcshift_mct_fwd(ps, SMP_I32, stride, p, w, h, numcomps, sh, mct, irreversible, (hipStream_t)stream));
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_dcshift_mct_fwd_from(const grkgpu_planes *src, uint32_t numcomps, uint32_t w, uint32_t h,
+                                           uint32_t src_stride, const int32_t *shift, int32_t mct,
+                                           int32_t irreversible, int32_t *const *dst, uint32_t dst_stride,
+                                           void *stream) {
+    if (!src || !shift || !dst || numcomps < 1 || numcomps > 16) return set_err(GRKGPU_EINVAL, "bad arguments");
+    const int32_t fmt = (int32_t)(src->sample_fmt & 0xffu), flags = (int32_t)(src->sample_fmt & ~0xffu);
+    if (flags & ~(SMP_INTERLEAVED | SMP_BIG_ENDIAN)) return set_err(GRKGPU_EINVAL, "unknown sample format flags");
+    if (fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if ((flags & SMP_BIG_ENDIAN) && fmt != SMP_U16 && fmt != SMP_I16)
+        return set_err(GRKGPU_EINVAL, "big-endian samples are 16-bit (U16 / I16)");
+    const bool il = (flags & SMP_INTERLEAVED) != 0;
+    if ((uint64_t)src_stride < (uint64_t)w * (il ? numcomps : 1) || dst_stride < w)
+        return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
+    SrcPlanes ps{};
+    PlanePtrs p{};
+    ShiftArr sh{};
+    for (uint32_t k = 0; k < numcomps; ++k) {
+        if (!dst[k] || (uintptr_t)dst[k] % 4 || (!(il && k) && !src->planes[k]))
+            return set_err(GRKGPU_EINVAL, "null or misaligned plane");
+        p.p[k] = dst[k];
+        ps.p[k] = il ? src->planes[0] : src->planes[k];
+        sh.v[k] = shift[k];
+    }
+    int rc = check_device(-1);
+    if (rc) return rc;
+    HIPCHK(launch_dcshift_mct_fwd_from(ps, fmt | flags, src_stride, p, dst_stride, w, h, numcomps, sh, mct,
+                                       irreversible, (hipStream_t)stream));
     return GRKGPU_OK;
 }
 

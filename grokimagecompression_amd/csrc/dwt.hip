@@ -223,6 +223,13 @@ template <> struct Smp<int32_t> {
         a = (int32_t)p[0]; b = (int32_t)p[1];
     }
     static __device__ __forceinline__ int32_t one(rsrc_t r, int vo, int so) { return ld32(r, vo, so); }
+    // two adjacent 3-component pixels (6 samples in a row): two 12-byte loads
+    static __device__ __forceinline__ void six(rsrc_t r, int vo, int so, int32_t (&o)[6]) {
+        const auto p = __builtin_amdgcn_raw_buffer_load_b96(r, vo, so, 0);
+        const auto q = __builtin_amdgcn_raw_buffer_load_b96(r, vo + 12, so, 0);
+        o[0] = (int32_t)p[0]; o[1] = (int32_t)p[1]; o[2] = (int32_t)p[2];
+        o[3] = (int32_t)q[0]; o[4] = (int32_t)q[1]; o[5] = (int32_t)q[2];
+    }
 };
 template <> struct Smp<uint16_t> {
     static constexpr int B = 2;
@@ -233,6 +240,12 @@ template <> struct Smp<uint16_t> {
     static __device__ __forceinline__ int32_t one(rsrc_t r, int vo, int so) {
         return (int32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(r, vo, so, 0);
     }
+    // two adjacent 3-component pixels: one 12-byte load
+    static __device__ __forceinline__ void six(rsrc_t r, int vo, int so, int32_t (&o)[6]) {
+        const auto p = __builtin_amdgcn_raw_buffer_load_b96(r, vo, so, 0);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { o[2 * i] = (int32_t)(p[i] & 0xffffu); o[2 * i + 1] = (int32_t)(p[i] >> 16); }
+    }
 };
 template <> struct Smp<uint8_t> {
     static constexpr int B = 1;
@@ -242,6 +255,11 @@ template <> struct Smp<uint8_t> {
     }
     static __device__ __forceinline__ int32_t one(rsrc_t r, int vo, int so) {
         return (int32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(r, vo, so, 0);
+    }
+    // two adjacent 3-component pixels: 6 bytes, 2-byte aligned -- three 2-byte loads
+    static __device__ __forceinline__ void six(rsrc_t r, int vo, int so, int32_t (&o)[6]) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) pair(r, vo + 2 * i, so, o[2 * i], o[2 * i + 1]);
     }
 };
 
@@ -411,7 +429,13 @@ __global__ __launch_bounds__(64 * DWT_WAVES) void k_dwt_fwd(const DwtJob *__rest
 // the three image planes are read once (8-byte loads), the DC shift + RCT /
 // ICT forms all three components in registers, and each component
 // is lifted and stored in turn.  jobs = component triples (blockIdx.y).
-template <bool IRREV, int TH, typename S = int32_t>
+// IL: the planes are one buffer of interleaved pixels (r g b r g b ...; J0.src[i]
+// = component i of the first pixel, J0.src_pitch = 3).  A lane's two pixels are
+// 6 samples in a row, read through src[0]'s descriptor with as few loads as
+// their alignment allows (Smp<S>::six: uint16 one 12-byte load, int32 two,
+// uint8 three 2-byte loads -- the planar twin issues three pair loads);
+// mirrored borders load per sample at the pixel pitch.
+template <bool IRREV, int TH, typename S = int32_t, bool IL = false>
 __global__ __launch_bounds__(64 * DWT_WAVES) void k_dwt_fwd_mct3(const DwtJob *__restrict__ jobs, int lay) {
     using G = DwtGeo<IRREV, TH>;
     constexpr int R = G::R;
@@ -433,20 +457,29 @@ __global__ __launch_bounds__(64 * DWT_WAVES) void k_dwt_fwd_mct3(const DwtJob *_
     {
         constexpr int B = Smp<S>::B;
         const int st = (int)J0.src_stride * B;
-        const rsrc_t p0 = mkbuf(J0.src[0], J0.src_bytes), p1 = mkbuf(J0.src[1], J0.src_bytes),
-                     p2 = mkbuf(J0.src[2], J0.src_bytes);
+        // src_bytes: to the end of the shortest plane; IL: from src[0] to the end of the pixels
+        const rsrc_t p0 = mkbuf(J0.src[0], J0.src_bytes), p1 = mkbuf(J0.src[1], J0.src_bytes - (IL ? B : 0)),
+                     p2 = mkbuf(J0.src[2], J0.src_bytes - (IL ? 2 * B : 0));
         const bool vec = J0.src_vec && casx == 0 && xw >= 0 && xw + DWT_WIN <= rw;  // wave-uniform
         const bool rows_in = yw >= 0 && yw + R <= rh;
         if (vec) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int so = (rows_in ? yw + r : mirror_idx(yw + r, rh)) * st;
-                Smp<S>::pair(p0, gx0 * B, so, a0[r], a1[r]);
-                Smp<S>::pair(p1, gx0 * B, so, b0[r], b1[r]);
-                Smp<S>::pair(p2, gx0 * B, so, c0[r], c1[r]);
+                if constexpr (IL) {
+                    int32_t px[6];  // r0 g0 b0 r1 g1 b1
+                    Smp<S>::six(p0, gx0 * 3 * B, so, px);
+                    a0[r] = px[0]; b0[r] = px[1]; c0[r] = px[2];
+                    a1[r] = px[3]; b1[r] = px[4]; c1[r] = px[5];
+                } else {
+                    Smp<S>::pair(p0, gx0 * B, so, a0[r], a1[r]);
+                    Smp<S>::pair(p1, gx0 * B, so, b0[r], b1[r]);
+                    Smp<S>::pair(p2, gx0 * B, so, c0[r], c1[r]);
+                }
             }
         } else {
-            const int o0 = mirror_idx(gx0, rw) * B, o1 = mirror_idx(gx1, rw) * B;
+            constexpr int PB = IL ? 3 * B : B;  // bytes between adjacent columns
+            const int o0 = mirror_idx(gx0, rw) * PB, o1 = mirror_idx(gx1, rw) * PB;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int so = mirror_idx(yw + r, rh) * st;
@@ -1338,14 +1371,24 @@ constexpr int kDwtLay = 1;
 
 template <int TH>
 static void launch_th(const DwtJob *jobs, dim3 grid, dim3 block, int irrev, int inverse, int fused, int fmt,
-                      hipStream_t s) {
+                      bool pixels, hipStream_t s) {
     const int lay = kDwtLay;
     if (fused == 3) {  // forward level 0, MCT triples: one wavefront = the 3 components of one window
         const dim3 g3(grid.x, grid.y / 3);
 #define GRK_M3(S)                                                                         \
     if (irrev) hipLaunchKernelGGL((k_dwt_fwd_mct3<true, TH, S>), g3, block, 0, s, jobs, lay); \
     else hipLaunchKernelGGL((k_dwt_fwd_mct3<false, TH, S>), g3, block, 0, s, jobs, lay)
+#define GRK_M3P(S)                                                                                   \
+    if (irrev) hipLaunchKernelGGL((k_dwt_fwd_mct3<true, TH, S, true>), g3, block, 0, s, jobs, lay); \
+    else hipLaunchKernelGGL((k_dwt_fwd_mct3<false, TH, S, true>), g3, block, 0, s, jobs, lay)
+        if constexpr (TH == 8) {  // the only window height an MCT-triple level 0 is planned at
+            if (pixels) {
+                if (fmt == SMP_U16) { GRK_M3P(uint16_t); } else if (fmt == SMP_U8) { GRK_M3P(uint8_t); } else { GRK_M3P(int32_t); }
+                return;
+            }
+        }
         if (fmt == SMP_U16) { GRK_M3(uint16_t); } else if (fmt == SMP_U8) { GRK_M3(uint8_t); } else { GRK_M3(int32_t); }
+#undef GRK_M3P
 #undef GRK_M3
         return;
     }
@@ -1392,11 +1435,13 @@ hipError_t launch_dwt_jobs(const DwtJob *jobs_dev, uint32_t njobs, uint32_t max_
     dim3 grid((max_tiles + DWT_WAVES - 1) / DWT_WAVES, njobs), block(64 * DWT_WAVES);
     const int fused = inverse ? 0 : (code & DWT_FUSED_MCT3) ? 3 : (code & DWT_FUSED) ? 1 : 0;
     const int fmt = (code >> DWT_FMT_SHIFT) & 7;  // image sample format of a fused level 0
+    const bool pixels = fused == 3 && (code & DWT_FUSED_PIXELS);  // ... read from interleaved pixels
+    if (pixels && (code & 0xff) != 8) return hipErrorInvalidValue;
     switch (code & 0xff) {
-        case 8: launch_th<8>(jobs_dev, grid, block, irrev, inverse, fused, fmt, s); break;
-        case 16: launch_th<16>(jobs_dev, grid, block, irrev, inverse, fused, fmt, s); break;
-        case 24: launch_th<24>(jobs_dev, grid, block, irrev, inverse, fused, fmt, s); break;
-        case 32: launch_th<32>(jobs_dev, grid, block, irrev, inverse, fused, fmt, s); break;
+        case 8: launch_th<8>(jobs_dev, grid, block, irrev, inverse, fused, fmt, pixels, s); break;
+        case 16: launch_th<16>(jobs_dev, grid, block, irrev, inverse, fused, fmt, pixels, s); break;
+        case 24: launch_th<24>(jobs_dev, grid, block, irrev, inverse, fused, fmt, pixels, s); break;
+        case 32: launch_th<32>(jobs_dev, grid, block, irrev, inverse, fused, fmt, pixels, s); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

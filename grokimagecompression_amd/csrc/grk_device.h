@@ -17,7 +17,13 @@ struct PlanePtrs { int32_t *p[GRK_MAX_COMPS]; };
 // DWT level 0) -- an 8K 12-bit frame crosses PCIe as 2 B/sample.
 struct SrcPlanes { const void *p[GRK_MAX_COMPS]; };
 enum SampleFmt : int32_t { SMP_I32 = 0, SMP_U8 = 1, SMP_I8 = 2, SMP_U16 = 3, SMP_I16 = 4 };
-constexpr uint32_t sample_bytes(int32_t fmt) { return fmt == SMP_I32 ? 4u : (fmt <= SMP_I8 ? 1u : 2u); }
+// flags on a source format (GRKGPU_SAMPLE_INTERLEAVED / _BIG_ENDIAN): pixels
+// in p[0], sample (y, x, c) at p[0][y * stride + x * ncomp + c]; 16-bit
+// samples stored most-significant byte first
+constexpr int32_t SMP_INTERLEAVED = 0x100, SMP_BIG_ENDIAN = 0x200;
+constexpr uint32_t sample_bytes(int32_t fmt) {
+    return (fmt & 0xff) == SMP_I32 ? 4u : ((fmt & 0xff) <= SMP_I8 ? 1u : 2u);
+}
 struct ShiftArr { int32_t v[GRK_MAX_COMPS]; };
 
 // One code-block to encode (T1Part1::preEncode + t1_encode_cblk inputs,
@@ -59,6 +65,15 @@ struct GatherItem { uint64_t src, dst; uint32_t len, pad; };  // pad: 0 = header
 hipError_t launch_dcshift_mct_fwd(const SrcPlanes &src, int32_t fmt, uint32_t sstride, const PlanePtrs &dst,
                                   uint32_t tw, uint32_t th, uint32_t ncomp, const ShiftArr &shift, int32_t mct,
                                   int32_t irrev, hipStream_t s);
+// The same pass from a source format with flags (fmt = SampleFmt |
+// SMP_INTERLEAVED | SMP_BIG_ENDIAN; launch_dcshift_mct_fwd forwards a flagged
+// format here): src rows sstride samples apart starting at any byte, dst rows
+// dstride apart.  Interleaved 3 / 4 components: k_dcshift_mct_fwd_pixels (runs
+// of 4 pixels: wide loads, one dwordx4 store per component); else one thread
+// per sample position.
+hipError_t launch_dcshift_mct_fwd_from(const SrcPlanes &src, int32_t fmt, uint32_t sstride, const PlanePtrs &dst,
+                                       uint32_t dstride, uint32_t tw, uint32_t th, uint32_t ncomp,
+                                       const ShiftArr &shift, int32_t mct, int32_t irrev, hipStream_t s);
 // src rows at sstride elements (a window of a tile buffer), dst rows at dstride;
 // irrev: bit k set = component k holds 9/7 (float) samples; MCT follows
 // component 0's wavelet
@@ -100,8 +115,12 @@ struct DwtJob {
     const void *src[3];         // image planes at the tile origin
     uint32_t src_stride, src_bytes;  // elements; bytes from src[i] to its plane's end (min)
     int32_t shift[3];
-    int32_t mct_mode, comp, src_vec;  // src_vec: pair loads allowed (base aligned to 2 samples, even stride)
-    int32_t src_fmt, pad_;
+    // Interleaved pixels (k_dwt_fwd_mct3 only): src[i] = component i of the
+    // tile's first pixel, adjacent columns src_pitch (= 3) samples apart,
+    // src_stride the row of pixels in samples.
+    int32_t mct_mode, comp, src_vec;  // src_vec: pair loads allowed (base aligned to 2 samples, even stride;
+                                      // interleaved: src[0] and the row pitch aligned to 2 samples)
+    int32_t src_fmt, src_pitch;       // src_pitch: samples between adjacent columns (planar: 1)
     // the windows a launch runs for this job: columns [win_x0, win_x0 +
     // tiles_x), rows [win_y0, win_y0 + win_ny) of the level's window grid
     // (dwt_job_tiles; all of them unless reg_* restricts the output region:
@@ -141,6 +160,7 @@ int dwt_pick_th(int irrev, uint64_t level_samples, int minw, int minh);
 constexpr int DWT_FUSED = 1 << 16;       // geometry-code flag: forward level with fused DC shift loads
 constexpr int DWT_FUSED_MCT3 = 1 << 17;  // ... with fused DC shift + MCT (jobs in component triples)
 constexpr int DWT_FMT_SHIFT = 18;        // bits 18-20: SampleFmt of the fused level's image planes (I32 / U8 / U16)
+constexpr int DWT_FUSED_PIXELS = 1 << 21;  // ... read from interleaved pixels (MCT triples only)
 // the window grid of a job at `th` window rows: tiles_x, ntiles (whole
 // workgroups) and win_* (restricted to reg_* when set)
 void dwt_job_tiles(int irrev, int th, DwtJob &j);

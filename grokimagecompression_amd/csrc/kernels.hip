@@ -37,6 +37,19 @@ __device__ __forceinline__ void put(int32_t *p, int32_t v) {
     else *p = v;
 }
 
+// one sample of type S at byte address p (any alignment); BE: stored
+// most-significant byte first
+template <typename S, bool BE>
+__device__ __forceinline__ int32_t ld_sample(const uint8_t *p) {
+    S v;
+    __builtin_memcpy(&v, p, sizeof(S));
+    if constexpr (BE) {
+        static_assert(sizeof(S) == 2, "big-endian: 16-bit samples");
+        v = (S)__builtin_bswap16((uint16_t)v);
+    }
+    return (int32_t)v;
+}
+
 // src: image planes of samples S (row stride sstride), dst: tile-component
 // buffers (row stride tw).  One thread per sample of the tile.
 template <bool NT, typename S>
@@ -73,16 +86,28 @@ __global__ void k_dcshift_mct_fwd(SrcPlanes src, uint32_t sstride, PlanePtrs dst
 // then mct::encode_custom (mct.cpp:429-475) -- (x - shift) << 11, then per
 // output component j the int32 sum over k of int_fix_mul(C[j][k], x_k), C the
 // encoding matrix in 13-bit fixed point, in the reference's order.
-template <typename S>
+// M: 0 = planar samples in host byte order; bit 0 = big-endian, bit 1 =
+// interleaved (k_dcshift_mct_fwd_from's loads, any byte alignment).
+template <typename S, int M = 0>
 __global__ void k_dcshift_mct_custom(SrcPlanes src, uint32_t sstride, PlanePtrs dst, uint32_t tw, uint32_t th,
                                      uint32_t ncomp, ShiftArr shift, MctMatrix m) {
     uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t y = blockIdx.y;
     if (x >= tw || y >= th) return;
     size_t si = (size_t)y * sstride + x, di = (size_t)y * tw + x;
+    auto smp = [&](uint32_t c) {
+        if constexpr (M == 0) {
+            return (int32_t)((const S *)src.p[c])[si];
+        } else {
+            const size_t srow = (size_t)y * sstride;
+            const uint8_t *p = (M & 2) ? (const uint8_t *)src.p[0] + (srow + (size_t)x * ncomp + c) * sizeof(S)
+                                       : (const uint8_t *)src.p[c] + (srow + x) * sizeof(S);
+            return ld_sample<S, (M & 1) != 0>(p);
+        }
+    };
     int32_t v[GRK_MAX_COMPS];
     for (uint32_t c = 0; c < ncomp; ++c)
-        v[c] = (int32_t)((uint32_t)((int32_t)((const S *)src.p[c])[si] - shift.v[c]) << 11);
+        v[c] = (int32_t)((uint32_t)(smp(c) - shift.v[c]) << 11);
     for (uint32_t j = 0; j < ncomp; ++j) {
         uint32_t acc = 0;
         for (uint32_t k = 0; k < ncomp; ++k)
@@ -339,6 +364,204 @@ __global__ void k_mct_inv_dcshift_pixels_any(PlanePtrs src, uint32_t sstride, ui
         inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
         __builtin_nontemporal_store((T)a[0], d + k);
     }
+}
+
+// ---------------------------------------------------------------------------
+// DC shift + forward MCT from the layouts a producer of frames holds: pixel-
+// interleaved samples (image loaders, video capture, the PPM raster) and
+// big-endian 16-bit samples (the 16-bit PGM / PPM raster) -- the mirror image
+// of the narrowing decode kernels above.  k_dcshift_mct_fwd's arithmetic,
+// statement for statement; only the loads differ.
+// ---------------------------------------------------------------------------
+// the 4 / sizeof(S) samples of one loaded dword, low address first; a
+// big-endian dword's two samples are put right by one v_perm_b32
+template <typename S, bool BE>
+__device__ __forceinline__ void unpack_word(uint32_t w, int32_t *o) {
+    if constexpr (sizeof(S) == 4) {
+        o[0] = (int32_t)w;
+    } else if constexpr (sizeof(S) == 2) {
+        if constexpr (BE) w = __builtin_amdgcn_perm(w, w, 0x02030001u);
+        o[0] = (int32_t)(S)(w & 0xffffu);
+        o[1] = (int32_t)(S)(w >> 16);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = (int32_t)(S)((w >> (8 * i)) & 0xffu);
+    }
+}
+
+// NS samples (a whole number of dwords) of which the first n are read: as
+// dwordx4 where p is 16-byte aligned, dwordx2 where 8-byte aligned, dwords
+// where 4-byte aligned (as far as the run's size divides), single samples
+// otherwise
+template <typename S, int NS, bool BE>
+__device__ __forceinline__ void load_samples(const uint8_t *p, int32_t (&v)[NS], int n) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    constexpr int BYTES = NS * (int)sizeof(S);
+    constexpr int W = 4 / (int)sizeof(S);  // samples per dword
+    static_assert(BYTES % 4 == 0, "a run is a whole number of dwords");
+    const uintptr_t a = (uintptr_t)p;
+    if (BYTES % 16 == 0 && n == NS && !(a & 15)) {
+#pragma unroll
+        for (int g = 0; g < BYTES / 16; ++g) {
+            const u32x4 q = ((const u32x4 *)p)[g];
+            unpack_word<S, BE>(q.x, v + g * 4 * W);
+            unpack_word<S, BE>(q.y, v + g * 4 * W + W);
+            unpack_word<S, BE>(q.z, v + g * 4 * W + 2 * W);
+            unpack_word<S, BE>(q.w, v + g * 4 * W + 3 * W);
+        }
+    } else if (BYTES % 8 == 0 && n == NS && !(a & 7)) {
+#pragma unroll
+        for (int g = 0; g < BYTES / 8; ++g) {
+            const u32x2 q = ((const u32x2 *)p)[g];
+            unpack_word<S, BE>(q.x, v + g * 2 * W);
+            unpack_word<S, BE>(q.y, v + g * 2 * W + W);
+        }
+    } else if (n == NS && !(a & 3)) {
+#pragma unroll
+        for (int j = 0; j < BYTES / 4; ++j) unpack_word<S, BE>(((const uint32_t *)p)[j], v + j * W);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) v[i] = i < n ? ld_sample<S, BE>(p + (size_t)i * sizeof(S)) : 0;
+    }
+}
+
+// the run of thread t of a source row at byte address a whose pixels are pxb
+// bytes (run_of's layout: thread 0 takes the `lead` pixels before the grid,
+// thread t > 0 the run from lead + (t - 1) * N, the last run cut at tw), the
+// grid laid where the runs are best aligned: on a 16-byte boundary if one is
+// within a run's length, else an 8-, else a 4-byte one
+template <int N>
+__device__ __forceinline__ int src_run_of(uintptr_t a, uint32_t pxb, uint32_t t, uint32_t tw, uint32_t &x0) {
+    uint32_t lead = 0;
+    bool found = false;
+#pragma unroll
+    for (uint32_t al = 16; al >= 4; al >>= 1)
+#pragma unroll
+        for (uint32_t l = 0; l < (uint32_t)N; ++l)
+            if (!found && !((a + (uintptr_t)l * pxb) & (al - 1))) { lead = l; found = true; }
+    const uint64_t first = t ? (uint64_t)lead + (uint64_t)(t - 1) * N : 0;
+    const uint64_t end = t ? first + N : lead;
+    x0 = (uint32_t)(first < tw ? first : tw);
+    return (int)((end < tw ? end : tw) - x0);
+}
+
+// n <= N int32 results of one component's row
+template <int N>
+__device__ __forceinline__ void store_run(int32_t *p, const int32_t (&v)[N], int n) {
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    if (n == N && !((uintptr_t)p & 15)) {
+#pragma unroll
+        for (int g = 0; g < N / 4; ++g) {
+            const i32x4 q = {v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
+            __builtin_nontemporal_store(q, (i32x4 *)p + g);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (i < n) put<true>(p + i, v[i]);
+    }
+}
+
+// M: bit 0 = big-endian samples, bit 1 = interleaved (sample (y, x, c) at
+// src.p[0][y * sstride + x * ncomp + c]; else planar, src.p[c][y * sstride +
+// x]).  One thread per sample position, one load per component, any byte
+// alignment; dst rows dstride apart.
+template <typename S, int M>
+__global__ void k_dcshift_mct_fwd_from(SrcPlanes src, uint32_t sstride, PlanePtrs dst, uint32_t dstride, uint32_t tw,
+                                       uint32_t th, uint32_t ncomp, ShiftArr shift, int32_t mct, int32_t irrev) {
+    uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t y = blockIdx.y;
+    if (x >= tw || y >= th) return;
+    const size_t srow = (size_t)y * sstride, di = (size_t)y * dstride + x;
+    auto smp = [&](uint32_t c) {
+        const uint8_t *p = (M & 2) ? (const uint8_t *)src.p[0] + (srow + (size_t)x * ncomp + c) * sizeof(S)
+                                   : (const uint8_t *)src.p[c] + (srow + x) * sizeof(S);
+        return ld_sample<S, (M & 1) != 0>(p);
+    };
+    uint32_t c0 = 0;
+    if (mct && ncomp >= 3) {
+        int32_t r = smp(0) - shift.v[0], g = smp(1) - shift.v[1], b = smp(2) - shift.v[2];
+        int32_t o0, o1, o2;
+        if (!irrev) {
+            o0 = (r + (g * 2) + b) >> 2;
+            o1 = b - g;
+            o2 = r - g;
+        } else {
+            o0 = ict_term(r, 2449) + ict_term(g, 4809) + ict_term(b, 934);
+            o1 = -ict_term(r, 1382) - ict_term(g, 2714) + ict_term(b, 4096);
+            o2 = ict_term(r, 4096) - ict_term(g, 3430) - ict_term(b, 666);
+        }
+        put<true>(&dst.p[0][di], o0); put<true>(&dst.p[1][di], o1); put<true>(&dst.p[2][di], o2);
+        c0 = 3;
+    }
+    for (uint32_t c = c0; c < ncomp; ++c) {
+        int32_t v = smp(c) - shift.v[c];
+        put<true>(&dst.p[c][di], irrev ? (int32_t)((uint32_t)v << 11) : v);
+    }
+}
+
+// Interleaved, NC = 3 or 4 components.  A thread owns a run of PIX_RUN = 4
+// adjacent pixels of one row: it reads the run's 4 * NC contiguous samples
+// with the widest loads their address allows (load_samples), unpacks them,
+// applies the DC shift + RCT / ICT, and stores each component's run to its
+// int32 tile buffer as ONE non-temporal dwordx4, so every store instruction of
+// a wavefront writes whole lines -- two thirds of this pass's bytes are its
+// stores.  (Runs of 16 / sizeof(S) pixels, the narrowing decode kernel's, were
+// measured first: a lane then stores two / four dwordx4 per component, 32 / 64
+// bytes from its neighbour's, each instruction covering half / a quarter of
+// every line it touches -- 0.176 ms for the 8K 12-bit uint16 frame against
+// 0.125 planar and 0.118 with runs of 4)  Runs lie on the best
+// aligned grid of the source row (src_run_of: thread 0 takes the pixels before
+// it, the last run is cut at tw), so any byte offset, column origin and row
+// stride is correct and the aligned interior is fast.
+constexpr int PIX_RUN = 4;
+template <typename S, int NC, bool BE>
+__global__ __launch_bounds__(256) void k_dcshift_mct_fwd_pixels(SrcPlanes src, uint32_t sstride, PlanePtrs dst, uint32_t dstride, uint32_t tw,
+                                         uint32_t th, ShiftArr shift, int32_t mct, int32_t irrev) {
+    constexpr int N = PIX_RUN;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (y >= th) return;
+    const uint8_t *const srow = (const uint8_t *)src.p[0] + (size_t)y * sstride * sizeof(S);
+    uint32_t x0;
+    const int n = src_run_of<N>((uintptr_t)srow, NC * sizeof(S), t, tw, x0);
+    if (n <= 0) return;
+    int32_t px[N * NC];
+    load_samples<S, N * NC, BE>(srow + (size_t)x0 * NC * sizeof(S), px, n * NC);
+    int32_t v[NC][N];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int k = 0; k < NC; ++k) v[k][i] = px[i * NC + k];
+    if (mct) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            int32_t r = v[0][i] - shift.v[0], g = v[1][i] - shift.v[1], b = v[2][i] - shift.v[2];
+            int32_t o0, o1, o2;
+            if (!irrev) {
+                o0 = (r + (g * 2) + b) >> 2;
+                o1 = b - g;
+                o2 = r - g;
+            } else {
+                o0 = ict_term(r, 2449) + ict_term(g, 4809) + ict_term(b, 934);
+                o1 = -ict_term(r, 1382) - ict_term(g, 2714) + ict_term(b, 4096);
+                o2 = ict_term(r, 4096) - ict_term(g, 3430) - ict_term(b, 666);
+            }
+            v[0][i] = o0; v[1][i] = o1; v[2][i] = o2;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        if (mct && k < 3) continue;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            int32_t s = v[k][i] - shift.v[k];
+            v[k][i] = irrev ? (int32_t)((uint32_t)s << 11) : s;
+        }
+    }
+    const size_t di = (size_t)y * dstride + x0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) store_run<N>(dst.p[k] + di, v[k], n);
 }
 
 // ---------------------------------------------------------------------------
@@ -987,9 +1210,21 @@ __global__ void k_gather(const uint8_t *__restrict__ hdr, const uint8_t *__restr
 // ---------------------------------------------------------------------------
 // launchers (host side, used by codec.cpp)
 // ---------------------------------------------------------------------------
+// the load mode of a source format with its flags (kernel template M: bit 0
+// big-endian, bit 1 interleaved; one component's pixels are its plane); -1: a
+// flag the format cannot carry
+static int src_mode(int32_t fmt, uint32_t ncomp) {
+    if (fmt & ~(0xff | SMP_INTERLEAVED | SMP_BIG_ENDIAN)) return -1;
+    const int32_t w = fmt & 0xff;
+    if ((fmt & SMP_BIG_ENDIAN) && w != SMP_U16 && w != SMP_I16) return -1;
+    return ((fmt & SMP_BIG_ENDIAN) ? 1 : 0) | ((fmt & SMP_INTERLEAVED) && ncomp > 1 ? 2 : 0);
+}
+
 hipError_t launch_dcshift_mct_fwd(const SrcPlanes &src, int32_t fmt, uint32_t sstride, const PlanePtrs &dst,
                                   uint32_t tw, uint32_t th, uint32_t ncomp, const ShiftArr &shift, int32_t mct,
                                   int32_t irrev, hipStream_t s) {
+    // interleaved and / or big-endian sources: the loaders for those layouts
+    if (fmt & ~0xff) return launch_dcshift_mct_fwd_from(src, fmt, sstride, dst, tw, tw, th, ncomp, shift, mct, irrev, s);
     dim3 grid((tw + 255) / 256, th);
     // Non-temporal output stores: with plain stores the 8 B/sample this pass
     // writes sit dirty in L2 / MALL and are written back while the first DWT
@@ -1015,17 +1250,76 @@ hipError_t launch_dcshift_mct_custom(const SrcPlanes &src, int32_t fmt, uint32_t
                                      const MctMatrix &m, hipStream_t s) {
     if (ncomp > GRK_MAX_COMPS) return hipErrorInvalidValue;
     dim3 grid((tw + 255) / 256, th);
-#define GRK_DCC(S) hipLaunchKernelGGL((k_dcshift_mct_custom<S>), grid, dim3(256), 0, s, src, sstride, dst, tw, th, ncomp, \
-                                      shift, m)
-    switch (fmt) {
+    const int M = src_mode(fmt, ncomp);
+    if (M < 0) return hipErrorInvalidValue;
+#define GRK_DCM(S, MM) hipLaunchKernelGGL((k_dcshift_mct_custom<S, MM>), grid, dim3(256), 0, s, src, sstride, dst, tw, th, \
+                                          ncomp, shift, m)
+#define GRK_DCC(S) \
+    if (M == 0) GRK_DCM(S, 0); \
+    else GRK_DCM(S, 2)
+#define GRK_DCC16(S) \
+    if (M == 0) GRK_DCM(S, 0); \
+    else if (M == 1) GRK_DCM(S, 1); \
+    else if (M == 2) GRK_DCM(S, 2); \
+    else GRK_DCM(S, 3)
+    switch (fmt & 0xff) {
         case SMP_I32: GRK_DCC(int32_t); break;
         case SMP_U8: GRK_DCC(uint8_t); break;
         case SMP_I8: GRK_DCC(int8_t); break;
-        case SMP_U16: GRK_DCC(uint16_t); break;
-        case SMP_I16: GRK_DCC(int16_t); break;
+        case SMP_U16: GRK_DCC16(uint16_t); break;
+        case SMP_I16: GRK_DCC16(int16_t); break;
         default: return hipErrorInvalidValue;
     }
+#undef GRK_DCC16
 #undef GRK_DCC
+#undef GRK_DCM
+    return hipGetLastError();
+}
+
+template <typename S, bool BE>
+static void launch_fwd_from(const SrcPlanes &src, bool il, uint32_t sstride, const PlanePtrs &dst, uint32_t dstride,
+                            uint32_t tw, uint32_t th, uint32_t ncomp, const ShiftArr &shift, int32_t mct, int32_t irrev,
+                            hipStream_t s) {
+    mct = mct && ncomp >= 3;
+    if (il && (ncomp == 3 || ncomp == 4)) {
+        // threads of a row: the lead run + the runs of N pixels
+        const uint32_t runs = (uint32_t)(((uint64_t)tw + PIX_RUN - 1) / PIX_RUN + 1);
+        const dim3 grid((runs + 255) / 256, th);
+        if (ncomp == 3)
+            hipLaunchKernelGGL((k_dcshift_mct_fwd_pixels<S, 3, BE>), grid, dim3(256), 0, s, src, sstride, dst, dstride, tw,
+                               th, shift, mct, irrev);
+        else
+            hipLaunchKernelGGL((k_dcshift_mct_fwd_pixels<S, 4, BE>), grid, dim3(256), 0, s, src, sstride, dst, dstride, tw,
+                               th, shift, mct, irrev);
+        return;
+    }
+    const dim3 grid((tw + 255) / 256, th);
+    if (il)
+        hipLaunchKernelGGL((k_dcshift_mct_fwd_from<S, 2 | (BE ? 1 : 0)>), grid, dim3(256), 0, s, src, sstride, dst,
+                           dstride, tw, th, ncomp, shift, mct, irrev);
+    else
+        hipLaunchKernelGGL((k_dcshift_mct_fwd_from<S, BE ? 1 : 0>), grid, dim3(256), 0, s, src, sstride, dst, dstride, tw,
+                           th, ncomp, shift, mct, irrev);
+}
+
+hipError_t launch_dcshift_mct_fwd_from(const SrcPlanes &src, int32_t fmt, uint32_t sstride, const PlanePtrs &dst,
+                                       uint32_t dstride, uint32_t tw, uint32_t th, uint32_t ncomp,
+                                       const ShiftArr &shift, int32_t mct, int32_t irrev, hipStream_t s) {
+    if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS) return hipErrorInvalidValue;
+    const int M = src_mode(fmt, ncomp);
+    if (M < 0) return hipErrorInvalidValue;
+    if (!tw || !th) return hipSuccess;
+    const bool il = (M & 2) != 0;
+#define GRK_FROM(S, BE) launch_fwd_from<S, BE>(src, il, sstride, dst, dstride, tw, th, ncomp, shift, mct, irrev, s)
+    switch (fmt & 0xff) {
+        case SMP_I32: GRK_FROM(int32_t, false); break;
+        case SMP_U8: GRK_FROM(uint8_t, false); break;
+        case SMP_I8: GRK_FROM(int8_t, false); break;
+        case SMP_U16: if (M & 1) GRK_FROM(uint16_t, true); else GRK_FROM(uint16_t, false); break;
+        case SMP_I16: if (M & 1) GRK_FROM(int16_t, true); else GRK_FROM(int16_t, false); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_FROM
     return hipGetLastError();
 }
 

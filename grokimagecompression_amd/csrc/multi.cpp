@@ -212,8 +212,11 @@ extern "C" int grkgpu_compress_multi(const grkgpu_device_set *devs, const grkgpu
             const uint32_t q0 = b / tw, q1 = (e - 1) / tw;
             const uint32_t r0 = std::max(img->y0, ty0 + q0 * tdy) - img->y0;
             const uint32_t r1 = std::min(img->y1, ty0 + (q1 + 1) * tdy) - img->y0;
-            const size_t skip = (size_t)r0 * w * smp_bytes(planes->sample_fmt);
-            for (uint32_t c = 0; c < img->numcomps; ++c) pl.planes[c] = (const uint8_t *)planes->planes[c] + skip;
+            // interleaved: rows of w * numcomps samples, all in planes[0]
+            const bool il = (planes->sample_fmt & GRKGPU_SAMPLE_INTERLEAVED) != 0;
+            const size_t skip = (size_t)r0 * w * (il ? img->numcomps : 1) * smp_bytes(planes->sample_fmt & 0xffu);
+            for (uint32_t c = 0; c < (il ? 1u : img->numcomps); ++c)
+                pl.planes[c] = (const uint8_t *)planes->planes[c] + skip;
             pl.row0 = r0;
             pl.nrows = r1 - r0;
         }

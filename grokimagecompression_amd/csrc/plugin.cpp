@@ -64,10 +64,21 @@ void log(const char *msg) {
 
 // ---- input image: binary PGM / PPM, as grk_compress's PNMFormat reads it
 // (PNMFormat.cpp:343-460: precision = bits of maxval, at least 8; 1 byte per
-// sample up to 8 bits, else 2 big-endian bytes) ----
+// sample up to 8 bits, else 2 big-endian bytes).  The raster is kept as it
+// stands in the file -- pixel-interleaved for P6, big-endian at 16 bits -- and
+// goes to the GPU that way (grkgpu_encode_blocks_ex: 1 or 2 bytes per sample
+// across PCIe, unpacked by the kernel that first reads it) ----
 struct Pnm {
     uint32_t w = 0, h = 0, c = 0, prec = 0;
-    std::vector<int32_t> planes;  // (c, h, w)
+    std::vector<uint8_t> raster;  // (h, w, c) samples of 1 byte, or 2 big-endian bytes (prec > 8)
+    uint32_t sample_bytes() const { return prec < 9 ? 1 : 2; }
+    uint32_t sample_fmt() const {
+        return (prec < 9 ? (uint32_t)GRKGPU_SAMPLE_U8 : GRKGPU_SAMPLE_U16 | GRKGPU_SAMPLE_BIG_ENDIAN) |
+               GRKGPU_SAMPLE_INTERLEAVED;
+    }
+    int32_t sample(size_t i) const {  // sample i of the raster
+        return prec < 9 ? raster[i] : (int32_t)((raster[2 * i] << 8) | raster[2 * i + 1]);
+    }
 };
 
 bool pnm_token(FILE *f, uint32_t *v) {
@@ -101,20 +112,8 @@ bool read_pnm(const char *path, Pnm &img) {
     uint32_t prec = 1;
     while (prec < 16 && (maxval >> prec)) ++prec;
     img.prec = prec < 8 ? 8 : prec;
-    const bool one = img.prec < 9;
-    const uint64_t area = (uint64_t)img.w * img.h;
-    img.planes.resize(area * img.c);
-    std::vector<uint8_t> row((size_t)img.w * img.c * (one ? 1 : 2));
-    for (uint32_t y = 0; y < img.h; ++y) {
-        if (fread(row.data(), 1, row.size(), f) != row.size()) return false;
-        for (uint32_t x = 0; x < img.w; ++x)
-            for (uint32_t k = 0; k < img.c; ++k) {
-                const size_t i = (size_t)x * img.c + k;
-                const int32_t v = one ? row[i] : (int32_t)((row[2 * i] << 8) | row[2 * i + 1]);
-                img.planes[(size_t)k * area + (size_t)y * img.w + x] = v;
-            }
-    }
-    return true;
+    img.raster.resize((size_t)img.w * img.h * img.c * img.sample_bytes());
+    return fread(img.raster.data(), 1, img.raster.size(), f) == img.raster.size();
 }
 
 // grk_cparameters -> grkgpu_cparams (the subset that shapes the partition
@@ -377,12 +376,13 @@ int32_t encode_file(grkgpu_ctx *ctx, grkp_cparameters *params, const char *path,
         log("coding options outside the plugin's path");
         return -1;
     }
-    std::vector<const int32_t *> planes(pnm.c);
     const size_t area = (size_t)pnm.w * pnm.h;
-    for (uint32_t k = 0; k < pnm.c; ++k) planes[k] = pnm.planes.data() + k * area;
+    grkgpu_planes pl{};
+    pl.planes[0] = pnm.raster.data();
+    pl.sample_fmt = pnm.sample_fmt();
     const grkgpu_block_info *blocks = nullptr;
     uint32_t nblocks = 0;
-    if (grkgpu_encode_blocks(ctx, &d, &p, planes.data(), 0, needs_distortion(params) ? 1 : 0, &blocks, &nblocks)) {
+    if (grkgpu_encode_blocks_ex(ctx, &d, &p, &pl, needs_distortion(params) ? 1 : 0, &blocks, &nblocks)) {
         log(grkgpu_last_error());
         return -1;
     }
@@ -412,8 +412,9 @@ int32_t encode_file(grkgpu_ctx *ctx, grkp_cparameters *params, const char *path,
                 destroy(img);
                 return -1;
             }
-        } else {
-            memcpy(img->comps[k].data, planes[k], area * 4);
+        } else {  // the host's int32 planes, straight from the raster
+            int32_t *dst = img->comps[k].data;
+            for (size_t i = 0; i < area; ++i) dst[i] = pnm.sample(i * pnm.c + k);
         }
     }
     plugin_encode_user_callback_info info{};

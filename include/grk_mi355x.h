@@ -384,7 +384,24 @@ int grkgpu_compress_tile_rows(grkgpu_ctx *ctx, const grkgpu_image_desc *img, con
  * whole codestream, as grkgpu_compress).  *out points into the context's
  * pinned output buffer, valid until the next call on ctx (as
  * grkgpu_compress_view).  A sample format must hold the component's
- * precision and signedness (U16: unsigned, prec <= 16), else GRKGPU_EINVAL. */
+ * precision and signedness (U16: unsigned, prec <= 16), else GRKGPU_EINVAL.
+ *
+ * sample_fmt = a GRKGPU_SAMPLE_* width in its low byte, or'ed with flags (the
+ * struct keeps its size and offsets; a plain width means what it always has):
+ *   GRKGPU_SAMPLE_INTERLEAVED  planes[0] holds pixels, as image loaders, video
+ *     capture and the PPM raster hold them (PNMFormat.cpp reads "P6" so):
+ *     sample (y, x, c) of the rows and columns held is at
+ *     planes[0][((y - row0) * ncols + (x - col0)) * numcomps + c], rows tight
+ *     (ncols * numcomps samples); planes[1..] are not read.  Every component
+ *     must be on one grid (equal dx, equal dy), else GRKGPU_EUNSUPPORTED --
+ *     grkgpu_decompress_to's rule for interleaved output.
+ *   GRKGPU_SAMPLE_BIG_ENDIAN   16-bit samples stored most-significant byte
+ *     first, as the 16-bit PGM / PPM raster is; with U16 / I16 only, planar or
+ *     interleaved (any other width: GRKGPU_EINVAL).  The swap is one permute
+ *     per dword in the kernel that first reads the samples.
+ * Unknown flag bits: GRKGPU_EINVAL.  All of this is checked before the context
+ * or a device is touched.  The codestream does not depend on the format or
+ * layout the samples arrive in. */
 enum {
     GRKGPU_SAMPLE_I32 = 0, /* int32_t (grk_image) */
     GRKGPU_SAMPLE_U8 = 1,
@@ -392,9 +409,11 @@ enum {
     GRKGPU_SAMPLE_U16 = 3,
     GRKGPU_SAMPLE_I16 = 4
 };
+#define GRKGPU_SAMPLE_INTERLEAVED 0x100u
+#define GRKGPU_SAMPLE_BIG_ENDIAN 0x200u
 typedef struct {
-    const void *planes[GRKGPU_MAX_COMPS];
-    uint32_t sample_fmt;  /* GRKGPU_SAMPLE_* */
+    const void *planes[GRKGPU_MAX_COMPS]; /* planar: one per component; interleaved: planes[0] */
+    uint32_t sample_fmt;  /* GRKGPU_SAMPLE_* | GRKGPU_SAMPLE_INTERLEAVED | GRKGPU_SAMPLE_BIG_ENDIAN */
     int32_t on_device;
     uint32_t row0, nrows; /* rows held (relative to y0); nrows = 0: every row */
     uint32_t col0, ncols; /* columns held (relative to x0), = the row stride; ncols = 0: every column
@@ -429,6 +448,13 @@ typedef struct {
 int grkgpu_encode_blocks(grkgpu_ctx *ctx, const grkgpu_image_desc *img, const grkgpu_cparams *p,
                          const int32_t *const *planes, int planes_on_device, int with_distortion,
                          const grkgpu_block_info **blocks, uint32_t *nblocks);
+/* The same from a grkgpu_planes: the samples at the file's width, planar or
+ * interleaved, host byte order or big-endian (what the plugin hands over: the
+ * PGM / PPM raster as it stands in the file).  Every tile is encoded, so the
+ * planes hold the whole image.  grkgpu_encode_blocks forwards here. */
+int grkgpu_encode_blocks_ex(grkgpu_ctx *ctx, const grkgpu_image_desc *img, const grkgpu_cparams *p,
+                            const grkgpu_planes *planes, int with_distortion, const grkgpu_block_info **blocks,
+                            uint32_t *nblocks);
 
 /* After grkgpu_encode_blocks on ctx (and before any other call on it): the
  * forward DWT output of one tile-component -- the reference's tile buffer
@@ -568,6 +594,18 @@ int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t numcomps, uint
                               uint32_t src_stride, const uint32_t *prec, const int32_t *sgnd, int32_t mct,
                               int32_t irreversible, const grkgpu_out_planes *dst, uint32_t dst_stride,
                               void *stream);
+/* grkgpu_dcshift_mct_fwd out of place, from the sample format and layout of
+ * src (the first kernel of grkgpu_compress_ex on its own; the counterpart of
+ * grkgpu_mct_inv_dcshift_to): src->planes are device pointers (on_device, row0
+ * .. ncols are not read), src->sample_fmt a width with its flags, rows
+ * src_stride samples apart (>= w, interleaved >= w * numcomps), starting at
+ * any byte; dst[c] = int32 planes, rows dst_stride (>= w) apart.  The values
+ * are those grkgpu_dcshift_mct_fwd leaves from the same samples.  A
+ * big-endian flag on a width other than 16 bits, or unknown flag bits:
+ * GRKGPU_EINVAL. */
+int grkgpu_dcshift_mct_fwd_from(const grkgpu_planes *src, uint32_t numcomps, uint32_t w, uint32_t h,
+                                uint32_t src_stride, const int32_t *shift, int32_t mct, int32_t irreversible,
+                                int32_t *const *dst, uint32_t dst_stride, void *stream);
 /* In-place (Mallat layout) forward / inverse DWT of one tile-component with
  * origin (x0,y0), size (x1-x0) x (y1-y0), row stride x1-x0.  scratch must
  * hold grkgpu_dwt_scratch_bytes(...) device bytes.  For 9/7 inverse the buffer

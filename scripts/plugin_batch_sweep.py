@@ -18,7 +18,8 @@ import numpy as np  # noqa: E402
 import synth  # noqa: E402
 
 DRIVER = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
-PLUGIN_DIR = os.path.join(ROOT, "grokimagecompression_amd", "lib")
+# GRKGPU_PLUGIN_DIR: another build of the plugin and its library (A/B runs)
+PLUGIN_DIR = os.environ.get("GRKGPU_PLUGIN_DIR") or os.path.join(ROOT, "grokimagecompression_amd", "lib")
 
 
 def main():
