@@ -325,6 +325,8 @@ def lib():
         L.grkgpu_t1_scratch_bytes_n.restype = ctypes.c_size_t
         L.grkgpu_t1_scratch_bytes_n.argtypes = [U32]
         L.grkgpu_t1_encode_blocks.argtypes = [VP, U32, VP, VP, VP, VP, ctypes.c_int, VP]
+        if hasattr(L, "grkgpu_t1_encode_blocks_sty"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_t1_encode_blocks_sty.argtypes = [VP, U32, VP, VP, VP, VP, ctypes.c_int, U32, VP]
         L.grkgpu_t1_decode_blocks.argtypes = [VP, U32, VP, VP, VP, VP]
         _lib = L
     return _lib

@@ -3223,14 +3223,21 @@ static_assert(sizeof(grkgpu_dec_block) == sizeof(DecBlock), "DecBlock ABI");
 extern "C" int grkgpu_t1_encode_blocks(const grkgpu_enc_block *blocks, uint32_t nblocks, const int32_t *coef,
                                        void *scratch, uint8_t *out, grkgpu_enc_result *results, int with_distortion,
                                        void *stream) {
+    return grkgpu_t1_encode_blocks_sty(blocks, nblocks, coef, scratch, out, results, with_distortion, 0, stream);
+}
+
+extern "C" int grkgpu_t1_encode_blocks_sty(const grkgpu_enc_block *blocks, uint32_t nblocks, const int32_t *coef,
+                                           void *scratch, uint8_t *out, grkgpu_enc_result *results,
+                                           int with_distortion, uint32_t cblk_sty, void *stream) {
     if (!blocks || !coef || !scratch || !out || !results) return set_err(GRKGPU_EINVAL, "null argument");
+    if (cblk_sty & ~0x3Fu) return set_err(GRKGPU_EINVAL, "code-block style outside 0..63");
     int rc = check_device(-1);
     if (rc) return rc;
     // scratch layout: the encoder's rows for nblocks (rounded up to 64) blocks
     // of 32 planes, then 32 fixed symbol slots per block
     uint8_t *sym = (uint8_t *)scratch + t1e_scratch_bytes(nblocks, 32);
     HIPCHK(launch_t1_encode((const EncBlock *)blocks, nblocks, coef, scratch, sym, nullptr, 32, out,
-                            (EncResult *)results, (hipStream_t)stream));
+                            (EncResult *)results, (hipStream_t)stream, cblk_sty));
     if (with_distortion)
         HIPCHK(launch_t1_dist((const EncBlock *)blocks, nblocks, 32, coef, scratch, (EncResult *)results,
                               (hipStream_t)stream));

@@ -686,9 +686,9 @@ template <bool COND>
 __global__ __launch_bounds__(64) void k_t1_model(
     const EncBlock *__restrict__ blocks, uint32_t n, uint32_t maxdepth, uint8_t *__restrict__ scr,
     uint8_t *__restrict__ sym, const uint64_t *__restrict__ sym_off, EncResult *__restrict__ res, uint32_t cblksty) {
-    __shared__ uint8_t s_sc[256];
+    __shared__ __attribute__((aligned(8))) uint32_t s_ctab[512];  // compact_sel {lo, hi} of every presence byte
     __shared__ uint32_t s_ring[32 * 64];  // SymOut: 32 words per lane, word j at (j % 32) * 64 + lane
-    for (uint32_t k = threadIdx.x; k < 256; k += 64) s_sc[k] = sc_lut_entry(k);
+    for (uint32_t k = threadIdx.x; k < 256; k += 64) compact_sel(k, &s_ctab[2 * k], &s_ctab[2 * k + 1]);
     __syncthreads();
     // wavefront = (group, depth): lane = the group's block
     const uint32_t n64 = t1_scratch_records(n), w0 = blockIdx.x * 64;
@@ -713,9 +713,9 @@ __global__ __launch_bounds__(64) void k_t1_model(
     const LRow ref{gr, (d ? dr - T1E_DEPTH_ROWS + T1E_ABOVE : 0) * 512, lo}, negr{gr, T1E_NEG * 512, lo};
     const LRow tmp{gr, (dr + T1E_POST) * 512, lo};
     uint8_t *base = sym + off + (uint64_t)p * slot;
-    t1_model_plane<LRow, LRow, COND>(b.w, b.h, b.orient, bits, above, ref, d > 0, negr, tmp, s_sc, (uint32_t *)base,
+    t1_model_plane<LRow, LRow, COND>(b.w, b.h, b.orient, bits, above, ref, d > 0, negr, tmp, nullptr, (uint32_t *)base,
                    E.cnt + (size_t)i * 128 + p * 4, cblksty, t1_pass_raw(cblksty, (int32_t)p, 0, numbps),
-                   s_ring + threadIdx.x);
+                   s_ring + threadIdx.x, s_ctab);
 }
 
 constexpr uint32_t MQ_CX_STRIDE = 21;  // LDS words per lane for the MQ encoder's context words

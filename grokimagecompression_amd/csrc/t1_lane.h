@@ -476,49 +476,44 @@ struct SymOut {
         }
         done += 16;
     }
-    __device__ void room() {  // a dense stripe: keep <= 26 words unwritten (a put adds <= 2)
-        if ((n >> 2) - done >= 24) run16();
-    }
 #endif
+    // A dense stripe: called before every 4-column group (<= 44 symbols, 11
+    // words and a carry), it leaves < 16 words unwritten, so the group's
+    // stores stay inside the 32-word ring.
+    GRK_HD void room() {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if ((n >> 2) - done >= 16) run16();
+#endif
+    }
     GRK_HD void put(uint32_t b) {
         acc |= b << ((n & 3) * 8);
         ++n;
         if ((n & 3) == 0) {
             store((n >> 2) - 1, acc);
             acc = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
             room();
-#endif
         }
     }
-    // cnt (<= 4) symbols at once, packed in `word` from its low byte up: at
-    // most one store
-    GRK_HD void put_n(uint32_t word, uint32_t cnt) {
-        const uint32_t f = (n & 3) * 8;
-        const uint64_t v = (uint64_t)acc | ((uint64_t)word << f);
+    // cnt (<= 4) symbols at once, packed in `word` from its low byte up (the
+    // bytes above them zero): at most one store
+    GRK_HD void put4(uint32_t word, uint32_t cnt) {
+        const uint32_t k = n & 3, f = k * 8, i = n >> 2;
+        const uint32_t v0 = acc | (word << f), v1 = f ? word >> (32 - f) : 0u;
         n += cnt;
-        if (f + cnt * 8 >= 32) {
-            store((n >> 2) - 1, (uint32_t)v);
-            acc = (uint32_t)(v >> 32);
-#if defined(__HIP_DEVICE_COMPILE__)
-            room();
-#endif
-        } else {
-            acc = (uint32_t)v;
-        }
+        if (k + cnt >= 4) store(i, v0);
+        acc = k + cnt >= 4 ? v1 : v0;
     }
-    // cnt (<= 8) symbols at once: at most two stores
-    GRK_HD void put_n64(uint64_t word, uint32_t cnt) {
-        const uint32_t f = (n & 3) * 8, tot = (n & 3) + cnt, i = n >> 2;
-        const uint64_t lo = (uint64_t)acc | (word << f);
-        const uint32_t hi = f ? (uint32_t)(word >> (64 - f)) : 0u;
+    // cnt (<= 8) symbols at once, {whi, wlo} packed the same way: at most two
+    // stores.  All shifts are 32-bit (a variable 64-bit shift costs 1.5x).
+    GRK_HD void put8(uint32_t wlo, uint32_t whi, uint32_t cnt) {
+        const uint32_t k = n & 3, f = k * 8, tot = k + cnt, i = n >> 2;
+        const uint32_t v0 = acc | (wlo << f);
+        const uint32_t v1 = f ? alignbit32(whi, wlo, 32 - f) : whi;
+        const uint32_t v2 = f ? whi >> (32 - f) : 0u;
         n += cnt;
-        if (tot >= 4) store(i, (uint32_t)lo);
-        if (tot >= 8) store(i + 1, (uint32_t)(lo >> 32));
-        acc = tot >= 8 ? hi : tot >= 4 ? (uint32_t)(lo >> 32) : (uint32_t)lo;
-#if defined(__HIP_DEVICE_COMPILE__)
-        if (tot >= 4) room();
-#endif
+        if (tot >= 4) store(i, v0);
+        if (tot >= 8) store(i + 1, v1);
+        acc = tot >= 8 ? v2 : tot >= 4 ? v1 : v0;
     }
     // the lanes of the wavefront write their complete 64-byte runs together
     GRK_HD void stripe_flush() {
@@ -573,20 +568,179 @@ GRK_HD Ctx4 zc_slices(uint64_t NW, uint64_t N, uint64_t NE, uint64_t W, uint64_t
     return r;
 }
 
-GRK_HD uint32_t ctx_at(const Ctx4 &c, uint32_t x) {
-    return (uint32_t)((c.c0 >> x) & 1) | (uint32_t)((c.c1 >> x) & 1) << 1 | (uint32_t)((c.c2 >> x) & 1) << 2 |
-           (uint32_t)((c.c3 >> x) & 1) << 3;
+// Bit-sliced sign coding (sc_ctx, Table D.3) for 64 samples at once: the W / E
+// / N / S significance (s*) and sign (n*) masks aligned to the sample.  The
+// horizontal and vertical contributions are in {-1, 0, +1}: positive where a
+// neighbour is positive and none negative, and the other way round.  b0..b2
+// are the low bits of the symbol's context number (9..13, bit 3 always set),
+// d its decision: the sign XOR the prediction, or the sign itself in a raw
+// (BYPASS) pass (t1.cpp:221-222).
+struct Sc4 { uint64_t b0, b1, b2, d; };
+
+GRK_HD Sc4 sc_slices(uint64_t sW, uint64_t nW, uint64_t sE, uint64_t nE, uint64_t sN, uint64_t nN, uint64_t sS,
+                     uint64_t nS, uint64_t neg, bool raw) {
+    const uint64_t hp = (sW & ~nW) | (sE & ~nE), hn = (sW & nW) | (sE & nE);
+    const uint64_t vp = (sN & ~nN) | (sS & ~nS), vn = (sN & nN) | (sS & nS);
+    const uint64_t hpos = hp & ~hn, hneg = hn & ~hp, vpos = vp & ~vn, vneg = vn & ~vp;
+    const uint64_t hnz = hpos | hneg, vnz = vpos | vneg;
+    const uint64_t opp = (hpos & vneg) | (hneg & vpos);  // vc == -1 after the flip that makes hc positive
+    Sc4 r;
+    r.b0 = ~(hnz ^ vnz);          // contexts 9, 11, 13
+    r.b1 = (~hnz & vnz) | opp;    // 10, 11
+    r.b2 = hnz & ~opp;            // 12, 13
+    r.d = raw ? neg : neg ^ (hneg | (~hnz & vneg));
+    return r;
 }
 
-// sign symbol for sample x: W/E/N/S significance masks already aligned to x
-GRK_HD uint32_t sc_symbol(const uint8_t *sc, uint64_t sW, uint64_t nW, uint64_t sE, uint64_t nE, uint64_t sN,
-                          uint64_t nN, uint64_t sS, uint64_t nS, uint64_t neg, uint32_t x, bool raw = false) {
-    uint32_t i = (uint32_t)((sW >> x) & 1) | (uint32_t)((nW >> x) & 1) << 1 | (uint32_t)((sE >> x) & 1) << 2 |
-                 (uint32_t)((nE >> x) & 1) << 3 | (uint32_t)((sN >> x) & 1) << 4 | (uint32_t)((nN >> x) & 1) << 5 |
-                 (uint32_t)((sS >> x) & 1) << 6 | (uint32_t)((nS >> x) & 1) << 7;
-    uint32_t si = sc[i];
-    // a raw (BYPASS) pass codes the sign itself, not its XOR with the prediction (t1.cpp:221-222)
-    return (si & 0x7f) | ((((uint32_t)(neg >> x) & 1u) ^ (raw ? 0u : (si >> 7))) << 5);
+// v_perm_b32: byte j of the result is byte sel.j of {hi, lo} (0-3: lo, 4-7:
+// hi), 0x0c: zero
+GRK_HD uint32_t perm32(uint32_t hi, uint32_t lo, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t v = (uint64_t)hi << 32 | lo;
+    uint32_t r = 0;
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t s = (sel >> (8 * j)) & 0xffu;
+        r |= (s < 8 ? (uint32_t)(v >> (8 * s)) & 0xffu : 0u) << (8 * j);
+    }
+    return r;
+#endif
+}
+// bit c of a nibble -> bit 0 of byte c: the product puts bit c at c + 7j
+// (j = 0..3, no two terms meet in one bit), the mask keeps j = c.  A 24-bit
+// multiply (v_mul_u32_u24) is full rate; written as such, since the compiler
+// folds a shift of the result into the constant, which then needs the
+// quarter-rate 32-bit multiply.  B: the bit of each byte to land in (the
+// constant takes the shift while it fits 24 bits).
+template <int B = 0>
+GRK_HD uint32_t spread4(uint32_t nib) {
+    constexpr int M = B <= 2 ? B : 2;
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t p;
+    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(p) : "i"(0x204081u << M), "v"(nib));
+#else
+    const uint32_t p = nib * (0x204081u << M);
+#endif
+    return (p & (0x01010101u << M)) << (B - M);
+}
+// columns sh..sh+3 of a 32-column row mask, one per byte (in its bit B)
+template <int B = 0>
+GRK_HD uint32_t nib_bytes(uint32_t v, uint32_t sh) { return spread4<B>(bfe32(v, sh, 4)); }
+// byte c of r[j] -> byte j of t[c]
+GRK_HD void tr4x4(const uint32_t *r, uint32_t *t) {
+    const uint32_t a = perm32(r[1], r[0], 0x05010400u), b = perm32(r[1], r[0], 0x07030602u);
+    const uint32_t c = perm32(r[3], r[2], 0x05010400u), d = perm32(r[3], r[2], 0x07030602u);
+    t[0] = perm32(c, a, 0x05040100u);
+    t[1] = perm32(c, a, 0x07060302u);
+    t[2] = perm32(d, b, 0x05040100u);
+    t[3] = perm32(d, b, 0x07060302u);
+}
+// The selectors that compact a column's present symbols: the candidates are
+// bytes 0-3 (the rows' ZC / MAG symbols) and 4-7 (their SC symbols) of a
+// perm32 source pair, idx bit r / 4 + r says row r's is present, the output
+// order is Z0 S0 Z1 S1 ..; absent tail bytes read as zero.
+GRK_HD void compact_sel(uint32_t idx, uint32_t *lo, uint32_t *hi) {
+    uint64_t s = 0x0c0c0c0c0c0c0c0cull;
+    uint32_t k = 0;
+    for (uint32_t r = 0; r < 4; ++r)
+        for (uint32_t j = 0; j < 2; ++j)
+            if ((idx >> (r + 4 * j)) & 1u) {
+                s ^= (uint64_t)(0x0cu ^ (r + 4 * j)) << (8 * k);
+                ++k;
+            }
+    *lo = (uint32_t)s;
+    *hi = (uint32_t)(s >> 32);
+}
+// ctab: compact_sel of all 256 idx as {lo, hi} pairs (the kernel's LDS), or
+// null (host)
+GRK_HD void compact_get(const uint32_t *ctab, uint32_t idx, uint32_t *lo, uint32_t *hi) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (!ctab) {
+        compact_sel(idx, lo, hi);
+        return;
+    }
+#endif
+    *lo = ctab[2 * idx];
+    *hi = ctab[2 * idx + 1];
+}
+GRK_HD uint32_t popc32(uint32_t v) { return (uint32_t)__builtin_popcount(v); }
+// true for every lane of the wavefront when it is for any of them
+GRK_HD bool lanes_any(bool p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __ballot(p) != 0;
+#else
+    return p;
+#endif
+}
+
+// The rows of a stripe as their symbols' bit slices (64 columns each): the
+// zero-coding byte (context bits c0..c3, decision s), where it is present
+// (pz), the sign byte (Sc4) and where it is present (ps).
+struct RowSl { uint64_t z[5], pz, ps, s[4]; };
+
+// Emit the ZC / SC symbols of a stripe's columns (SPP; CUP with its
+// aggregation columns in agg).  The stripe is walked as two 32-column halves
+// so that every bit test is a 32-bit field extract, and in groups of four
+// columns: a row's slices are spread to one symbol byte per column, the
+// rows' bytes transposed to one word per column, and a column's present
+// symbols compacted with a byte permute -- no branch on a row or a sign.
+template <bool CUP>
+GRK_HD void emit_stripe(SymOut &so, const uint32_t *ctab, const RowSl *R, uint64_t cols64, uint64_t agg64, bool any_ps) {
+#pragma unroll 1
+    for (uint32_t half = 0; half < 2; ++half) {
+        const uint32_t cols = half ? (uint32_t)(cols64 >> 32) : (uint32_t)cols64;
+        if (!cols) continue;
+        const uint32_t agg = half ? (uint32_t)(agg64 >> 32) : (uint32_t)agg64;
+        uint32_t z[4][5], s[4][4], pz[4], ps[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int b = 0; b < 5; ++b) z[r][b] = half ? (uint32_t)(R[r].z[b] >> 32) : (uint32_t)R[r].z[b];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) s[r][b] = half ? (uint32_t)(R[r].s[b] >> 32) : (uint32_t)R[r].s[b];
+            pz[r] = half ? (uint32_t)(R[r].pz >> 32) : (uint32_t)R[r].pz;
+            ps[r] = half ? (uint32_t)(R[r].ps >> 32) : (uint32_t)R[r].ps;
+        }
+#pragma unroll 1
+        for (uint32_t sh = 0; sh < 32; sh += 4) {
+            if (!bfe32(cols, sh, 4)) continue;
+            uint32_t zr[4], sr[4] = {0, 0, 0, 0}, idx4 = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                zr[r] = nib_bytes<0>(z[r][0], sh) | nib_bytes<1>(z[r][1], sh) | nib_bytes<2>(z[r][2], sh) |
+                        nib_bytes<3>(z[r][3], sh) | nib_bytes<5>(z[r][4], sh);
+                idx4 |= nib_bytes(pz[r], sh) << r | nib_bytes(ps[r], sh) << (4 + r);
+            }
+            if (any_ps && (idx4 & 0xf0f0f0f0u)) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    sr[r] = 0x08080808u | nib_bytes<0>(s[r][0], sh) | nib_bytes<1>(s[r][1], sh) |
+                            nib_bytes<2>(s[r][2], sh) | nib_bytes<5>(s[r][3], sh);
+            }
+            uint32_t zt[4], st[4];
+            tr4x4(zr, zt);
+            tr4x4(sr, st);
+            so.room();
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const uint32_t idx = (idx4 >> (8 * c)) & 0xffu;
+                if (CUP && ((agg >> (sh + c)) & 1u)) {
+                    // all four rows are candidates: idx's high nibble is the column's bits
+                    const uint32_t colbits = idx >> 4;
+                    if (!colbits) {
+                        so.put4(CX_AGG, 1);
+                    } else {
+                        const uint32_t run = (uint32_t)__builtin_ctz(colbits);
+                        so.put4((CX_AGG | 1u << 5) | (CX_UNI | (run >> 1) << 5) << 8 | (CX_UNI | (run & 1) << 5) << 16, 3);
+                    }
+                }
+                uint32_t lo, hi;
+                compact_get(ctab, idx, &lo, &hi);
+                so.put8(perm32(st[c], zt[c], lo), perm32(st[c], zt[c], hi), popc32(idx));
+            }
+        }
+    }
 }
 
 // a: a row array (host: a pointer; device: the lane-interleaved rows of
@@ -611,7 +765,9 @@ GRK_HD uint64_t ldrow(const A &a, int32_t y, uint32_t h) {
 template <class R, class T, bool COND = true>
 GRK_HD void t1_model_plane(uint32_t w, uint32_t h, uint32_t orient, const R &bitp, const R &above, const R &ref,
                            bool has_ref, const R &negr, const T &tmp, const uint8_t *sc, uint32_t *out, uint32_t *cnt,
-                           uint32_t cblksty = 0, bool raw_spp = false, uint32_t *ring = nullptr) {
+                           uint32_t cblksty = 0, bool raw_spp = false, uint32_t *ring = nullptr,
+                           const uint32_t *ctab = nullptr) {
+    (void)sc;  // the sign contexts are formed bit-parallel (sc_slices)
     const uint64_t wm = w >= 64 ? ~(uint64_t)0 : (((uint64_t)1 << w) - 1);
     const bool vsc = (cblksty & CBLKSTY_VSC) != 0;
     const T postS = tmp, visS = tmp + 64;
@@ -660,40 +816,32 @@ GRK_HD void t1_model_plane(uint32_t w, uint32_t h, uint32_t orient, const R &bit
             for (int i = 0; i < 6; ++i) ng[i] = negr[k + i];
             if (vsc) ng[5] = 0;
         }
-        uint64_t coded[4];
-        Ctx4 cz[4];
+        // the sign slices only where the lane gained significance in the stripe
+        const bool gained = ((post[0] ^ pre[0]) | (post[1] ^ pre[1]) | (post[2] ^ pre[2]) | (post[3] ^ pre[3])) != 0;
+        RowSl rs[4];
+        uint64_t cols = 0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const uint64_t up = r == 0 ? U : post[r - 1], ne = r == 0 ? U : pre[r - 1];
             const uint64_t dnp = r == 3 ? D : post[r + 1], dn = r == 3 ? D : pre[r + 1];
             const uint64_t NW = up << 1, N = up, NE = ne >> 1, W = post[r] << 1, E = pre[r] >> 1, SW = dnp << 1,
                            S = dn, SE = dn >> 1;
-            coded[r] = C[r] & (NW | N | NE | W | E | SW | S | SE);
-            cz[r] = zc_slices(NW, N, NE, W, E, SW, S, SE, orient);
-            if ((uint32_t)r < nr) { postS[k + r] = post[r]; visS[k + r] = coded[r]; }
-        }
-        uint64_t cols = coded[0] | coded[1] | coded[2] | coded[3];
-        // a column's symbols (<= 4 ZC + 4 SC) go out as one packed word
-        while (cols) {
-            const uint32_t x = ctz64(cols);
-            cols &= cols - 1;
-            uint64_t word = 0;
-            uint32_t sh = 0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (!((coded[r] >> x) & 1)) continue;
-                const uint32_t s = (uint32_t)((post[r] >> x) & 1);
-                word |= (uint64_t)(ctx_at(cz[r], x) | s << 5) << sh;
-                sh += 8;
-                if (s) {
-                    const uint64_t up = r == 0 ? U : post[r - 1], dn = r == 3 ? D : pre[r + 1];
-                    word |= (uint64_t)sc_symbol(sc, post[r] << 1, ng[r + 1] << 1, pre[r] >> 1, ng[r + 1] >> 1, up,
-                                                ng[r], dn, ng[r + 2], ng[r + 1], x, raw_spp) << sh;
-                    sh += 8;
-                }
+            const uint64_t coded = C[r] & (NW | N | NE | W | E | SW | S | SE);
+            const Ctx4 cz = zc_slices(NW, N, NE, W, E, SW, S, SE, orient);
+            rs[r].z[0] = cz.c0; rs[r].z[1] = cz.c1; rs[r].z[2] = cz.c2; rs[r].z[3] = cz.c3;
+            rs[r].z[4] = post[r];
+            rs[r].pz = coded;
+            rs[r].ps = coded & post[r];
+            rs[r].s[0] = rs[r].s[1] = rs[r].s[2] = rs[r].s[3] = 0;
+            if (gained) {
+                const Sc4 sc4 = sc_slices(W, ng[r + 1] << 1, E, ng[r + 1] >> 1, N, ng[r], S, ng[r + 2], ng[r + 1], raw_spp);
+                rs[r].s[0] = sc4.b0; rs[r].s[1] = sc4.b1; rs[r].s[2] = sc4.b2; rs[r].s[3] = sc4.d;
             }
-            so.put_n64(word, sh >> 3);
+            cols |= coded;
+            if ((uint32_t)r < nr) { postS[k + r] = post[r]; visS[k + r] = coded; }
         }
+        // a column's symbols (<= 4 ZC + 4 SC) go out as one packed word
+        emit_stripe<false>(so, ctab, rs, cols, 0, gained);
         U = post[3];
         so.stripe_flush();
     }
@@ -718,19 +866,48 @@ GRK_HD void t1_model_plane(uint32_t w, uint32_t h, uint32_t orient, const R &bit
             const uint64_t nb = dil(sS[r]) | dil(sS[r + 2]) | (sS[r + 1] << 1) | (sS[r + 1] >> 1);
             o0[r] = nb & ~o1[r];
         }
-        while (cols) {
-            const uint32_t x = ctz64(cols);
-            cols &= cols - 1;
-            uint32_t word = 0, sh = 0;
+        // A member's symbol is CX_MAG (14) + o0 + 2 * o1 | bit << 5, and o0
+        // excludes o1: 0x0e plus o1 in bit 1 (no carry leaves the byte), o0
+        // in bit 0.  Four
+        // columns at a time: the rows' bytes, transposed to a word per column;
+        // where all four rows of all four columns are members, in every lane
+        // (the dense low planes), the word goes out as it is.
+#pragma unroll 1
+        for (uint32_t half = 0; half < 2; ++half) {
+            const uint32_t colsh = half ? (uint32_t)(cols >> 32) : (uint32_t)cols;
+            if (!colsh) continue;
+            uint32_t mh[4], o0h[4], o1h[4], bh[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const uint32_t pr = (uint32_t)(m[r] >> x) & 1;
-                const uint32_t sym = CX_MAG + ((uint32_t)(o0[r] >> x) & 1) + (((uint32_t)(o1[r] >> x) & 1) << 1) +
-                                     (((uint32_t)(bit[r] >> x) & 1) << 5);
-                word |= pr ? sym << sh : 0;
-                sh += pr << 3;
+                mh[r] = half ? (uint32_t)(m[r] >> 32) : (uint32_t)m[r];
+                o0h[r] = half ? (uint32_t)(o0[r] >> 32) : (uint32_t)o0[r];
+                o1h[r] = half ? (uint32_t)(o1[r] >> 32) : (uint32_t)o1[r];
+                bh[r] = half ? (uint32_t)(bit[r] >> 32) : (uint32_t)bit[r];
             }
-            so.put_n(word, sh >> 3);
+#pragma unroll 1
+            for (uint32_t sh = 0; sh < 32; sh += 4) {
+                if (!bfe32(colsh, sh, 4)) continue;
+                uint32_t mr[4], mt[4], idx4 = 0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    mr[r] = (0x0e0e0e0eu + nib_bytes<1>(o1h[r], sh)) | nib_bytes<0>(o0h[r], sh) | nib_bytes<5>(bh[r], sh);
+                    idx4 |= nib_bytes(mh[r], sh) << r;
+                }
+                tr4x4(mr, mt);
+                so.room();
+                if (!lanes_any(idx4 != 0x0f0f0f0fu)) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) so.put4(mt[c], 4);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const uint32_t idx = (idx4 >> (8 * c)) & 0xffu;
+                        uint32_t lo, hi;
+                        compact_get(ctab, idx, &lo, &hi);
+                        so.put4(perm32(0, mt[c], lo), popc32(idx));
+                    }
+                }
+            }
         }
         so.stripe_flush();
     }
@@ -764,52 +941,31 @@ GRK_HD void t1_model_plane(uint32_t w, uint32_t h, uint32_t orient, const R &bit
             agg &= ~((sS[0] | sS[1] | sS[2] | sS[3]) >> 1);
             agg &= ~(dil(U) | dil(D));
         }
-        Ctx4 cz[4];
+        const bool gained = ((cand[0] & bit[0]) | (cand[1] & bit[1]) | (cand[2] & bit[2]) | (cand[3] & bit[3])) != 0;
+        RowSl rs[4];
+        uint64_t anyb = 0;  // an aggregation column's rows above have a set bit
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const uint64_t up = r == 0 ? U : pc[r - 1], ne = r == 0 ? U : sS[r - 1];
             const uint64_t dnc = r == 3 ? D : pc[r + 1], dn = r == 3 ? D : sS[r + 1];
-            cz[r] = zc_slices(up << 1, up, ne >> 1, pc[r] << 1, sS[r] >> 1, dnc << 1, dn, dn >> 1, orient);
+            const uint64_t W = pc[r] << 1, E = sS[r] >> 1;
+            const Ctx4 cz = zc_slices(up << 1, up, ne >> 1, W, E, dnc << 1, dn, dn >> 1, orient);
+            rs[r].z[0] = cz.c0; rs[r].z[1] = cz.c1; rs[r].z[2] = cz.c2; rs[r].z[3] = cz.c3;
+            rs[r].z[4] = bit[r];
+            // in an aggregation column the rows before the first set bit have
+            // no symbol and that row only its sign (the run symbols stand for them)
+            rs[r].pz = cand[r] & (~agg | anyb);
+            rs[r].ps = cand[r] & bit[r];
+            anyb |= bit[r];
+            rs[r].s[0] = rs[r].s[1] = rs[r].s[2] = rs[r].s[3] = 0;
+            if (gained) {
+                const Sc4 sc4 = sc_slices(W, ng[r + 1] << 1, E, ng[r + 1] >> 1, up, ng[r], dn, ng[r + 2], ng[r + 1], false);
+                rs[r].s[0] = sc4.b0; rs[r].s[1] = sc4.b1; rs[r].s[2] = sc4.b2; rs[r].s[3] = sc4.d;
+            }
         }
-        uint64_t cols = cand[0] | cand[1] | cand[2] | cand[3];
         // a column's symbols go out as packed words: the aggregation / run
         // symbols (<= 3), then the rows' ZC / SC symbols (<= 8)
-        while (cols) {
-            const uint32_t x = ctz64(cols);
-            cols &= cols - 1;
-            int r0 = 0;
-            bool rl = false;
-            if ((agg >> x) & 1) {
-                uint32_t colbits = (uint32_t)((bit[0] >> x) & 1) | (uint32_t)((bit[1] >> x) & 1) << 1 |
-                                   (uint32_t)((bit[2] >> x) & 1) << 2 | (uint32_t)((bit[3] >> x) & 1) << 3;
-                if (!colbits) {
-                    so.put(CX_AGG);
-                    continue;
-                }
-                const uint32_t run = (uint32_t)__builtin_ctz(colbits);
-                so.put_n((CX_AGG | 1u << 5) | (CX_UNI | (run >> 1) << 5) << 8 | (CX_UNI | (run & 1) << 5) << 16, 3);
-                r0 = (int)run;
-                rl = true;
-            }
-            uint64_t word = 0;
-            uint32_t sh = 0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (r < r0 || !((cand[r] >> x) & 1)) continue;
-                const uint32_t s = (uint32_t)((bit[r] >> x) & 1);
-                if (!(rl && r == r0)) {
-                    word |= (uint64_t)(ctx_at(cz[r], x) | s << 5) << sh;
-                    sh += 8;
-                }
-                if (s) {
-                    const uint64_t up = r == 0 ? U : pc[r - 1], dn = r == 3 ? D : sS[r + 1];
-                    word |= (uint64_t)sc_symbol(sc, pc[r] << 1, ng[r + 1] << 1, sS[r] >> 1, ng[r + 1] >> 1, up, ng[r],
-                                                dn, ng[r + 2], ng[r + 1], x) << sh;
-                    sh += 8;
-                }
-            }
-            so.put_n64(word, sh >> 3);
-        }
+        emit_stripe<true>(so, ctab, rs, cand[0] | cand[1] | cand[2] | cand[3], agg, gained);
         U = pc[3];
         so.stripe_flush();
     }

@@ -659,6 +659,11 @@ size_t grkgpu_t1_scratch_bytes_n(uint32_t nblocks);
 int grkgpu_t1_encode_blocks(const grkgpu_enc_block *blocks, uint32_t nblocks, const int32_t *coef,
                             void *scratch, uint8_t *out, grkgpu_enc_result *results, int with_distortion,
                             void *stream);
+/* the same with a code-block style (COD SPcod bits 0..5: BYPASS 1, RESET 2,
+ * TERMALL 4, VSC 8, PTERM 16, SEGSYM 32) */
+int grkgpu_t1_encode_blocks_sty(const grkgpu_enc_block *blocks, uint32_t nblocks, const int32_t *coef,
+                                void *scratch, uint8_t *out, grkgpu_enc_result *results, int with_distortion,
+                                uint32_t cblk_sty, void *stream);
 int grkgpu_t1_decode_blocks(const grkgpu_dec_block *blocks, uint32_t nblocks, const uint8_t *data,
                             void *scratch, int32_t *dst, void *stream);
 
