@@ -194,12 +194,15 @@ class Planes(ctypes.Structure):
 
 
 LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
+# flag on a grkgpu_out_planes layout: subsampled components replicated to the image grid (grk_decompress -u)
+LAYOUT_UPSAMPLE = 0x100
 _LAYOUTS = {"chw": LAYOUT_PLANAR, "hwc": LAYOUT_INTERLEAVED}
 
 
 class OutPlanes(ctypes.Structure):
     """grkgpu_out_planes: where grkgpu_decompress_to / grkgpu_mct_inv_dcshift_to
-    store their samples (format GRKGPU_SAMPLE_*, layout GRKGPU_LAYOUT_*)."""
+    / grkgpu_upsample_to store their samples (format GRKGPU_SAMPLE_*, layout
+    GRKGPU_LAYOUT_* | GRKGPU_LAYOUT_UPSAMPLE)."""
     _fields_ = [("planes", ctypes.c_void_p * MAXC), ("sample_fmt", ctypes.c_uint32), ("layout", ctypes.c_uint32),
                 ("on_device", ctypes.c_int32), ("pad_", ctypes.c_uint32)]
 
@@ -315,6 +318,9 @@ def lib():
         L.grkgpu_decompress_to.argtypes = [VP, VP, ctypes.c_size_t, P(DParams), U32, U32, P(ImageDesc), P(OutPlanes)]
         L.grkgpu_mct_inv_dcshift_to.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), I32, I32, P(OutPlanes), U32,
                                                 VP]
+        if hasattr(L, "grkgpu_upsample_to"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_upsample_to.argtypes = [P(VP), P(U32), U32, P(U32), P(U32), U32, U32, U32, U32, P(OutPlanes),
+                                             U32, VP]
         L.grkgpu_dcshift_mct_fwd.argtypes = [P(VP), U32, U32, U32, U32, P(I32), I32, I32, VP]
         L.grkgpu_mct_inv_dcshift.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), I32, I32, VP]
         L.grkgpu_dwt_fwd.argtypes = [VP, VP, U32, U32, U32, U32, U32, I32, VP]
@@ -733,7 +739,8 @@ class Codec:
         _check(lib().grkgpu_decompress_tiles(self._ctx, bp, bn, tile_begin, tile_end, ptrs, 1 if on_dev else 0))
         return out
 
-    def decompress(self, buf, device_out=False, out=None, reduce=0, window=None, layers=0, dtype=None, layout="chw"):
+    def decompress(self, buf, device_out=False, out=None, reduce=0, window=None, layers=0, dtype=None, layout="chw",
+                   upsample=False):
         """Decode a .j2k codestream -> (c,h,w) int32 (numpy, or torch.cuda when
         device_out / out is a cuda tensor).  dtype = uint8 / int8 / uint16 /
         int16: samples of that type, stored by the last decode kernel (the
@@ -743,7 +750,16 @@ class Codec:
         resolution numres-1-reduce (grk_decompress -r), ceil(size / 2^reduce)
         samples a side (a window: ceil(x1 / 2^reduce) - ceil(x0 / 2^reduce)).  window = (x0, y0, x1, y1) in image coordinates:
         only that region (grk_set_decode_area), clipped to the image.
-        layers > 0: only the first `layers` quality layers (grk_decompress -l)."""
+        layers > 0: only the first `layers` quality layers (grk_decompress -l).
+        Subsampled components (4:2:0, 4:2:2, ...) come back as a list of host
+        planes, each on its grid -- or, with upsample=True (grk_decompress -u),
+        replicated to the image grid by the last decode kernel: one (c,h,w) /
+        (h,w,c) array or cuda tensor like any other decode (every dtype, out=,
+        device_out=, window=, layers=; not with reduce).  The sample at (X, Y)
+        is the component's sample (floor(X / dx) - ceil(x0 / dx), floor(Y / dy)
+        - ceil(y0 / dy)) with (x0, y0) the image's or window's origin, zero
+        where that index is negative.  Without subsampled components
+        upsample changes nothing."""
         d = read_header(buf)
         if window is not None:  # the window (reference grid) clipped to the image
             wx0, wy0, wx1, wy1 = window
@@ -772,7 +788,8 @@ class Codec:
             dt, fmt = _out_format(_out_dtype(out))
         shape = _layout_shape((c, h, w), layout)
         narrow = fmt != SAMPLE_I32 or layout != "chw"  # grkgpu_decompress_to; else today's entry points
-        if any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)):
+        up = bool(upsample) and any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c))
+        if not up and any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)):
             # subsampled components: a list of host planes, each on its grid
             if out is not None or device_out:
                 raise GrkGpuError("subsampled components decode to host planes only")
@@ -799,7 +816,7 @@ class Codec:
             on_dev = _check_out(out, (c, h, w), self.device, dt, layout)
         else:
             on_dev = bool(device_out)
-        if narrow:
+        if narrow or up:
             if layers < 0:
                 raise GrkGpuError("layers must be >= 0")
             if on_dev:
@@ -809,6 +826,8 @@ class Codec:
             elif out is None:
                 out = np.empty(shape, dtype=dt)
             op = self._out_planes(out, c, fmt, layout, on_dev)
+            if up:
+                op.layout |= LAYOUT_UPSAMPLE
             bp, bn, keep = _buf_ptr(buf)
             dp = DParams(cp_reduce=reduce, cp_layer=layers)
             if window is not None:
@@ -932,6 +951,48 @@ class dwt_options:
     def __exit__(self, *exc):
         _check(lib().grkgpu_set_dwt_options(ctypes.byref(self.old)))
         return False
+
+
+def upsample_to(src, dst, rect, subsampling, layout="chw", dst_stride=None):
+    """grkgpu_upsample_to.  src: one 2-D cuda tensor per component, of dst's
+    dtype, on the component's grid of rect = (x0, y0, x1, y1) -- component k
+    subsampled by subsampling[k] = (dx, dy) has ceil(y1 / dy) - ceil(y0 / dy)
+    rows of ceil(x1 / dx) - ceil(x0 / dx) samples; any view whose rows are
+    contiguous (its row stride is passed on).  dst: a 1-D cuda tensor -- any
+    view, so it may start at any sample -- filled from its first sample, rows
+    dst_stride samples apart (default: tight): "chw" plane k from k * h *
+    dst_stride, "hwc" pixels of c samples.  Returns dst."""
+    x0, y0, x1, y1 = rect
+    c, w, h = len(src), x1 - x0, y1 - y0
+    dt, fmt = _out_format(_out_dtype(dst))
+    _layout_shape((c, h, w), layout)  # refuses an unknown layout
+    cd = lambda v, s: -(-v // s)  # noqa: E731
+    if len(subsampling) != c or not 1 <= c <= MAXC or w <= 0 or h <= 0:
+        raise GrkGpuError("upsample_to: one (dx, dy) per component, 1 .. %d components, a non-empty rect" % MAXC)
+    il = layout == "hwc"
+    row = w * c if il else w
+    stride = row if dst_stride is None else dst_stride
+    need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
+    if dst.dim() != 1 or not dst.is_contiguous() or not dst.is_cuda or stride < row or dst.numel() < need:
+        raise GrkGpuError("upsample_to: dst flat, %d samples, on a cuda device" % need)
+    for a, (dx, dy) in zip(src, subsampling):
+        if dx < 1 or dy < 1:
+            break  # the library's refusal
+        shape = (cd(y1, dy) - cd(y0, dy), cd(x1, dx) - cd(x0, dx))
+        if (a.dtype != dst.dtype or a.device != dst.device or tuple(a.shape) != shape
+                or (a.numel() and shape[1] > 1 and a.stride(1) != 1)):
+            raise GrkGpuError("upsample_to: component plane %s %s, its grid needs %s %s on dst's device"
+                              % (tuple(a.shape), a.dtype, shape, dst.dtype))
+    op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout] | LAYOUT_UPSAMPLE, on_device=1)
+    for k in range(1 if il else c):
+        op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
+    ptrs = (ctypes.c_void_p * c)(*[a.data_ptr() for a in src])
+    ss = (ctypes.c_uint32 * c)(*[a.stride(0) if a.shape[0] > 1 and a.numel() else max(1, a.shape[1]) for a in src])
+    dxs = (ctypes.c_uint32 * c)(*[s[0] for s in subsampling])
+    dys = (ctypes.c_uint32 * c)(*[s[1] for s in subsampling])
+    _check(lib().grkgpu_upsample_to(ptrs, ss, c, dxs, dys, x0, y0, x1, y1, ctypes.byref(op), stride,
+                                    _stream_handle(dst.device)))
+    return dst
 
 
 def walk_tiles(cs):

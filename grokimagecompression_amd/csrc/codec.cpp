@@ -2335,6 +2335,7 @@ struct DecodeOut {
     int32_t fmt;          // SampleFmt
     int32_t interleaved;
     int on_device;
+    int upsample;  // GRKGPU_LAYOUT_UPSAMPLE: subsampled components replicated to the image grid
 };
 static DecodeOut i32_planes(int32_t *const *planes, int on_device) {
     return {(void *const *)planes, SMP_I32, 0, on_device};
@@ -2370,6 +2371,16 @@ static DecodeOut i32_planes(int32_t *const *planes, int on_device) {
 // that width, and the staging image, the zero fills and the copies to the host
 // are sized by it.  Interleaved: one destination of ncomp-sample pixels, every
 // component on one grid.
+//
+// od.upsample (grk_decompress -u, upsample_image_components,
+// grk_decompress.cpp:891-1040) on a stream with subsampled components: every
+// component on the image grid.  The launches that today write the planes
+// write the subsampled components -- shifted, clamped, narrowed, after their
+// MCT when all are subsampled alike -- to staging planes on their image-level
+// grids where a tile's first pixels may map to a sample of the neighbouring
+// tile (tile-component x0 = ceil(tx0 / dx): `staged` below), and one launch
+// per tile (launch_upsample_to) writes the output: the other components
+// straight from the tile buffer, the staged ones replicated from their planes.
 static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu_image_desc *img,
                            const DecodeOut &od, uint32_t tb, uint32_t te,
                            uint32_t reduce = 0, const Rect *win = nullptr, uint32_t max_layers = 0,
@@ -2430,12 +2441,17 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     }
     if (subs && !whole) return set_err(GRKGPU_EUNSUPPORTED, "tile-range decode of subsampled images is not supported");
     if (win && !whole) return set_err(GRKGPU_EINVAL, "window decode of a tile range is not supported");
+    const bool up = od.upsample && subs;
+    if (up && reduce)  // grk_decompress refuses -u with -r
+        return set_err(GRKGPU_EINVAL, "upsampled output of a reduced decode is not supported");
+    if (img && up)
+        for (uint32_t k = 0; k < nc; ++k) img->dx[k] = img->dy[k] = 1;
     for (uint32_t k = 0; od.fmt != SMP_I32 && k < nc; ++k) {
         const bool sg = od.fmt == SMP_I8 || od.fmt == SMP_I16;
         if ((cp.sgnd[k] != 0) != sg || cp.prec[k] > 8 * sb)
             return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
     }
-    if (il && mixed)
+    if (il && mixed && !up)
         return set_err(GRKGPU_EUNSUPPORTED, "interleaved output needs every component on one grid");
     if (il && (uint64_t)iw * nc > 0xffffffffull)  // the kernel's row stride is 32 bits of samples
         return set_err(GRKGPU_EUNSUPPORTED, "image too wide for interleaved output");
@@ -2871,22 +2887,52 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     // (interleaved: all ooff[nc] of them)
     const uint32_t nout = il ? 1 : nc;
     const size_t eb = il ? (size_t)nc * sb : sb;
-    auto region_bytes = [&](uint32_t k) { return (size_t)(il ? ooff[nc] : ooff[k + 1] - ooff[k]) * sb; };
-    DstPlanes dst{};
-    if (planes_on_device) {
-        for (uint32_t k = 0; k < nout; ++k) dst.p[k] = planes[k];
-    } else {
-        // staging image: every region on a 16-byte boundary, so that the
-        // kernel's packed stores stay aligned whatever the sample width
-        size_t off[GRKGPU_MAX_COMPS + 1] = {0};
-        for (uint32_t k = 0; k < nout; ++k) off[k + 1] = (off[k] + region_bytes(k) + 15) & ~(size_t)15;
-        HIPCHK(c->img.ensure(off[nout] + 256));
-        for (uint32_t k = 0; k < nout; ++k) dst.p[k] = c->img.as<uint8_t>() + off[k];
+    // (upsampled: every component has the output rectangle's iw x (oy1 - iy0) samples)
+    const uint64_t opix = (uint64_t)iw * (oy1 - iy0);
+    auto region_bytes = [&](uint32_t k) {
+        if (up) return (size_t)(opix * (il ? nc : 1)) * sb;
+        return (size_t)(il ? ooff[nc] : ooff[k + 1] - ooff[k]) * sb;
+    };
+    // upsampled: which components go through a staging plane -- all when they
+    // share one subsampled grid (their MCT runs first); otherwise those with a
+    // tile boundary that is no multiple of dx / dy, where the tile's first
+    // pixels map to a sample of the neighbouring tile-component (it starts at
+    // ceil(tx0 / dx)).  The others are read from the tile buffers, like the
+    // full-resolution components.
+    auto staged = [&](uint32_t k) {
+        if (!up || (cp.dx[k] == 1 && cp.dy[k] == 1)) return false;
+        const bool xseam = cp.tw > 1 && (cp.tx0 % cp.dx[k] || cp.tdx % cp.dx[k]);
+        const bool yseam = cp.th > 1 && (cp.ty0 % cp.dy[k] || cp.tdy % cp.dy[k]);
+        return !mixed || xseam || yseam;
+    };
+    DstPlanes dst{}, stg{};  // stg: the staging planes of an upsampled decode's subsampled components
+    {
+        // staging image (host planes) and staging planes: every region on a
+        // 16-byte boundary, so that the kernel's packed stores stay aligned
+        // whatever the sample width
+        size_t off[GRKGPU_MAX_COMPS + 1] = {0}, soff[GRKGPU_MAX_COMPS + 1];
+        if (!planes_on_device)
+            for (uint32_t k = 0; k < nout; ++k) off[k + 1] = (off[k] + region_bytes(k) + 15) & ~(size_t)15;
+        soff[0] = planes_on_device ? 0 : off[nout];
+        for (uint32_t k = 0; k < nc; ++k)
+            soff[k + 1] = soff[k] + (staged(k) ? ((size_t)(ooff[k + 1] - ooff[k]) * sb + 15) & ~(size_t)15 : 0);
+        if (soff[nc]) HIPCHK(c->img.ensure(soff[nc] + 256));
+        for (uint32_t k = 0; k < nout; ++k)
+            dst.p[k] = planes_on_device ? planes[k] : (void *)(c->img.as<uint8_t>() + off[k]);
+        for (uint32_t k = 0; k < nc; ++k)
+            if (staged(k)) stg.p[k] = c->img.as<uint8_t>() + soff[k];
+        // tiles the stream never reached are zero in the staging planes; in
+        // the output the upsampling launch writes their pixels
+        for (uint32_t k = 0; missing && k < nc; ++k)
+            if (staged(k)) HIPCHK(hipMemsetAsync(stg.p[k], 0, soff[k + 1] - soff[k], s));
     }
     auto at = [&](uint32_t k, uint64_t elem) { return (void *)((uint8_t *)dst.p[k] + elem * eb); };
+    // where the launches on the components' own grids store component k: the
+    // output, or (upsampled) its staging plane
+    auto cat = [&](uint32_t k, uint64_t elem) { return up ? (void *)((uint8_t *)stg.p[k] + elem * sb) : at(k, elem); };
     if (opad)
         for (uint32_t k = 0; k < nout; ++k) HIPCHK(hipMemsetAsync(dst.p[k], 0, region_bytes(k), s));
-    else if (missing)  // tiles the tile-part walk never reached: zero (their regions only -- a shard's
+    else if (missing && !up)  // tiles the tile-part walk never reached: zero (their regions only -- a shard's
                        // device planes hold other tiles)
         for (uint32_t t = tb; t < te; ++t) {
             if (walk.decoded[t] || wskip[t]) continue;
@@ -2914,12 +2960,12 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                 const TileComp &tc = tile.comps[k];
                 const Rect tr = tc.res[tc.numres - 1 - reduce].r;
                 const Rect out = intersect(tr, orect[k]);
-                if (out.empty()) continue;
+                if (out.empty() || (up && !staged(k))) continue;
                 PlanePtrs tsrc{};
                 DstPlanes tdst{};
                 ShiftArr sk{}, mnk{}, mxk{};
                 tsrc.p[0] = c->work.as<int32_t>() + tc.arena_off + (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0);
-                tdst.p[0] = at(k, (uint64_t)(out.y0 - orect[k].y0) * orect[k].w() + (out.x0 - orect[k].x0));
+                tdst.p[0] = cat(k, (uint64_t)(out.y0 - orect[k].y0) * orect[k].w() + (out.x0 - orect[k].x0));
                 sk.v[0] = sh.v[k];
                 mnk.v[0] = mn.v[k];
                 mxk.v[0] = mx.v[k];
@@ -2939,13 +2985,49 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         for (uint32_t k = 0; k < nc; ++k)
             tsrc.p[k] = c->work.as<int32_t>() + tile.comps[k].arena_off + (uint64_t)(out.y0 - tr.y0) * tr.w() +
                         (out.x0 - tr.x0);
-        for (uint32_t k = 0; k < nout; ++k)
-            tdst.p[k] = at(k, (uint64_t)(out.y0 - orect[0].y0) * ow + (out.x0 - orect[0].x0));
+        for (uint32_t k = 0; k < (up ? nc : nout); ++k)
+            tdst.p[k] = cat(k, (uint64_t)(out.y0 - orect[0].y0) * ow + (out.x0 - orect[0].x0));
         int32_t wmask = 0;  // components holding 9/7 (float) samples
         for (uint32_t k = 0; k < nc; ++k) wmask |= tile.comps[k].irrev << k;
         // row stride in samples: a row of an interleaved image holds ow pixels of nc samples
-        HIPCHK(launch_mct_inv_dcshift_to(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * nc : ow, nc, sh,
-                                         mn, mx, tmct[tile.index - tb], wmask, s));
+        HIPCHK(launch_mct_inv_dcshift_to(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il && !up,
+                                         il && !up ? ow * nc : ow, nc, sh, mn, mx, tmct[tile.index - tb], wmask, s));
+    }
+    // upsampled: the output, tile by tile (the tiles never reached included)
+    for (auto &tile : tiles) {
+        const Rect out = intersect(tile.r, {ix0, iy0, ix1, iy1});  // the tile's pixels of the output
+        if (!up || out.empty()) continue;
+        UpPlan pl{};
+        for (uint32_t k = 0; k < nc; ++k) {
+            UpComp &u = pl.c[k];
+            u.dx = (uint8_t)cp.dx[k];
+            u.dy = (uint8_t)cp.dy[k];
+            if (staged(k)) {
+                u.src = stg.p[k];
+                u.stride = orect[k].w();
+                u.gx0 = (int32_t)orect[k].x0;
+                u.gy0 = (int32_t)orect[k].y0;
+            } else {  // the tile buffer (a tile never reached: zeros)
+                const Rect tr = comp_rect(tile.r, cp.dx[k], cp.dy[k]);
+                u.raw = 1;
+                u.gx0 = (int32_t)tr.x0;
+                u.gy0 = (int32_t)tr.y0;
+                u.stride = tr.w();
+                if (!tile.comps.empty()) {
+                    u.src = c->work.as<int32_t>() + tile.comps[k].arena_off;
+                    u.irrev = (uint8_t)tile.comps[k].irrev;
+                }
+                u.shift = sh.v[k];
+                u.mn = mn.v[k];
+                u.mx = mx.v[k];
+            }
+            // the zero lead-in: left of / above the output rectangle's origin on the component's grid
+            u.zx0 = std::max((int32_t)orect[k].x0, u.gx0);
+            u.zy0 = std::max((int32_t)orect[k].y0, u.gy0);
+        }
+        DstPlanes tdst{};
+        for (uint32_t k = 0; k < nout; ++k) tdst.p[k] = at(k, (uint64_t)(out.y0 - iy0) * iw + (out.x0 - ix0));
+        HIPCHK(launch_upsample_to(pl, nc, out.x0, out.y0, out.w(), out.h(), tdst, od.fmt, il, il ? iw * nc : iw, s));
     }
     HIPCHK(hipEventRecord(c->ev[4], s));
     if (!planes_on_device) {
@@ -3030,7 +3112,8 @@ extern "C" int grkgpu_decompress_tiles(grkgpu_ctx *c, const uint8_t *csb, size_t
 static int check_out_planes(const grkgpu_out_planes *out) {
     if (!out) return set_err(GRKGPU_EINVAL, "null argument");
     if (out->sample_fmt > GRKGPU_SAMPLE_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
-    if (out->layout > GRKGPU_LAYOUT_INTERLEAVED) return set_err(GRKGPU_EINVAL, "unknown layout");
+    if ((out->layout & ~GRKGPU_LAYOUT_UPSAMPLE) > GRKGPU_LAYOUT_INTERLEAVED)
+        return set_err(GRKGPU_EINVAL, "unknown layout");
     return GRKGPU_OK;
 }
 
@@ -3039,8 +3122,9 @@ extern "C" int grkgpu_decompress_to(grkgpu_ctx *c, const uint8_t *csb, size_t le
                                     const grkgpu_out_planes *out) {
     int rc = check_out_planes(out);
     if (rc) return rc;
-    const DecodeOut od{out->planes, (int32_t)out->sample_fmt, out->layout == GRKGPU_LAYOUT_INTERLEAVED,
-                       out->on_device};
+    const DecodeOut od{out->planes, (int32_t)out->sample_fmt,
+                       (out->layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED, out->on_device,
+                       (out->layout & GRKGPU_LAYOUT_UPSAMPLE) != 0};
     if (!dp) return decompress_impl(c, csb, len, img, od, tile_begin, tile_end);
     const bool win = dp->DA_x0 || dp->DA_y0 || dp->DA_x1 || dp->DA_y1;
     const Rect w{dp->DA_x0, dp->DA_y0, dp->DA_x1, dp->DA_y1};
@@ -3122,6 +3206,7 @@ extern "C" int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t num
                                          void *stream) {
     int rc = check_out_planes(dst);
     if (rc) return rc;
+    if (dst->layout & GRKGPU_LAYOUT_UPSAMPLE) return set_err(GRKGPU_EINVAL, "unknown layout");
     const bool il = dst->layout == GRKGPU_LAYOUT_INTERLEAVED;
     const int32_t fmt = (int32_t)dst->sample_fmt;
     const uint32_t sb = sample_bytes(fmt);
@@ -3150,6 +3235,43 @@ extern "C" int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t num
     if (rc) return rc;
     HIPCHK(launch_mct_inv_dcshift_to(p, src_stride, w, h, d, fmt, il, dst_stride, numcomps, sh, mn, mx, mct,
                                      irreversible ? 0xFFFF : 0, (hipStream_t)stream));
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_upsample_to(const void *const *src, const uint32_t *src_stride, uint32_t numcomps,
+                                  const uint32_t *dx, const uint32_t *dy, uint32_t x0, uint32_t y0, uint32_t x1,
+                                  uint32_t y1, const grkgpu_out_planes *dst, uint32_t dst_stride, void *stream) {
+    int rc = check_out_planes(dst);
+    if (rc) return rc;
+    const bool il = (dst->layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED;
+    const int32_t fmt = (int32_t)dst->sample_fmt;
+    const uint32_t sb = sample_bytes(fmt);
+    if (!src || !src_stride || !dx || !dy || numcomps < 1 || numcomps > 16 || x1 <= x0 || y1 <= y0 ||
+        x1 > 0x7fffffffu || y1 > 0x7fffffffu)
+        return set_err(GRKGPU_EINVAL, "bad arguments");
+    if ((uint64_t)dst_stride < (uint64_t)(x1 - x0) * (il ? numcomps : 1))
+        return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
+    UpPlan pl{};
+    DstPlanes d{};
+    for (uint32_t k = 0; k < numcomps; ++k) {
+        if (dx[k] < 1 || dx[k] > 255 || dy[k] < 1 || dy[k] > 255)
+            return set_err(GRKGPU_EINVAL, "bad arguments (dx / dy must be 1 .. 255)");
+        const Rect cr = comp_rect({x0, y0, x1, y1}, dx[k], dy[k]);
+        if (src_stride[k] < cr.w()) return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
+        // (a grid without a sample inside the rectangle has no plane: every index is negative)
+        if ((!src[k] && !cr.empty()) || (uintptr_t)src[k] % sb)
+            return set_err(GRKGPU_EINVAL, "null or misaligned plane");
+        pl.c[k] = UpComp{src[k], src_stride[k], (int32_t)cr.x0, (int32_t)cr.y0, (int32_t)cr.x0, (int32_t)cr.y0,
+                         (uint8_t)dx[k], (uint8_t)dy[k], 0, 0, 0, 0, 0};
+    }
+    for (uint32_t k = 0; k < (il ? 1u : numcomps); ++k) {
+        if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
+            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+        d.p[k] = dst->planes[k];
+    }
+    rc = check_device(-1);
+    if (rc) return rc;
+    HIPCHK(launch_upsample_to(pl, numcomps, x0, y0, x1 - x0, y1 - y0, d, fmt, il, dst_stride, (hipStream_t)stream));
     return GRKGPU_OK;
 }
 

@@ -96,6 +96,31 @@ hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uin
                                      const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
                                      uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn, const ShiftArr &mx,
                                      int32_t mct, int32_t irrev, hipStream_t s);
+// The decoded image with its subsampled components replicated to the image
+// grid (GRKGPU_LAYOUT_UPSAMPLE, grk_decompress -u): output pixel (X, Y) of the
+// reference grid takes component k's sample at column floor(X / dx), row
+// floor(Y / dy) of its grid -- zero left of column zx0 or above row zy0 (the
+// output rectangle's origin on that grid, ceil(ox0 / dx): the reference's zero
+// lead-in).  src holds the grid from (gx0, gy0) on, rows `stride` elements
+// apart.  raw: src is a tile buffer of int32 coefficients (irrev: 9/7 float
+// bit patterns), finished on the way by k_mct_inv_dcshift's second loop
+// (shift, mn, mx); else finished samples of the destination's type (a staging
+// plane).  src = null: zeros (a tile the stream never reached).
+struct UpComp {
+    const void *src;
+    uint32_t stride;
+    int32_t gx0, gy0, zx0, zy0;
+    uint8_t dx, dy, raw, irrev;
+    int32_t shift, mn, mx;
+};
+struct UpPlan { UpComp c[GRK_MAX_COMPS]; };
+// The w x h pixels from (X0, Y0) on the reference grid, dst at the first of
+// them (format, layout and dstride as launch_mct_inv_dcshift_to).  Three
+// components at (1,1), (2,dy), (2,dy) with dy 1 or 2 in U8 / U16 / I32 run
+// k_upsample_420 (16-byte runs, chroma replicated in registers); everything
+// else k_upsample_any (a thread per pixel, dx / dy 1 .. 255).
+hipError_t launch_upsample_to(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                              const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride, hipStream_t s);
 // One DWT level of one tile-component (dwt.hip).  A launch runs one level of
 // every job in a table (grid.y = job).
 struct DwtJob {

@@ -367,6 +367,130 @@ __global__ void k_mct_inv_dcshift_pixels_any(PlanePtrs src, uint32_t sstride, ui
 }
 
 // ---------------------------------------------------------------------------
+// The decoded image with its subsampled components replicated to the image
+// grid (GRKGPU_LAYOUT_UPSAMPLE; grk_decompress -u, upsample_image_components,
+// grk_decompress.cpp:891-1040): output pixel (X, Y) of the reference grid
+// takes component k's sample (floor(X / dx) - gx0, floor(Y / dy) - gy0) -- zero
+// where that index is negative, the reference's lead-in when the origin is no
+// multiple of dx / dy.  A component comes straight from the tile buffer
+// (UpComp::raw: k_mct_inv_dcshift's second loop, statement for statement) or,
+// where a tile's first pixels map to a sample of the neighbouring tile or the
+// MCT ran first, from its finished staging plane, which spans the tile seams;
+// the stores are k_mct_inv_dcshift_planar / _pixels'.
+// ---------------------------------------------------------------------------
+// component c's sample for the pixel whose column / row on c's grid are (col, row)
+template <typename T>
+__device__ __forceinline__ int32_t up_sample(const UpComp &c, int32_t col, int32_t row) {
+    if (col < c.zx0 || row < c.zy0 || !c.src) return 0;
+    const size_t i = (size_t)(row - c.gy0) * c.stride + (uint32_t)(col - c.gx0);
+    if (c.raw) {
+        int32_t a[1] = {((const int32_t *)c.src)[i]};
+        inv_plain_run<1>(a, c.irrev, c.shift, c.mn, c.mx);
+        return a[0];
+    }
+    return (int32_t)((const T *)c.src)[i];
+}
+
+// 4:2:0 / 4:2:2: three components at (1,1), (2,dy), (2,dy), dy = 1 or 2.  A
+// thread owns the run of N pixels k_mct_inv_dcshift_planar / _pixels give it
+// (16 bytes of a destination row per component, on the destination's 16-byte
+// grid; lead-in and cut last run sample by sample).  The run's chroma is the
+// N / 2 (+ 1 when the run starts on an odd X) source samples from floor(X / 2)
+// on, each stored twice: what counts is the parity of the absolute X, not of
+// the run's place in the tile.  Row Y reads chroma row floor(Y / dy).
+template <typename T, bool IL>
+__global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h, DstPlanes dst,
+                               uint32_t dstride) {
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    constexpr int N = NarrowRun<T>::N, H = N / 2, NS = H + 1;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (y >= h) return;
+    const size_t drow = (size_t)y * dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)((T *)dst.p[0] + drow), (IL ? 3 : 1) * sizeof(T), t, w, x0);
+    if (n <= 0) return;
+    const uint32_t X = X0 + x0, Y = Y0 + y;
+    int32_t v[3][N];
+    {
+        const UpComp &c = p.c[0];  // (1,1): every pixel has its sample
+        const size_t si = (size_t)(Y - (uint32_t)c.gy0) * c.stride + (X - (uint32_t)c.gx0);
+        if (!c.src) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[0][i] = 0;
+        } else if (c.raw) {
+            load_run<N>((const int32_t *)c.src + si, n, v[0]);
+            inv_plain_run<N>(v[0], c.irrev, c.shift, c.mn, c.mx);
+        } else {
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[0][i] = i < n ? (int32_t)((const T *)c.src)[si + i] : 0;
+        }
+    }
+    const int32_t c0 = (int32_t)(X >> 1);                             // the run's first chroma column
+    const int last = (int)(((X + (uint32_t)n - 1) >> 1) - (X >> 1));  // ... and how many more it needs
+    const bool odd = X & 1;
+#pragma unroll
+    for (int k = 1; k < 3; ++k) {
+        const UpComp &c = p.c[k];
+        const int32_t row = (int32_t)(Y >> (c.dy - 1));
+        int32_t s[NS];
+        if (row < c.zy0 || !c.src) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j) s[j] = 0;
+        } else if (c.raw) {
+            const int32_t *const q = (const int32_t *)c.src + ((int64_t)(row - c.gy0) * c.stride + (c0 - c.gx0));
+            if (H % 4 == 0 && n == N && c0 >= c.zx0 && !((uintptr_t)q & 15)) {
+#pragma unroll
+                for (int g = 0; g < H / 4; ++g) {
+                    const i32x4 u = ((const i32x4 *)q)[g];
+                    s[4 * g] = u.x; s[4 * g + 1] = u.y; s[4 * g + 2] = u.z; s[4 * g + 3] = u.w;
+                }
+                s[H] = odd ? q[H] : 0;
+                inv_plain_run<NS>(s, c.irrev, c.shift, c.mn, c.mx);
+            } else {
+#pragma unroll
+                for (int j = 0; j < NS; ++j) s[j] = c0 + j >= c.zx0 && j <= last ? q[j] : 0;
+                inv_plain_run<NS>(s, c.irrev, c.shift, c.mn, c.mx);
+#pragma unroll
+                for (int j = 0; j < NS; ++j) s[j] = c0 + j >= c.zx0 ? s[j] : 0;  // the zero lead-in
+            }
+        } else {
+            const int64_t b = (int64_t)(row - c.gy0) * c.stride + (c0 - c.gx0);
+#pragma unroll
+            for (int j = 0; j < NS; ++j) s[j] = c0 + j >= c.zx0 && j <= last ? (int32_t)((const T *)c.src)[b + j] : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[k][i] = odd ? s[(i + 1) >> 1] : s[i >> 1];
+    }
+    if constexpr (IL) {
+        int32_t px[N * 3];
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) px[i * 3 + k] = v[k][i];
+        store_samples<T, N * 3>((T *)dst.p[0] + drow + (size_t)x0 * 3, px, n * 3);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) store_samples<T, N>((T *)dst.p[k] + drow + x0, v[k], n);
+    }
+}
+
+// any component count and any dx / dy in 1 .. 255: one thread per pixel, one store per sample
+template <typename T>
+__global__ void k_upsample_any(UpPlan p, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                               DstPlanes dst, int32_t il, uint32_t dstride) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w || y >= h) return;
+    const uint32_t X = X0 + x, Y = Y0 + y;
+    const size_t drow = (size_t)y * dstride;
+    for (uint32_t k = 0; k < ncomp; ++k) {
+        const UpComp &c = p.c[k];
+        const int32_t v = up_sample<T>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy));
+        T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * ncomp + k : (T *)dst.p[k] + drow + x;
+        __builtin_nontemporal_store((T)v, d);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // DC shift + forward MCT from the layouts a producer of frames holds: pixel-
 // interleaved samples (image loaders, video capture, the PPM raster) and
 // big-endian 16-bit samples (the 16-bit PGM / PPM raster) -- the mirror image
@@ -1375,6 +1499,45 @@ hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uin
         default: return hipErrorInvalidValue;
     }
 #undef GRK_INV
+    return hipGetLastError();
+}
+
+template <typename T, bool FAST>
+static void launch_up(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                      const DstPlanes &dst, bool interleaved, uint32_t dstride, hipStream_t s) {
+    const UpComp *c = src.c;
+    if constexpr (FAST) {
+        if (ncomp == 3 && c[0].dx == 1 && c[0].dy == 1 && c[1].dx == 2 && c[2].dx == 2 && c[1].dy == c[2].dy &&
+            (c[1].dy == 1 || c[1].dy == 2)) {
+            const uint32_t runs = (uint32_t)(((uint64_t)w + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
+            const dim3 grid((runs + 255) / 256, h);
+            if (interleaved)
+                hipLaunchKernelGGL((k_upsample_420<T, true>), grid, dim3(256), 0, s, src, X0, Y0, w, h, dst, dstride);
+            else
+                hipLaunchKernelGGL((k_upsample_420<T, false>), grid, dim3(256), 0, s, src, X0, Y0, w, h, dst, dstride);
+            return;
+        }
+    }
+    hipLaunchKernelGGL(k_upsample_any<T>, dim3((w + 255) / 256, h), dim3(256), 0, s, src, ncomp, X0, Y0, w, h, dst,
+                       interleaved ? 1 : 0, dstride);
+}
+
+hipError_t launch_upsample_to(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                              const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride, hipStream_t s) {
+    if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS) return hipErrorInvalidValue;
+    for (uint32_t k = 0; k < ncomp; ++k)
+        if (!src.c[k].dx || !src.c[k].dy) return hipErrorInvalidValue;
+    if (!w || !h) return hipSuccess;
+#define GRK_UP(T, FAST) launch_up<T, FAST>(src, ncomp, X0, Y0, w, h, dst, interleaved, dstride, s)
+    switch (fmt) {
+        case SMP_I32: GRK_UP(int32_t, true); break;
+        case SMP_U8: GRK_UP(uint8_t, true); break;
+        case SMP_I8: GRK_UP(int8_t, false); break;
+        case SMP_U16: GRK_UP(uint16_t, true); break;
+        case SMP_I16: GRK_UP(int16_t, false); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_UP
     return hipGetLastError();
 }
 

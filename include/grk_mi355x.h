@@ -549,12 +549,29 @@ int grkgpu_decompress_tiles(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, uint
  * image's zero margin included.
  * p = NULL: whole image, all layers.  tile_begin / tile_end = 0, 0xffffffff:
  * every tile; a proper range has grkgpu_decompress_tiles' rules (no reduce /
- * window, the other tiles' samples untouched). */
+ * window, the other tiles' samples untouched).
+ *
+ * layout | GRKGPU_LAYOUT_UPSAMPLE (grk_decompress -u, upsample_image_components,
+ * grk_decompress.cpp:891-1040): every subsampled component is replicated to
+ * the image grid by the store of the last decode kernel, so a 4:2:0 / 4:2:2
+ * stream decodes to full-size planes or to (y, x, c) pixels of numcomps
+ * samples (the one-grid rule above no longer applies).  With O = [ox0, ox1) x
+ * [oy0, oy1) the image, or the decode window clipped to it, and P_k the plane
+ * component k (dx, dy) decodes to without the flag, the sample at (X, Y) in O
+ * is P_k[floor(Y / dy) - ceil(oy0 / dy)][floor(X / dx) - ceil(ox0 / dx)], or 0
+ * where an index is negative (an origin that is no multiple of dx / dy: the
+ * reference's zero lead-in).  Components all subsampled alike are expanded
+ * after their inverse MCT.  Every sample format, host or device planes, window
+ * and cp_layer; cp_reduce > 0 on a stream with a subsampled component is
+ * GRKGPU_EINVAL (the reference refuses -u with -r), a proper tile range stays
+ * GRKGPU_EUNSUPPORTED.  img receives O with dx = dy = 1.  On a stream without
+ * subsampled components the flag changes nothing. */
 enum { GRKGPU_LAYOUT_PLANAR = 0, GRKGPU_LAYOUT_INTERLEAVED = 1 };
+#define GRKGPU_LAYOUT_UPSAMPLE 0x100u
 typedef struct {
     void *planes[GRKGPU_MAX_COMPS]; /* planar: one per component; interleaved: planes[0] */
     uint32_t sample_fmt;            /* GRKGPU_SAMPLE_* */
-    uint32_t layout;                /* GRKGPU_LAYOUT_* */
+    uint32_t layout;                /* GRKGPU_LAYOUT_* | GRKGPU_LAYOUT_UPSAMPLE */
     int32_t on_device;
     uint32_t pad_;
 } grkgpu_out_planes;
@@ -594,6 +611,18 @@ int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t numcomps, uint
                               uint32_t src_stride, const uint32_t *prec, const int32_t *sgnd, int32_t mct,
                               int32_t irreversible, const grkgpu_out_planes *dst, uint32_t dst_stride,
                               void *stream);
+/* The upsampling store of grkgpu_decompress_to (GRKGPU_LAYOUT_UPSAMPLE) on its
+ * own -- the kernels the decode runs, fed finished samples: src[k] = device
+ * plane of component k on its own grid, [ceil(x0 / dx[k]), ceil(x1 / dx[k])) x
+ * [ceil(y0 / dy[k]), ceil(y1 / dy[k])), samples of dst's format, rows
+ * src_stride[k] samples apart, starting at any sample; dx / dy in 1 .. 255.
+ * dst (planar or interleaved; on_device is not read, the upsample flag may be
+ * set or not) receives the rectangle [x0, x1) x [y0, y1) of the reference
+ * grid by grkgpu_decompress_to's rule, rows dst_stride samples apart (>= x1 -
+ * x0, interleaved >= (x1 - x0) * numcomps), starting at any sample. */
+int grkgpu_upsample_to(const void *const *src, const uint32_t *src_stride, uint32_t numcomps, const uint32_t *dx,
+                       const uint32_t *dy, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                       const grkgpu_out_planes *dst, uint32_t dst_stride, void *stream);
 /* grkgpu_dcshift_mct_fwd out of place, from the sample format and layout of
  * src (the first kernel of grkgpu_compress_ex on its own; the counterpart of
  * grkgpu_mct_inv_dcshift_to): src->planes are device pointers (on_device, row0
