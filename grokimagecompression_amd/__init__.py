@@ -361,13 +361,26 @@ def _buf_ptr(buf):
 PART_TILES, PART_HEADER, PART_EOC, PART_ALL = 0, 1, 2, 3
 
 
+def _per_comp(v, c):
+    """prec / sgnd as one value per component: a scalar for all c, or a sequence of c."""
+    if isinstance(v, (list, tuple, np.ndarray)):
+        if len(v) != c:
+            raise GrkGpuError("one value per component (got %d for %d components)" % (len(v), c))
+        return [int(x) for x in v]
+    return [int(v)] * c
+
+
 def _fmt_fits(fmt, prec, sgnd):
     """Can samples of format fmt carry a (prec, sgnd) component at their own
-    width (grkgpu_compress_ex's rule)?  Otherwise the caller widens to int32."""
+    width (grkgpu_compress_ex's rule)?  Otherwise the caller widens to int32.
+    prec / sgnd sequences (one entry per component): every component must fit."""
     if fmt == SAMPLE_I32:
         return True
     bits = 8 if fmt in (SAMPLE_U8, SAMPLE_I8) else 16
     signed = fmt in (SAMPLE_I8, SAMPLE_I16)
+    if isinstance(prec, (list, tuple, np.ndarray)) or isinstance(sgnd, (list, tuple, np.ndarray)):
+        n = len(prec) if isinstance(prec, (list, tuple, np.ndarray)) else len(sgnd)
+        return all(bool(s) == signed and p <= bits for p, s in zip(_per_comp(prec, n), _per_comp(sgnd, n)))
     return bool(sgnd) == signed and prec <= bits
 
 
@@ -603,9 +616,9 @@ class Codec:
         d.x0, d.y0 = offset
         d.x1, d.y1 = offset[0] + w, offset[1] + h
         d.numcomps = c
-        for k in range(c):
-            d.prec[k] = prec
-            d.sgnd[k] = 1 if sgnd else 0
+        for k, (pk, sk) in enumerate(zip(_per_comp(prec, c), _per_comp(sgnd, c))):
+            d.prec[k] = pk
+            d.sgnd[k] = 1 if sk else 0
         on_dev = False
         if is_tensor:
             torch = _torch()
@@ -631,7 +644,8 @@ class Codec:
         frames -- contiguous, read in place by the first kernel (no permute,
         no host copy).  numpy '>u2' / '>i2' arrays are read big-endian as they
         are.  The codestream does not depend on the dtype or layout the
-        samples arrive in.  Returns the .j2k codestream as
+        samples arrive in.  prec / sgnd: one value for every component, or
+        a sequence with one entry per component.  Returns the .j2k codestream as
         bytes, or (view=True) as a zero-copy numpy uint8 view of the context's
         pinned output buffer, valid for as long as the view lives (_CtxView)."""
         return self.compress_tiles(img, prec, params or CParams.make(), 0, 0xFFFFFFFF, PART_ALL, offset, sgnd,

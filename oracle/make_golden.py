@@ -254,13 +254,14 @@ def build_ref():
     subprocess.run(["make", "-s", "-f", "oracle/ref.mk", "-j8"], cwd=ROOT, check=True)
 
 
-def ref_encode(img, bits, args, tmp, signed=False):
+def ref_encode(img, bits, args, tmp, signed=False, stderr=None):
+    """stderr=subprocess.PIPE: a refusal's message arrives in the CalledProcessError"""
     c, h, w = img.shape
     src = os.path.join(tmp, "in.i32")
     out = os.path.join(tmp, "out.j2k")
     np.ascontiguousarray(img, dtype="<i4").tofile(src)
     subprocess.run([DRIVER, "enc", src, out, str(w), str(h), str(c), str(bits), str(int(signed))] + list(args),
-                   check=True, stdout=subprocess.DEVNULL)
+                   check=True, stdout=subprocess.DEVNULL, stderr=stderr, text=True)
     with open(out, "rb") as f:
         return f.read()
 

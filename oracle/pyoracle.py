@@ -120,16 +120,19 @@ def image_offset_from_args(args):
 
 
 def encode(img, prec, p, offset=(0, 0), sgnd=False):
-    """img: (c,h,w) int32 -> bytes"""
+    """img: (c,h,w) int32 -> bytes; prec / sgnd: one value, or one per component"""
     img = np.ascontiguousarray(img, dtype=np.int32)
     c, h, w = img.shape
     oi = OrcImage()
     oi.x0, oi.y0 = offset
     oi.x1, oi.y1 = offset[0] + w, offset[1] + h
     oi.numcomps = c
+    precs = list(prec) if isinstance(prec, (list, tuple)) else [prec] * c
+    sgnds = list(sgnd) if isinstance(sgnd, (list, tuple)) else [sgnd] * c
+    assert len(precs) == c and len(sgnds) == c
     for k in range(c):
-        oi.prec[k] = prec
-        oi.sgnd[k] = 1 if sgnd else 0
+        oi.prec[k] = precs[k]
+        oi.sgnd[k] = 1 if sgnds[k] else 0
         oi.data[k] = img[k].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
     out = ctypes.POINTER(ctypes.c_uint8)()
     n = ctypes.c_size_t()

@@ -22,7 +22,7 @@
 //           grk_end_decompress (grk_decompress.cpp:1427-1530).
 //
 // usage:
-//   ref_driver enc IN.i32 OUT.j2k W H C BITS SGND [options]
+//   ref_driver enc IN.i32 OUT.j2k W H C BITS SGND [options] [-prec a,b,...] [-sgnd a,b,...]
 //   ref_driver dec IN.j2k OUT.i32 [-r reduce] [-l layers] [-d x0,y0,x1,y1]
 //   ref_driver bench IN.i32 W H C BITS SGND THREADS REPS [options]   (enc+dec timing)
 //   ref_driver plugin PLUGIN_DIR IN.i32 OUT.j2k W H C BITS [options]
@@ -121,6 +121,19 @@ static std::vector<std::pair<uint32_t, uint32_t>> g_sub;
 // row-major n x n encoding matrix and n DC shifts
 static std::vector<float> g_mct;
 static std::vector<int32_t> g_mct_shift;
+// -prec a,b,... / -sgnd a,b,...: per-component precision / signedness of the
+// grk_image the driver builds (grk_image_cmptparm prec / sgnd), overriding
+// the single BITS / SGND for the components listed
+static std::vector<uint32_t> g_prec, g_sgnd;
+
+static void parse_list(const char *s, std::vector<uint32_t> &out) {
+    out.clear();
+    while (*s) {
+        out.push_back((uint32_t)strtoul(s, (char **)&s, 10));
+        if (*s == ',') s++;
+        else break;
+    }
+}
 
 // grk_compress option subset -> parameters (citations in the header)
 static bool parse_enc_opts(grk_cparameters *p, int argc, char **argv) {
@@ -157,6 +170,8 @@ static bool parse_enc_opts(grk_cparameters *p, int argc, char **argv) {
                 else break;
             }
         }
+        else if (a == "-prec") parse_list(v, g_prec);
+        else if (a == "-sgnd") parse_list(v, g_sgnd);
         else if (a == "-sub") {
             g_sub.clear();
             const char *s = v;
@@ -261,8 +276,8 @@ static grk_image *make_image(const int32_t *planes, uint32_t w, uint32_t h, uint
     std::vector<grk_image_cmptparm> cm(c);
     memset(cm.data(), 0, c * sizeof(grk_image_cmptparm));
     for (uint32_t k = 0; k < c; ++k) {
-        cm[k].prec = bits;
-        cm[k].sgnd = sgnd;
+        cm[k].prec = k < g_prec.size() ? g_prec[k] : bits;
+        cm[k].sgnd = k < g_sgnd.size() ? g_sgnd[k] : sgnd;
         cm[k].dx = k < g_sub.size() ? g_sub[k].first : 1;
         cm[k].dy = k < g_sub.size() ? g_sub[k].second : 1;
         comp_size(p, w, h, k, &cm[k].w, &cm[k].h);

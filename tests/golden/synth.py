@@ -71,6 +71,12 @@ def synth_image(h, w, ncomp, bits, seed, kind="smooth", signed=False):
     return np.stack([synth_plane(h, w, bits, seed, c, kind, signed) for c in range(ncomp)])
 
 
+def synth_image_mixed(h, w, precs, sgnds, seed, kind="smooth"):
+    """(len(precs), h, w) int32 planar image whose component k has precs[k]
+    bits and is signed where sgnds[k]; with equal entries it is synth_image's."""
+    return np.stack([synth_plane(h, w, p, seed, c, kind, bool(s)) for c, (p, s) in enumerate(zip(precs, sgnds))])
+
+
 def image_sha256(img):
     return hashlib.sha256(np.ascontiguousarray(img, dtype=np.int32).tobytes()).hexdigest()
 

@@ -19,6 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import prec_fixtures
 import synth
 from conftest import GOLD, ROOT, load_manifest
 
@@ -143,6 +144,37 @@ def test_grk_api_decode_matches_reference(name, tmp_path):
     h, w, c, bits = m["shape"]
     ox, oy = map(int, m["args"][m["args"].index("-d") + 1].split(",")) if "-d" in m["args"] else (0, 0)
     assert hdr == (ox, oy, ox + w, oy + h, bits, 0)
+
+
+# the grk_* API picks its sample width from prec and sgnd ((prec + 7) >> 3): the p_* family's corners
+PREC_CASES = ["p_g1u_I", "p_rgb7s", "p_rgb9s_I", "p_x_rgb16s_uni_I_r4", "p_x_c4_8u", "p_x_c2_10s_I"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", PREC_CASES)
+def test_grk_api_encode_matches_reference_precisions(name, tmp_path):
+    _need_driver()
+    m = prec_fixtures.PREC[name]
+    h, w, c, bits = m["shape"]
+    assert "prec" not in m and m.get("ref_enc") != "refused"
+    src, out = tmp_path / "in.i32", tmp_path / "out.j2k"
+    np.ascontiguousarray(prec_fixtures.image(m), dtype="<i4").tofile(src)
+    r = subprocess.run([DRIVER, "enc", str(src), str(out), str(w), str(h), str(c), str(bits), str(int(m["signed"]))] +
+                       m["args"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert out.read_bytes() == prec_fixtures.stream(name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", PREC_CASES)
+def test_grk_api_decode_matches_reference_precisions(name, tmp_path):
+    _need_driver()
+    m = prec_fixtures.PREC[name]
+    h, w, c, bits = m["shape"]
+    d, hdr = _dec(name, tmp_path)
+    ref = prec_fixtures.ref_decode(name)
+    assert d.shape == ref.shape and np.array_equal(d, ref)
+    assert hdr == (0, 0, w, h, bits, int(m["signed"]))
 
 
 @pytest.mark.gpu

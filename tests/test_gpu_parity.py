@@ -547,6 +547,28 @@ def test_mct_stage_vs_oracle(oracle, irrev):
     assert np.array_equal(t.cpu().numpy(), np.stack(ref))
 
 
+@pytest.mark.parametrize("sgnd", [False, True])
+@pytest.mark.parametrize("prec", [1, 2, 7, 9, 15, 16])
+def test_mct_stage_vs_oracle_precisions(oracle, prec, sgnd):
+    """The forward DC shift (0 for signed samples, 2^(prec-1) otherwise) + MCT
+    on full-range samples of the narrowest and widest precisions: RCT, ICT,
+    and the shift alone on two planes (5/3 and the 9/7 path's << 11)."""
+    import torch
+    import grokimagecompression_amd as grk
+    shift = 0 if sgnd else 1 << (prec - 1)
+    img = synth.synth_image(61, 129, 3, prec, 50 + prec, "uniform", signed=sgnd)
+    lo = -(1 << (prec - 1)) if sgnd else 0
+    hi = lo + (1 << prec) - 1
+    img[:, 0, 0], img[:, 0, 1], img[:, 0, 2], img[:, 0, 3] = lo, hi, (lo, hi, lo), (hi, lo, hi)  # the range's corners
+    for planes, mct, irrev in ((img, 1, False), (img, 1, True), (img[:2], 0, False), (img[:2], 0, True)):
+        c = len(planes)
+        ref = oracle.dcshift_mct_fwd(list(planes), [shift] * c, mct, irrev)
+        t = torch.from_numpy(np.ascontiguousarray(planes)).cuda()
+        grk.dcshift_mct_fwd(t, [shift] * c, mct, irrev)
+        torch.cuda.synchronize()
+        assert np.array_equal(t.cpu().numpy(), np.stack(ref)), (c, mct, irrev)
+
+
 @pytest.mark.parametrize("name", ["C1_512_gray8", "C2_4k_rgb8", "C3_8k_rgb12_I", "C3_8k_rgb12", "C3_8k_rgb12_I_r20",
                                   "C5_dci4k_rgb12_cinema", "C5b_dci2k_rgb12_cinema",
                                   "C3_8k_rgb12_I_uniform", "C3_8k_rgb12_uniform", "C3_8k_rgb12_I_const",

@@ -176,14 +176,20 @@ def test_t1_decode_blocks_vs_oracle(oracle, seed):
         assert np.array_equal(o, r), (i, items[i][1:6])
 
 
-def _ict_inv_ref(yuv, prec):
+def _range(prec, sgnd):
+    """(DC shift, minimum, maximum) of a component (TileProcessor.cpp:1303-1432)."""
+    return (0, -(1 << (prec - 1)), (1 << (prec - 1)) - 1) if sgnd else (1 << (prec - 1), 0, (1 << prec) - 1)
+
+
+def _ict_inv_ref(yuv, prec, sgnd=False):
     y, u, v = [p.view(np.float32) for p in yuv]
     f = np.float32
     r = y + v * f(1.402)
     g = (y - u * f(0.34413)) - v * f(0.71414)
     b = y + u * f(1.772)
-    out = [np.rint(c).astype(np.int32) + (1 << (prec - 1)) for c in (r, g, b)]
-    return [np.clip(c, 0, (1 << prec) - 1) for c in out]
+    shift, lo, hi = _range(prec, sgnd)
+    out = [np.rint(c).astype(np.int32) + shift for c in (r, g, b)]
+    return [np.clip(c, lo, hi) for c in out]
 
 
 @pytest.mark.parametrize("prec", [8, 12])
@@ -212,3 +218,37 @@ def test_mct_inv_dcshift(oracle, prec):
     t = torch.from_numpy(planes.copy()).cuda()
     grk.mct_inv_dcshift(t, prec, False, 0, False)
     assert np.array_equal(t.cpu().numpy(), np.clip(planes + shift, 0, (1 << prec) - 1))
+
+
+@pytest.mark.parametrize("sgnd", [False, True])
+@pytest.mark.parametrize("prec", range(1, 17))
+def test_mct_inv_dcshift_every_precision(oracle, prec, sgnd):
+    """Every precision, signed (shift 0, clamp [-2^(prec-1), 2^(prec-1) - 1])
+    and unsigned: RCT round trip of a full-range image, ICT of float planes as
+    wide as the range against the restatement -- which reaches both clamps --
+    and the shift + clamp alone on two planes."""
+    import torch
+    import grokimagecompression_amd as grk
+    import synth
+    shift, lo, hi = _range(prec, sgnd)
+    img = synth.synth_image(37, 53, 3, prec, 40 + prec, "uniform", signed=sgnd)
+    img[:, 0, 0], img[:, 0, 1], img[:, 0, 2], img[:, 0, 3] = lo, hi, (lo, hi, lo), (hi, lo, hi)  # the range's corners
+    fwd = oracle.dcshift_mct_fwd(list(img), [shift] * 3, 1, False)
+    t = torch.from_numpy(np.stack(fwd)).cuda()
+    grk.mct_inv_dcshift(t, prec, sgnd, 1, False)
+    assert np.array_equal(t.cpu().numpy(), img)
+    rng = np.random.default_rng(100 + 2 * prec + sgnd)
+    yuv = [(rng.standard_normal((37, 53)) * (1 << (prec - 1))).astype(np.float32) for _ in range(3)]
+    yuv[0] += np.float32(0.37)
+    raw = [p.view(np.int32) for p in yuv]
+    ref = np.stack(_ict_inv_ref(raw, prec, sgnd))
+    assert all((ref[k] == lo).any() and (ref[k] == hi).any() for k in range(3))  # both clamps work
+    t = torch.from_numpy(np.stack(raw)).cuda()
+    grk.mct_inv_dcshift(t, prec, sgnd, 1, True)
+    assert np.array_equal(t.cpu().numpy(), ref)
+    planes = rng.integers(-(1 << prec), 1 << prec, size=(2, 37, 53)).astype(np.int32)
+    want = np.clip(planes + shift, lo, hi)
+    assert (want == lo).any() and (want == hi).any() and ((want > lo) & (want < hi)).any() == (prec > 1)
+    t = torch.from_numpy(planes.copy()).cuda()
+    grk.mct_inv_dcshift(t, prec, sgnd, 0, False)
+    assert np.array_equal(t.cpu().numpy(), want)

@@ -9,6 +9,7 @@ import hashlib
 import numpy as np
 import pytest
 
+import prec_fixtures
 import synth
 from conftest import GOLD, load_manifest, oracle_supported
 
@@ -35,6 +36,47 @@ def test_oracle_decode_matches_reference(oracle, name):
     d = oracle.decode(gold, nthreads=4)
     assert d.shape == ref.shape
     assert np.array_equal(d, ref)
+
+
+PMAN = {k: v for k, v in prec_fixtures.PREC.items() if oracle_supported(v["args"])}
+
+
+@pytest.mark.parametrize("name", sorted(PMAN))
+def test_oracle_encode_matches_precision_fixtures(oracle, name):
+    """The p_* family (oracle/make_golden_prec.py): every precision 1 .. 16,
+    signed samples, 2 / 4 components, components of mixed precision and sign.
+    Where the reference refuses the image ("ref_enc": "refused") the fixture IS
+    the oracle's stream; its decode below is still the reference's."""
+    m = PMAN[name]
+    p = oracle.params_from_args(m["args"], nthreads=4)
+    b = oracle.encode(prec_fixtures.image(m), prec_fixtures.precs(m), p, sgnd=prec_fixtures.sgnds(m))
+    gold = prec_fixtures.stream(name)
+    assert hashlib.sha256(gold).hexdigest() == m["j2k_sha256"] and len(gold) == m["j2k_len"]
+    assert b == gold
+
+
+@pytest.mark.parametrize("name", sorted(PMAN))
+def test_oracle_decode_matches_precision_fixtures(oracle, name):
+    ref = prec_fixtures.ref_decode(name)
+    d = oracle.decode(prec_fixtures.stream(name), nthreads=4)
+    assert d.shape == ref.shape
+    assert np.array_equal(d, ref)
+
+
+def test_precision_fixtures_reach_the_clamps():
+    """A clamp is tested only by a decode that reaches it: lossy 9/7 decodes
+    holding both ends of the range exist for signed and unsigned, gray and
+    ICT images; and every family is present."""
+    P = prec_fixtures.PREC
+    for signed in (False, True):
+        for c in (1, 3):
+            both = [n for n, m in P.items() if m["clamp_hits"] == [True, True] and m["dec_vs_src_maxabs"]
+                    and m["signed"] == signed and m["shape"][2] == c and "prec" not in m and "-I" in m["args"]]
+            assert len(both) >= 3, (signed, c, both)
+    gray = {(m["shape"][3], m["signed"], "-I" in m["args"]) for m in P.values() if m["shape"][2] == 1}
+    assert all((p, s, i) in gray for p in range(1, 17) for s in (False, True) for i in (False, True))
+    assert {m["shape"][2] for m in P.values()} == {1, 2, 3, 4, 5} and sum("prec" in m for m in P.values()) == 4
+    assert len(PMAN) >= 130
 
 
 def test_oracle_lossless_roundtrip_random(oracle):

@@ -69,6 +69,16 @@ def test_subsampled_fixtures_regenerate():
     assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
 
 
+def test_precision_fixtures_regenerate():
+    """tests/golden/p_*: every precision 1 .. 16, signed samples, 1 .. 5 and
+    mixed components, encoded and decoded by the reference
+    (oracle/make_golden_prec.py; the few busy low-precision images it refuses
+    to encode carry the oracle's stream and the reference's decode of it)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "make_golden_prec.py"), "--check"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
+
+
 def test_index_fixtures_regenerate():
     """tests/golden/cstr_index.json: the reference's grk_get_cstr_index of
     every golden (oracle/make_golden_index.py)."""
