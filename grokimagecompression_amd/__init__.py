@@ -304,6 +304,8 @@ def lib():
         L.grkgpu_give_output.argtypes = [VP, VP, ctypes.c_size_t]
         L.grkgpu_free_output.argtypes = [VP]
         L.grkgpu_free_output.restype = None
+        if hasattr(L, "grkgpu_debug_fill"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_debug_fill.argtypes = [VP, ctypes.c_int, P(ctypes.c_size_t)]
         L.grkgpu_num_tiles.argtypes = [P(ImageDesc), P(CParams), P(U32)]
         L.grkgpu_compress_tiles.argtypes = [VP, P(ImageDesc), P(CParams), P(VP), ctypes.c_int, U32, U32, U32,
                                             P(P(ctypes.c_uint8)), P(ctypes.c_size_t)]
@@ -591,6 +593,16 @@ class Codec:
         s = Stats()
         _check(lib().grkgpu_get_stats(self._ctx, ctypes.byref(s)))
         return s.as_dict()
+
+    def debug_fill(self, byte):
+        """Test hook (grkgpu_debug_fill): set every byte of every device and
+        pinned host buffer the context owns, and its kept host records, to
+        `byte`; views returned by earlier calls are invalid afterwards.  The
+        next call must give what it gives on a fresh Codec.  Returns the number
+        of bytes filled."""
+        n = ctypes.c_size_t()
+        _check(lib().grkgpu_debug_fill(self._ctx, int(byte) & 0xFF, ctypes.byref(n)))
+        return n.value
 
     def set_launch_timing(self, on=True):
         """Time every forward-DWT launch of later compress calls (HIP events)."""
@@ -1023,20 +1035,34 @@ def walk_tiles(cs):
 
 # ---- stage entry points on torch device tensors (per-kernel parity tests) ----
 
-def dwt_fwd(t, x0, y0, numres, irreversible):
-    """In-place forward DWT of a (h,w) int32 cuda tensor (Mallat layout)."""
+def _dwt_scratch(t, x0, y0, numres, scratch):
+    """The scratch of a DWT stage call: a fresh tensor, or the caller's
+    `scratch` -- a contiguous cuda tensor on t's device holding at least
+    grkgpu_dwt_scratch_bytes bytes (any dtype; its contents do not matter)."""
     torch = _torch()
     h, w = t.shape
-    scratch = torch.empty(lib().grkgpu_dwt_scratch_bytes(x0, y0, x0 + w, y0 + h, numres) // 4 + 64, dtype=torch.int32, device=t.device)
+    need = lib().grkgpu_dwt_scratch_bytes(x0, y0, x0 + w, y0 + h, numres)
+    if scratch is None:
+        return torch.empty(need // 4 + 64, dtype=torch.int32, device=t.device)
+    if (not isinstance(scratch, torch.Tensor) or not scratch.is_contiguous() or scratch.device != t.device
+            or scratch.numel() * scratch.element_size() < need or scratch.data_ptr() % 4):
+        raise GrkGpuError("dwt scratch: a contiguous tensor of >= %d bytes on %s" % (need, t.device))
+    return scratch
+
+
+def dwt_fwd(t, x0, y0, numres, irreversible, scratch=None):
+    """In-place forward DWT of a (h,w) int32 cuda tensor (Mallat layout).
+    scratch: the caller's scratch tensor (_dwt_scratch) instead of a fresh one."""
+    h, w = t.shape
+    scratch = _dwt_scratch(t, x0, y0, numres, scratch)
     _check(lib().grkgpu_dwt_fwd(t.data_ptr(), scratch.data_ptr(), x0, y0, x0 + w, y0 + h, numres,
                                 1 if irreversible else 0, _stream_handle(t.device)))
     return t
 
 
-def dwt_inv(t, x0, y0, numres, irreversible):
-    torch = _torch()
+def dwt_inv(t, x0, y0, numres, irreversible, scratch=None):
     h, w = t.shape
-    scratch = torch.empty(lib().grkgpu_dwt_scratch_bytes(x0, y0, x0 + w, y0 + h, numres) // 4 + 64, dtype=torch.int32, device=t.device)
+    scratch = _dwt_scratch(t, x0, y0, numres, scratch)
     _check(lib().grkgpu_dwt_inv(t.data_ptr(), scratch.data_ptr(), x0, y0, x0 + w, y0 + h, numres,
                                 1 if irreversible else 0, _stream_handle(t.device)))
     return t

@@ -86,27 +86,39 @@ double now_ms() {
 
 }  // namespace
 
-struct grkgpu_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+// The context's grow-only buffers.  None is ever cleared between calls (the
+// read-before-write table in DESIGN.md says why each call may rely on that),
+// so grkgpu_debug_fill must reach every one: a new buffer goes into one of
+// these two structs -- never into grkgpu_ctx itself -- and into the matching
+// list of ctx_buffers() below, whose static_asserts count the members.
+struct CtxDevBufs {
     DevBuf img, work, coef, ll, scratch, mqout, blocks, results, gather, packed, cs, sym, symoff, dwtjobs, ubuf, segs;
-    HostBuf h_results, h_packed, h_gather, h_blocks, h_out, h_symoff, h_dwtjobs, h_segs;
     DevBuf dwtjobs53;  // decode: the 5/3 tile-components' job table when 9/7 ones share the call
     DevBuf t1order;    // encode: the MQ coder's work order (keys, permutation, bucket counters)
     // encode with rate control: the pass records formed on the device
     // (launch_pass_records): per block its distortion factor and record slots
     // (in), its summary and records (out)
     DevBuf pinfo, precs;
+};
+struct CtxHostBufs {
+    HostBuf h_results, h_packed, h_gather, h_blocks, h_out, h_symoff, h_dwtjobs, h_segs;
     HostBuf h_pinfo, h_psum, h_precs;
+    HostBuf h_dwtjobs53;
+    // grkgpu_encode_blocks output (valid until the next call on the context)
+    HostBuf h_slab;
+};
+
+struct grkgpu_ctx : CtxDevBufs, CtxHostBufs {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
     // encode: the pass records of the last call, kept so that a frame of the
     // same size does not zero ~20 MB again before overwriting every record
+    // (kept host records like this one are dirtied by grkgpu_debug_fill too)
     std::vector<EncPass> enc_passes;
-    HostBuf h_dwtjobs53;
     hipEvent_t ev[8] = {};
     grkgpu_stats stats = {};
     // grkgpu_encode_blocks output (valid until the next call on the context)
-    HostBuf h_slab;
     std::vector<grkgpu_block_info> bexp;
     struct CoefRec { uint32_t tileno, compno, w, h; uint64_t off; };  // coefficient arena of each tile-component
     std::vector<CoefRec> bexp_coef;
@@ -219,6 +231,69 @@ int grkgpu_set_stream(grkgpu_ctx *c, void *stream) {
 }
 
 }  // extern "C"
+
+// Every buffer of CtxDevBufs / CtxHostBufs, for grkgpu_debug_fill.
+namespace {
+struct CtxBuffers {
+    DevBuf *dev[20];
+    HostBuf *host[13];
+};
+CtxBuffers ctx_buffers(grkgpu_ctx *c) {
+    CtxBuffers b{{&c->img, &c->work, &c->coef, &c->ll, &c->scratch, &c->mqout, &c->blocks, &c->results, &c->gather,
+                  &c->packed, &c->cs, &c->sym, &c->symoff, &c->dwtjobs, &c->ubuf, &c->segs, &c->dwtjobs53, &c->t1order,
+                  &c->pinfo, &c->precs},
+                 {&c->h_results, &c->h_packed, &c->h_gather, &c->h_blocks, &c->h_out, &c->h_symoff, &c->h_dwtjobs,
+                  &c->h_segs, &c->h_pinfo, &c->h_psum, &c->h_precs, &c->h_dwtjobs53, &c->h_slab}};
+    static_assert(sizeof(CtxDevBufs) == sizeof(b.dev) / sizeof(b.dev[0]) * sizeof(DevBuf),
+                  "a DevBuf was added to CtxDevBufs: list it in ctx_buffers()");
+    static_assert(sizeof(CtxHostBufs) == sizeof(b.host) / sizeof(b.host[0]) * sizeof(HostBuf),
+                  "a HostBuf was added to CtxHostBufs: list it in ctx_buffers()");
+    return b;
+}
+}  // namespace
+
+extern "C" int grkgpu_debug_fill(grkgpu_ctx *c, int byte, size_t *filled) {
+    if (!c) return set_err(GRKGPU_EINVAL, "null ctx");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int v = byte & 0xff;
+    size_t n = 0;
+    const CtxBuffers b = ctx_buffers(c);
+    for (DevBuf *d : b.dev) {
+        if (!d->p || !d->cap) continue;
+        HIPCHK(hipMemsetAsync(d->p, v, d->cap, c->stream));
+        n += d->cap;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    {
+        // h_out and the spares given back are the context's; a buffer taken
+        // with grkgpu_take_output is the caller's until it comes back
+        std::lock_guard<std::mutex> lk(c->out_mu);
+        for (HostBuf *h : b.host) {
+            if (!h->p || !h->cap) continue;
+            memset(h->p, v, h->cap);
+            n += h->cap;
+        }
+        for (auto &sp : c->out_spare) {
+            memset(sp.first, v, sp.second);
+            n += sp.second;
+        }
+    }
+    // kept host records: the pass records keep their count (the encode reuses
+    // them without clearing), everything a getter hands out becomes empty
+    if (!c->enc_passes.empty()) {
+        memset((void *)c->enc_passes.data(), v, c->enc_passes.size() * sizeof(EncPass));
+        n += c->enc_passes.size() * sizeof(EncPass);
+    }
+    c->bexp.clear();
+    c->bexp_coef.clear();
+    c->bexp_rate.clear();
+    c->bexp_dist.clear();
+    c->ltimes.clear();
+    c->lidx.clear();
+    if (filled) *filled = n;
+    return GRKGPU_OK;
+}
 
 namespace grkgpu {
 static DwtOptions g_dwt_opts;
@@ -632,8 +707,10 @@ static LLGeom ll_geom(const TileComp &tc) {
 struct DwtPlan {
     std::vector<std::vector<DwtJob>> levels;  // [level][job]
     std::vector<int> th;                      // window rows per level (dwt_finalize)
-    std::vector<std::pair<int32_t *, const int32_t *>> copies;  // numres == 1: dst <- src
-    uint64_t copy_elems = 0;
+    // numres == 1: dst <- src, each tile-component's own sample count (edge
+    // tiles and subsampled components are smaller than the others)
+    struct Copy1D { int32_t *dst; const int32_t *src; uint64_t elems; };
+    std::vector<Copy1D> copies;
     struct Copy2D { int32_t *dst; const int32_t *src; uint32_t dpitch, spitch, w, h; };  // elements
     std::vector<Copy2D> copies2d;  // reduced decode at resolution 0: LL band -> compact output
     bool fused0 = false;  // forward level 0 reads the image planes (DC shift + MCT fused, dwt.hip)
@@ -666,9 +743,8 @@ static void dwt_plan_tc(DwtPlan &P, const TileComp &tc, int32_t *work, int32_t *
         return;
     }
     if (tc.numres == 1) {
-        if (inverse) P.copies.push_back({work, coef});
-        else P.copies.push_back({coef, work});
-        P.copy_elems = (uint64_t)stride * rows;
+        if (inverse) P.copies.push_back({work, coef, (uint64_t)stride * rows});
+        else P.copies.push_back({coef, work, (uint64_t)stride * rows});
         return;
     }
     const LLGeom g = ll_geom(tc);
@@ -1040,7 +1116,8 @@ static void log_collect(grkgpu_ctx *c) {
 static hipError_t dwt_launch(DwtPlan &P, DevBuf &djobs, int irrev, bool inverse, hipStream_t s,
                              LaunchLog *log = nullptr) {
     for (auto &cp : P.copies) {
-        hipError_t e = hipMemcpyAsync(cp.first, cp.second, P.copy_elems * 4, hipMemcpyDeviceToDevice, s);
+        if (!cp.elems) continue;
+        hipError_t e = hipMemcpyAsync(cp.dst, cp.src, cp.elems * 4, hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) return e;
     }
     for (auto &cp : P.copies2d) {
@@ -3319,7 +3396,7 @@ static int dwt_common(int32_t *buf, int32_t *scratch, uint32_t x0, uint32_t y0, 
         HIPCHK(hipMemcpyAsync(djobs, flat.data(), flat.size() * sizeof(DwtJob), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
     }
-    for (auto &cpy : P.copies) HIPCHK(hipMemcpyAsync(cpy.first, cpy.second, P.copy_elems * 4, hipMemcpyDeviceToDevice, s));
+    for (auto &cpy : P.copies) HIPCHK(hipMemcpyAsync(cpy.dst, cpy.src, cpy.elems * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(dwt_run_levels(P, djobs, irrev, inverse, s));
     return GRKGPU_OK;
 }

@@ -313,6 +313,16 @@ int grkgpu_take_output(grkgpu_ctx *ctx, void **buf, size_t *cap);
 int grkgpu_give_output(grkgpu_ctx *ctx, void *buf, size_t cap);
 void grkgpu_free_output(void *buf);
 
+/* Test hook: after synchronising the context's stream, set every byte of every
+ * device and pinned host buffer the context owns (their whole capacity) to
+ * `byte`, and every kept host record (enc_passes, bexp*, ltimes) to that
+ * pattern or empty.  Views and pointers returned by earlier calls on the
+ * context are invalid afterwards.  Buffers taken with grkgpu_take_output are
+ * the caller's and are not touched.  Returns the number of bytes filled in
+ * *filled (may be NULL).  The next call on the context must give the result
+ * it gives on a fresh one: no call may read what it has not written. */
+int grkgpu_debug_fill(grkgpu_ctx *ctx, int byte, size_t *filled);
+
 /* Tile shards (multi-GPU): tiles are independent through the
  * whole path, and a codestream is [main header][tile-parts in tile order]
  * [EOC] (j2k.cpp:2088-2111, 2376-2435), so each GPU encodes a contiguous
