@@ -207,6 +207,33 @@ class OutPlanes(ctypes.Structure):
                 ("on_device", ctypes.c_int32), ("pad_", ctypes.c_uint32)]
 
 
+COLOUR_NONE, COLOUR_SYCC = 0, 1
+PREC_CLIP, PREC_SCALE = 0, 1
+_COLOURS = {None: COLOUR_NONE, "sycc": COLOUR_SYCC}
+_PREC_MODES = {"clip": PREC_CLIP, "scale": PREC_SCALE}
+
+
+class OutOps(ctypes.Structure):
+    """grkgpu_out_ops: the colour (COLOUR_*) and precision (prec 1 .. 16, 0 =
+    keep; prec_mode PREC_*) steps grkgpu_decompress_convert / grkgpu_convert_to
+    apply in their store."""
+    _fields_ = [("colour", ctypes.c_uint32), ("prec", ctypes.c_uint32), ("prec_mode", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def _out_ops(colour, out_prec, prec_mode):
+    """OutOps of decompress / convert_to's arguments (None: no conversion asked for)."""
+    if colour not in _COLOURS:
+        raise GrkGpuError("colour must be None or 'sycc' (got %r)" % (colour,))
+    if prec_mode not in _PREC_MODES:
+        raise GrkGpuError("prec_mode must be 'clip' or 'scale' (got %r)" % (prec_mode,))
+    if out_prec is not None and not 1 <= int(out_prec) <= 16:
+        raise GrkGpuError("out_prec must be 1 .. 16 (got %r)" % (out_prec,))
+    if colour is None and out_prec is None:
+        return None
+    return OutOps(colour=_COLOURS[colour], prec=int(out_prec or 0), prec_mode=_PREC_MODES[prec_mode])
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("h2d_ms", ctypes.c_float), ("dcshift_mct_ms", ctypes.c_float), ("dwt_ms", ctypes.c_float),
                 ("t1_ms", ctypes.c_float), ("gather_ms", ctypes.c_float), ("d2h_ms", ctypes.c_float),
@@ -323,6 +350,11 @@ def lib():
         if hasattr(L, "grkgpu_upsample_to"):  # not in an older library given by GRKGPU_LIB (A/B runs)
             L.grkgpu_upsample_to.argtypes = [P(VP), P(U32), U32, P(U32), P(U32), U32, U32, U32, U32, P(OutPlanes),
                                              U32, VP]
+        if hasattr(L, "grkgpu_decompress_convert"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_decompress_convert.argtypes = [VP, VP, ctypes.c_size_t, P(DParams), U32, U32, P(ImageDesc),
+                                                    P(OutPlanes), P(OutOps)]
+            L.grkgpu_convert_to.argtypes = [P(VP), P(U32), U32, U32, P(U32), P(U32), P(U32), P(I32), U32, U32, U32,
+                                            U32, P(OutPlanes), U32, P(OutOps), VP]
         L.grkgpu_dcshift_mct_fwd.argtypes = [P(VP), U32, U32, U32, U32, P(I32), I32, I32, VP]
         L.grkgpu_mct_inv_dcshift.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), I32, I32, VP]
         L.grkgpu_dwt_fwd.argtypes = [VP, VP, U32, U32, U32, U32, U32, I32, VP]
@@ -765,8 +797,17 @@ class Codec:
         _check(lib().grkgpu_decompress_tiles(self._ctx, bp, bn, tile_begin, tile_end, ptrs, 1 if on_dev else 0))
         return out
 
+    def _decode_to(self, bp, bn, dp, op, ops):
+        """grkgpu_decompress_to, or grkgpu_decompress_convert when output ops are asked for."""
+        if ops is None:
+            _check(lib().grkgpu_decompress_to(self._ctx, bp, bn, ctypes.byref(dp), 0, 0xFFFFFFFF, None,
+                                              ctypes.byref(op)))
+        else:
+            _check(lib().grkgpu_decompress_convert(self._ctx, bp, bn, ctypes.byref(dp), 0, 0xFFFFFFFF, None,
+                                                   ctypes.byref(op), ctypes.byref(ops)))
+
     def decompress(self, buf, device_out=False, out=None, reduce=0, window=None, layers=0, dtype=None, layout="chw",
-                   upsample=False):
+                   upsample=False, colour=None, out_prec=None, prec_mode="clip"):
         """Decode a .j2k codestream -> (c,h,w) int32 (numpy, or torch.cuda when
         device_out / out is a cuda tensor).  dtype = uint8 / int8 / uint16 /
         int16: samples of that type, stored by the last decode kernel (the
@@ -785,7 +826,15 @@ class Codec:
         is the component's sample (floor(X / dx) - ceil(x0 / dx), floor(Y / dy)
         - ceil(y0 / dy)) with (x0, y0) the image's or window's origin, zero
         where that index is negative.  Without subsampled components
-        upsample changes nothing."""
+        upsample changes nothing.
+        colour="sycc" (grk_decompress's sYCC -> RGB step, color_sycc_to_rgb): a
+        3-component unsigned 4:4:4 / 4:2:2 / 4:2:0 stream comes back as R, G, B
+        (implies upsample=True).  out_prec = 1 .. 16 (grk_decompress -p): every
+        component at that precision, prec_mode "clip" or "scale"; dtype / out
+        then have to hold the output precision, so a 12-bit stream decodes to
+        uint8 with out_prec=8.  Both run in the last decode kernel's store
+        (grkgpu_decompress_convert, include/grk_mi355x.h has the closed forms)."""
+        ops = _out_ops(colour, out_prec, prec_mode)
         d = read_header(buf)
         if window is not None:  # the window (reference grid) clipped to the image
             wx0, wy0, wx1, wy1 = window
@@ -813,8 +862,14 @@ class Codec:
                 raise GrkGpuError("out holds %s samples, dtype asks for %s" % (_out_dtype(out).name, dt.name))
             dt, fmt = _out_format(_out_dtype(out))
         shape = _layout_shape((c, h, w), layout)
-        narrow = fmt != SAMPLE_I32 or layout != "chw"  # grkgpu_decompress_to; else today's entry points
-        up = bool(upsample) and any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c))
+        if ops is not None:  # the output's precision, not the stream's, is what the samples must hold
+            oprec = [ops.prec or d.prec[k] for k in range(c)]
+            if not _fmt_fits(fmt, oprec, [d.sgnd[k] for k in range(c)]):
+                raise GrkGpuError("%s samples do not hold the output precision / signedness (%s bits)"
+                                  % (dt.name, "/".join(str(v) for v in oprec)))
+        # grkgpu_decompress_to / _convert; else today's entry points
+        narrow = fmt != SAMPLE_I32 or layout != "chw" or ops is not None
+        up = (bool(upsample) or colour == "sycc") and any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c))
         if not up and any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)):
             # subsampled components: a list of host planes, each on its grid
             if out is not None or device_out:
@@ -833,8 +888,7 @@ class Codec:
                 # (the library refuses before it touches the planes)
                 op = self._out_planes(outs, c, fmt, "chw", False)
                 op.layout = _LAYOUTS[layout]
-                _check(lib().grkgpu_decompress_to(self._ctx, bp, bn, ctypes.byref(dp), 0, 0xFFFFFFFF, None,
-                                                  ctypes.byref(op)))
+                self._decode_to(bp, bn, dp, op, ops)
                 return outs
             _check(lib().grkgpu_decompress_ex(self._ctx, bp, bn, ctypes.byref(dp), None, ptrs, 0))
             return outs
@@ -858,8 +912,7 @@ class Codec:
             dp = DParams(cp_reduce=reduce, cp_layer=layers)
             if window is not None:
                 dp.DA_x0, dp.DA_y0, dp.DA_x1, dp.DA_y1 = [int(v) for v in window]
-            _check(lib().grkgpu_decompress_to(self._ctx, bp, bn, ctypes.byref(dp), 0, 0xFFFFFFFF, None,
-                                              ctypes.byref(op)))
+            self._decode_to(bp, bn, dp, op, ops)
             return out
         if on_dev:
             torch = _torch()
@@ -1018,6 +1071,50 @@ def upsample_to(src, dst, rect, subsampling, layout="chw", dst_stride=None):
     dys = (ctypes.c_uint32 * c)(*[s[1] for s in subsampling])
     _check(lib().grkgpu_upsample_to(ptrs, ss, c, dxs, dys, x0, y0, x1, y1, ctypes.byref(op), stride,
                                     _stream_handle(dst.device)))
+    return dst
+
+
+def convert_to(src, dst, rect, subsampling, prec, sgnd=False, layout="chw", dst_stride=None, colour=None,
+               out_prec=None, prec_mode="clip"):
+    """grkgpu_convert_to: upsample_to with the colour / precision steps of
+    Codec.decompress(colour=, out_prec=, prec_mode=) in its store.  src: one 2-D
+    cuda tensor per component on its grid (as upsample_to), all of one dtype
+    that holds every (prec, sgnd) -- it may differ from dst's, which has to hold
+    the output precision.  prec / sgnd: one value, or one per component."""
+    x0, y0, x1, y1 = rect
+    c, w, h = len(src), x1 - x0, y1 - y0
+    ops = _out_ops(colour, out_prec, prec_mode)
+    dt, fmt = _out_format(_out_dtype(dst))
+    _layout_shape((c, h, w), layout)  # refuses an unknown layout
+    cd = lambda v, s: -(-v // s)  # noqa: E731
+    if len(subsampling) != c or not 1 <= c <= MAXC or w <= 0 or h <= 0:
+        raise GrkGpuError("convert_to: one (dx, dy) per component, 1 .. %d components, a non-empty rect" % MAXC)
+    precs, sgnds = _per_comp(prec, c), _per_comp(sgnd, c)
+    sdt, sfmt = _out_format(_out_dtype(src[0]))
+    il = layout == "hwc"
+    row = w * c if il else w
+    stride = row if dst_stride is None else dst_stride
+    need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
+    if dst.dim() != 1 or not dst.is_contiguous() or not dst.is_cuda or stride < row or dst.numel() < need:
+        raise GrkGpuError("convert_to: dst flat, %d samples, on a cuda device" % need)
+    for a, (dx, dy) in zip(src, subsampling):
+        if dx < 1 or dy < 1:
+            break  # the library's refusal
+        shape = (cd(y1, dy) - cd(y0, dy), cd(x1, dx) - cd(x0, dx))
+        if (a.dtype != src[0].dtype or a.device != dst.device or tuple(a.shape) != shape
+                or (a.numel() and shape[1] > 1 and a.stride(1) != 1)):
+            raise GrkGpuError("convert_to: component plane %s %s, its grid needs %s %s on dst's device"
+                              % (tuple(a.shape), a.dtype, shape, src[0].dtype))
+    op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout] | LAYOUT_UPSAMPLE, on_device=1)
+    for k in range(1 if il else c):
+        op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
+    ptrs = (ctypes.c_void_p * c)(*[a.data_ptr() for a in src])
+    ss = (ctypes.c_uint32 * c)(*[a.stride(0) if a.shape[0] > 1 and a.numel() else max(1, a.shape[1]) for a in src])
+    dxs = (ctypes.c_uint32 * c)(*[s[0] for s in subsampling])
+    dys = (ctypes.c_uint32 * c)(*[s[1] for s in subsampling])
+    _check(lib().grkgpu_convert_to(ptrs, ss, sfmt, c, dxs, dys, (ctypes.c_uint32 * c)(*precs),
+                                   (ctypes.c_int32 * c)(*sgnds), x0, y0, x1, y1, ctypes.byref(op), stride,
+                                   ctypes.byref(ops) if ops is not None else None, _stream_handle(dst.device)))
     return dst
 
 

@@ -2413,9 +2413,79 @@ struct DecodeOut {
     int32_t interleaved;
     int on_device;
     int upsample;  // GRKGPU_LAYOUT_UPSAMPLE: subsampled components replicated to the image grid
+    const grkgpu_out_ops *ops;  // grkgpu_decompress_convert: colour / precision in the last store (null: none)
 };
 static DecodeOut i32_planes(int32_t *const *planes, int on_device) {
     return {(void *const *)planes, SMP_I32, 0, on_device};
+}
+
+// grkgpu_out_ops' own rules, checked before anything touches a device; fmt = the
+// output's sample format
+static int check_out_ops(const grkgpu_out_ops *o, uint32_t fmt) {
+    if (!o) return GRKGPU_OK;
+    if (o->colour > GRKGPU_COLOUR_SYCC) return set_err(GRKGPU_EINVAL, "unknown colour conversion");
+    if (o->prec > 16) return set_err(GRKGPU_EINVAL, "output precision must be 1 .. 16 (0: the component's own)");
+    if (o->prec && o->prec_mode > GRKGPU_PREC_SCALE) return set_err(GRKGPU_EINVAL, "unknown precision mode");
+    if (o->reserved) return set_err(GRKGPU_EINVAL, "reserved field of the output ops must be 0");
+    if (o->prec && fmt != SMP_I32 && o->prec > 8 * sample_bytes((int32_t)fmt))
+        return set_err(GRKGPU_EINVAL, "sample format does not hold the output precision");
+    return GRKGPU_OK;
+}
+static bool out_ops_active(const grkgpu_out_ops *o) { return o && (o->colour || o->prec); }
+
+// The device form of checked ops for components of (prec, sgnd, dx, dy): the
+// sYCC shape rules (color_sycc_to_rgb, color.cpp:384-418) and each component's
+// precision op (clip_component / scale_component, convert.cpp:82-161).
+// oprec[k] = the output precision.
+static int resolve_out_ops(const grkgpu_out_ops *o, uint32_t nc, const uint32_t *prec, const int32_t *sgnd,
+                           const uint32_t *dx, const uint32_t *dy, OutOps &dev, uint32_t *oprec) {
+    dev = OutOps{};
+    if (o->colour == GRKGPU_COLOUR_SYCC) {
+        if (nc != 3) return set_err(GRKGPU_EINVAL, "sYCC conversion needs exactly 3 components");
+        for (uint32_t k = 0; k < 3; ++k)
+            if (sgnd[k] || prec[k] != prec[0] || prec[k] < 1 || prec[k] > 16)
+                return set_err(GRKGPU_EINVAL, "sYCC conversion needs unsigned components of one precision (1 .. 16)");
+        const bool shape = dx[0] == 1 && dy[0] == 1 && dx[1] == dx[2] && dy[1] == dy[2] &&
+                           ((dx[1] == 1 && dy[1] == 1) || (dx[1] == 2 && (dy[1] == 1 || dy[1] == 2)));
+        if (!shape) return set_err(GRKGPU_EINVAL, "sYCC conversion needs 4:4:4, 4:2:2 or 4:2:0 subsampling");
+        dev.sycc = 1;
+        dev.off = 1 << (prec[0] - 1);
+        dev.upb = (int32_t)((1u << prec[0]) - 1);
+    }
+    for (uint32_t k = 0; k < nc; ++k) {
+        const uint32_t q = prec[k], p = o->prec;
+        PrecOp &op = dev.pc[k];
+        oprec[k] = p ? p : q;
+        if (!p || p == q) continue;
+        if (o->prec_mode == GRKGPU_PREC_CLIP) {
+            if (p > q) continue;  // every value is inside the wider range
+            op.mode = POP_CLIP;
+            op.a = sgnd[k] ? -(1 << (p - 1)) : 0;
+            op.b = sgnd[k] ? (1 << (p - 1)) - 1 : (int32_t)((1u << p) - 1);
+        } else if (p < q) {
+            op.mode = POP_SHR;
+            op.a = (int32_t)(q - p);
+        } else if (sgnd[k]) {
+            op.mode = POP_MUL;
+            op.a = 1 << (p - q);
+        } else {
+            op.mode = POP_MULDIV;
+            op.a = (int32_t)((1u << p) - 1);
+            op.b = (int32_t)((1u << q) - 1);
+        }
+    }
+    return GRKGPU_OK;
+}
+// the narrowest sample format holding every component (a staging plane that keeps the stream's precision)
+static int32_t holding_fmt(uint32_t nc, const uint32_t *prec, const int32_t *sgnd) {
+    uint32_t mp = 0;
+    bool any_s = false, any_u = false;
+    for (uint32_t k = 0; k < nc; ++k) {
+        mp = std::max(mp, prec[k]);
+        (sgnd[k] ? any_s : any_u) = true;
+    }
+    if ((any_s && any_u) || mp > 16) return SMP_I32;
+    return mp <= 8 ? (any_s ? SMP_I8 : SMP_U8) : (any_s ? SMP_I16 : SMP_U16);
 }
 
 // reduce > 0 (whole-image decode only): the image at resolution
@@ -2518,16 +2588,36 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     }
     if (subs && !whole) return set_err(GRKGPU_EUNSUPPORTED, "tile-range decode of subsampled images is not supported");
     if (win && !whole) return set_err(GRKGPU_EINVAL, "window decode of a tile range is not supported");
-    const bool up = od.upsample && subs;
+    // od.ops (grkgpu_decompress_convert): the colour and precision steps of
+    // grk_decompress in the store of the last kernel -- dops their device
+    // form, oprec the precision the samples leave with.  sYCC needs every
+    // component of the pixel, so it implies the upsampled output.
+    const bool conv = out_ops_active(od.ops);
+    const bool sycc = conv && od.ops->colour == GRKGPU_COLOUR_SYCC;
+    OutOps dops{};
+    uint32_t oprec[GRKGPU_MAX_COMPS];
+    for (uint32_t k = 0; k < nc; ++k) oprec[k] = cp.prec[k];
+    if (conv) {
+        int rc = resolve_out_ops(od.ops, nc, cp.prec, cp.sgnd, cp.dx, cp.dy, dops, oprec);
+        if (rc) return rc;
+    }
+    const bool up = (od.upsample || sycc) && subs;
     if (up && reduce)  // grk_decompress refuses -u with -r
         return set_err(GRKGPU_EINVAL, "upsampled output of a reduced decode is not supported");
     if (img && up)
         for (uint32_t k = 0; k < nc; ++k) img->dx[k] = img->dy[k] = 1;
+    if (img && conv)
+        for (uint32_t k = 0; k < nc; ++k) img->prec[k] = oprec[k];
     for (uint32_t k = 0; od.fmt != SMP_I32 && k < nc; ++k) {
         const bool sg = od.fmt == SMP_I8 || od.fmt == SMP_I16;
-        if ((cp.sgnd[k] != 0) != sg || cp.prec[k] > 8 * sb)
+        if ((cp.sgnd[k] != 0) != sg || oprec[k] > 8 * sb)
             return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
     }
+    // the staging planes of an upsampled decode keep the stream's precision:
+    // the ops run in the replicating launch, which reads one sample type and
+    // writes another (12 bits staged, 8 stored)
+    const int32_t sfmt = conv ? holding_fmt(nc, cp.prec, cp.sgnd) : od.fmt;
+    const uint32_t ssb = sample_bytes(sfmt);
     if (il && mixed && !up)
         return set_err(GRKGPU_EUNSUPPORTED, "interleaved output needs every component on one grid");
     if (il && (uint64_t)iw * nc > 0xffffffffull)  // the kernel's row stride is 32 bits of samples
@@ -2992,7 +3082,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
             for (uint32_t k = 0; k < nout; ++k) off[k + 1] = (off[k] + region_bytes(k) + 15) & ~(size_t)15;
         soff[0] = planes_on_device ? 0 : off[nout];
         for (uint32_t k = 0; k < nc; ++k)
-            soff[k + 1] = soff[k] + (staged(k) ? ((size_t)(ooff[k + 1] - ooff[k]) * sb + 15) & ~(size_t)15 : 0);
+            soff[k + 1] = soff[k] + (staged(k) ? ((size_t)(ooff[k + 1] - ooff[k]) * ssb + 15) & ~(size_t)15 : 0);
         if (soff[nc]) HIPCHK(c->img.ensure(soff[nc] + 256));
         for (uint32_t k = 0; k < nout; ++k)
             dst.p[k] = planes_on_device ? planes[k] : (void *)(c->img.as<uint8_t>() + off[k]);
@@ -3006,8 +3096,33 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     auto at = [&](uint32_t k, uint64_t elem) { return (void *)((uint8_t *)dst.p[k] + elem * eb); };
     // where the launches on the components' own grids store component k: the
     // output, or (upsampled) its staging plane
-    auto cat = [&](uint32_t k, uint64_t elem) { return up ? (void *)((uint8_t *)stg.p[k] + elem * sb) : at(k, elem); };
-    if (opad)
+    auto cat = [&](uint32_t k, uint64_t elem) { return up ? (void *)((uint8_t *)stg.p[k] + elem * ssb) : at(k, elem); };
+    // The fills below stand for samples nothing decoded: zero, which every
+    // precision op maps to zero.  The reference's colour step converts them
+    // like any other sample, so with sYCC (no subsampling here: an upsampled
+    // decode's launch writes such pixels itself, from null sources) the fill
+    // is the converting store run over zero samples -- sYCC(0, 0, 0), then
+    // the precision op -- in the output's format and layout.
+    auto fill_converted = [&](const Rect &o) -> hipError_t {
+        UpPlan zero{};
+        for (uint32_t k = 0; k < nc; ++k) zero.c[k].dx = zero.c[k].dy = 1;
+        const uint32_t ow = orect[0].w();
+        DstPlanes fdst{};
+        for (uint32_t k = 0; k < nout; ++k)
+            fdst.p[k] = at(k, (uint64_t)(o.y0 - orect[0].y0) * ow + (o.x0 - orect[0].x0));
+        return launch_upsample_ops(zero, nc, o.x0, o.y0, o.w(), o.h(), fdst, od.fmt, il, il ? ow * nc : ow, dops, s);
+    };
+    if (sycc && !up && opad) {
+        HIPCHK(fill_converted(orect[0]));
+    } else if (sycc && !up && missing) {
+        for (uint32_t t = tb; t < te; ++t) {
+            if (walk.decoded[t] || wskip[t]) continue;
+            const Rect cr = tile_rect(cp, t);
+            const Rect o = intersect({ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
+                                      ceil_pow2(cr.y1, reduce)}, orect[0]);
+            if (!o.empty()) HIPCHK(fill_converted(o));
+        }
+    } else if (opad)
         for (uint32_t k = 0; k < nout; ++k) HIPCHK(hipMemsetAsync(dst.p[k], 0, region_bytes(k), s));
     else if (missing && !up)  // tiles the tile-part walk never reached: zero (their regions only -- a shard's
                        // device planes hold other tiles)
@@ -3046,8 +3161,15 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                 sk.v[0] = sh.v[k];
                 mnk.v[0] = mn.v[k];
                 mxk.v[0] = mx.v[k];
-                HIPCHK(launch_mct_inv_dcshift_to(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, false, orect[k].w(), 1,
-                                                 sk, mnk, mxk, 0, tc.irrev, s));
+                if (conv && !up) {  // each plane on its own grid, converted
+                    OutOps ok{};
+                    ok.pc[0] = dops.pc[k];
+                    HIPCHK(launch_mct_inv_dcshift_ops(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, false,
+                                                      orect[k].w(), 1, sk, mnk, mxk, 0, tc.irrev, ok, s));
+                    continue;
+                }
+                HIPCHK(launch_mct_inv_dcshift_to(tsrc, tr.w(), out.w(), out.h(), tdst, up ? sfmt : od.fmt, false,
+                                                 orect[k].w(), 1, sk, mnk, mxk, 0, tc.irrev, s));
             }
             continue;
         }
@@ -3067,8 +3189,13 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         int32_t wmask = 0;  // components holding 9/7 (float) samples
         for (uint32_t k = 0; k < nc; ++k) wmask |= tile.comps[k].irrev << k;
         // row stride in samples: a row of an interleaved image holds ow pixels of nc samples
-        HIPCHK(launch_mct_inv_dcshift_to(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il && !up,
-                                         il && !up ? ow * nc : ow, nc, sh, mn, mx, tmct[tile.index - tb], wmask, s));
+        if (conv && !up)
+            HIPCHK(launch_mct_inv_dcshift_ops(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * nc : ow, nc,
+                                              sh, mn, mx, tmct[tile.index - tb], wmask, dops, s));
+        else
+            HIPCHK(launch_mct_inv_dcshift_to(tsrc, tr.w(), out.w(), out.h(), tdst, up ? sfmt : od.fmt, il && !up,
+                                             il && !up ? ow * nc : ow, nc, sh, mn, mx, tmct[tile.index - tb], wmask,
+                                             s));
     }
     // upsampled: the output, tile by tile (the tiles never reached included)
     for (auto &tile : tiles) {
@@ -3081,6 +3208,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
             u.dy = (uint8_t)cp.dy[k];
             if (staged(k)) {
                 u.src = stg.p[k];
+                if (conv) u.raw = (uint8_t)(UPCOMP_FIN + sfmt);  // finished samples of the staging format
                 u.stride = orect[k].w();
                 u.gx0 = (int32_t)orect[k].x0;
                 u.gy0 = (int32_t)orect[k].y0;
@@ -3104,7 +3232,12 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         }
         DstPlanes tdst{};
         for (uint32_t k = 0; k < nout; ++k) tdst.p[k] = at(k, (uint64_t)(out.y0 - iy0) * iw + (out.x0 - ix0));
-        HIPCHK(launch_upsample_to(pl, nc, out.x0, out.y0, out.w(), out.h(), tdst, od.fmt, il, il ? iw * nc : iw, s));
+        if (conv)
+            HIPCHK(launch_upsample_ops(pl, nc, out.x0, out.y0, out.w(), out.h(), tdst, od.fmt, il, il ? iw * nc : iw,
+                                       dops, s));
+        else
+            HIPCHK(launch_upsample_to(pl, nc, out.x0, out.y0, out.w(), out.h(), tdst, od.fmt, il, il ? iw * nc : iw,
+                                      s));
     }
     HIPCHK(hipEventRecord(c->ev[4], s));
     if (!planes_on_device) {
@@ -3194,20 +3327,34 @@ static int check_out_planes(const grkgpu_out_planes *out) {
     return GRKGPU_OK;
 }
 
-extern "C" int grkgpu_decompress_to(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
-                                    uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
-                                    const grkgpu_out_planes *out) {
+static int decompress_to_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
+                              uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                              const grkgpu_out_planes *out, const grkgpu_out_ops *ops) {
     int rc = check_out_planes(out);
+    if (rc) return rc;
+    rc = check_out_ops(ops, out->sample_fmt);
     if (rc) return rc;
     const DecodeOut od{out->planes, (int32_t)out->sample_fmt,
                        (out->layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED, out->on_device,
-                       (out->layout & GRKGPU_LAYOUT_UPSAMPLE) != 0};
+                       (out->layout & GRKGPU_LAYOUT_UPSAMPLE) != 0, out_ops_active(ops) ? ops : nullptr};
     if (!dp) return decompress_impl(c, csb, len, img, od, tile_begin, tile_end);
     const bool win = dp->DA_x0 || dp->DA_y0 || dp->DA_x1 || dp->DA_y1;
     const Rect w{dp->DA_x0, dp->DA_y0, dp->DA_x1, dp->DA_y1};
     if (win && (dp->DA_x1 <= dp->DA_x0 || dp->DA_y1 <= dp->DA_y0)) return set_err(GRKGPU_EINVAL, "empty decode area");
     return decompress_impl(c, csb, len, img, od, tile_begin, tile_end, dp->cp_reduce, win ? &w : nullptr,
                            dp->cp_layer);
+}
+
+extern "C" int grkgpu_decompress_to(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
+                                    uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                                    const grkgpu_out_planes *out) {
+    return decompress_to_impl(c, csb, len, dp, tile_begin, tile_end, img, out, nullptr);
+}
+
+extern "C" int grkgpu_decompress_convert(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
+                                         uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                                         const grkgpu_out_planes *out, const grkgpu_out_ops *ops) {
+    return decompress_to_impl(c, csb, len, dp, tile_begin, tile_end, img, out, ops);
 }
 
 // ---------------------------------------------------------------------------
@@ -3349,6 +3496,83 @@ extern "C" int grkgpu_upsample_to(const void *const *src, const uint32_t *src_st
     rc = check_device(-1);
     if (rc) return rc;
     HIPCHK(launch_upsample_to(pl, numcomps, x0, y0, x1 - x0, y1 - y0, d, fmt, il, dst_stride, (hipStream_t)stream));
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_stride, uint32_t src_fmt,
+                                 uint32_t numcomps, const uint32_t *dx, const uint32_t *dy, const uint32_t *prec,
+                                 const int32_t *sgnd, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                                 const grkgpu_out_planes *dst, uint32_t dst_stride, const grkgpu_out_ops *ops,
+                                 void *stream) {
+    int rc = check_out_planes(dst);
+    if (rc) return rc;
+    rc = check_out_ops(ops, dst->sample_fmt);
+    if (rc) return rc;
+    if (src_fmt > GRKGPU_SAMPLE_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    const bool il = (dst->layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED;
+    const int32_t fmt = (int32_t)dst->sample_fmt, sfmt = (int32_t)src_fmt;
+    const uint32_t sb = sample_bytes(fmt), ssb = sample_bytes(sfmt);
+    if (!src || !src_stride || !dx || !dy || !prec || !sgnd || numcomps < 1 || numcomps > 16 || x1 <= x0 ||
+        y1 <= y0 || x1 > 0x7fffffffu || y1 > 0x7fffffffu)
+        return set_err(GRKGPU_EINVAL, "bad arguments");
+    if ((uint64_t)dst_stride < (uint64_t)(x1 - x0) * (il ? numcomps : 1))
+        return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
+    bool full = true;  // every component at (1,1)
+    for (uint32_t k = 0; k < numcomps; ++k) {
+        if (dx[k] < 1 || dx[k] > 255 || dy[k] < 1 || dy[k] > 255)
+            return set_err(GRKGPU_EINVAL, "bad arguments (dx / dy must be 1 .. 255)");
+        if (prec[k] < 1 || prec[k] > 31) return set_err(GRKGPU_EINVAL, "bad arguments (prec must be 1 .. 31)");
+        const bool sg = sfmt == SMP_I8 || sfmt == SMP_I16;
+        if (sfmt != SMP_I32 && ((sgnd[k] != 0) != sg || prec[k] > 8 * ssb))
+            return set_err(GRKGPU_EINVAL, "source format does not hold the component's precision / signedness");
+        full = full && dx[k] == 1 && dy[k] == 1;
+    }
+    const grkgpu_out_ops none{};
+    OutOps dops{};
+    uint32_t oprec[GRKGPU_MAX_COMPS];
+    rc = resolve_out_ops(ops ? ops : &none, numcomps, prec, sgnd, dx, dy, dops, oprec);
+    if (rc) return rc;
+    UpPlan pl{};
+    DstPlanes d{};
+    for (uint32_t k = 0; k < numcomps; ++k) {
+        const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
+        if (fmt != SMP_I32 && ((sgnd[k] != 0) != sg || oprec[k] > 8 * sb))
+            return set_err(GRKGPU_EINVAL, "sample format does not hold the output precision / signedness");
+        const Rect cr = comp_rect({x0, y0, x1, y1}, dx[k], dy[k]);
+        if (src_stride[k] < cr.w()) return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
+        // (a grid without a sample inside the rectangle has no plane: every index is negative)
+        if ((!src[k] && !cr.empty()) || (uintptr_t)src[k] % ssb)
+            return set_err(GRKGPU_EINVAL, "null or misaligned plane");
+        pl.c[k] = UpComp{src[k], src_stride[k], (int32_t)cr.x0, (int32_t)cr.y0, (int32_t)cr.x0, (int32_t)cr.y0,
+                         (uint8_t)dx[k], (uint8_t)dy[k], (uint8_t)(UPCOMP_FIN + sfmt), 0, 0, 0, 0};
+    }
+    for (uint32_t k = 0; k < (il ? 1u : numcomps); ++k) {
+        if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
+            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+        d.p[k] = dst->planes[k];
+    }
+    rc = check_device(-1);
+    if (rc) return rc;
+    if (full && sfmt == SMP_I32) {
+        // finished int32 samples on the image grid: the inverse-MCT kernels'
+        // stores, their shift 0 and their clamp the component's own range
+        PlanePtrs p{};
+        ShiftArr sh{}, mn{}, mx{};
+        uint32_t ss = src_stride[0];
+        for (uint32_t k = 0; k < numcomps; ++k) {
+            p.p[k] = (int32_t *)const_cast<void *>(src[k]);
+            if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
+            else { mn.v[k] = 0; mx.v[k] = (int32_t)((1u << prec[k]) - 1); }
+            full = full && src_stride[k] == ss;
+        }
+        if (full) {
+            HIPCHK(launch_mct_inv_dcshift_ops(p, ss, x1 - x0, y1 - y0, d, fmt, il, dst_stride, numcomps, sh, mn, mx, 0,
+                                              0, dops, (hipStream_t)stream));
+            return GRKGPU_OK;
+        }
+    }
+    HIPCHK(launch_upsample_ops(pl, numcomps, x0, y0, x1 - x0, y1 - y0, d, fmt, il, dst_stride, dops,
+                               (hipStream_t)stream));
     return GRKGPU_OK;
 }
 

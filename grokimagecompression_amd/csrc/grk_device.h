@@ -121,6 +121,38 @@ struct UpPlan { UpComp c[GRK_MAX_COMPS]; };
 // else k_upsample_any (a thread per pixel, dx / dy 1 .. 255).
 hipError_t launch_upsample_to(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
                               const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride, hipStream_t s);
+// Output conversions of grkgpu_decompress_convert / grkgpu_convert_to, applied
+// by the last kernel to the finished int32 run values right before the store
+// (grk_decompress's colour and -p steps, color.cpp:136-418 and
+// convert.cpp:82-161): sycc != 0 turns the three components (Y, Cb, Cr;
+// unsigned, one precision, off = 2^(P-1), upb = 2^P - 1) into R, G, B; then
+// pc[k] maps component k to the output precision --
+//   POP_CLIP    clamp(v, a, b)
+//   POP_SHR     v >> a (arithmetic)
+//   POP_MULDIV  (uint32) v * a / b, the unsigned scale-up (the product fits 32 bits)
+//   POP_MUL     v * a, the signed scale-up by a power of two
+// Everything here is uniform over a launch.
+enum : int32_t { POP_NONE = 0, POP_CLIP = 1, POP_SHR = 2, POP_MULDIV = 3, POP_MUL = 4 };
+struct PrecOp { int32_t mode, a, b; };
+struct OutOps {
+    int32_t sycc, off, upb;
+    PrecOp pc[GRK_MAX_COMPS];
+};
+// launch_mct_inv_dcshift_to / launch_upsample_to with the conversions in their
+// stores (the same kernels, instantiated with the ops; int32 planes run
+// k_mct_inv_dcshift_planar<int32_t>).  sycc needs ncomp == 3 and an unsigned
+// or int32 format.  A finished (not raw) UpComp of launch_upsample_ops carries
+// its samples' own format f, which may differ from the destination's, as
+// raw = UPCOMP_FIN + f: a staging plane keeps the stream's precision when the
+// output is narrower.
+constexpr uint8_t UPCOMP_FIN = 2;
+hipError_t launch_mct_inv_dcshift_ops(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th,
+                                      const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
+                                      uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn, const ShiftArr &mx,
+                                      int32_t mct, int32_t irrev, const OutOps &ops, hipStream_t s);
+hipError_t launch_upsample_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                               const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
+                               const OutOps &ops, hipStream_t s);
 // One DWT level of one tile-component (dwt.hip).  A launch runs one level of
 // every job in a table (grid.y = job).
 struct DwtJob {

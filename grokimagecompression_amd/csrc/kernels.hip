@@ -280,11 +280,89 @@ __device__ __forceinline__ void inv_plain_run(int32_t (&a)[N], int32_t irrev_c, 
     }
 }
 
+// ---------------------------------------------------------------------------
+// The output conversions (OutOps, grk_device.h) on a run's finished values,
+// between the clamp / replication and store_samples.  The kernels below carry
+// them as the template parameter OP: 0 = none (the instantiations every decode
+// without ops runs: no ops argument, the code as it was), OP_PREC = the
+// precision op of each component, OP_SYCC = sYCC -> RGB on the three
+// components, then their precision ops.
+// ---------------------------------------------------------------------------
+constexpr int OP_PREC = 1, OP_SYCC = 2;
+
+// clip_component / scale_component (convert.cpp:82-161); o is uniform over the
+// launch, so the switch does not diverge
+template <int N>
+__device__ __forceinline__ void prec_run(int32_t (&v)[N], const PrecOp &o) {
+    const int32_t a = o.a, b = o.b;
+    switch (o.mode) {
+        case POP_CLIP:
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[i] = v[i] < a ? a : (v[i] > b ? b : v[i]);
+            break;
+        case POP_SHR:
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[i] >>= a;
+            break;
+        case POP_MULDIV:  // plain 32-bit division: exact
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[i] = (int32_t)((uint32_t)v[i] * (uint32_t)a / (uint32_t)b);
+            break;
+        case POP_MUL:
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[i] *= a;
+            break;
+        default: break;
+    }
+}
+
+// sycc_to_rgb (color.cpp:136-162): the three terms depend on the chroma pair
+// only -- (int32_t)(1.402 * cr), (int32_t)(0.344 * cb + 0.714 * cr),
+// (int32_t)(1.772 * cb) in IEEE double, every product and the sum rounded on
+// its own (no FMA), the conversion truncating
+// __dmul_rn / __dadd_rn are plain * and + to the compiler: what keeps them
+// apart is that nothing here may be contracted, whatever flags the file is
+// built with -- hence the pragma, not only the Makefile's -ffp-contract=off.
+__device__ __forceinline__ void sycc_terms(int32_t cb, int32_t cr, int32_t off, int32_t &tr, int32_t &tg,
+                                           int32_t &tb) {
+#pragma clang fp contract(off)
+    const double b = (double)(cb - off), r = (double)(cr - off);
+    tr = (int32_t)__dmul_rn(1.402, r);
+    tg = (int32_t)__dadd_rn(__dmul_rn(0.344, b), __dmul_rn(0.714, r));
+    tb = (int32_t)__dmul_rn(1.772, b);
+}
+__device__ __forceinline__ int32_t clamp_upb(int32_t v, int32_t upb) { return v < 0 ? 0 : (v > upb ? upb : v); }
+// ... and the pixel: y, the chroma terms -> R, G, B
+__device__ __forceinline__ void sycc_pixel(int32_t y, int32_t tr, int32_t tg, int32_t tb, int32_t upb, int32_t &r,
+                                           int32_t &g, int32_t &b) {
+    r = clamp_upb(y + tr, upb);
+    g = clamp_upb(y - tg, upb);
+    b = clamp_upb(y + tb, upb);
+}
+// N pixels with a chroma pair each (4:4:4)
+template <int N>
+__device__ __forceinline__ void sycc_run(int32_t (&a)[N], int32_t (&b)[N], int32_t (&c)[N], const OutOps &ops) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        int32_t tr, tg, tb;
+        sycc_terms(b[i], c[i], ops.off, tr, tg, tb);
+        sycc_pixel(a[i], tr, tg, tb, ops.upb, a[i], b[i], c[i]);
+    }
+}
+
+// The kernels take the ops as a trailing parameter pack O: empty for OP = 0, so
+// those instantiations keep the parameters and the code they always had, and
+// one OutOps otherwise.
+__device__ __forceinline__ const OutOps *ops_ptr() { return nullptr; }
+__device__ __forceinline__ const OutOps *ops_ptr(const OutOps &o) { return &o; }
+
 // planar: dst.p[c] = plane c (samples T), rows dstride samples apart
-template <typename T>
+template <typename T, int OP = 0, typename... O>
 __global__ void k_mct_inv_dcshift_planar(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
                                          uint32_t dstride, uint32_t ncomp, ShiftArr shift, ShiftArr minv,
-                                         ShiftArr maxv, int32_t mct, int32_t irrev) {
+                                         ShiftArr maxv, int32_t mct, int32_t irrev, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
     constexpr int N = NarrowRun<T>::N;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (y >= th) return;
@@ -294,12 +372,24 @@ __global__ void k_mct_inv_dcshift_planar(PlanePtrs src, uint32_t sstride, uint32
     if (n <= 0) return;
     const size_t si = (size_t)y * sstride + x0, di = drow + x0;
     uint32_t c0 = 0;
-    if (mct && ncomp >= 3) {
+    if (OP == OP_SYCC || (mct && ncomp >= 3)) {  // (sYCC: exactly three components, with or without an MCT)
         int32_t a[N], b[N], c[N];
         load_run<N>(src.p[0] + si, n, a);
         load_run<N>(src.p[1] + si, n, b);
         load_run<N>(src.p[2] + si, n, c);
-        inv_mct_run<N>(a, b, c, irrev, shift, minv, maxv);
+        if (OP != OP_SYCC || mct) {
+            inv_mct_run<N>(a, b, c, irrev, shift, minv, maxv);
+        } else {
+            inv_plain_run<N>(a, irrev & 1, shift.v[0], minv.v[0], maxv.v[0]);
+            inv_plain_run<N>(b, (irrev >> 1) & 1, shift.v[1], minv.v[1], maxv.v[1]);
+            inv_plain_run<N>(c, (irrev >> 2) & 1, shift.v[2], minv.v[2], maxv.v[2]);
+        }
+        if constexpr (OP == OP_SYCC) sycc_run<N>(a, b, c, *ops);
+        if constexpr (OP != 0) {
+            prec_run<N>(a, ops->pc[0]);
+            prec_run<N>(b, ops->pc[1]);
+            prec_run<N>(c, ops->pc[2]);
+        }
         store_samples<T, N>((T *)dst.p[0] + di, a, n);
         store_samples<T, N>((T *)dst.p[1] + di, b, n);
         store_samples<T, N>((T *)dst.p[2] + di, c, n);
@@ -309,15 +399,18 @@ __global__ void k_mct_inv_dcshift_planar(PlanePtrs src, uint32_t sstride, uint32
         int32_t a[N];
         load_run<N>(src.p[k] + si, n, a);
         inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        if constexpr (OP != 0) prec_run<N>(a, ops->pc[k]);
         store_samples<T, N>((T *)dst.p[k] + di, a, n);
     }
 }
 
 // interleaved, NC = 3 or 4 components: sample (y, x, c) at dst.p[0][y * dstride + x * NC + c]
-template <typename T, int NC>
+template <typename T, int NC, int OP = 0, typename... O>
 __global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
                                          uint32_t dstride, ShiftArr shift, ShiftArr minv, ShiftArr maxv, int32_t mct,
-                                         int32_t irrev) {
+                                         int32_t irrev, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
     constexpr int N = NarrowRun<T>::N;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (y >= th) return;
@@ -333,6 +426,11 @@ __global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32
 #pragma unroll
     for (int k = 0; k < NC; ++k)
         if (!mct || k >= 3) inv_plain_run<N>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+    if constexpr (OP == OP_SYCC) sycc_run<N>(v[0], v[1], v[2], *ops);
+    if constexpr (OP != 0) {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) prec_run<N>(v[k], ops->pc[k]);
+    }
     int32_t px[N * NC];
 #pragma unroll
     for (int i = 0; i < N; ++i)
@@ -342,10 +440,12 @@ __global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32
 }
 
 // interleaved, any other component count: one thread per pixel, one store per sample
-template <typename T>
+template <typename T, int OP = 0, typename... O>
 __global__ void k_mct_inv_dcshift_pixels_any(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
                                              uint32_t dstride, uint32_t ncomp, ShiftArr shift, ShiftArr minv,
-                                             ShiftArr maxv, int32_t mct, int32_t irrev) {
+                                             ShiftArr maxv, int32_t mct, int32_t irrev, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= tw || y >= th) return;
     const size_t si = (size_t)y * sstride + x;
@@ -354,6 +454,11 @@ __global__ void k_mct_inv_dcshift_pixels_any(PlanePtrs src, uint32_t sstride, ui
     if (mct && ncomp >= 3) {
         int32_t a[1] = {src.p[0][si]}, b[1] = {src.p[1][si]}, c[1] = {src.p[2][si]};
         inv_mct_run<1>(a, b, c, irrev, shift, minv, maxv);
+        if constexpr (OP != 0) {
+            prec_run<1>(a, ops->pc[0]);
+            prec_run<1>(b, ops->pc[1]);
+            prec_run<1>(c, ops->pc[2]);
+        }
         __builtin_nontemporal_store((T)a[0], d);
         __builtin_nontemporal_store((T)b[0], d + 1);
         __builtin_nontemporal_store((T)c[0], d + 2);
@@ -362,6 +467,7 @@ __global__ void k_mct_inv_dcshift_pixels_any(PlanePtrs src, uint32_t sstride, ui
     for (uint32_t k = c0; k < ncomp; ++k) {
         int32_t a[1] = {src.p[k][si]};
         inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        if constexpr (OP != 0) prec_run<1>(a, ops->pc[k]);
         __builtin_nontemporal_store((T)a[0], d + k);
     }
 }
@@ -379,16 +485,38 @@ __global__ void k_mct_inv_dcshift_pixels_any(PlanePtrs src, uint32_t sstride, ui
 // the stores are k_mct_inv_dcshift_planar / _pixels'.
 // ---------------------------------------------------------------------------
 // component c's sample for the pixel whose column / row on c's grid are (col, row)
-template <typename T>
+// a finished (not raw) sample: of the destination's type T, or (OP != 0) of the
+// format the component carries (UPCOMP_FIN + SampleFmt, uniform over the launch)
+template <typename T, int OP>
+__device__ __forceinline__ int32_t fin_sample(const UpComp &c, size_t i) {
+    if constexpr (OP == 0) {
+        return (int32_t)((const T *)c.src)[i];
+    } else {
+        switch (c.raw - UPCOMP_FIN) {
+            case SMP_U8: return (int32_t)((const uint8_t *)c.src)[i];
+            case SMP_I8: return (int32_t)((const int8_t *)c.src)[i];
+            case SMP_U16: return (int32_t)((const uint16_t *)c.src)[i];
+            case SMP_I16: return (int32_t)((const int16_t *)c.src)[i];
+            default: return ((const int32_t *)c.src)[i];
+        }
+    }
+}
+template <int OP>
+__device__ __forceinline__ bool is_raw(const UpComp &c) {
+    if constexpr (OP == 0) return c.raw;
+    else return c.raw == 1;
+}
+
+template <typename T, int OP = 0>
 __device__ __forceinline__ int32_t up_sample(const UpComp &c, int32_t col, int32_t row) {
     if (col < c.zx0 || row < c.zy0 || !c.src) return 0;
     const size_t i = (size_t)(row - c.gy0) * c.stride + (uint32_t)(col - c.gx0);
-    if (c.raw) {
+    if (is_raw<OP>(c)) {
         int32_t a[1] = {((const int32_t *)c.src)[i]};
         inv_plain_run<1>(a, c.irrev, c.shift, c.mn, c.mx);
         return a[0];
     }
-    return (int32_t)((const T *)c.src)[i];
+    return fin_sample<T, OP>(c, i);
 }
 
 // 4:2:0 / 4:2:2: three components at (1,1), (2,dy), (2,dy), dy = 1 or 2.  A
@@ -398,9 +526,14 @@ __device__ __forceinline__ int32_t up_sample(const UpComp &c, int32_t col, int32
 // N / 2 (+ 1 when the run starts on an odd X) source samples from floor(X / 2)
 // on, each stored twice: what counts is the parity of the absolute X, not of
 // the run's place in the tile.  Row Y reads chroma row floor(Y / dy).
-template <typename T, bool IL>
+//
+// OP != 0 (OutOps): the sYCC chroma terms are computed once per source sample
+// (NS pairs), not per pixel, and replicated like the samples themselves.
+template <typename T, bool IL, int OP = 0, typename... O>
 __global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h, DstPlanes dst,
-                               uint32_t dstride) {
+                               uint32_t dstride, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
     typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
     constexpr int N = NarrowRun<T>::N, H = N / 2, NS = H + 1;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
@@ -417,14 +550,18 @@ __global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, u
         if (!c.src) {
 #pragma unroll
             for (int i = 0; i < N; ++i) v[0][i] = 0;
-        } else if (c.raw) {
+        } else if (OP ? c.raw == 1 : c.raw) {
             load_run<N>((const int32_t *)c.src + si, n, v[0]);
             inv_plain_run<N>(v[0], c.irrev, c.shift, c.mn, c.mx);
         } else {
 #pragma unroll
-            for (int i = 0; i < N; ++i) v[0][i] = i < n ? (int32_t)((const T *)c.src)[si + i] : 0;
+            for (int i = 0; i < N; ++i) {
+                if constexpr (OP == 0) v[0][i] = i < n ? (int32_t)((const T *)c.src)[si + i] : 0;
+                else v[0][i] = i < n ? fin_sample<T, OP>(c, si + i) : 0;
+            }
         }
     }
+    int32_t cs[2][NS];  // (sYCC: the chroma samples of the run, Cb and Cr)
     const int32_t c0 = (int32_t)(X >> 1);                             // the run's first chroma column
     const int last = (int)(((X + (uint32_t)n - 1) >> 1) - (X >> 1));  // ... and how many more it needs
     const bool odd = X & 1;
@@ -436,7 +573,7 @@ __global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, u
         if (row < c.zy0 || !c.src) {
 #pragma unroll
             for (int j = 0; j < NS; ++j) s[j] = 0;
-        } else if (c.raw) {
+        } else if (OP ? c.raw == 1 : c.raw) {
             const int32_t *const q = (const int32_t *)c.src + ((int64_t)(row - c.gy0) * c.stride + (c0 - c.gx0));
             if (H % 4 == 0 && n == N && c0 >= c.zx0 && !((uintptr_t)q & 15)) {
 #pragma unroll
@@ -456,10 +593,33 @@ __global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, u
         } else {
             const int64_t b = (int64_t)(row - c.gy0) * c.stride + (c0 - c.gx0);
 #pragma unroll
-            for (int j = 0; j < NS; ++j) s[j] = c0 + j >= c.zx0 && j <= last ? (int32_t)((const T *)c.src)[b + j] : 0;
+            for (int j = 0; j < NS; ++j) {
+                if constexpr (OP == 0) s[j] = c0 + j >= c.zx0 && j <= last ? (int32_t)((const T *)c.src)[b + j] : 0;
+                else s[j] = c0 + j >= c.zx0 && j <= last ? fin_sample<T, OP>(c, (size_t)(b + j)) : 0;
+            }
         }
+        if constexpr (OP == OP_SYCC) {
 #pragma unroll
-        for (int i = 0; i < N; ++i) v[k][i] = odd ? s[(i + 1) >> 1] : s[i >> 1];
+            for (int j = 0; j < NS; ++j) cs[k - 1][j] = s[j];
+        } else {
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[k][i] = odd ? s[(i + 1) >> 1] : s[i >> 1];
+        }
+    }
+    if constexpr (OP == OP_SYCC) {
+        int32_t tr[NS], tg[NS], tb[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) sycc_terms(cs[0][j], cs[1][j], ops->off, tr[j], tg[j], tb[j]);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int j0 = i >> 1, j1 = (i + 1) >> 1;
+            sycc_pixel(v[0][i], odd ? tr[j1] : tr[j0], odd ? tg[j1] : tg[j0], odd ? tb[j1] : tb[j0], ops->upb,
+                       v[0][i], v[1][i], v[2][i]);
+        }
+    }
+    if constexpr (OP != 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) prec_run<N>(v[k], ops->pc[k]);
     }
     if constexpr (IL) {
         int32_t px[N * 3];
@@ -474,19 +634,48 @@ __global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, u
     }
 }
 
-// any component count and any dx / dy in 1 .. 255: one thread per pixel, one store per sample
-template <typename T>
+// any component count and any dx / dy in 1 .. 255: one thread per pixel, one store per sample.
+// OP != 0 (one OutOps in the pack): the precision op of each component, and
+// sYCC (ops.sycc, three components -- the shapes k_upsample_420 does not take:
+// chroma at (1,1) fed finished samples, and the converted value of samples
+// nothing decoded) at run time.
+template <typename T, int OP = 0, typename... O>
 __global__ void k_upsample_any(UpPlan p, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
-                               DstPlanes dst, int32_t il, uint32_t dstride) {
+                               DstPlanes dst, int32_t il, uint32_t dstride, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w || y >= h) return;
     const uint32_t X = X0 + x, Y = Y0 + y;
     const size_t drow = (size_t)y * dstride;
+    if constexpr (OP != 0) {
+        if (ops->sycc) {
+            int32_t v[3][1];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                v[k][0] = up_sample<T, OP>(p.c[k], (int32_t)(X / p.c[k].dx), (int32_t)(Y / p.c[k].dy));
+            sycc_run<1>(v[0], v[1], v[2], *ops);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                prec_run<1>(v[k], ops->pc[k]);
+                T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * 3 + k : (T *)dst.p[k] + drow + x;
+                __builtin_nontemporal_store((T)v[k][0], d);
+            }
+            return;
+        }
+    }
     for (uint32_t k = 0; k < ncomp; ++k) {
         const UpComp &c = p.c[k];
-        const int32_t v = up_sample<T>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy));
-        T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * ncomp + k : (T *)dst.p[k] + drow + x;
-        __builtin_nontemporal_store((T)v, d);
+        if constexpr (OP == 0) {
+            const int32_t v = up_sample<T>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy));
+            T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * ncomp + k : (T *)dst.p[k] + drow + x;
+            __builtin_nontemporal_store((T)v, d);
+        } else {
+            int32_t v[1] = {up_sample<T, OP>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy))};
+            prec_run<1>(v, ops->pc[k]);
+            T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * ncomp + k : (T *)dst.p[k] + drow + x;
+            __builtin_nontemporal_store((T)v[0], d);
+        }
     }
 }
 
@@ -1529,6 +1718,112 @@ hipError_t launch_upsample_to(const UpPlan &src, uint32_t ncomp, uint32_t X0, ui
         if (!src.c[k].dx || !src.c[k].dy) return hipErrorInvalidValue;
     if (!w || !h) return hipSuccess;
 #define GRK_UP(T, FAST) launch_up<T, FAST>(src, ncomp, X0, Y0, w, h, dst, interleaved, dstride, s)
+    switch (fmt) {
+        case SMP_I32: GRK_UP(int32_t, true); break;
+        case SMP_U8: GRK_UP(uint8_t, true); break;
+        case SMP_I8: GRK_UP(int8_t, false); break;
+        case SMP_U16: GRK_UP(uint16_t, true); break;
+        case SMP_I16: GRK_UP(int16_t, false); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_UP
+    return hipGetLastError();
+}
+
+// the same launches with the OutOps in their stores (the grids are those above)
+template <typename T, bool SY>
+static void launch_inv_ops(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
+                           bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift,
+                           const ShiftArr &mn, const ShiftArr &mx, int32_t mct, int32_t irrev, const OutOps &ops,
+                           hipStream_t s) {
+    const uint32_t runs = (uint32_t)(((uint64_t)tw + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
+    const dim3 grid((runs + 255) / 256, th);
+    mct = mct && ncomp >= 3;
+    if constexpr (SY) {
+        if (ops.sycc) {  // three components (checked by the caller)
+            if (!interleaved)
+                hipLaunchKernelGGL((k_mct_inv_dcshift_planar<T, OP_SYCC>), grid, dim3(256), 0, s, src, sstride, tw,
+                                   th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
+            else
+                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 3, OP_SYCC>), grid, dim3(256), 0, s, src, sstride,
+                                   tw, th, dst, dstride, shift, mn, mx, mct, irrev, ops);
+            return;
+        }
+    }
+    if (!interleaved || ncomp == 1)
+        hipLaunchKernelGGL((k_mct_inv_dcshift_planar<T, OP_PREC>), grid, dim3(256), 0, s, src, sstride, tw, th, dst,
+                           dstride, ncomp, shift, mn, mx, mct, irrev, ops);
+    else if (ncomp == 3)
+        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 3, OP_PREC>), grid, dim3(256), 0, s, src, sstride, tw, th,
+                           dst, dstride, shift, mn, mx, mct, irrev, ops);
+    else if (ncomp == 4)
+        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 4, OP_PREC>), grid, dim3(256), 0, s, src, sstride, tw, th,
+                           dst, dstride, shift, mn, mx, mct, irrev, ops);
+    else
+        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels_any<T, OP_PREC>), dim3((tw + 255) / 256, th), dim3(256), 0, s, src,
+                           sstride, tw, th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
+}
+
+// sYCC output is unsigned: its formats are U8 / U16 / I32
+static bool sycc_launchable(const OutOps &ops, uint32_t ncomp, int32_t fmt) {
+    return !ops.sycc || (ncomp == 3 && (fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16));
+}
+
+hipError_t launch_mct_inv_dcshift_ops(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th,
+                                      const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
+                                      uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn, const ShiftArr &mx,
+                                      int32_t mct, int32_t irrev, const OutOps &ops, hipStream_t s) {
+    if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS || !sycc_launchable(ops, ncomp, fmt))
+        return hipErrorInvalidValue;
+    if (!tw || !th) return hipSuccess;
+#define GRK_INV(T, SY) \
+    launch_inv_ops<T, SY>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev, ops, s)
+    switch (fmt) {
+        case SMP_I32: GRK_INV(int32_t, true); break;
+        case SMP_U8: GRK_INV(uint8_t, true); break;
+        case SMP_I8: GRK_INV(int8_t, false); break;
+        case SMP_U16: GRK_INV(uint16_t, true); break;
+        case SMP_I16: GRK_INV(int16_t, false); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_INV
+    return hipGetLastError();
+}
+
+template <typename T, bool FAST>
+static void launch_up_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                          const DstPlanes &dst, bool interleaved, uint32_t dstride, const OutOps &ops,
+                          hipStream_t s) {
+    const UpComp *c = src.c;
+    if constexpr (FAST) {
+        if (ncomp == 3 && c[0].dx == 1 && c[0].dy == 1 && c[1].dx == 2 && c[2].dx == 2 && c[1].dy == c[2].dy &&
+            (c[1].dy == 1 || c[1].dy == 2)) {
+            const uint32_t runs = (uint32_t)(((uint64_t)w + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
+            const dim3 grid((runs + 255) / 256, h);
+#define GRK_420(IL, OP) \
+    hipLaunchKernelGGL((k_upsample_420<T, IL, OP>), grid, dim3(256), 0, s, src, X0, Y0, w, h, dst, dstride, ops)
+            if (interleaved) {
+                if (ops.sycc) GRK_420(true, OP_SYCC); else GRK_420(true, OP_PREC);
+            } else {
+                if (ops.sycc) GRK_420(false, OP_SYCC); else GRK_420(false, OP_PREC);
+            }
+#undef GRK_420
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_upsample_any<T, OP_PREC>), dim3((w + 255) / 256, h), dim3(256), 0, s, src, ncomp, X0, Y0, w, h,
+                       dst, interleaved ? 1 : 0, dstride, ops);
+}
+
+hipError_t launch_upsample_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                               const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
+                               const OutOps &ops, hipStream_t s) {
+    if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS || !sycc_launchable(ops, ncomp, fmt))
+        return hipErrorInvalidValue;
+    for (uint32_t k = 0; k < ncomp; ++k)
+        if (!src.c[k].dx || !src.c[k].dy) return hipErrorInvalidValue;
+    if (!w || !h) return hipSuccess;
+#define GRK_UP(T, FAST) launch_up_ops<T, FAST>(src, ncomp, X0, Y0, w, h, dst, interleaved, dstride, ops, s)
     switch (fmt) {
         case SMP_I32: GRK_UP(int32_t, true); break;
         case SMP_U8: GRK_UP(uint8_t, true); break;

@@ -588,6 +588,70 @@ typedef struct {
 int grkgpu_decompress_to(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, const grkgpu_dparams *p,
                          uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
                          const grkgpu_out_planes *out);
+/* grkgpu_decompress_to with the two remaining per-sample steps of
+ * grk_decompress between the decode and displayable pixels, done by the store
+ * of the last decode kernel on the values it holds in registers -- in the
+ * reference's order colour -> precision, on the upsampled samples
+ * (precision(colour(upsample(decode))): the reference's sYCC routines
+ * replicate the chroma themselves, and replication commutes with a per-sample
+ * map).  Let U_k(X, Y) be the GRKGPU_LAYOUT_UPSAMPLE value above (zero where
+ * an index is negative, the identity for a component at (1,1)).
+ *
+ * colour = GRKGPU_COLOUR_SYCC (grk_decompress.cpp:1585-1609 ->
+ * color_sycc_to_rgb, bin/common/color.cpp:136-418): exactly 3 components, all
+ * unsigned and of one precision P, component 0 at (1,1), components 1 and 2
+ * both at (1,1), both at (2,1) or both at (2,2); anything else is
+ * GRKGPU_EINVAL.  It implies GRKGPU_LAYOUT_UPSAMPLE.  Per pixel, with
+ * off = 2^(P-1), upb = 2^P - 1, y = U_0, cb = U_1 - off, cr = U_2 - off:
+ *   R = clamp(y + trunc(1.402 * cr), 0, upb)
+ *   G = clamp(y - trunc(0.344 * cb + 0.714 * cr), 0, upb)
+ *   B = clamp(y + trunc(1.772 * cb), 0, upb)
+ * in IEEE double, every product and the sum rounded on its own (no FMA), the
+ * conversion to int32 truncating.  A zero lead-in chroma sample enters as raw
+ * 0 (cb = -off), as in the reference.  Equal to sycc444_to_rgb / sycc422_to_rgb
+ * at any origin and to sycc420_to_rgb at any origin with even x.  The one
+ * deviation: 4:2:0 with an odd x origin, where the reference's loop disagrees
+ * with its own 4:2:2 loop and with -u (the second row of each row pair takes
+ * cb[0] for the first column, the tail row ignores the offset) -- this keeps
+ * the upsample rule.
+ *
+ * prec = p in 1 .. 16 (grk_decompress -p, grk_decompress.cpp:1690-1716;
+ * clip_component / scale_component, bin/jp2/convert.cpp:82-161), applied after
+ * the colour step to every component, q its own precision:
+ *   clip,  unsigned         min(v, 2^p - 1)
+ *   clip,  signed           clamp(v, -2^(p-1), 2^(p-1) - 1)
+ *   scale, p == q           v
+ *   scale, p < q            v >> (q - p)  (signed: arithmetic)
+ *   scale, p > q, unsigned  (v * (2^p - 1)) / (2^q - 1), integer division
+ *   scale, p > q, signed    v * 2^(p-q)
+ * prec = 0 keeps each component's precision.
+ *
+ * out->sample_fmt must hold the OUTPUT precision (prec, or the component's own
+ * when prec = 0) and signedness of every component, else GRKGPU_EINVAL -- so a
+ * 12-bit stream decodes to U8 with prec = 8.  img receives the output
+ * precision, and dx = dy = 1 with SYCC.  ops = NULL or all zero:
+ * grkgpu_decompress_to, launch for launch.  Unknown colour / prec_mode, prec >
+ * 16, reserved != 0 or a format narrower than prec: GRKGPU_EINVAL before any
+ * device call.  Window, cp_layer, host or device planes, both layouts and
+ * every sample format as grkgpu_decompress_to; cp_reduce > 0 where no
+ * component is subsampled (with SYCC or the upsample flag on a subsampled
+ * stream: GRKGPU_EINVAL, as there); a proper tile range keeps its rules.
+ * Precision alone on a subsampled stream without the upsample flag converts
+ * each plane on its own grid.  Samples nothing decoded (the zero margin of a
+ * reduced decode at an odd origin, tiles a cut stream never reached) are
+ * converted like any other, as the reference's colour step does with them:
+ * with SYCC they come out as the conversion of (0, 0, 0). */
+enum { GRKGPU_COLOUR_NONE = 0, GRKGPU_COLOUR_SYCC = 1 };
+enum { GRKGPU_PREC_CLIP = 0, GRKGPU_PREC_SCALE = 1 };
+typedef struct {
+    uint32_t colour;     /* GRKGPU_COLOUR_* */
+    uint32_t prec;       /* 0: keep each component's precision; 1..16: output precision of every component */
+    uint32_t prec_mode;  /* GRKGPU_PREC_*; read only when prec != 0 */
+    uint32_t reserved;   /* 0 */
+} grkgpu_out_ops;
+int grkgpu_decompress_convert(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, const grkgpu_dparams *p,
+                              uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                              const grkgpu_out_planes *out, const grkgpu_out_ops *ops);
 /* (multi-device decode into host planes: see grkgpu_device_set above) */
 int grkgpu_decompress_multi(const grkgpu_device_set *devs, const uint8_t *cs, size_t len, grkgpu_image_desc *img,
                             int32_t *const *planes);
@@ -633,6 +697,19 @@ int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t numcomps, uint
 int grkgpu_upsample_to(const void *const *src, const uint32_t *src_stride, uint32_t numcomps, const uint32_t *dx,
                        const uint32_t *dy, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
                        const grkgpu_out_planes *dst, uint32_t dst_stride, void *stream);
+/* The converting store of grkgpu_decompress_convert on its own -- the kernels
+ * the decode runs, fed finished samples; the counterpart of
+ * grkgpu_upsample_to, whose geometry and refusals it keeps.  src[k] = device
+ * plane of component k on its own grid, samples of src_fmt (a GRKGPU_SAMPLE_*
+ * width that holds every (prec[k], sgnd[k]), else GRKGPU_EINVAL); dst's format
+ * must hold the output precision and signedness.  ops as above (NULL: no
+ * conversion -- the samples replicated and stored in dst's format).  Int32
+ * sources with every component at (1,1) run the inverse-MCT kernels' stores,
+ * every other shape the upsampling kernels'. */
+int grkgpu_convert_to(const void *const *src, const uint32_t *src_stride, uint32_t src_fmt, uint32_t numcomps,
+                      const uint32_t *dx, const uint32_t *dy, const uint32_t *prec, const int32_t *sgnd,
+                      uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                      const grkgpu_out_planes *dst, uint32_t dst_stride, const grkgpu_out_ops *ops, void *stream);
 /* grkgpu_dcshift_mct_fwd out of place, from the sample format and layout of
  * src (the first kernel of grkgpu_compress_ex on its own; the counterpart of
  * grkgpu_mct_inv_dcshift_to): src->planes are device pointers (on_device, row0
