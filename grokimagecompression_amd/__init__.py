@@ -234,6 +234,38 @@ def _out_ops(colour, out_prec, prec_mode):
     return OutOps(colour=_COLOURS[colour], prec=int(out_prec or 0), prec_mode=_PREC_MODES[prec_mode])
 
 
+COLOUR_AUTO = 2  # grkgpu_jp2_decompress only: sYCC -> RGB when the file's colr box says sYCC
+JP2_MAX_CDEF = 64
+# GRKGPU_CS_* (GRK_CLRSPC_*): the colour space a JP2 file signals / is written with
+COLOUR_SPACES = {"unknown": 0, "unspecified": 1, "srgb": 2, "gray": 3, "sycc": 4, "eycc": 5, "cmyk": 6,
+                 "default_cie": 7, "custom_cie": 8, "icc": 9}
+_COLOUR_SPACE_NAMES = {v: k for k, v in COLOUR_SPACES.items()}
+
+
+class Jp2Info(ctypes.Structure):
+    """grkgpu_jp2_info (include/grk_mi355x.h)."""
+    _fields_ = [("cs_offset", ctypes.c_uint64), ("cs_length", ctypes.c_uint64),
+                ("ihdr_w", ctypes.c_uint32), ("ihdr_h", ctypes.c_uint32), ("ihdr_nc", ctypes.c_uint32),
+                ("ihdr_bpc", ctypes.c_uint32), ("meth", ctypes.c_uint32), ("enumcs", ctypes.c_uint32),
+                ("colour_space", ctypes.c_uint32), ("icc_length", ctypes.c_uint32), ("icc_offset", ctypes.c_uint64),
+                ("cielab_words", ctypes.c_uint32), ("cielab", ctypes.c_uint32 * 9),
+                ("pal_entries", ctypes.c_uint32), ("pal_columns", ctypes.c_uint32),
+                ("pal_prec", ctypes.c_uint32 * MAXC), ("pal_sgnd", ctypes.c_int32 * MAXC),
+                ("cmap_cmp", ctypes.c_uint32 * MAXC), ("cmap_mtyp", ctypes.c_uint32 * MAXC),
+                ("cmap_pcol", ctypes.c_uint32 * MAXC), ("cdef_n", ctypes.c_uint32),
+                ("cdef_cn", ctypes.c_uint16 * JP2_MAX_CDEF), ("cdef_typ", ctypes.c_uint16 * JP2_MAX_CDEF),
+                ("cdef_asoc", ctypes.c_uint16 * JP2_MAX_CDEF), ("numchannels", ctypes.c_uint32),
+                ("chan_prec", ctypes.c_uint32 * MAXC), ("chan_sgnd", ctypes.c_int32 * MAXC),
+                ("chan_alpha", ctypes.c_uint32 * MAXC), ("chan_comp", ctypes.c_uint32 * MAXC),
+                ("chan_pcol", ctypes.c_int32 * MAXC), ("mapped", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class Jp2WParams(ctypes.Structure):
+    """grkgpu_jp2_wparams: what grkgpu_jp2_compress writes into the boxes."""
+    _fields_ = [("colour_space", ctypes.c_uint32), ("icc_len", ctypes.c_uint32), ("icc", ctypes.c_void_p),
+                ("alpha", ctypes.c_uint32 * MAXC)]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("h2d_ms", ctypes.c_float), ("dcshift_mct_ms", ctypes.c_float), ("dwt_ms", ctypes.c_float),
                 ("t1_ms", ctypes.c_float), ("gather_ms", ctypes.c_float), ("d2h_ms", ctypes.c_float),
@@ -361,6 +393,18 @@ def lib():
             L.grkgpu_read_mct.argtypes = [VP, ctypes.c_size_t, P(ImageDesc), P(ctypes.c_float), P(I32), P(U32)]
             L.grkgpu_mct_inv_custom_to.argtypes = [P(VP), U32, U32, U32, U32, P(ctypes.c_float), P(I32), P(U32),
                                                    P(I32), P(OutPlanes), U32, VP]
+        if hasattr(L, "grkgpu_jp2_read_info"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            U16 = ctypes.c_uint16
+            L.grkgpu_jp2_read_info.argtypes = [VP, ctypes.c_size_t, P(Jp2Info), P(ImageDesc)]
+            L.grkgpu_jp2_read_palette.argtypes = [VP, ctypes.c_size_t, P(U16), U32, P(U32)]
+            L.grkgpu_jp2_decompress.argtypes = [VP, VP, ctypes.c_size_t, P(DParams), U32, U32, P(ImageDesc),
+                                                P(OutPlanes), P(OutOps), P(Jp2Info)]
+            L.grkgpu_jp2_compress.argtypes = [VP, P(ImageDesc), P(CParams), P(Jp2WParams), P(Planes),
+                                              P(P(ctypes.c_uint8)), P(ctypes.c_size_t)]
+            L.grkgpu_jp2_write_boxes.argtypes = [P(ImageDesc), P(Jp2WParams), ctypes.c_uint64, VP, ctypes.c_size_t,
+                                                 P(ctypes.c_size_t)]
+            L.grkgpu_palette_to.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), U32, P(U32), P(I32), P(U32), VP,
+                                            U32, U32, P(OutPlanes), U32, VP]
         L.grkgpu_dcshift_mct_fwd.argtypes = [P(VP), U32, U32, U32, U32, P(I32), I32, I32, VP]
         L.grkgpu_mct_inv_dcshift.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), I32, I32, VP]
         L.grkgpu_dwt_fwd.argtypes = [VP, VP, U32, U32, U32, U32, U32, I32, VP]
@@ -562,6 +606,84 @@ def read_mct(buf):
     return None if m is None else (m, o)
 
 
+def _jp2_read(buf):
+    """grkgpu_jp2_read_info + grkgpu_jp2_read_palette: (Jp2Info, ImageDesc of the output channels, info dict)."""
+    bp, bn, keep = _buf_ptr(buf)
+    ji, d = Jp2Info(), ImageDesc()
+    _check(lib().grkgpu_jp2_read_info(bp, bn, ctypes.byref(ji), ctypes.byref(d)))
+    n = ji.numchannels
+    info = {
+        "codestream": (ji.cs_offset, ji.cs_length),
+        "ihdr": {"w": ji.ihdr_w, "h": ji.ihdr_h, "nc": ji.ihdr_nc, "bpc": ji.ihdr_bpc},
+        "meth": ji.meth, "enumcs": ji.enumcs,
+        "colour_space": _COLOUR_SPACE_NAMES.get(ji.colour_space, "unknown"),
+        "icc": bytes(memoryview(buf)[ji.icc_offset:ji.icc_offset + ji.icc_length]) if ji.icc_length else None,
+        "cielab": [int(v) for v in ji.cielab[:ji.cielab_words]] or None,
+        "palette": None,
+        "cdef": [(ji.cdef_cn[i], ji.cdef_typ[i], ji.cdef_asoc[i]) for i in range(ji.cdef_n)] or None,
+        "channels": [{"prec": ji.chan_prec[i], "sgnd": bool(ji.chan_sgnd[i]), "alpha": ji.chan_alpha[i],
+                      "comp": ji.chan_comp[i], "pcol": None if ji.chan_pcol[i] < 0 else ji.chan_pcol[i]}
+                     for i in range(n)],
+        "mapped": bool(ji.mapped),
+    }
+    if ji.pal_entries:
+        ne, npc = ji.pal_entries, ji.pal_columns
+        tab = np.empty(ne * npc, dtype=np.uint16)
+        got = ctypes.c_uint32(0)
+        _check(lib().grkgpu_jp2_read_palette(bp, bn, tab.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), tab.size,
+                                             ctypes.byref(got)))
+        info["palette"] = {"entries": tab.reshape(ne, npc), "prec": [ji.pal_prec[i] for i in range(npc)],
+                           "sgnd": [bool(ji.pal_sgnd[i]) for i in range(npc)],
+                           "cmap": [(ji.cmap_cmp[i], ji.cmap_mtyp[i], ji.cmap_pcol[i]) for i in range(npc)]}
+    return ji, d, info
+
+
+def jp2_info(buf):
+    """What a .jp2 file's boxes say (grkgpu_jp2_read_info; host only, no GPU):
+    a dict with "codestream" (offset, length of the jp2c payload inside buf),
+    "ihdr", "meth" / "enumcs", "colour_space" (a COLOUR_SPACES name, mapped as
+    the reference's jp2_decode maps it), "icc" (the profile's bytes or None),
+    "cielab" (the parameter words or None), "palette" (None, or entries (NE,
+    NPC) uint16, per-column prec / sgnd and the cmap triples), "cdef" (the
+    (cn, typ, asoc) triples or None), "channels" (per output channel: prec,
+    sgnd, alpha type, the component that feeds it and the palette column it is
+    looked up in, or None) and "mapped" (the channels are not the components in
+    order).  Raises GrkGpuError where the reference refuses the file, and for
+    the handful of files it decodes and this decoder does not."""
+    return _jp2_read(buf)[2]
+
+
+def _jp2_wparams(c, colour_space, icc, alpha):
+    if colour_space not in COLOUR_SPACES:
+        raise GrkGpuError("colour_space must be one of %s (got %r)" % (sorted(COLOUR_SPACES), colour_space))
+    wp = Jp2WParams(colour_space=COLOUR_SPACES[colour_space])
+    keep = None
+    if icc is not None:
+        keep = ctypes.create_string_buffer(bytes(icc), len(icc))
+        wp.icc = ctypes.cast(keep, ctypes.c_void_p)
+        wp.icc_len = len(icc)
+    for k, a in enumerate(_per_comp(alpha or 0, c)):
+        wp.alpha[k] = a
+    return wp, keep
+
+
+def jp2_boxes(shape, prec, cs_len, colour_space="unknown", icc=None, alpha=None, sgnd=False, offset=(0, 0)):
+    """The boxes Codec.compress_jp2 writes ahead of a codestream of cs_len
+    bytes for a (c, h, w) image (grkgpu_jp2_write_boxes; host only)."""
+    c, h, w = shape
+    d = ImageDesc()
+    d.x0, d.y0 = offset
+    d.x1, d.y1 = offset[0] + w, offset[1] + h
+    d.numcomps = c
+    for k, (pk, sk) in enumerate(zip(_per_comp(prec, c), _per_comp(sgnd, c))):
+        d.prec[k], d.sgnd[k], d.dx[k], d.dy[k] = pk, 1 if sk else 0, 1, 1
+    wp, keep = _jp2_wparams(c, colour_space, icc, alpha)
+    n = ctypes.c_size_t(0)
+    buf = ctypes.create_string_buffer(4096 + (len(icc) if icc else 0))
+    _check(lib().grkgpu_jp2_write_boxes(ctypes.byref(d), ctypes.byref(wp), cs_len, buf, len(buf), ctypes.byref(n)))
+    return buf.raw[:n.value]
+
+
 def _torch():
     import torch
     return torch
@@ -731,6 +853,15 @@ class Codec:
         reference grid (w_k = ceil((x0 + w) / dx) - ceil(x0 / dx)); host numpy
         planes, int32 or their 8 / 16-bit samples.  MCT is disabled when the
         first three components differ in subsampling (j2k.cpp:1963-1971)."""
+        d, pl, keep = self._image_subsampled(planes, prec, size, subsampling, offset, sgnd)
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        n = ctypes.c_size_t()
+        _check(lib().grkgpu_compress_ex(self._ctx, ctypes.byref(d), ctypes.byref(params or CParams.make()),
+                                        ctypes.byref(pl), 0, 0xFFFFFFFF, PART_ALL, ctypes.byref(out), ctypes.byref(n)))
+        return ctypes.string_at(out, n.value)
+
+    def _image_subsampled(self, planes, prec, size, subsampling, offset, sgnd):
+        """Image descriptor + grkgpu_planes of compress_subsampled's arguments."""
         c = len(planes)
         if len(subsampling) != c:
             raise GrkGpuError("one (dx, dy) per component")
@@ -761,11 +892,7 @@ class Codec:
             fmts = {SAMPLE_I32}
         pl.sample_fmt = fmts.pop()
         pl.on_device = 0
-        out = ctypes.POINTER(ctypes.c_uint8)()
-        n = ctypes.c_size_t()
-        _check(lib().grkgpu_compress_ex(self._ctx, ctypes.byref(d), ctypes.byref(params or CParams.make()),
-                                        ctypes.byref(pl), 0, 0xFFFFFFFF, PART_ALL, ctypes.byref(out), ctypes.byref(n)))
-        return ctypes.string_at(out, n.value)
+        return d, pl, keep
 
     def compress_tiles(self, img, prec, params, tile_begin, tile_end, parts=PART_TILES, offset=(0, 0), sgnd=False,
                        row0=None, height=None, view=False, layout="chw"):
@@ -978,6 +1105,87 @@ class Codec:
         else:
             _check(lib().grkgpu_decompress(self._ctx, bp, bn, None, ptrs, 1 if on_dev else 0))
         return out
+
+    def decompress_jp2(self, buf, dtype=None, layout="chw", colour="auto", out_prec=None, prec_mode="clip",
+                       window=None, reduce=0, layers=0, device_out=False):
+        """Decode a .jp2 file (grkgpu_jp2_decompress) -> (array, info): the
+        output CHANNELS as a (c,h,w) / (h,w,c) array -- numpy, or a cuda tensor
+        with device_out -- and jp2_info(buf).  A palette (pclr + cmap) and the
+        channel order of a cdef box are applied by the store of the last
+        decode kernel, as the reference's jp2_decode applies them on the CPU;
+        the alpha types and the colour space are in info.  colour="auto": sYCC
+        -> RGB when the file says sYCC (then the shape rules of
+        decompress(colour="sycc") hold), nothing otherwise; None: never.  dtype
+        has to hold the channels' precision (the palette's column sizes, or
+        out_prec).  dtype / layout / out_prec / prec_mode / window / reduce /
+        layers / device_out as decompress.  A file with subsampled components
+        and no sYCC conversion decodes to a list of host planes, as there."""
+        if colour not in ("auto", None):
+            raise GrkGpuError("colour must be 'auto' or None (got %r)" % (colour,))
+        ji, d, info = _jp2_read(buf)
+        c = d.numcomps
+        sycc = colour == "auto" and info["colour_space"] == "sycc"
+        if any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)) and not sycc:
+            mv = memoryview(buf)[ji.cs_offset:ji.cs_offset + ji.cs_length]
+            return self.decompress(np.frombuffer(mv, dtype=np.uint8), dtype=dtype, layout=layout, out_prec=out_prec,
+                                   prec_mode=prec_mode, window=window, reduce=reduce, layers=layers), info
+        _out_ops(None, out_prec, prec_mode)  # (argument checks)
+        ops = OutOps(colour=COLOUR_AUTO if colour == "auto" else COLOUR_NONE, prec=int(out_prec or 0),
+                     prec_mode=_PREC_MODES[prec_mode])
+        if window is not None:
+            wx0, wy0, wx1, wy1 = window
+            d.x0, d.y0, d.x1, d.y1 = max(d.x0, wx0), max(d.y0, wy0), min(d.x1, wx1), min(d.y1, wy1)
+            if d.x1 <= d.x0 or d.y1 <= d.y0:
+                raise GrkGpuError("decode window outside the image")
+        cd = lambda v, s: -(-v // s)  # noqa: E731
+        R = 1 << reduce
+
+        def extent(a0, a1):  # as decompress: a window's exact extent, the whole image's ceil(size / 2^r)
+            return cd(a1, R) - cd(a0, R) if window is not None else cd(a1 - a0, R)
+        h, w = extent(d.y0, d.y1), extent(d.x0, d.x1)
+        dt, fmt = _out_format(dtype)
+        oprec = [ops.prec or d.prec[k] for k in range(c)]
+        if not _fmt_fits(fmt, oprec, [d.sgnd[k] for k in range(c)]):
+            raise GrkGpuError("%s samples do not hold the output precision / signedness (%s bits)"
+                              % (dt.name, "/".join(str(v) for v in oprec)))
+        if layers < 0:
+            raise GrkGpuError("layers must be >= 0")
+        shape = _layout_shape((c, h, w), layout)
+        if device_out:
+            out = _torch().empty(shape, dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
+            lib().grkgpu_set_stream(self._ctx, _stream_handle(out.device))
+        else:
+            out = np.empty(shape, dtype=dt)
+        op = self._out_planes(out, c, fmt, layout, bool(device_out))
+        bp, bn, keep = _buf_ptr(buf)
+        dp = DParams(cp_reduce=reduce, cp_layer=layers)
+        if window is not None:
+            dp.DA_x0, dp.DA_y0, dp.DA_x1, dp.DA_y1 = [int(v) for v in window]
+        _check(lib().grkgpu_jp2_decompress(self._ctx, bp, bn, ctypes.byref(dp), 0, 0xFFFFFFFF, None, ctypes.byref(op),
+                                           ctypes.byref(ops), None))
+        return out, info
+
+    def compress_jp2(self, img, prec, colour_space="unknown", icc=None, alpha=None, params=None, offset=(0, 0),
+                     sgnd=False, layout="chw", subsampling=None, size=None):
+        """Encode img as a .jp2 file (grkgpu_jp2_compress): compress's
+        codestream inside the boxes the reference's encoder writes for an image
+        of that colour space (a COLOUR_SPACES name; "icc" takes the profile's
+        bytes in icc) and per-component alpha types (alpha: one cdef Typ per
+        component, 0 = colour; a cdef box is written for exactly one alpha
+        channel behind the colour channels).  The boxes are gathered ahead of
+        the packets on the device, so the file leaves in the one copy compress
+        makes.  img / prec / params / offset / sgnd / layout as compress; with
+        subsampling and size, img is compress_subsampled's list of planes."""
+        if subsampling is not None:
+            d, pl, keep = self._image_subsampled(img, prec, size, subsampling, offset, sgnd)
+        else:
+            d, pl, keep = self._image(img, prec, offset, sgnd, layout)
+        wp, keep_icc = _jp2_wparams(d.numcomps, colour_space, icc, alpha)
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        n = ctypes.c_size_t()
+        _check(lib().grkgpu_jp2_compress(self._ctx, ctypes.byref(d), ctypes.byref(params or CParams.make()),
+                                         ctypes.byref(wp), ctypes.byref(pl), ctypes.byref(out), ctypes.byref(n)))
+        return ctypes.string_at(out, n.value)
 
 
 def device_set(device=-1):
@@ -1318,4 +1526,48 @@ def mct_inv_custom_to(src, dst, w, matrix, offsets, prec, sgnd, layout="chw", ds
     _check(lib().grkgpu_mct_inv_custom_to(ptrs, c, w, h, sstride, m.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                           None if o is None else o.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                           pr, sg, ctypes.byref(op), stride, _stream_handle(src.device)))
+    return dst
+
+
+def palette_to(src, dst, w, prec, sgnd, chan_comp, chan_pcol, chan_prec, table=None, layout="chw", dst_stride=None):
+    """grkgpu_palette_to: the palette store of Codec.decompress_jp2 on its own.
+    src: (c,h,src_stride) int32 cuda tensor, the components after the inverse
+    5/3 wavelet (rows hold the w samples first); prec / sgnd: the components';
+    output channel k takes component chan_comp[k]'s finished sample
+    (chan_pcol[k] None) or table[clamp(sample, 0, NE - 1), chan_pcol[k]];
+    table: (NE, NPC) uint16 cuda tensor (int16 storage is read as uint16) or
+    None; chan_prec: what the channels leave with; dst, layout and dst_stride
+    as mct_inv_dcshift_to, over the channels.  Returns dst."""
+    c, h, sstride = src.shape
+    nch = len(chan_comp)
+    dt, fmt = _out_format(_out_dtype(dst))
+    _layout_shape((nch, h, w), layout)  # refuses an unknown layout
+    il = layout == "hwc"
+    row = w * nch if il else w
+    stride = row if dst_stride is None else dst_stride
+    need = (h - 1) * stride + row if il else (nch * h - 1) * stride + row
+    torch = _torch()
+    if (src.dtype != torch.int32 or not src.is_contiguous() or not src.is_cuda or dst.dim() != 1
+            or not dst.is_contiguous() or dst.device != src.device or w > sstride or stride < row
+            or dst.numel() < need or len(chan_pcol) != nch or len(chan_prec) != nch):
+        raise GrkGpuError("palette_to: src (c,h,stride >= w) int32, one comp / pcol / prec per channel, dst flat, "
+                          "%d samples, on src's device" % need)
+    ne = npc = 0
+    tp = None
+    if table is not None:
+        if (table.dim() != 2 or table.element_size() != 2 or not table.is_contiguous() or table.device != src.device):
+            raise GrkGpuError("palette_to: table (NE, NPC) of 16-bit entries on src's device")
+        ne, npc = table.shape
+        tp = table.data_ptr()
+    op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout], on_device=1)
+    for k in range(1 if il else nch):
+        op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
+    ptrs = (ctypes.c_void_p * c)(*[src[k].data_ptr() for k in range(c)])
+    pr = (ctypes.c_uint32 * c)(*_per_comp(prec, c))
+    sg = (ctypes.c_int32 * c)(*[1 if v else 0 for v in _per_comp(sgnd, c)])
+    cc = (ctypes.c_uint32 * nch)(*[int(v) for v in chan_comp])
+    cpc = (ctypes.c_int32 * nch)(*[-1 if v is None else int(v) for v in chan_pcol])
+    cpr = (ctypes.c_uint32 * nch)(*[int(v) for v in chan_prec])
+    _check(lib().grkgpu_palette_to(ptrs, c, w, h, sstride, pr, sg, nch, cc, cpc, cpr, tp, ne, npc, ctypes.byref(op),
+                                   stride, _stream_handle(src.device)))
     return dst

@@ -29,6 +29,7 @@
 #include "codestream.h"
 #include "grk_device.h"
 #include "host_pool.h"
+#include "jp2.h"
 #include "t2.h"
 
 using namespace grkgpu;
@@ -99,6 +100,7 @@ struct CtxDevBufs {
     // (launch_pass_records): per block its distortion factor and record slots
     // (in), its summary and records (out)
     DevBuf pinfo, precs;
+    DevBuf pal;  // JP2 decode: the palette table, uploaded again by every call that looks up
 };
 struct CtxHostBufs {
     HostBuf h_results, h_packed, h_gather, h_blocks, h_out, h_symoff, h_dwtjobs, h_segs;
@@ -235,13 +237,13 @@ int grkgpu_set_stream(grkgpu_ctx *c, void *stream) {
 // Every buffer of CtxDevBufs / CtxHostBufs, for grkgpu_debug_fill.
 namespace {
 struct CtxBuffers {
-    DevBuf *dev[20];
+    DevBuf *dev[21];
     HostBuf *host[13];
 };
 CtxBuffers ctx_buffers(grkgpu_ctx *c) {
     CtxBuffers b{{&c->img, &c->work, &c->coef, &c->ll, &c->scratch, &c->mqout, &c->blocks, &c->results, &c->gather,
                   &c->packed, &c->cs, &c->sym, &c->symoff, &c->dwtjobs, &c->ubuf, &c->segs, &c->dwtjobs53, &c->t1order,
-                  &c->pinfo, &c->precs},
+                  &c->pinfo, &c->precs, &c->pal},
                  {&c->h_results, &c->h_packed, &c->h_gather, &c->h_blocks, &c->h_out, &c->h_symoff, &c->h_dwtjobs,
                   &c->h_segs, &c->h_pinfo, &c->h_psum, &c->h_precs, &c->h_dwtjobs53, &c->h_slab}};
     static_assert(sizeof(CtxDevBufs) == sizeof(b.dev) / sizeof(b.dev[0]) * sizeof(DevBuf),
@@ -1200,7 +1202,7 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
                          size_t *outlen,
                          uint32_t tb = 0, uint32_t te = 0xffffffffu, uint32_t parts = GRKGPU_PART_ALL,
                          bool export_blocks = false, int force_dist = 0, uint32_t row0 = 0, uint32_t nrows = 0,
-                         uint32_t col0 = 0, uint32_t ncols = 0) {
+                         uint32_t col0 = 0, uint32_t ncols = 0, const std::vector<uint8_t> *jp2_boxes = nullptr) {
     if (!c || !planes) return set_err(GRKGPU_EINVAL, "null argument");
     ActiveCall active;
     CodingParams cp;
@@ -1938,6 +1940,19 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
         hdr.put16(0xFFD9);
         plan.push_back({eoc, 2, 0});
     }
+    if (jp2_boxes) {
+        // grkgpu_jp2_compress: the file's boxes (ending in the jp2c box header)
+        // are one more run of the header blob, gathered ahead of everything
+        // else; the plan's total is the codestream's length, so jp2c's LBox
+        // (jp2_write_jp2c, jp2.cpp:2075-2116) is known before the launch
+        uint64_t cslen = 0;
+        for (auto &pi : plan) cslen += pi.len;
+        if (cslen + 8 >= (1ull << 32)) return set_err(GRKGPU_EUNSUPPORTED, "JP2: codestream too long for a 32-bit LBox");
+        const size_t at = hdr.size();
+        hdr.putn(jp2_boxes->data(), jp2_boxes->size());
+        hdr.set32(at + jp2_boxes->size() - 8, (uint32_t)(cslen + 8));
+        plan.insert(plan.begin(), PlanItem{at, (uint32_t)jp2_boxes->size(), 0});
+    }
     // gather list: dst offsets = prefix sum of run lengths
     std::vector<GatherItem> gi;
     gi.reserve(plan.size());
@@ -2442,6 +2457,20 @@ struct DecodeOut {
     int upsample;  // GRKGPU_LAYOUT_UPSAMPLE: subsampled components replicated to the image grid
     const grkgpu_out_ops *ops;  // grkgpu_decompress_convert: colour / precision in the last store (null: none)
     int custom_mct;  // grkgpu_decompress_mct: a COD with MCT = 2 (Part 2 array-based) is decoded, not refused
+    const struct ChanMap *chan;  // grkgpu_jp2_decompress: the output channels where they are not the components in order
+};
+// The output channels of a JP2 file with a palette or a channel swap
+// (jp2_resolve_channels): channel c takes component comp[c]'s sample, or entry
+// [sample][pcol[c]] of the ne x npc table (host memory), and leaves with prec[c]
+// bits.  Planes, sample format, layout and ops of the call describe channels.
+struct ChanMap {
+    uint32_t nch;
+    uint32_t comp[GRKGPU_MAX_COMPS];
+    int32_t pcol[GRKGPU_MAX_COMPS];
+    uint32_t prec[GRKGPU_MAX_COMPS];
+    int32_t sgnd[GRKGPU_MAX_COMPS];
+    uint32_t ne, npc;
+    const uint16_t *table;
 };
 static DecodeOut i32_planes(int32_t *const *planes, int on_device) {
     return {(void *const *)planes, SMP_I32, 0, on_device};
@@ -2624,7 +2653,34 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     OutOps dops{};
     uint32_t oprec[GRKGPU_MAX_COMPS];
     for (uint32_t k = 0; k < nc; ++k) oprec[k] = cp.prec[k];
-    if (conv) {
+    // od.chan (grkgpu_jp2_decompress): `no` output channels instead of the nc
+    // components -- what the planes, the format and the ops describe from here on
+    const ChanMap *const cm = od.chan;
+    const uint32_t no = cm ? cm->nch : nc;
+    if (cm) {
+        if (subs) return set_err(GRKGPU_EUNSUPPORTED, "JP2 palette / channel order over subsampled components");
+        if (sycc) return set_err(GRKGPU_EUNSUPPORTED, "sYCC conversion behind a JP2 palette or channel swap");
+        if (no < 1 || no > GRKGPU_MAX_COMPS) return set_err(GRKGPU_EINVAL, "bad channel map");
+        for (uint32_t ch = 0; ch < no; ++ch) {
+            if (cm->comp[ch] >= nc || (cm->pcol[ch] >= 0 && (!cm->table || !cm->ne || (uint32_t)cm->pcol[ch] >= cm->npc)))
+                return set_err(GRKGPU_EINVAL, "bad channel map");
+            oprec[ch] = cm->prec[ch];
+        }
+        if (img) {
+            img->numcomps = no;
+            for (uint32_t ch = 0; ch < no; ++ch) {
+                img->prec[ch] = cm->prec[ch];
+                img->sgnd[ch] = cm->sgnd[ch];
+                img->dx[ch] = img->dy[ch] = 1;
+            }
+        }
+        if (conv) {
+            uint32_t one[GRKGPU_MAX_COMPS];
+            for (uint32_t ch = 0; ch < GRKGPU_MAX_COMPS; ++ch) one[ch] = 1;
+            int rc = resolve_out_ops(od.ops, no, cm->prec, cm->sgnd, one, one, dops, oprec);
+            if (rc) return rc;
+        }
+    } else if (conv) {
         int rc = resolve_out_ops(od.ops, nc, cp.prec, cp.sgnd, cp.dx, cp.dy, dops, oprec);
         if (rc) return rc;
     }
@@ -2634,11 +2690,15 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     if (img && up)
         for (uint32_t k = 0; k < nc; ++k) img->dx[k] = img->dy[k] = 1;
     if (img && conv)
-        for (uint32_t k = 0; k < nc; ++k) img->prec[k] = oprec[k];
-    for (uint32_t k = 0; od.fmt != SMP_I32 && k < nc; ++k) {
+        for (uint32_t k = 0; k < no; ++k) img->prec[k] = oprec[k];
+    for (uint32_t k = 0; od.fmt != SMP_I32 && k < no; ++k) {
         const bool sg = od.fmt == SMP_I8 || od.fmt == SMP_I16;
-        if ((cp.sgnd[k] != 0) != sg || oprec[k] > 8 * sb)
+        if (((cm ? cm->sgnd[k] : cp.sgnd[k]) != 0) != sg || oprec[k] > 8 * sb)
             return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
+        // a channel used directly carries its component's samples whatever the palette box says of its size
+        if (cm && cm->pcol[k] < 0 && (cm->prec[k] != cp.prec[cm->comp[k]] || (cm->sgnd[k] != 0) != (cp.sgnd[cm->comp[k]] != 0)))
+            return set_err(GRKGPU_EINVAL, "a directly mapped channel whose declared size differs from its component's "
+                                          "needs int32 samples");
     }
     // the staging planes of an upsampled decode keep the stream's precision:
     // the ops run in the replicating launch, which reads one sample type and
@@ -2647,18 +2707,19 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     const uint32_t ssb = sample_bytes(sfmt);
     if (il && mixed && !up)
         return set_err(GRKGPU_EUNSUPPORTED, "interleaved output needs every component on one grid");
-    if (il && (uint64_t)iw * nc > 0xffffffffull)  // the kernel's row stride is 32 bits of samples
+    if (il && (uint64_t)iw * no > 0xffffffffull)  // the kernel's row stride is 32 bits of samples
         return set_err(GRKGPU_EUNSUPPORTED, "image too wide for interleaved output");
-    for (uint32_t k = 0; !host_only && k < (il ? 1u : nc); ++k)
+    for (uint32_t k = 0; !host_only && k < (il ? 1u : no); ++k)
         if (!planes[k] || (uintptr_t)planes[k] % sb) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
     Rect orect[GRKGPU_MAX_COMPS];
     uint64_t ooff[GRKGPU_MAX_COMPS + 1];
     ooff[0] = 0;
     bool opad = false;  // planes extending past the decoded samples (zero filled)
-    for (uint32_t k = 0; k < nc; ++k) {
-        orect[k] = comp_rect({ix0, iy0, ix1, iy1}, cp.dx[k], cp.dy[k]);
+    for (uint32_t k = 0; k < std::max(nc, no); ++k) {  // (a channel map: every component at (1,1))
+        const uint32_t kdx = k < nc ? cp.dx[k] : 1, kdy = k < nc ? cp.dy[k] : 1;
+        orect[k] = comp_rect({ix0, iy0, ix1, iy1}, kdx, kdy);
         if (!win) {  // ceil(ceil(size on the component grid) / 2^reduce)
-            const Rect cr = comp_rect(cp.image, cp.dx[k], cp.dy[k]);
+            const Rect cr = comp_rect(cp.image, kdx, kdy);
             const Rect sized{orect[k].x0, orect[k].y0, orect[k].x0 + ceil_pow2(cr.w(), reduce),
                              orect[k].y0 + ceil_pow2(cr.h(), reduce)};
             opad = opad || sized.x1 != orect[k].x1 || sized.y1 != orect[k].y1;
@@ -3072,6 +3133,27 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     // zero (they lie outside every window sample's support; zero keeps the
     // 9/7 float lifting free of stale NaNs)
     if (win && arena) HIPCHK(hipMemsetAsync(c->coef.p, 0, arena * 4, s));
+    // a channel map: the table goes to the device with the codestream, inside
+    // the H2D interval (uploaded by every call, so nothing of an earlier one
+    // is read) -- the store stage's events then bracket launches only
+    PalMap pmap{};
+    const uint16_t *ptable = nullptr;
+    if (cm) {
+        pmap.nch = no;
+        pmap.ne = cm->table ? cm->ne : 0;
+        pmap.npc = cm->table ? cm->npc : 0;
+        for (uint32_t ch = 0; ch < no; ++ch) {
+            pmap.comp[ch] = (uint8_t)cm->comp[ch];
+            pmap.pcol[ch] = (int8_t)cm->pcol[ch];
+        }
+        set_pal_used(pmap);
+        if (pmap.ne) {
+            const size_t tbytes = (size_t)pmap.ne * pmap.npc * sizeof(uint16_t);
+            HIPCHK(c->pal.ensure(tbytes));
+            HIPCHK(hipMemcpyAsync(c->pal.p, cm->table, tbytes, hipMemcpyHostToDevice, s));
+            ptable = c->pal.as<uint16_t>();
+        }
+    }
     HIPCHK(hipEventRecord(c->ev[1], s));
     for (const StyRange &g : sranges)
         HIPCHK(launch_t1_decode(c->blocks.as<DecBlock>() + g.b0, g.n, c->cs.as<uint8_t>(),
@@ -3091,13 +3173,13 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     // or the one interleaved image) of elements `eb` bytes wide (a sample, or
     // a pixel of nc samples); region k holds ooff[k + 1] - ooff[k] samples
     // (interleaved: all ooff[nc] of them)
-    const uint32_t nout = il ? 1 : nc;
-    const size_t eb = il ? (size_t)nc * sb : sb;
+    const uint32_t nout = il ? 1 : no;
+    const size_t eb = il ? (size_t)no * sb : sb;
     // (upsampled: every component has the output rectangle's iw x (oy1 - iy0) samples)
     const uint64_t opix = (uint64_t)iw * (oy1 - iy0);
     auto region_bytes = [&](uint32_t k) {
         if (up) return (size_t)(opix * (il ? nc : 1)) * sb;
-        return (size_t)(il ? ooff[nc] : ooff[k + 1] - ooff[k]) * sb;
+        return (size_t)(il ? ooff[no] : ooff[k + 1] - ooff[k]) * sb;
     };
     // upsampled: which components go through a staging plane -- all when they
     // share one subsampled grid (their MCT runs first); otherwise those with a
@@ -3151,7 +3233,30 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
             fdst.p[k] = at(k, (uint64_t)(o.y0 - orect[0].y0) * ow + (o.x0 - orect[0].x0));
         return launch_upsample_ops(zero, nc, o.x0, o.y0, o.w(), o.h(), fdst, od.fmt, il, il ? ow * nc : ow, dops, s);
     };
-    if (sycc && !up && opad) {
+    // a channel map's fills: the palette store run over zero samples -- entry 0
+    // of each looked-up channel, then the precision op -- since the
+    // reference's pass maps the zeros it finds
+    auto fill_mapped = [&](const Rect &o) -> hipError_t {
+        const uint32_t ow = orect[0].w();
+        DstPlanes fdst{};
+        for (uint32_t k = 0; k < nout; ++k)
+            fdst.p[k] = at(k, (uint64_t)(o.y0 - orect[0].y0) * ow + (o.x0 - orect[0].x0));
+        PalMap z = pmap;
+        z.zero = 1;
+        return launch_palette(PlanePtrs{}, 0, o.w(), o.h(), fdst, od.fmt, il, il ? ow * no : ow, nc, ShiftArr{},
+                              ShiftArr{}, ShiftArr{}, 0, 0, z, ptable, conv ? &dops : nullptr, s);
+    };
+    if (cm && opad) {
+        HIPCHK(fill_mapped(orect[0]));
+    } else if (cm && missing) {
+        for (uint32_t t = tb; t < te; ++t) {
+            if (walk.decoded[t] || wskip[t]) continue;
+            const Rect cr = tile_rect(cp, t);
+            const Rect o = intersect({ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
+                                      ceil_pow2(cr.y1, reduce)}, orect[0]);
+            if (!o.empty()) HIPCHK(fill_mapped(o));
+        }
+    } else if (sycc && !up && opad) {
         HIPCHK(fill_converted(orect[0]));
     } else if (sycc && !up && missing) {
         for (uint32_t t = tb; t < te; ++t) {
@@ -3234,7 +3339,10 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         int32_t wmask = 0;  // components holding 9/7 (float) samples
         for (uint32_t k = 0; k < nc; ++k) wmask |= tile.comps[k].irrev << k;
         // row stride in samples: a row of an interleaved image holds ow pixels of nc samples
-        if (tmct[tile.index - tb] == 2)  // (every component at (1,1): never upsampled)
+        if (cm)  // (every component at (1,1); a custom MCT is refused at the COD)
+            HIPCHK(launch_palette(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * no : ow, nc, sh, mn, mx,
+                                  tmct[tile.index - tb], wmask, pmap, ptable, conv ? &dops : nullptr, s));
+        else if (tmct[tile.index - tb] == 2)  // (every component at (1,1): never upsampled)
             HIPCHK(launch_mct_inv_custom(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * nc : ow, nc, minv,
                                          moff, mn, mx, conv ? &dops : nullptr, s));
         else if (conv && !up)
@@ -3377,7 +3485,8 @@ static int check_out_planes(const grkgpu_out_planes *out) {
 
 static int decompress_to_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
                               uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
-                              const grkgpu_out_planes *out, const grkgpu_out_ops *ops, bool custom_mct = false) {
+                              const grkgpu_out_planes *out, const grkgpu_out_ops *ops, bool custom_mct = false,
+                              const ChanMap *chan = nullptr) {
     int rc = check_out_planes(out);
     if (rc) return rc;
     rc = check_out_ops(ops, out->sample_fmt);
@@ -3385,7 +3494,7 @@ static int decompress_to_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, con
     const DecodeOut od{out->planes, (int32_t)out->sample_fmt,
                        (out->layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED, out->on_device,
                        (out->layout & GRKGPU_LAYOUT_UPSAMPLE) != 0, out_ops_active(ops) ? ops : nullptr,
-                       custom_mct ? 1 : 0};
+                       custom_mct ? 1 : 0, chan};
     if (!dp) return decompress_impl(c, csb, len, img, od, tile_begin, tile_end);
     const bool win = dp->DA_x0 || dp->DA_y0 || dp->DA_x1 || dp->DA_y1;
     const Rect w{dp->DA_x0, dp->DA_y0, dp->DA_x1, dp->DA_y1};
@@ -3410,6 +3519,203 @@ extern "C" int grkgpu_decompress_mct(grkgpu_ctx *c, const uint8_t *csb, size_t l
                                      uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
                                      const grkgpu_out_planes *out, const grkgpu_out_ops *ops) {
     return decompress_to_impl(c, csb, len, dp, tile_begin, tile_end, img, out, ops, true);
+}
+
+// ---------------------------------------------------------------------------
+// JP2 files: the box layer (jp2.cpp) around the entry points above
+// ---------------------------------------------------------------------------
+namespace {
+struct Jp2Parsed {
+    Jp2Boxes boxes;
+    Jp2Channels ch;
+    CodingParams cp;
+    std::vector<uint16_t> table;  // the applied palette, ne x npc
+};
+}  // namespace
+
+// boxes, the codestream's main header and the channel list; info / img (either may be null) filled
+static int jp2_parse(const uint8_t *file, size_t len, Jp2Parsed &j, grkgpu_jp2_info *info, grkgpu_image_desc *img) {
+    if (!file) return set_err(GRKGPU_EINVAL, "null argument");
+    std::string err;
+    Jp2Status st = jp2_read_boxes(file, len, j.boxes, err);
+    if (st) return set_err(st == JP2_CORRUPT ? GRKGPU_ECORRUPT : GRKGPU_EUNSUPPORTED, err);
+    Jp2Boxes &b = j.boxes;
+    size_t sot = 0;
+    if (!parse_main_header(file + b.cs_off, (size_t)b.cs_len, j.cp, sot, err)) return set_err(GRKGPU_EUNSUPPORTED, err);
+    const CodingParams &cp = j.cp;
+    st = jp2_resolve_channels(b, cp.numcomps, cp.prec, cp.sgnd, cp.dx, cp.dy, GRKGPU_MAX_COMPS, j.ch, err);
+    if (st) return set_err(st == JP2_CORRUPT ? GRKGPU_ECORRUPT : GRKGPU_EUNSUPPORTED, err);
+    if (b.have_cdef && b.cdef.size() > GRKGPU_JP2_MAX_CDEF)
+        return set_err(GRKGPU_EUNSUPPORTED, "JP2: more channel definitions than this decoder keeps");
+    if (j.ch.mapped)
+        for (uint32_t k = 0; k < cp.numcomps; ++k)
+            if (cp.dx[k] != 1 || cp.dy[k] != 1)
+                return set_err(GRKGPU_EUNSUPPORTED, "JP2: palette / channel swap on an image with subsampled components");
+    if (j.ch.palette) {
+        j.table.resize(b.entries.size());
+        for (size_t i = 0; i < b.entries.size(); ++i) j.table[i] = (uint16_t)b.entries[i];  // (columns of <= 16 bits)
+    }
+    const uint32_t nch = (uint32_t)j.ch.ch.size();
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->cs_offset = b.cs_off;
+        info->cs_length = b.cs_len;
+        info->ihdr_w = b.w; info->ihdr_h = b.h; info->ihdr_nc = b.numcomps; info->ihdr_bpc = b.bpc;
+        if (b.have_colr) { info->meth = b.meth; info->enumcs = b.meth == 1 ? b.enumcs : 0; }
+        info->colour_space = j.ch.colour_space;
+        info->icc_offset = b.icc_off;
+        info->icc_length = b.icc_len;
+        info->cielab_words = b.ncielab;
+        for (uint32_t i = 0; i < b.ncielab; ++i) info->cielab[i] = b.cielab[i];
+        if (j.ch.palette) {
+            info->pal_entries = b.ne;
+            info->pal_columns = b.npc;
+            for (uint32_t i = 0; i < b.npc; ++i) {
+                info->pal_prec[i] = b.pal_size[i];
+                info->pal_sgnd[i] = b.pal_sign[i];
+                info->cmap_cmp[i] = b.cmap[i].cmp;
+                info->cmap_mtyp[i] = b.cmap[i].mtyp;
+                info->cmap_pcol[i] = b.cmap[i].pcol;
+            }
+        }
+        info->cdef_n = b.have_cdef ? (uint32_t)b.cdef.size() : 0;
+        for (uint32_t i = 0; i < info->cdef_n; ++i) {
+            info->cdef_cn[i] = b.cdef[i].cn;
+            info->cdef_typ[i] = b.cdef[i].typ;
+            info->cdef_asoc[i] = b.cdef[i].asoc;
+        }
+        info->numchannels = nch;
+        for (uint32_t i = 0; i < nch; ++i) {
+            const Jp2Channel &ch = j.ch.ch[i];
+            info->chan_prec[i] = ch.prec;
+            info->chan_sgnd[i] = ch.sgnd;
+            info->chan_alpha[i] = ch.alpha;
+            info->chan_comp[i] = ch.comp;
+            info->chan_pcol[i] = ch.pcol;
+        }
+        info->mapped = j.ch.mapped ? 1 : 0;
+    }
+    if (img) {
+        image_desc_of(cp, img);
+        img->numcomps = nch;
+        for (uint32_t i = 0; i < nch; ++i) {
+            const Jp2Channel &ch = j.ch.ch[i];
+            img->prec[i] = ch.prec;
+            img->sgnd[i] = ch.sgnd;
+            img->dx[i] = ch.dx;
+            img->dy[i] = ch.dy;
+        }
+    }
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_jp2_read_info(const uint8_t *file, size_t len, grkgpu_jp2_info *info, grkgpu_image_desc *img) {
+    if (!file || !info) return set_err(GRKGPU_EINVAL, "null argument");
+    Jp2Parsed j;
+    return jp2_parse(file, len, j, info, img);
+}
+
+extern "C" int grkgpu_jp2_read_palette(const uint8_t *file, size_t len, uint16_t *entries, uint32_t cap, uint32_t *n) {
+    if (!file || !n) return set_err(GRKGPU_EINVAL, "null argument");
+    Jp2Parsed j;
+    int rc = jp2_parse(file, len, j, nullptr, nullptr);
+    if (rc) return rc;
+    *n = (uint32_t)j.table.size();
+    if (*n && (!entries || cap < *n)) return set_err(GRKGPU_EINVAL, "palette buffer too small");
+    for (uint32_t i = 0; i < *n; ++i) entries[i] = j.table[i];
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_jp2_decompress(grkgpu_ctx *c, const uint8_t *file, size_t len, const grkgpu_dparams *dp,
+                                     uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                                     const grkgpu_out_planes *out, const grkgpu_out_ops *ops, grkgpu_jp2_info *info) {
+    if (!c || !file || !out) return set_err(GRKGPU_EINVAL, "null argument");
+    Jp2Parsed j;
+    int rc = jp2_parse(file, len, j, info, nullptr);
+    if (rc) return rc;
+    grkgpu_out_ops o{};
+    if (ops) {
+        o = *ops;
+        if (o.colour == GRKGPU_COLOUR_AUTO)
+            o.colour = j.ch.colour_space == JP2_CS_SYCC ? GRKGPU_COLOUR_SYCC : GRKGPU_COLOUR_NONE;
+    }
+    const uint8_t *cs = file + j.boxes.cs_off;
+    const size_t cslen = (size_t)j.boxes.cs_len;
+    if (!j.ch.mapped) return decompress_to_impl(c, cs, cslen, dp, tile_begin, tile_end, img, out, ops ? &o : nullptr);
+    ChanMap cm{};
+    cm.nch = (uint32_t)j.ch.ch.size();
+    for (uint32_t i = 0; i < cm.nch; ++i) {
+        cm.comp[i] = j.ch.ch[i].comp;
+        cm.pcol[i] = j.ch.ch[i].pcol;
+        cm.prec[i] = j.ch.ch[i].prec;
+        cm.sgnd[i] = j.ch.ch[i].sgnd;
+    }
+    if (j.ch.palette) {
+        cm.ne = j.boxes.ne;
+        cm.npc = j.boxes.npc;
+        cm.table = j.table.data();
+    }
+    return decompress_to_impl(c, cs, cslen, dp, tile_begin, tile_end, img, out, ops ? &o : nullptr, false, &cm);
+}
+
+static int jp2_wparams_of(const grkgpu_image_desc *img, const grkgpu_jp2_wparams *wp, Jp2WriteParams &w) {
+    if (!img || !wp) return set_err(GRKGPU_EINVAL, "null argument");
+    if (img->numcomps < 1 || img->numcomps > GRKGPU_MAX_COMPS || img->x1 <= img->x0 || img->y1 <= img->y0)
+        return set_err(GRKGPU_EINVAL, "bad image");
+    if (wp->colour_space > GRKGPU_CS_ICC) return set_err(GRKGPU_EINVAL, "unknown colour space");
+    w.w = img->x1 - img->x0;
+    w.h = img->y1 - img->y0;
+    w.numcomps = img->numcomps;
+    uint64_t bytes = 0;  // jp2_start_compress (:2681-2688): above 2^30 the reference writes an XL jp2c
+    for (uint32_t k = 0; k < img->numcomps; ++k) {
+        if (img->prec[k] < 1 || img->prec[k] > 16) return set_err(GRKGPU_EINVAL, "bad component precision");
+        if (wp->alpha[k] > 0xffff) return set_err(GRKGPU_EINVAL, "alpha type out of range");
+        w.prec[k] = img->prec[k];
+        w.sgnd[k] = img->sgnd[k];
+        w.alpha[k] = wp->alpha[k];
+        const uint32_t dx = img->dx[k] ? img->dx[k] : 1, dy = img->dy[k] ? img->dy[k] : 1;
+        const uint64_t cw = ((uint64_t)img->x1 + dx - 1) / dx - ((uint64_t)img->x0 + dx - 1) / dx;
+        const uint64_t chh = ((uint64_t)img->y1 + dy - 1) / dy - ((uint64_t)img->y0 + dy - 1) / dy;
+        bytes += cw * chh * ((img->prec[k] + 7) / 8);
+    }
+    if (bytes > (1ull << 30)) return set_err(GRKGPU_EUNSUPPORTED, "JP2: an image this large needs an XL jp2c box, which is not written");
+    w.colour_space = wp->colour_space;
+    w.icc = wp->icc;
+    w.icc_len = wp->icc_len;
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_jp2_write_boxes(const grkgpu_image_desc *img, const grkgpu_jp2_wparams *wp, uint64_t cs_len,
+                                      uint8_t *buf, size_t cap, size_t *n) {
+    if (!n) return set_err(GRKGPU_EINVAL, "null argument");
+    Jp2WriteParams w;
+    int rc = jp2_wparams_of(img, wp, w);
+    if (rc) return rc;
+    std::vector<uint8_t> boxes;
+    std::string err;
+    if (!jp2_write_boxes(w, boxes, err)) return set_err(GRKGPU_EINVAL, err);
+    if (cs_len + 8 >= (1ull << 32)) return set_err(GRKGPU_EUNSUPPORTED, "JP2: codestream too long for a 32-bit LBox");
+    const uint32_t lbox = (uint32_t)(cs_len + 8);
+    for (int i = 0; i < 4; ++i) boxes[boxes.size() - 8 + i] = (uint8_t)(lbox >> (8 * (3 - i)));
+    *n = boxes.size();
+    if (!buf || cap < boxes.size()) return set_err(GRKGPU_EINVAL, "box buffer too small");
+    memcpy(buf, boxes.data(), boxes.size());
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_jp2_compress(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkgpu_cparams *p,
+                                   const grkgpu_jp2_wparams *wp, const grkgpu_planes *in, const uint8_t **out,
+                                   size_t *outlen) {
+    if (!c || !in || !out || !outlen) return set_err(GRKGPU_EINVAL, "null argument");
+    if (in->nrows || in->row0 || in->ncols || in->col0) return set_err(GRKGPU_EINVAL, "a JP2 file holds the whole image");
+    Jp2WriteParams w;
+    int rc = jp2_wparams_of(img, wp, w);
+    if (rc) return rc;
+    std::vector<uint8_t> boxes;
+    std::string err;
+    if (!jp2_write_boxes(w, boxes, err)) return set_err(GRKGPU_EINVAL, err);
+    return compress_impl(c, img, p, in->planes, in->on_device, (int32_t)in->sample_fmt, out, outlen, 0, 0xffffffffu,
+                         GRKGPU_PART_ALL, false, 0, 0, 0, 0, 0, &boxes);
 }
 
 // ---------------------------------------------------------------------------
@@ -3557,6 +3863,59 @@ extern "C" int grkgpu_mct_inv_custom_to(const float *const *src, uint32_t numcom
     if (rc) return rc;
     HIPCHK(launch_mct_inv_custom(p, src_stride, w, h, d, fmt, il, dst_stride, numcomps, m, off, mn, mx, nullptr,
                                  (hipStream_t)stream));
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_palette_to(const int32_t *const *src, uint32_t numcomps, uint32_t w, uint32_t h,
+                                 uint32_t src_stride, const uint32_t *prec, const int32_t *sgnd, uint32_t numchannels,
+                                 const uint32_t *chan_comp, const int32_t *chan_pcol, const uint32_t *chan_prec,
+                                 const uint16_t *table, uint32_t ne, uint32_t npc, const grkgpu_out_planes *dst,
+                                 uint32_t dst_stride, void *stream) {
+    int rc = check_out_planes(dst);
+    if (rc) return rc;
+    if (dst->layout & GRKGPU_LAYOUT_UPSAMPLE) return set_err(GRKGPU_EINVAL, "unknown layout");
+    const bool il = dst->layout == GRKGPU_LAYOUT_INTERLEAVED;
+    const int32_t fmt = (int32_t)dst->sample_fmt;
+    const uint32_t sb = sample_bytes(fmt);
+    if (!src || !prec || !sgnd || !chan_comp || !chan_pcol || !chan_prec || numcomps < 1 || numcomps > 16 ||
+        numchannels < 1 || numchannels > 16 || src_stride < w ||
+        (uint64_t)dst_stride < (uint64_t)w * (il ? numchannels : 1))
+        return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
+    if (ne > 1024 || npc > 16 || (table && (!ne || !npc))) return set_err(GRKGPU_EINVAL, "palette of 1 .. 1024 x 1 .. 16 entries");
+    PlanePtrs p{};
+    DstPlanes d{};
+    ShiftArr sh{}, mn{}, mx{};
+    for (uint32_t k = 0; k < numcomps; ++k) {
+        if (prec[k] < 1 || prec[k] > 31 || !src[k] || (uintptr_t)src[k] % 4) return set_err(GRKGPU_EINVAL, "bad arguments");
+        p.p[k] = const_cast<int32_t *>(src[k]);
+        if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
+        else { sh.v[k] = 1 << (prec[k] - 1); mn.v[k] = 0; mx.v[k] = (int32_t)((1u << prec[k]) - 1); }
+    }
+    PalMap map{};
+    map.nch = numchannels;
+    map.ne = table ? ne : 0;
+    map.npc = table ? npc : 0;
+    const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
+    for (uint32_t ch = 0; ch < numchannels; ++ch) {
+        if (chan_comp[ch] >= numcomps || chan_pcol[ch] >= (int32_t)map.npc || chan_prec[ch] < 1 || chan_prec[ch] > 31)
+            return set_err(GRKGPU_EINVAL, "channel map outside the components / the palette");
+        const bool chs = chan_pcol[ch] < 0 && sgnd[chan_comp[ch]];
+        const uint32_t chp = chan_pcol[ch] < 0 ? std::max(chan_prec[ch], prec[chan_comp[ch]]) : chan_prec[ch];
+        if (fmt != SMP_I32 && (chs != sg || chp > 8 * sb))
+            return set_err(GRKGPU_EINVAL, "sample format does not hold the channel's precision / signedness");
+        map.comp[ch] = (uint8_t)chan_comp[ch];
+        map.pcol[ch] = (int8_t)(chan_pcol[ch] < 0 ? -1 : chan_pcol[ch]);
+    }
+    set_pal_used(map);
+    for (uint32_t k = 0; k < (il ? 1u : numchannels); ++k) {
+        if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
+            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+        d.p[k] = dst->planes[k];
+    }
+    rc = check_device(-1);
+    if (rc) return rc;
+    HIPCHK(launch_palette(p, src_stride, w, h, d, fmt, il, dst_stride, numcomps, sh, mn, mx, 0, 0, map, table, nullptr,
+                          (hipStream_t)stream));
     return GRKGPU_OK;
 }
 

@@ -170,6 +170,30 @@ hipError_t launch_mct_inv_custom(const PlanePtrs &src, uint32_t sstride, uint32_
                                  const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
                                  uint32_t ncomp, const MctInv &m, const ShiftArr &off, const ShiftArr &mn,
                                  const ShiftArr &mx, const OutOps *ops, hipStream_t s);
+// The JP2 palette / channel order in the last store (jp2_apply_pclr and the
+// swaps of jp2_apply_cdef, jp2.cpp:1301-1407, 1564-1623), where
+// launch_mct_inv_dcshift_to / _ops run for a file without either: the ncomp
+// components are finished as there (mct, irrev, shift, mn, mx), then output
+// channel c < nch takes component comp[c]'s sample (pcol[c] < 0) or
+// table[clamp(sample, 0, ne - 1) * npc + pcol[c]].  table: ne x npc uint16
+// entries in device memory (null when no channel looks up).  zero: src is not
+// read, every component counts as finished zero samples.  dst, fmt, layout and
+// dstride describe the nch channels; ops (null: none; no sycc) index channels.
+struct PalMap {
+    uint8_t comp[GRK_MAX_COMPS];
+    int8_t pcol[GRK_MAX_COMPS];
+    uint32_t nch, ne, npc;
+    uint32_t used;  // bit k: component k feeds a channel (set_pal_used)
+    int32_t zero;
+};
+inline void set_pal_used(PalMap &m) {
+    m.used = 0;
+    for (uint32_t c = 0; c < m.nch && c < (uint32_t)GRK_MAX_COMPS; ++c) m.used |= 1u << (m.comp[c] & 15);
+}
+hipError_t launch_palette(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
+                          int32_t fmt, bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift,
+                          const ShiftArr &mn, const ShiftArr &mx, int32_t mct, int32_t irrev, const PalMap &map,
+                          const uint16_t *table, const OutOps *ops, hipStream_t s);
 // One DWT level of one tile-component (dwt.hip).  A launch runs one level of
 // every job in a table (grid.y = job).
 struct DwtJob {

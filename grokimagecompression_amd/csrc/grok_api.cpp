@@ -212,6 +212,12 @@ struct Codec {
     std::vector<int32_t> reduced;  // reduced-resolution decode of the whole image (cp_reduce > 0), decoded once
     grkgpu_image_desc reduced_desc{};
     bool decoded = false;  // grk_decode has read every tile-part (what grk_get_cstr_index reports)
+    // GRK_CODEC_JP2: the box layer is grkgpu_jp2_* (csrc/jp2.cpp).  Decode: cs holds the jp2c payload, so
+    // everything that reads the codestream works as on J2K; the whole file is kept only where grk_decode
+    // needs it (a palette or a channel swap: grkgpu_jp2_decompress).
+    bool jp2 = false;
+    grkgpu_jp2_info jinfo{};
+    std::vector<uint8_t> file, icc;
 };
 
 uint32_t cdivpow2(uint32_t v, uint32_t r) { return (uint32_t)(((uint64_t)v + (1ull << r) - 1) >> r); }
@@ -557,9 +563,10 @@ GRK_EXPORT bool grk_set_error_handler(grk_msg_callback cb, void *u) { g_err = {c
 // decompression
 // ---------------------------------------------------------------------------
 GRK_EXPORT grk_codec *grk_create_decompress(GRK_CODEC_FORMAT format, grk_stream *stream) {
-    if (format != GRK_CODEC_J2K) { GRK_ERROR("only raw J2K codestreams are supported (no JP2)"); return nullptr; }
+    if (format != GRK_CODEC_J2K && format != GRK_CODEC_JP2) { GRK_ERROR("unknown codec format"); return nullptr; }
     if (!stream) return nullptr;
     Codec *c = new Codec();
+    c->jp2 = format == GRK_CODEC_JP2;
     c->decompressor = true;
     c->stream = (Stream *)stream;
     grk_set_default_decoder_parameters(&c->dparams);
@@ -598,6 +605,17 @@ GRK_EXPORT bool grk_read_header(grk_codec *codec, grk_header_info *hi, grk_image
     if (!c || !c->decompressor || !image) return false;
     if (!c->have_header) {
         if (!c->stream->read_all(c->cs) || c->cs.empty()) { GRK_ERROR("empty stream"); return false; }
+        if (c->jp2) {  // jp2_read_header: the boxes, then the codestream header of the jp2c payload
+            if (grkgpu_jp2_read_info(c->cs.data(), c->cs.size(), &c->jinfo, nullptr)) {
+                GRK_ERROR("%s", grkgpu_last_error());
+                return false;
+            }
+            const grkgpu_jp2_info &ji = c->jinfo;
+            c->icc.assign(c->cs.begin() + ji.icc_offset, c->cs.begin() + ji.icc_offset + ji.icc_length);
+            std::vector<uint8_t> payload(c->cs.begin() + ji.cs_offset, c->cs.begin() + ji.cs_offset + ji.cs_length);
+            if (ji.mapped) c->file.swap(c->cs);
+            c->cs.swap(payload);
+        }
         if (grkgpu_read_header(c->cs.data(), c->cs.size(), &c->desc) ||
             grkgpu_read_header_info(c->cs.data(), c->cs.size(), &c->hinfo)) {
             GRK_ERROR("%s", grkgpu_last_error());
@@ -652,6 +670,7 @@ GRK_EXPORT bool grk_read_header(grk_codec *codec, grk_header_info *hi, grk_image
         hi->cp_tx0 = h.tx0; hi->cp_ty0 = h.ty0; hi->cp_tdx = h.tdx; hi->cp_tdy = h.tdy;
         hi->cp_tw = h.tw; hi->cp_th = h.th;
         hi->tcp_numlayers = h.numlayers;
+        if (c->jp2) hi->enumcs = c->jinfo.enumcs;  // (xml, resolutions and the color struct stay zero)
     }
     return true;
 }
@@ -688,11 +707,84 @@ GRK_EXPORT bool grk_set_decode_area(grk_codec *codec, grk_image *image, uint32_t
     return true;
 }
 
+// jp2_decode's last steps (jp2.cpp:1843-1901) on a decoded image: the colour
+// space, each channel's alpha type (jp2_apply_cdef) and the ICC profile -- or
+// the CIELab block, handed over with length 0 as jp2_read_colr builds it
+static void jp2_finish_image(Codec *c, grk_image *image) {
+    const grkgpu_jp2_info &ji = c->jinfo;
+    image->color_space = (GRK_COLOR_SPACE)ji.colour_space;
+    for (uint32_t k = 0; k < image->numcomps && k < ji.numchannels; ++k) image->comps[k].alpha = (uint16_t)ji.chan_alpha[k];
+    const size_t n = ji.cielab_words ? ji.cielab_words * sizeof(uint32_t) : c->icc.size();
+    if (!n) return;
+    free(image->icc_profile_buf);
+    image->icc_profile_buf = (uint8_t *)malloc(n);
+    if (!image->icc_profile_buf) { image->icc_profile_len = 0; return; }
+    memcpy(image->icc_profile_buf, ji.cielab_words ? (const void *)ji.cielab : (const void *)c->icc.data(), n);
+    image->icc_profile_len = ji.cielab_words ? 0 : (uint32_t)n;
+}
+
+// grk_decode of a JP2 file with a palette or a channel swap: the image's
+// components are replaced by the output channels (jp2_apply_pclr: count, prec,
+// sgnd), whose planes the palette store (k_palette_planar<int32_t>) writes
+static bool decode_mapped(Codec *c, grk_image *image, const grkgpu_device_set &ds) {
+    const grkgpu_jp2_info &ji = c->jinfo;
+    const grkgpu_image_desc &d = c->desc;
+    const uint32_t r = c->dparams.cp_reduce;
+    if (r >= c->hinfo.numresolutions) {
+        GRK_ERROR("Error decoding component: the number of resolutions to remove is higher than the number of "
+                  "resolutions of this component");
+        return false;
+    }
+    grk_image_all_components_data_free(image);
+    free(image->comps);
+    image->comps = (grk_image_comp *)calloc(ji.numchannels, sizeof(grk_image_comp));
+    image->numcomps = image->comps ? ji.numchannels : 0;
+    if (!image->comps) return false;
+    grkgpu_out_planes op{};
+    op.sample_fmt = GRKGPU_SAMPLE_I32;
+    op.layout = GRKGPU_LAYOUT_PLANAR;
+    for (uint32_t k = 0; k < ji.numchannels; ++k) {  // (every component at (1,1): grkgpu_jp2_read_info's rule)
+        grk_image_comp &cp = image->comps[k];
+        cp.dx = cp.dy = 1;
+        cp.prec = ji.chan_prec[k];
+        cp.sgnd = (uint32_t)ji.chan_sgnd[k];
+        if (c->window) {
+            comp_geom(cp, c->win[0], c->win[1], c->win[2], c->win[3], r);
+            cp.x0 = c->win[0];
+            cp.y0 = c->win[1];
+        } else {
+            cp.x0 = d.x0;
+            cp.y0 = d.y0;
+            cp.w = cdivpow2(d.x1 - d.x0, r);
+            cp.h = cdivpow2(d.y1 - d.y0, r);
+        }
+        if (!grk_image_single_component_data_alloc(&cp)) return false;
+        op.planes[k] = cp.data;
+    }
+    grkgpu_dparams dp{c->dparams.cp_reduce, c->dparams.cp_layer, 0, 0, 0, 0};
+    if (c->window) { dp.DA_x0 = c->win[0]; dp.DA_y0 = c->win[1]; dp.DA_x1 = c->win[2]; dp.DA_y1 = c->win[3]; }
+    Lease lease(ds.dev[0]);
+    if (!lease.ctx) return false;
+    if (grkgpu_jp2_decompress(lease.ctx, c->file.data(), c->file.size(), &dp, 0, 0xffffffffu, nullptr, &op, nullptr,
+                              nullptr)) {
+        GRK_ERROR("%s", grkgpu_last_error());
+        return false;
+    }
+    for (uint32_t k = 0; k < image->numcomps; ++k)
+        image->comps[k].resno_decoded = c->hinfo.numresolutions - 1 - c->dparams.cp_reduce;
+    c->decoded = true;
+    jp2_finish_image(c, image);
+    return true;
+}
+
 GRK_EXPORT bool grk_decode(grk_codec *codec, grk_plugin_tile *, grk_image *image) {
     Codec *c = (Codec *)codec;
-    if (!c || !c->decompressor || !c->have_header || !image || image->numcomps != c->desc.numcomps) return false;
+    if (!c || !c->decompressor || !c->have_header || !image) return false;
+    const bool mapped = c->jp2 && c->jinfo.mapped;  // palette / channel swap: the image leaves with the channels
+    if (image->numcomps != c->desc.numcomps && !(mapped && image->numcomps == c->jinfo.numchannels)) return false;
     grkgpu_device_set ds;
     if (!device_set(decode_device(), &ds)) return false;
+    if (mapped) return decode_mapped(c, image, ds);
     std::vector<int32_t *> planes(image->numcomps);
     // The planes take the extent the decode writes under the current settings
     // (cp_reduce and the decode area may have changed since grk_read_header /
@@ -742,6 +834,7 @@ GRK_EXPORT bool grk_decode(grk_codec *codec, grk_plugin_tile *, grk_image *image
     for (uint32_t k = 0; k < image->numcomps; ++k)
         image->comps[k].resno_decoded = c->hinfo.numresolutions - 1 - c->dparams.cp_reduce;
     c->decoded = true;
+    if (c->jp2) jp2_finish_image(c, image);
     return true;
 }
 
@@ -962,9 +1055,10 @@ GRK_EXPORT bool grk_decode_tile_data(grk_codec *codec, uint16_t tile_index, uint
 // compression
 // ---------------------------------------------------------------------------
 GRK_EXPORT grk_codec *grk_create_compress(GRK_CODEC_FORMAT format, grk_stream *stream) {
-    if (format != GRK_CODEC_J2K) { GRK_ERROR("only raw J2K codestreams are supported (no JP2)"); return nullptr; }
+    if (format != GRK_CODEC_J2K && format != GRK_CODEC_JP2) { GRK_ERROR("unknown codec format"); return nullptr; }
     if (!stream) return nullptr;
     Codec *c = new Codec();
+    c->jp2 = format == GRK_CODEC_JP2;
     c->stream = (Stream *)stream;
     return (grk_codec *)c;
 }
@@ -1012,6 +1106,17 @@ GRK_EXPORT bool grk_start_compress(grk_codec *codec, grk_image *image) {
     return c->image != nullptr;
 }
 
+static grkgpu_jp2_wparams jp2_wparams(const grk_image *img) {
+    grkgpu_jp2_wparams wp{};
+    wp.colour_space = (uint32_t)img->color_space;
+    if (img->color_space == GRK_CLRSPC_ICC) {
+        wp.icc = img->icc_profile_buf;
+        wp.icc_len = img->icc_profile_len;
+    }
+    for (uint32_t k = 0; k < img->numcomps && k < GRKGPU_MAX_COMPS; ++k) wp.alpha[k] = img->comps[k].alpha;
+    return wp;
+}
+
 GRK_EXPORT bool grk_encode_with_plugin(grk_codec *codec, grk_plugin_tile *tile) {
     Codec *c = (Codec *)codec;
     if (!c || c->decompressor || !c->setup || !c->image) return false;
@@ -1023,6 +1128,22 @@ GRK_EXPORT bool grk_encode_with_plugin(grk_codec *codec, grk_plugin_tile *tile) 
     if (!device_set(c->cparams.deviceId, &ds)) return false;
     std::vector<const int32_t *> planes(d.numcomps);
     for (uint32_t k = 0; k < d.numcomps; ++k) planes[k] = c->image->comps[k].data;
+    if (c->jp2) {  // jp2_setup_encoder's inputs: the image's colour space, ICC profile and alpha types
+        grkgpu_jp2_wparams wp = jp2_wparams(c->image);
+        grkgpu_planes pl{};
+        for (uint32_t k = 0; k < d.numcomps; ++k) pl.planes[k] = planes[k];
+        pl.sample_fmt = GRKGPU_SAMPLE_I32;
+        Lease lease(ds.dev[0]);
+        const uint8_t *out = nullptr;
+        size_t len = 0;
+        if (!lease.ctx) return false;
+        if (grkgpu_jp2_compress(lease.ctx, &d, &p, &wp, &pl, &out, &len)) {
+            GRK_ERROR("%s", grkgpu_last_error());
+            return false;
+        }
+        if (!c->stream->write_all(out, len)) { GRK_ERROR("stream write failed"); return false; }
+        return true;
+    }
     if (ds.n > 1) {  // deviceId -1: the tiles sharded over the device workers
         grkgpu_planes pl{};
         for (uint32_t k = 0; k < d.numcomps; ++k) pl.planes[k] = planes[k];
@@ -1133,7 +1254,19 @@ GRK_EXPORT bool grk_write_tile(grk_codec *codec, uint16_t tile_index, uint8_t *d
     if (!lease.ctx) return false;
     const uint8_t *out = nullptr;
     size_t len = 0;
-    if (ntiles == 1) {
+    if (c->jp2 && ntiles != 1) {  // (the boxes need the codestream's length: a seek back, which streaming has not)
+        GRK_ERROR("grk_write_tile of a JP2 file with several tiles is not supported");
+        return false;
+    }
+    if (c->jp2) {  // the one tile is the image
+        pl.row0 = pl.nrows = pl.col0 = pl.ncols = 0;
+        grkgpu_jp2_wparams wp = jp2_wparams(img);
+        if (grkgpu_jp2_compress(lease.ctx, &d, &p, &wp, &pl, &out, &len)) {
+            GRK_ERROR("%s", grkgpu_last_error());
+            return false;
+        }
+        c->header_written = c->eoc_written = true;
+    } else if (ntiles == 1) {
         if (grkgpu_compress_ex(lease.ctx, &d, &p, &pl, 0, 1, GRKGPU_PART_ALL, &out, &len)) {
             GRK_ERROR("%s", grkgpu_last_error());
             return false;

@@ -669,6 +669,215 @@ __global__ void __launch_bounds__(256) k_mct_inv_custom_pixels(PlanePtrs src, ui
 }
 
 // ---------------------------------------------------------------------------
+// The JP2 palette and channel order in the last store: jp2_apply_pclr
+// (jp2.cpp:1301-1407) and the channel swaps of jp2_apply_cdef (:1564-1623),
+// which the reference runs as CPU passes over the decoded int32 planes, applied
+// to the run values k_mct_inv_dcshift_planar / _pixels hold.  A component is
+// finished by the existing statements (inverse MCT, DC shift, clamp); then
+// output channel c, fed by component map.comp[c], receives
+//     map.pcol[c] < 0:  the component's sample                    (direct use)
+//     otherwise:        table[clamp(sample, 0, ne - 1) * npc + map.pcol[c]]
+// The cdef swaps are already folded into map on the host.  Channels and
+// components differ in number (1 -> 3, 2 -> 4, ...): a lane reads a
+// component's run once and stores every channel it feeds.
+//
+// The table (ne x npc entries of 16 bits, at most 1024 x 16 = 32 KB) lives in
+// LDS: each workgroup copies it from the device table before its first run
+// and keeps it for PAL_ROWS rows, so a full-size table costs 4 B of LDS fill
+// per 1 B of 8-bit index at worst and a 256 x 3 one 0.05 B.  map.zero: the
+// components are not read and count as finished zero samples (the fill of a
+// tile the stream never reached: entry 0, as the reference's pass over its
+// zero planes gives).  Run ownership, stores and the precision ops are the
+// existing kernels'.
+// ---------------------------------------------------------------------------
+constexpr int PAL_ROWS = 8;
+
+__device__ __forceinline__ void palette_load(uint16_t *lut, const uint16_t *table, uint32_t n) {
+    if (!((uintptr_t)table & 3)) {
+        for (uint32_t i = threadIdx.x; i < n / 2; i += blockDim.x) ((uint32_t *)lut)[i] = ((const uint32_t *)table)[i];
+        if ((n & 1) && threadIdx.x == 0) lut[n - 1] = table[n - 1];
+    } else {
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) lut[i] = table[i];
+    }
+    __syncthreads();
+}
+
+// the table rows a finished run indexes: clamp(sample, 0, ne - 1) * npc, made
+// once per sample for every channel the component feeds
+template <int N>
+__device__ __forceinline__ void palette_rows(const int32_t (&a)[N], const PalMap &map, uint32_t (&row)[N]) {
+    const int32_t top = (int32_t)map.ne - 1;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int32_t k = a[i] < 0 ? 0 : (a[i] > top ? top : a[i]);
+        row[i] = map.ne ? (uint32_t)k * map.npc : 0u;
+    }
+}
+
+// one channel's values from its component's finished run and rows
+template <int N>
+__device__ __forceinline__ void palette_run(const int32_t (&a)[N], const uint32_t (&row)[N], int32_t pcol,
+                                            const uint16_t *lut, int32_t (&o)[N]) {
+    if (pcol < 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) o[i] = a[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) o[i] = lut[row[i] + (uint32_t)pcol];
+    }
+}
+
+// load_run, also for the one-sample "run" of the thread-per-pixel path (whose
+// wide branch would load nothing)
+template <int N>
+__device__ __forceinline__ void pal_load(const int32_t *p, int n, int32_t (&v)[N]) {
+    if constexpr (N >= 4) {
+        load_run<N>(p, n, v);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = i < n ? p[i] : 0;
+    }
+}
+
+// The finished runs of the components that feed a channel, one after the
+// other, each handed to emit(component, run): the MCT triple first
+template <int N, typename F>
+__device__ __forceinline__ void palette_components(const PlanePtrs &src, size_t si, int n, uint32_t ncomp,
+                                                   const ShiftArr &shift, const ShiftArr &minv, const ShiftArr &maxv,
+                                                   int32_t mct, int32_t irrev, const PalMap &map, F emit) {
+    uint32_t k = 0;
+    if (mct && ncomp >= 3) {
+        int32_t a[N], b[N], c[N];
+        if (!map.zero) {
+            pal_load<N>(src.p[0] + si, n, a);
+            pal_load<N>(src.p[1] + si, n, b);
+            pal_load<N>(src.p[2] + si, n, c);
+            inv_mct_run<N>(a, b, c, irrev, shift, minv, maxv);
+        } else {
+#pragma unroll
+            for (int i = 0; i < N; ++i) a[i] = b[i] = c[i] = 0;
+        }
+        uint32_t row[N];
+        palette_rows<N>(a, map, row);
+        emit(0u, a, row);
+        palette_rows<N>(b, map, row);
+        emit(1u, b, row);
+        palette_rows<N>(c, map, row);
+        emit(2u, c, row);
+        k = 3;
+    }
+    for (; k < ncomp; ++k) {
+        if (!((map.used >> k) & 1)) continue;  // feeds no channel
+        int32_t a[N];
+        if (!map.zero) {
+            pal_load<N>(src.p[k] + si, n, a);
+            inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < N; ++i) a[i] = 0;
+        }
+        uint32_t row[N];
+        palette_rows<N>(a, map, row);
+        emit(k, a, row);
+    }
+}
+
+// planar: dst.p[c] = plane of channel c
+template <typename T, int OP = 0, typename... O>
+__global__ void __launch_bounds__(256) k_palette_planar(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th,
+                                                        DstPlanes dst, uint32_t dstride, uint32_t ncomp,
+                                                        ShiftArr shift, ShiftArr minv, ShiftArr maxv, int32_t mct,
+                                                        int32_t irrev, PalMap map, const uint16_t *table, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    static_assert(OP == 0 || OP == OP_PREC, "no colour conversion behind a palette");
+    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
+    extern __shared__ uint16_t pal_lut[];
+    palette_load(pal_lut, table, map.ne * map.npc);
+    constexpr int N = NarrowRun<T>::N;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t yb = blockIdx.y * PAL_ROWS, ye = yb + PAL_ROWS < th ? yb + PAL_ROWS : th;
+    for (uint32_t y = yb; y < ye; ++y) {
+        const size_t drow = (size_t)y * dstride;
+        uint32_t x0;
+        const int n = run_of<N>((uintptr_t)((T *)dst.p[0] + drow), sizeof(T), t, tw, x0);
+        if (n <= 0) continue;
+        const size_t si = (size_t)y * sstride + x0, di = drow + x0;
+        palette_components<N>(src, si, n, ncomp, shift, minv, maxv, mct, irrev, map,
+                              [&](uint32_t k, const int32_t (&a)[N], const uint32_t (&row)[N]) {
+                                  for (uint32_t c = 0; c < map.nch; ++c) {
+                                      if (map.comp[c] != k) continue;
+                                      int32_t v[N];
+                                      palette_run<N>(a, row, map.pcol[c], pal_lut, v);
+                                      if constexpr (OP != 0) prec_run<N>(v, ops->pc[c]);
+                                      store_samples<T, N>((T *)dst.p[c] + di, v, n);
+                                  }
+                              });
+    }
+}
+
+// interleaved: channel c of pixel (y, x) at dst.p[0][y * dstride + x * nch + c].
+// NCH = 3 / 4: that many channels, runs on the destination's 16-byte grid;
+// NCH = 0: map.nch of them, one thread per pixel, one store per sample
+template <typename T, int NCH, int OP = 0, typename... O>
+__global__ void __launch_bounds__(256) k_palette_pixels(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th,
+                                                        DstPlanes dst, uint32_t dstride, uint32_t ncomp,
+                                                        ShiftArr shift, ShiftArr minv, ShiftArr maxv, int32_t mct,
+                                                        int32_t irrev, PalMap map, const uint16_t *table, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    static_assert(OP == 0 || OP == OP_PREC, "no colour conversion behind a palette");
+    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
+    extern __shared__ uint16_t pal_lut[];
+    palette_load(pal_lut, table, map.ne * map.npc);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t yb = blockIdx.y * PAL_ROWS, ye = yb + PAL_ROWS < th ? yb + PAL_ROWS : th;
+    for (uint32_t y = yb; y < ye; ++y) {
+        T *const drow = (T *)dst.p[0] + (size_t)y * dstride;
+        if constexpr (NCH != 0) {
+            constexpr int N = NarrowRun<T>::N;
+            uint32_t x0;
+            const int n = run_of<N>((uintptr_t)drow, NCH * sizeof(T), t, tw, x0);
+            if (n <= 0) continue;
+            const size_t si = (size_t)y * sstride + x0;
+            int32_t v[NCH][N];
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int i = 0; i < N; ++i) v[c][i] = 0;
+            palette_components<N>(src, si, n, ncomp, shift, minv, maxv, mct, irrev, map,
+                                  [&](uint32_t k, const int32_t (&a)[N], const uint32_t (&row)[N]) {
+#pragma unroll
+                                      for (int c = 0; c < NCH; ++c)
+                                          if (map.comp[c] == k) palette_run<N>(a, row, map.pcol[c], pal_lut, v[c]);
+                                  });
+            if constexpr (OP != 0) {
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) prec_run<N>(v[c], ops->pc[c]);
+            }
+            int32_t px[N * NCH];
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) px[i * NCH + c] = v[c][i];
+            store_samples<T, N * NCH>(drow + (size_t)x0 * NCH, px, n * NCH);
+        } else {
+            if (t >= tw) continue;
+            const size_t si = (size_t)y * sstride + t;
+            T *const d = drow + (size_t)t * map.nch;
+            palette_components<1>(src, si, 1, ncomp, shift, minv, maxv, mct, irrev, map,
+                                  [&](uint32_t k, const int32_t (&a)[1], const uint32_t (&row)[1]) {
+                                      for (uint32_t c = 0; c < map.nch; ++c) {
+                                          if (map.comp[c] != k) continue;
+                                          int32_t v[1];
+                                          palette_run<1>(a, row, map.pcol[c], pal_lut, v);
+                                          if constexpr (OP != 0) prec_run<1>(v, ops->pc[c]);
+                                          __builtin_nontemporal_store((T)v[0], d + c);
+                                      }
+                                  });
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // The decoded image with its subsampled components replicated to the image
 // grid (GRKGPU_LAYOUT_UPSAMPLE; grk_decompress -u, upsample_image_components,
 // grk_decompress.cpp:891-1040): output pixel (X, Y) of the reference grid
@@ -2038,6 +2247,58 @@ hipError_t launch_mct_inv_custom(const PlanePtrs &src, uint32_t sstride, uint32_
         default: return hipErrorInvalidValue;
     }
 #undef GRK_INV
+    return hipGetLastError();
+}
+
+// the palette stores: launch_inv_to's run grid over PAL_ROWS rows per
+// workgroup, the table's bytes as dynamic LDS
+template <typename T, int OP, typename... O>
+static void launch_pal(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
+                       bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn,
+                       const ShiftArr &mx, int32_t mct, int32_t irrev, const PalMap &map, const uint16_t *table,
+                       hipStream_t s, const O &...ops) {
+    const uint32_t runs = (uint32_t)(((uint64_t)tw + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
+    const uint32_t rows = (th + PAL_ROWS - 1) / PAL_ROWS;
+    const dim3 grid((runs + 255) / 256, rows);
+    const size_t lds = ((size_t)map.ne * map.npc * 2 + 3) & ~(size_t)3;
+#define GRK_PAL(KERNEL, GRID) \
+    hipLaunchKernelGGL(KERNEL, GRID, dim3(256), lds, s, src, sstride, tw, th, dst, dstride, ncomp, shift, mn, mx, mct, \
+                       irrev, map, table, ops...)
+    if (!interleaved || map.nch == 1) GRK_PAL((k_palette_planar<T, OP>), grid);
+    else if (map.nch == 3) GRK_PAL((k_palette_pixels<T, 3, OP>), grid);
+    else if (map.nch == 4) GRK_PAL((k_palette_pixels<T, 4, OP>), grid);
+    else GRK_PAL((k_palette_pixels<T, 0, OP>), dim3((tw + 255) / 256, rows));
+#undef GRK_PAL
+}
+
+hipError_t launch_palette(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
+                          int32_t fmt, bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift,
+                          const ShiftArr &mn, const ShiftArr &mx, int32_t mct, int32_t irrev, const PalMap &map,
+                          const uint16_t *table, const OutOps *ops, hipStream_t s) {
+    if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS || map.nch < 1 || map.nch > (uint32_t)GRK_MAX_COMPS ||
+        map.ne > 1024 || map.npc > (uint32_t)GRK_MAX_COMPS || (ops && ops->sycc))
+        return hipErrorInvalidValue;
+    for (uint32_t c = 0; c < map.nch; ++c) {  // every index the kernel forms stays inside the table and the planes
+        if (map.comp[c] >= ncomp || !((map.used >> map.comp[c]) & 1)) return hipErrorInvalidValue;
+        if (map.pcol[c] >= 0 && (!table || !map.ne || (uint32_t)map.pcol[c] >= map.npc)) return hipErrorInvalidValue;
+    }
+    if (!tw || !th) return hipSuccess;
+#define GRK_PALF(T) \
+    do { \
+        if (!ops) launch_pal<T, 0>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev, \
+                                   map, table, s); \
+        else launch_pal<T, OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev, \
+                                    map, table, s, *ops); \
+    } while (0)
+    switch (fmt) {
+        case SMP_I32: GRK_PALF(int32_t); break;
+        case SMP_U8: GRK_PALF(uint8_t); break;
+        case SMP_I8: GRK_PALF(int8_t); break;
+        case SMP_U16: GRK_PALF(uint16_t); break;
+        case SMP_I16: GRK_PALF(int16_t); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_PALF
     return hipGetLastError();
 }
 

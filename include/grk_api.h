@@ -13,7 +13,11 @@
  *
  * Scope (what a call outside it does: returns false / nullptr after an error
  * message through the grk_set_error_handler callback):
- *   - raw J2K codestreams (GRK_CODEC_J2K); JP2 boxes are not written / read;
+ *   - raw J2K codestreams (GRK_CODEC_J2K) and JP2 files (GRK_CODEC_JP2): the
+ *     boxes of jp2.cpp read and written (grkgpu_jp2_*, grk_mi355x.h), a palette
+ *     and the channel definitions applied by grk_decode, header_info->enumcs
+ *     set (its xml, resolution and color fields stay zero); a multi-tile JP2
+ *     is not written tile by tile (grk_write_tile);
  *   - components with dx = dy = 1, up to 16 bits, at most 16 components;
  *   - coding options of grk_mi355x.h: any tiling, 5/3 or 9/7, RCT / ICT,
  *     code-block sizes, precincts, the five progressions, POC, SOP / EPH,

@@ -683,6 +683,128 @@ int grkgpu_decompress_mct(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, const 
  * grkgpu_decompress_mct applies them.  *n = 0: no custom MCT. */
 int grkgpu_read_mct(const uint8_t *cs, size_t len, grkgpu_image_desc *img, float *matrix, int32_t *offsets,
                     uint32_t *n);
+/* ---------------------------------------------------------------------------
+ * JP2 files (ISO/IEC 15444-1 Annex I): the box layer of Grok's
+ * codestream/jp2.cpp on the host, its palette and channel order in the store
+ * of the last decode kernel.
+ *
+ * Reader: jp2_read_header_procedure and its box handlers restated check for
+ * check, so a file is refused (GRKGPU_ECORRUPT) where the reference refuses
+ * it: signature box first, ftyp second, jp2h before jp2c, ihdr required and 14
+ * bytes, XL lengths, LBox 0 = to the end of the file, unknown boxes skipped,
+ * ihdr-family boxes outside jp2h read only after jp2h, a second ihdr / colr
+ * ignored, METH > 2 ignored, METH 2 without profile bytes refused, cmap only
+ * after pclr and only once, NE 1 .. 1024, NPC >= 1, every rule of
+ * jp2_check_color including its single-component cmap repair, a pclr without
+ * cmap dropped.  The codestream is the jp2c payload; the geometry is SIZ's and
+ * is not compared with ihdr, as in the reference.  res / xml / uuid boxes are
+ * checked for the sizes the reference insists on and their contents dropped.
+ * The jp2c LBox is trusted (the reference reads on to EOC whatever it says).
+ *
+ * Decoded by the reference, GRKGPU_EUNSUPPORTED here: a palette of more than
+ * GRKGPU_MAX_COMPS columns; a palette column wider than 16 bits or with the
+ * sign bit set (the reference stores the raw unsigned entry in a component it
+ * then marks signed); a cmap entry of MTYP 1 whose PCOL is not its own index
+ * (the reference asserts, and in a release build writes another channel's
+ * plane); a cmap over a subsampled component, or a cdef swap on a subsampled
+ * image; a jp2c payload of 4 GiB or more; more than GRKGPU_JP2_MAX_CDEF
+ * channel definitions.
+ * ------------------------------------------------------------------------- */
+#define GRKGPU_JP2_MAX_CDEF 64
+/* GRK_CLRSPC_* (grok.h), as jp2_decode maps METH / EnumCS: 12 CMYK, 14 CIE
+ * (default or custom), 16 sRGB, 17 gray, 18 sYCC, 24 eYCC, METH 2 ICC,
+ * anything else unknown */
+enum {
+    GRKGPU_CS_UNKNOWN = 0, GRKGPU_CS_UNSPECIFIED = 1, GRKGPU_CS_SRGB = 2, GRKGPU_CS_GRAY = 3, GRKGPU_CS_SYCC = 4,
+    GRKGPU_CS_EYCC = 5, GRKGPU_CS_CMYK = 6, GRKGPU_CS_DEFAULT_CIE = 7, GRKGPU_CS_CUSTOM_CIE = 8, GRKGPU_CS_ICC = 9
+};
+typedef struct {
+    uint64_t cs_offset, cs_length;   /* the codestream: the jp2c payload inside the file */
+    uint32_t ihdr_w, ihdr_h, ihdr_nc, ihdr_bpc; /* as read; informational */
+    uint32_t meth, enumcs;           /* of the first colr box with METH 1 or 2 (0, 0: none) */
+    uint32_t colour_space;           /* GRKGPU_CS_* */
+    uint32_t icc_length;             /* METH 2: the ICC profile, file[icc_offset .. + icc_length) */
+    uint64_t icc_offset;
+    uint32_t cielab_words;           /* EnumCS 14: 2 or 9 words of cielab[] as jp2_read_colr builds them */
+    uint32_t cielab[9];              /* 14, 'DEF\0' or 0 (custom), then rl, ol, ra, oa, rb, ob, il */
+    /* palette: present only when it is applied (pclr AND cmap) */
+    uint32_t pal_entries, pal_columns;         /* NE, NPC; 0, 0: no palette */
+    uint32_t pal_prec[GRKGPU_MAX_COMPS];       /* per column */
+    int32_t pal_sgnd[GRKGPU_MAX_COMPS];
+    uint32_t cmap_cmp[GRKGPU_MAX_COMPS], cmap_mtyp[GRKGPU_MAX_COMPS], cmap_pcol[GRKGPU_MAX_COMPS]; /* after the repair */
+    /* channel definitions as the file gives them */
+    uint32_t cdef_n;
+    uint16_t cdef_cn[GRKGPU_JP2_MAX_CDEF], cdef_typ[GRKGPU_JP2_MAX_CDEF], cdef_asoc[GRKGPU_JP2_MAX_CDEF];
+    /* the output channels after jp2_apply_pclr and jp2_apply_cdef (its swaps,
+     * and its rewrite of later cn entries): channel c leaves with chan_prec /
+     * chan_sgnd, carries alpha type chan_alpha (the cdef Typ: 0 colour, 1
+     * opacity, 2 premultiplied opacity, 65535 unspecified) and takes codestream
+     * component chan_comp's sample -- directly (chan_pcol < 0) or as the index
+     * into palette column chan_pcol */
+    uint32_t numchannels;
+    uint32_t chan_prec[GRKGPU_MAX_COMPS];
+    int32_t chan_sgnd[GRKGPU_MAX_COMPS];
+    uint32_t chan_alpha[GRKGPU_MAX_COMPS];
+    uint32_t chan_comp[GRKGPU_MAX_COMPS];
+    int32_t chan_pcol[GRKGPU_MAX_COMPS];
+    uint32_t mapped;                 /* 1: the channels are not the components in order (the palette store runs) */
+    uint32_t reserved;
+} grkgpu_jp2_info;
+/* Host only (no device needed): info = the fields above, img (may be NULL) =
+ * the OUTPUT channels on the image's grid (numcomps = numchannels, their
+ * precisions and signs, SIZ's rectangle and subsampling).  A raw codestream is
+ * GRKGPU_ECORRUPT (no signature box); a codestream header this decoder does
+ * not take keeps grkgpu_read_header's code. */
+int grkgpu_jp2_read_info(const uint8_t *file, size_t len, grkgpu_jp2_info *info, grkgpu_image_desc *img);
+/* The applied palette's table: pal_entries x pal_columns values, row-major, into
+ * entries[cap] (cap >= that product, else GRKGPU_EINVAL); *n = the product, 0
+ * for a file without an applied palette.  Host only. */
+int grkgpu_jp2_read_palette(const uint8_t *file, size_t len, uint16_t *entries, uint32_t cap, uint32_t *n);
+/* grkgpu_decompress_convert on the jp2c payload with the palette and the
+ * channel order applied by the store of the last decode kernel
+ * (k_palette_planar / k_palette_pixels): an index component is finished as
+ * ever (inverse MCT, DC shift, clamp to its range), then k = clamp(v, 0, NE - 1)
+ * and channel c receives entries[k * NPC + pcol_c]; a directly used channel
+ * receives its component's sample.  out, its sample format (which must hold
+ * each OUTPUT channel's precision: the palette sizes, or ops->prec) and ops
+ * describe channels; img receives them.  Window, cp_reduce, cp_layer, tile
+ * ranges, cut streams, host or device planes, the five formats and both
+ * layouts keep grkgpu_decompress_to's rules; samples nothing decoded are
+ * mapped like any other (entry 0), as the reference's pass does.
+ * ops->colour = GRKGPU_COLOUR_AUTO (valid only here): SYCC when EnumCS is 18
+ * (then SYCC's shape rules hold: GRKGPU_EINVAL otherwise), NONE for every other
+ * space -- CMYK, eYCC, CIELab and ICC are reported in info and not converted.
+ * SYCC together with a palette or a channel swap is GRKGPU_EUNSUPPORTED.  A
+ * file without palette or swap takes grkgpu_decompress_convert's launches,
+ * launch for launch.  info (may be NULL) as grkgpu_jp2_read_info. */
+#define GRKGPU_COLOUR_AUTO 2u
+int grkgpu_jp2_decompress(grkgpu_ctx *ctx, const uint8_t *file, size_t len, const grkgpu_dparams *p,
+                          uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                          const grkgpu_out_planes *out, const grkgpu_out_ops *ops, grkgpu_jp2_info *info);
+/* Writer: jp, ftyp (brand 'jp2 ', MinV 0, CL 'jp2 '), jp2h { ihdr, bpcc only
+ * when the depths differ (BPC 255), colr, cdef only for exactly one alpha
+ * channel behind the colour channels (jp2_setup_encoder, jp2.cpp:2264-2343) },
+ * jp2c -- byte for byte what the reference's encoder writes around the same
+ * codestream.  res / xml / uuid boxes and an XL jp2c (images above 2^30 sample
+ * bytes, where the reference writes one) are not written: GRKGPU_EUNSUPPORTED. */
+typedef struct {
+    uint32_t colour_space;            /* GRKGPU_CS_*: sRGB 16, gray 17, sYCC 18, CMYK 12, default CIE 14, ICC -> METH 2, else EnumCS 0 */
+    uint32_t icc_len;                 /* GRKGPU_CS_ICC: the profile */
+    const uint8_t *icc;
+    uint32_t alpha[GRKGPU_MAX_COMPS]; /* grk_image_comp::alpha of each component (0: colour) */
+} grkgpu_jp2_wparams;
+/* grkgpu_compress_ex of the whole image with those boxes ahead of the
+ * codestream: they travel in the header blob the gather kernel places ahead
+ * of the packets, jp2c's LBox set from the gather plan's total before the
+ * launch, so the file is assembled in device memory and leaves in the one
+ * D2H copy (*out: the context's buffer, as grkgpu_compress_ex). */
+int grkgpu_jp2_compress(grkgpu_ctx *ctx, const grkgpu_image_desc *img, const grkgpu_cparams *p,
+                        const grkgpu_jp2_wparams *wp, const grkgpu_planes *in, const uint8_t **out, size_t *out_len);
+/* The boxes alone, up to and including jp2c's 8-byte header with LBox = 8 +
+ * cs_len: what grkgpu_jp2_compress puts ahead of a codestream of cs_len bytes.
+ * Host only.  buf[cap] receives *n bytes (cap too small: GRKGPU_EINVAL, *n set). */
+int grkgpu_jp2_write_boxes(const grkgpu_image_desc *img, const grkgpu_jp2_wparams *wp, uint64_t cs_len, uint8_t *buf,
+                           size_t cap, size_t *n);
 /* (multi-device decode into host planes: see grkgpu_device_set above) */
 int grkgpu_decompress_multi(const grkgpu_device_set *devs, const uint8_t *cs, size_t len, grkgpu_image_desc *img,
                             int32_t *const *planes);
@@ -723,6 +845,19 @@ int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t numcomps, uint
 int grkgpu_mct_inv_custom_to(const float *const *src, uint32_t numcomps, uint32_t w, uint32_t h,
                              uint32_t src_stride, const float *matrix, const int32_t *offsets, const uint32_t *prec,
                              const int32_t *sgnd, const grkgpu_out_planes *dst, uint32_t dst_stride, void *stream);
+/* The palette store of grkgpu_jp2_decompress on its own: src[k] = device plane
+ * of component k's int32 samples after the inverse wavelet (5/3; no MCT), rows
+ * src_stride apart, finished as grkgpu_mct_inv_dcshift_to does (DC shift of an
+ * unsigned component, clamp to prec / sgnd); output channel c < numchannels
+ * takes component chan_comp[c]'s sample (chan_pcol[c] < 0) or
+ * table[clamp(sample, 0, ne - 1) * npc + chan_pcol[c]].  table: ne x npc uint16
+ * in DEVICE memory (may be NULL when no channel looks up); dst as
+ * grkgpu_mct_inv_dcshift_to, describing channels -- a narrow sample format has
+ * to hold chan_prec[c] bits, unsigned for a looked-up channel. */
+int grkgpu_palette_to(const int32_t *const *src, uint32_t numcomps, uint32_t w, uint32_t h, uint32_t src_stride,
+                      const uint32_t *prec, const int32_t *sgnd, uint32_t numchannels, const uint32_t *chan_comp,
+                      const int32_t *chan_pcol, const uint32_t *chan_prec, const uint16_t *table, uint32_t ne,
+                      uint32_t npc, const grkgpu_out_planes *dst, uint32_t dst_stride, void *stream);
 /* The upsampling store of grkgpu_decompress_to (GRKGPU_LAYOUT_UPSAMPLE) on its
  * own -- the kernels the decode runs, fed finished samples: src[k] = device
  * plane of component k on its own grid, [ceil(x0 / dx[k]), ceil(x1 / dx[k])) x
