@@ -2,7 +2,9 @@
 (oracle/_ref/ref_driver index: grk_get_cstr_index after grk_read_header and
 after a full grk_decode, every field printed) for every golden codestream
 but the p_* family (oracle/make_golden_prec.py: 150 small streams that differ
-in sample precision and sign, which no index field depends on), into
+in sample precision and sign, which no index field depends on) and the fg_*
+bases (oracle/make_golden_foreign.py: SOP / EPH streams with mode switches, as
+g8_sop_eph and the -M goldens here, kept for their packet bodies), into
 tests/golden/cstr_index.json.  The GPU test runs the same driver relinked
 against our libgrok.so (ref_driver_mi355x) and compares the text.
   python oracle/make_golden_index.py [--check]"""
@@ -23,7 +25,7 @@ def main():
     mg.build_ref()
     out = {}
     for f in sorted(glob.glob(os.path.join(mg.GOLD, "*.j2k"))):
-        if os.path.basename(f).startswith("p_"):
+        if os.path.basename(f).startswith(("p_", "fg_")):
             continue
         r = subprocess.run([mg.DRIVER, "index", f], capture_output=True, text=True, timeout=120)
         out[os.path.basename(f)] = r.stdout if r.returncode == 0 else "error"

@@ -87,6 +87,45 @@ def test_t1_mode_switches_host_sanitized(oracle, tmp_path):
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
 
 
+def _run_t1_foreign(oracle, tmp_path, flags, n):
+    import foreign_bytes as fb
+    exe, fin = tmp_path / "test_t1_foreign", tmp_path / "cases.bin"
+    ob = os.path.join(ROOT, "oracle", "build")
+    subprocess.run(["g++", *flags, "-std=c++17", "-Wno-unknown-pragmas", "-o", str(exe),
+                    os.path.join(ROOT, "tests/cpp/test_t1_foreign.cpp"), "-L" + ob, "-lgrk_oracle", "-Wl,-rpath," + ob],
+                   check=True)
+    cases = fb.host_cases(oracle, n)
+    # every value the case list is meant to hold
+    assert {c[0] for c in cases} == set(fb.KINDS)
+    fam = [c for c in cases if c[0] in fb.FAMILIES]
+    assert {len(c[4]) for c in fam} == set(fb.LENGTHS) and {c[10] for c in cases} == set(range(16))
+    assert {c[5] for c in fam} == set(fb.NUMBPS) and {(c[8], c[7]) for c in fam} == set(fb.SHAPES)
+    for nb in fb.NUMBPS:
+        assert {c[6] for c in fam if c[5] == nb} == {fb.passes_of(nb, k) for k in range(3)}
+    fb.write_host_cases(str(fin), cases)
+    r = subprocess.run([str(exe), str(fin)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "OK: 0 failures / %d cases" % n in r.stdout
+    return r
+
+
+def test_t1_foreign_bytes_host_match_oracle(oracle, tmp_path):
+    """tests/cpp/test_t1_foreign.cpp: code-block bytes no Grok encoder writes
+    (tests/foreign_bytes.py: the four byte families, trimmed segments, a
+    marker inside a segment, a segment ending in FF) through the host build
+    of unstuff + t1_decode_v5 + rebuild against the oracle's t1_decode_cblk,
+    with the unstuffed stream inside unstuff_word_cap / unstuff_carry_cap."""
+    _run_t1_foreign(oracle, tmp_path, ["-O2"], 2002)
+
+
+def test_t1_foreign_bytes_host_sanitized(oracle, tmp_path):
+    """The same stand-alone program under AddressSanitizer and UBSan, every
+    buffer sized exactly to its cap: no report, exit status 0."""
+    r = _run_t1_foreign(oracle, tmp_path, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                                           "-static-libasan", "-static-libubsan"], 301)
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
 def test_ict_term_identity():
     """grk_device.h ict_term: the forward ICT's int_fix_mul(r << 11, c)
     (mct.cpp:195-350, 64-bit product) equals floor((r c + 2) / 4) in 32-bit

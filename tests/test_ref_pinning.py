@@ -95,6 +95,16 @@ def test_mct_fixtures_regenerate():
     assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
 
 
+def test_foreign_fixtures_regenerate():
+    """tests/golden/fg_* and manifest_foreign.json: reference-encoded streams
+    whose packet bodies are overwritten in place, decoded by the reference
+    (oracle/make_golden_foreign.py) -- it decodes every one, differently from
+    the clean base and not to zero."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "make_golden_foreign.py"), "--check"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
+
+
 def test_cstr_info_matches_reference():
     """grk_get_cstr_info of our libgrok.so (ref_driver_mi355x: the same driver
     relinked against it; header parsing needs no GPU) prints exactly what the
