@@ -414,6 +414,8 @@ def lib():
         L.grkgpu_t1_scratch_bytes.restype = ctypes.c_size_t
         L.grkgpu_t1_scratch_bytes_n.restype = ctypes.c_size_t
         L.grkgpu_t1_scratch_bytes_n.argtypes = [U32]
+        L.grkgpu_t1_enc_out_bytes.restype = ctypes.c_size_t
+        L.grkgpu_t1_enc_out_bytes.argtypes = [U32, U32, U32]
         L.grkgpu_t1_encode_blocks.argtypes = [VP, U32, VP, VP, VP, VP, ctypes.c_int, VP]
         if hasattr(L, "grkgpu_t1_encode_blocks_sty"):  # not in an older library given by GRKGPU_LIB (A/B runs)
             L.grkgpu_t1_encode_blocks_sty.argtypes = [VP, U32, VP, VP, VP, VP, ctypes.c_int, U32, VP]

@@ -452,6 +452,10 @@ size_t grkgpu_t1_scratch_bytes(void) {
     return std::max<size_t>(t1e_scratch_bytes(64, 32) / 64 + 32 * (size_t)sym_slot_bytes(64, 64),
                             sizeof(T1Scratch) + (size_t)t1_stage_dec_words() * 4);
 }
+size_t grkgpu_t1_enc_out_bytes(uint32_t w, uint32_t h, uint32_t cblk_sty) {
+    if (w > 64 || h > 64) return 0;
+    return t1_enc_slab_bytes(w, h, cblk_sty & 0x3Fu, T1_MAX_ENC_BPS);
+}
 size_t grkgpu_t1_scratch_bytes_n(uint32_t nblocks) {
     return (((size_t)nblocks + 63) & ~(size_t)63) * grkgpu_t1_scratch_bytes();
 }
@@ -1354,10 +1358,11 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
     }
     const uint32_t nblk = (uint32_t)eb.size();
     uint64_t out_total = 0;
-    for (auto &b : eb) {  // MQ output slab: w*h*4 bytes (+ the zero pad byte before)
+    for (uint32_t i = 0; i < nblk; ++i) {  // MQ output slab: t1_enc_slab_bytes at the band's bound (+ the zero pad byte before)
+        EncBlock &b = eb[i];
         out_total += 16;
         b.out_off = out_total;
-        out_total += ((uint64_t)b.w * b.h * 4 + 64 + 15) & ~15ull;
+        out_total += ((uint64_t)t1_enc_slab_bytes(b.w, b.h, cp.cblksty, (pcap[i] + 2) / 3) + 15) & ~15ull;
     }
     HIPCHK(c->work.ensure(arena * 4 + 256));
     HIPCHK(c->coef.ensure(arena * 4 + 256));
@@ -1609,7 +1614,7 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
                 if (r.pad) return set_err(GRKGPU_EUNSUPPORTED, "code-block numbps exceeds its band's bound");
                 if (r.numpasses > GRK_MAX_PASSES) return set_err(GRKGPU_EUNSUPPORTED, "too many coding passes");
                 const uint32_t np = r.numpasses;
-                if (np && r.rate[np - 1] > eb[i].w * eb[i].h * 4 + 64) return set_err(GRKGPU_EUNSUPPORTED, "MQ slab overflow");
+                if (np && r.rate[np - 1] > t1_enc_slab_bytes(eb[i].w, eb[i].h, cp.cblksty, r.numbps)) return set_err(GRKGPU_EUNSUPPORTED, "MQ slab overflow");
                 nsym += r.nsym;
                 EncCblkState &st = cst[i];
                 st.numbps = r.numbps;

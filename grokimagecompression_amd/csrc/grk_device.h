@@ -30,7 +30,8 @@ struct ShiftArr { int32_t v[GRK_MAX_COMPS]; };
 // t1/Tier1.cpp:24-96 encodeBlockInfo).
 struct EncBlock {
     uint64_t coef_off;  // element offset of the block's top-left in the coefficient arena
-    uint64_t out_off;   // byte offset of the block's output in the MQ slab (out[-1] == 0)
+    uint64_t out_off;   // byte offset of the block's output in the MQ slab (out[-1] == 0); the block may write
+                        // t1_enc_slab_bytes(w, h, sty, numbps) bytes, rounded up to 4, from there on
     uint32_t stride, w, h, orient;
     int32_t qmfbid, inv_step;
 };

@@ -2481,7 +2481,7 @@ __global__ __launch_bounds__(256) void k_pass_records(const EncBlock *__restrict
     uint32_t np = r.numpasses;
     if (r.pad) ps.bad |= 1u;
     if (np > cap || np > GRK_MAX_PASSES) { ps.bad |= 2u; np = 0; }
-    if (np && r.rate[np - 1] > b.w * b.h * 4 + 64) ps.bad |= 4u;
+    if (np && r.rate[np - 1] > t1_enc_slab_bytes(b.w, b.h, sty, r.numbps)) ps.bad |= 4u;
     if (ps.bad) np = 0;
     const double f = wfac[i];
     double cum = 0.0, mn = DBL_MAX, mx = -1, m0 = -HUGE_VAL;

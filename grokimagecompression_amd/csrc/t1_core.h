@@ -91,7 +91,7 @@ GRK_HD int32_t fix_mul_t1(int32_t a, int32_t b) {
 GRK_HD uint32_t quant_mag(int32_t v, int32_t qmfbid, int32_t inv_step, uint32_t *neg) {
     int32_t q = (qmfbid == 1) ? (int32_t)((uint32_t)v << 6) : fix_mul_t1(v, inv_step);
     *neg = q < 0 ? 1u : 0u;
-    return (uint32_t)(q < 0 ? -q : q);
+    return q < 0 ? 0u - (uint32_t)q : (uint32_t)q;  // in unsigned: q = INT32_MIN (5/3, |v| = 2^25) is magnitude 2^31, 26 planes
 }
 
 }  // namespace grkgpu

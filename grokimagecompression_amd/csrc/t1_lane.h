@@ -421,6 +421,56 @@ struct LaneEncoder {
     }
 };
 
+// The bytes a block's MQ output slab must hold: an upper bound on
+// t1_mq_block's len for a w x h block of style sty with at most `bound`
+// bit-planes.  The coder's stores are whole dwords up to len rounded up to 4
+// (sink_commit, mqel_finish), so a slab of this size rounded up to 4 -- the
+// layouts round to 16 -- holds every one of them; the pad byte before the
+// block lands in the dword before the slab.
+//
+// Area term, w*h*4 + 64: the reference's code-block buffer for a block of
+// this size -- the sample bytes plus the one flush that ends a stream of a
+// single codeword segment.  tests/cpp/test_t1_model.cpp --sweep records how
+// much of it the symbols themselves take.
+//
+// Termination term: every pass but the last that t1_pass_term ends closes a
+// codeword segment whatever the block's size, and LaneEncoder::end_pass moves
+// bp for it by at most
+//   + 3  an MQ pass: mqel_flush is two BYTEOUTs (one byte each) and one more
+//        bp++ unless the last byte is 0xFF; mqel_erterm (PTERM) is at most two
+//        BYTEOUTs in its loop (k <= 11, each takes 7 or 8 off it) and one
+//        after it;
+//   + 1  a raw (BYPASS) pass: mqel_bypass_flush emits the partial byte or
+//        steps back;
+//   - 1  where the next pass is an MQ pass: mqel_restart steps bp back onto
+//        the segment's last byte (mqel_bypass_init, before a raw pass, leaves
+//        bp where it is).
+// So a terminated MQ pass costs 2 bytes before an MQ pass and 3 before a raw
+// one, a terminated raw pass 1 before a raw pass and 0 before an MQ pass,
+// counted here over the 3 bound - 2 passes of the deepest block.  The last
+// pass's flush is the one the area term's 64 bytes already hold.  A block of
+// fewer planes terminates a subset of these passes, so the bound covers it.
+// Without TERMALL and BYPASS the term is zero.
+GRK_HD uint32_t t1_enc_slab_bytes(uint32_t w, uint32_t h, uint32_t sty, uint32_t bound) {
+    uint32_t term = 0;
+    if ((sty & (CBLKSTY_TERMALL | CBLKSTY_LAZY)) && bound) {
+        const uint32_t np = 3 * bound - 2;
+        for (uint32_t k = 0; k + 1 < np; ++k) {
+            int32_t bp; int pt;
+            pass_info(k, bound, &bp, &pt);
+            if (!t1_pass_term(sty, bp, pt, bound)) continue;
+            int nt = pt + 1;
+            int32_t nb = bp;
+            if (nt == 3) { nt = 0; nb--; }
+            term += (t1_pass_raw(sty, bp, pt, bound) ? 1u : 3u) - (t1_pass_raw(sty, nb, nt, bound) ? 0u : 1u);
+        }
+    }
+    return w * h * 4 + 64 + term;
+}
+// The deepest block the encoder can produce: quant_mag keeps 6 fraction bits
+// of a 32-bit magnitude
+constexpr uint32_t T1_MAX_ENC_BPS = 26;
+
 // ===========================================================================
 // Encoder, split form.  Because the encoder knows every magnitude up front,
 // the significance state before bit-plane p is simply "magnitude >= 2^(p+1)"

@@ -913,7 +913,12 @@ typedef struct {
                              zeros to out[out_off - 4 .. out_off - 1] (the MQ
                              coder's pad byte before the block, Grok's
                              bp = start - 1, committed with its dword), so no
-                             other block's bytes may lie there */
+                             other block's bytes may lie there.  From out_off
+                             on the block needs grkgpu_t1_enc_out_bytes(w, h,
+                             cblk_sty) bytes of its own, rounded up to 4: the
+                             encoder stores whole dwords, and with TERMALL or
+                             BYPASS a block of a few samples writes far more
+                             than w*h*4 + 64 bytes */
     uint32_t stride, w, h, orient; /* orient = band number 0:LL 1:HL 2:LH 3:HH */
     int32_t qmfbid, inv_step;      /* qmfbid 1 = 5/3, 0 = 9/7 (13-bit inv step) */
 } grkgpu_enc_block;
@@ -945,6 +950,14 @@ typedef struct {
 #define GRKGPU_T1_MAX_SEG (64 * 64 * 4 + 64)
 size_t grkgpu_t1_scratch_bytes(void);
 size_t grkgpu_t1_scratch_bytes_n(uint32_t nblocks);
+/* The most bytes grkgpu_t1_encode_blocks[_sty] writes from a w x h block's
+ * out_off on (w, h <= 64, else 0): w*h*4 + 64, plus with TERMALL or BYPASS
+ * the bytes of every terminated coding pass -- up to 3 per pass, whatever the
+ * block's size -- for the deepest block the encoder produces (26 bit-planes).
+ * Lay blocks out at least this far apart (rounded up to 4) plus the 4 bytes
+ * before each out_off; a block that overran its neighbour is not detected by
+ * the stage call. */
+size_t grkgpu_t1_enc_out_bytes(uint32_t w, uint32_t h, uint32_t cblk_sty);
 int grkgpu_t1_encode_blocks(const grkgpu_enc_block *blocks, uint32_t nblocks, const int32_t *coef,
                             void *scratch, uint8_t *out, grkgpu_enc_result *results, int with_distortion,
                             void *stream);

@@ -18,8 +18,11 @@ Stores:
                                  codestream, for the MANY list: code-block
                                  mode switches (-M) on images of more than
                                  4,096 code-blocks (tests/test_gpu_t1_many.py)
+  tests/golden/manifest_tiny.json   the same for the TINY list: TERMALL on
+                                 code-blocks of one to a few samples
+                                 (tests/test_gpu_t1_tiny.py)
 
-Usage:  python oracle/make_golden.py [--large | --many] [--check] [--only NAME ...]
+Usage:  python oracle/make_golden.py [--large | --many | --tiny] [--check] [--only NAME ...]
   --check  regenerate into a temporary directory and compare with the
            committed files instead of overwriting them (exit 1 on a mismatch)
 """
@@ -242,6 +245,39 @@ MANY_DEC_VARIANTS = {
     "m_rgb12u_640_b16_I_r_M62": [["-l", "1"]],
     "m_g12_544_b8_M63": [["-r", "1"]],
 }
+
+# Code-blocks of one to a few samples under TERMALL (-M 4 and its combinations):
+# every coding pass is flushed and restarted, about two bytes a pass whatever
+# the block's size, so a 1x1 block of 13 or more bit-planes holds more bytes
+# than w*h*4 + 64 (t1_lane.h t1_enc_slab_bytes; tests/test_gpu_t1_tiny.py;
+# hash-only).  A band whose width and height are both 1 modulo the code-block
+# size has such a block: 2^k + 1 images with -n 1 (no DWT: the coefficient is
+# the sample minus 2^15), 98 = 2 * 49 with -b 16,16 -n 2 (four 49x49 bands).
+# 833 / 1041 with -b 16,16 have 2,809 / 4,356 blocks (the Tier-1 launch plans
+# by block count); -r / -q take the rate-controlled path.  Seeds (and the
+# uniform kind of two cases) are picked so that the bottom-right 1x1 block of
+# the -n 1 cases is in that regime where its style allows it -- the test
+# asserts it.  Not 17x17 / 18x17 with -b 16,16, 98x98x3 uniform -M 4, 98x98
+# uniform -M 4 -r 4,2,1: the reference refuses those itself ("Code block
+# layer size ... exceeds number of available bytes in tile buffer").
+TINY = [
+    ("t_g16_65_n1_M4", (65, 65, 1, 16), "smooth", 1, ["-n", "1", "-M", "4"]),
+    ("t_g16u_65_n1_M36", (65, 65, 1, 16), "uniform", 55, ["-n", "1", "-M", "36"]),
+    ("t_g16_65_n1_M5", (65, 65, 1, 16), "smooth", 1, ["-n", "1", "-M", "5"]),
+    ("t_g16_65_n1_M4_t33", (65, 65, 1, 16), "smooth", 2, ["-n", "1", "-M", "4", "-t", "33,33"]),
+    ("t_g16_67x66_n1_M4_d11", (67, 66, 1, 16), "smooth", 3, ["-n", "1", "-M", "4", "-d", "1,1"]),
+    ("t_g16_64_n1_M4_d11", (64, 64, 1, 16), "smooth", 3, ["-n", "1", "-M", "4", "-d", "1,1"]),
+    ("t_rgb16_129_n1_M12", (129, 129, 3, 16), "smooth", 312, ["-n", "1", "-M", "12"]),
+    ("t_g16_98_b16_n2_M4", (98, 98, 1, 16), "smooth", 5, ["-b", "16,16", "-n", "2", "-M", "4"]),
+    ("t_g16_98_b16_n2_M36", (98, 98, 1, 16), "smooth", 5, ["-b", "16,16", "-n", "2", "-M", "36"]),
+    ("t_g16_833_b16_n1_M6", (833, 833, 1, 16), "smooth", 7, ["-b", "16,16", "-n", "1", "-M", "6"]),
+    ("t_g16_1041_b16_n1_M4", (1041, 1041, 1, 16), "smooth", 47, ["-b", "16,16", "-n", "1", "-M", "4"]),
+    ("t_g16_1041_b16_n1_M4_r8_2", (1041, 1041, 1, 16), "smooth", 47, ["-b", "16,16", "-n", "1", "-M", "4", "-r", "8,2"]),
+    ("t_g16_1041_b16_n1_M4_q30_45", (1041, 1041, 1, 16), "smooth", 47, ["-b", "16,16", "-n", "1", "-M", "4", "-q", "30,45"]),
+    ("t_g16_545_b16_n1_M36_r20_1", (545, 545, 1, 16), "smooth", 1, ["-b", "16,16", "-n", "1", "-M", "36", "-r", "20,1"]),
+    ("t_g16u_545_b16_n1_M36_r20_1", (545, 545, 1, 16), "uniform", 432, ["-b", "16,16", "-n", "1", "-M", "36", "-r", "20,1"]),
+    ("t_g16_98_b16_n2_M4_r3_1", (98, 98, 1, 16), "smooth", 5, ["-b", "16,16", "-n", "2", "-M", "4", "-r", "3,1"]),
+]
 CHUNK = 64 * 1024  # chunk_sha256: one hash per successive 64 KiB of the codestream
 
 
@@ -331,17 +367,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--large", action="store_true")
     ap.add_argument("--many", action="store_true")
+    ap.add_argument("--tiny", action="store_true")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--only", nargs="*")
     a = ap.parse_args()
     build_ref()
-    if a.large and a.many:
-        ap.error("--large and --many are separate lists")
-    cases = LARGE if a.large else MANY if a.many else CASES
+    if a.large + a.many + a.tiny > 1:
+        ap.error("--large, --many and --tiny are separate lists")
+    cases = LARGE if a.large else MANY if a.many else TINY if a.tiny else CASES
     if a.only:
         cases = [cs for cs in cases if cs[0] in a.only]
-    mname = "manifest_large.json" if a.large else "manifest_many.json" if a.many else "manifest.json"
-    hash_only = a.large or a.many
+    mname = ("manifest_large.json" if a.large else "manifest_many.json" if a.many else
+             "manifest_tiny.json" if a.tiny else "manifest.json")
+    hash_only = a.large or a.many or a.tiny
+    whole_list = (a.many or a.tiny) and not a.only  # the committed list is exactly this one
     committed = {}
     if os.path.exists(os.path.join(GOLD, mname)):
         with open(os.path.join(GOLD, mname)) as f:
@@ -353,7 +392,7 @@ def main():
         for case in cases:
             # a case the reference refuses ends the run (check=True in ref_encode / ref_decode): never dropped
             rec = run_case(*case, tmp, keep_dir=keep, variants_of=MANY_DEC_VARIANTS if a.many else None,
-                           chunks=a.many)
+                           chunks=a.many or a.tiny)
             if a.check:
                 ref = committed.get(case[0])
                 same = ref is not None and all(ref.get(k) == rec.get(k)
@@ -372,14 +411,14 @@ def main():
                 man[case[0]] = rec
                 print(case[0], rec["j2k_len"], flush=True)
     if a.check:
-        if a.many and not a.only:  # the committed list is exactly this one
+        if whole_list:
             stale = sorted(set(committed) - {cs[0] for cs in cases})
             for n in stale:
-                print(n, "MISMATCH (not in MANY)", flush=True)
+                print(n, "MISMATCH (not in the list)", flush=True)
             bad += len(stale)
         print("mismatches", bad)
         sys.exit(1 if bad else 0)
-    if a.many and not a.only:
+    if whole_list:
         man = {cs[0]: man[cs[0]] for cs in cases}
     with open(os.path.join(GOLD, mname), "w") as f:
         json.dump(man, f, indent=1)

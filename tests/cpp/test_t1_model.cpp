@@ -13,6 +13,8 @@
 // allocation of exactly sym_slot_bytes(w, h), so the AddressSanitizer build
 // (tests/test_t1_model_host.py) reports a write past it.
 //   test_t1_model [stride]   every stride-th (w, h) pair (default 1: all)
+//   test_t1_model --encode IN OUT STY   the whole block encoder, file to file
+//   test_t1_model --sweep [rule]        the MQ slab rule against the encoder's len
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -137,9 +139,137 @@ static void plain_plane(int w, int h, uint32_t orient, const std::vector<uint32_
 // encoder does not have.  IN: u32 n, then per block u32 w, h, orient, qmfbid,
 // i32 inv_step, i32 coef[w * h]; OUT: per block u32 numbps, numpasses, len,
 // rate[96], then len bytes.
+static const uint32_t kTab[47] = GRK_MQ_TABLE_INIT;
+static T1Scratch scr;
+
+// --sweep [rule]: t1_enc_slab_bytes against the host encoder's len on the
+// blocks where the terminations, not the samples, decide the size: every
+// style 0..63 x the shapes below x depths 1..26 x five contents, 5/3 and 9/7
+// (inv_step 6553).  Each block goes through t1_prep_serial from coefficients
+// where a coefficient of that depth exists (5/3: up to 25 planes, 9/7 at this
+// step: up to 19; a magnitude of more bits is no int32 coefficient), and the
+// 26-plane blocks from the rows the prep would leave (pa / pb / neg written
+// directly).  Any len above the rule is reported with its case and fails the
+// run; the largest len / rule per style is printed.  Without `rule` the
+// output buffer is far larger than any block's bytes, so the check does not
+// depend on what lies after a slab; with it every block's buffer is an
+// allocation of exactly the 16 bytes of headroom plus the rule rounded up to
+// 4, for the AddressSanitizer build (tests/test_t1_slab_host.py).
+static uint64_t srng = 0xD1B54A32D192ED03ull;
+static uint32_t srnd() { srng ^= srng << 13; srng ^= srng >> 7; srng ^= srng << 17; return (uint32_t)srng; }
+
+static const int kSweepShapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {1, 3}, {3, 1}, {2, 2}, {1, 4}, {4, 1}, {3, 3}, {4, 4},
+                                      {5, 3}, {1, 8}, {2, 8}, {1, 16}, {16, 1}, {1, 64}, {64, 1}, {4, 64}, {64, 64}};  // (h, w)
+static const char *const kSweepKinds[] = {"full", "random", "alt5555", "single", "staircase"};
+
+// magnitudes of exactly nb bits (in some sample) and signs
+static void sweep_content(int kind, uint32_t n, uint32_t nb, std::vector<uint32_t> &mag, std::vector<uint8_t> &neg) {
+    const uint32_t top = 1u << (nb - 1), all = (uint32_t)(((uint64_t)1 << nb) - 1);
+    mag.assign(n, 0);
+    neg.assign(n, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (kind == 0) mag[i] = all;
+        if (kind == 1) { mag[i] = top | (srnd() & all); neg[i] = srnd() & 1; }
+        if (kind == 2) { mag[i] = top | (0x55555555u & all); neg[i] = 1; }
+        if (kind == 4) mag[i] = top >> (i % nb);  // one more sample turns significant at every plane
+    }
+    if (kind == 3) mag[n / 2] = all;
+}
+
+static int sweep(bool rule_sized) {
+    int fails = 0;
+    uint64_t blocks = 0, past_area = 0;  // past_area: blocks longer than w * h * 4 + 64
+    double worst[64];
+    uint32_t wcase[64][5];
+    for (int s = 0; s < 64; ++s) worst[s] = 0;
+    std::vector<uint32_t> mag;
+    std::vector<uint8_t> neg;
+    std::vector<uint32_t> sym;
+    std::vector<uint32_t> big((16 + 64 * 64 * 16 + 65536) / 4);
+    for (size_t si = 0; si < sizeof kSweepShapes / sizeof kSweepShapes[0]; ++si) {
+        const uint32_t h = (uint32_t)kSweepShapes[si][0], w = (uint32_t)kSweepShapes[si][1];
+        for (uint32_t nb = 1; nb <= T1_MAX_ENC_BPS; ++nb)
+            for (int kind = 0; kind < 5; ++kind)
+                for (int qmfbid = 1; qmfbid >= 0; --qmfbid) {
+                    const uint32_t orient = (uint32_t)(si + kind) % 4;
+                    sweep_content(kind, w * h, nb, mag, neg);
+                    uint32_t lnb = nb;
+                    if (qmfbid == 0 && nb > 19) continue;  // no such int32 coefficient at this step
+                    if (qmfbid == 1 && nb > 25) {
+                        // the rows t1_prep_serial leaves for these magnitudes
+                        memset(&scr.st, 0, sizeof scr.st);
+                        for (uint32_t p = 0; p < nb; ++p)
+                            for (uint32_t y = 0; y < h; ++y) {
+                                uint64_t row = 0;
+                                for (uint32_t x = 0; x < w; ++x) row |= (uint64_t)((mag[y * w + x] >> p) & 1u) << x;
+                                scr.pa[p * 64 + y] = row;
+                            }
+                        for (uint32_t i = 0; i < w * h; ++i)
+                            if (neg[i]) scr.st.neg[i / w + 1] |= (uint64_t)1 << (i % w);
+                    } else {
+                        std::vector<int32_t> coef(w * h);
+                        for (uint32_t i = 0; i < w * h; ++i) {
+                            // 9/7: the coefficient whose quantised magnitude (6 fraction bits) is mag.100000b or just under it
+                            const int64_t v = qmfbid ? (int64_t)mag[i] : mag[i] ? ((((int64_t)mag[i] << 6) | 32) << 18) / 6553 : 0;
+                            coef[i] = (int32_t)(neg[i] ? -v : v);
+                        }
+                        lnb = t1_prep_serial(coef.data(), w, w, h, qmfbid, 6553, scr.st, scr.pa);
+                    }
+                    if (lnb != nb) {
+                        printf("DEPTH h=%u w=%u nb=%u kind=%s qmfbid=%d: numbps %u\n", h, w, nb, kSweepKinds[kind], qmfbid, lnb);
+                        return 1;
+                    }
+                    t1_prep_above(h, nb, scr.pa, scr.pb);
+                    const uint32_t slot = sym_slot_bytes(w, h);
+                    sym.assign(((size_t)nb * slot + 256) / 4, 0);
+                    // the symbols depend on BYPASS, VSC and SEGSYM only: modelled once for the
+                    // eight styles that differ in RESET, TERMALL and PTERM
+                    for (uint32_t mv = 0; mv < 8; ++mv) {
+                        const uint32_t msty = (mv & 1 ? CBLKSTY_LAZY : 0) | (mv & 2 ? CBLKSTY_VSC : 0) | (mv & 4 ? CBLKSTY_SEGSYM : 0);
+                        uint64_t tmp[128];
+                        for (uint32_t p = 0; p < nb; ++p) {
+                            const uint64_t *ref = p + 1 < nb ? scr.pb + (p + 1) * 64 : scr.pb;
+                            t1_model_plane<const uint64_t *, uint64_t *>(w, h, orient, scr.pa + p * 64, scr.pb + p * 64, ref,
+                                                                         p + 1 < nb, scr.st.neg, tmp, nullptr,
+                                                                         sym.data() + (size_t)p * slot / 4, scr.cnt + p * 4, msty,
+                                                                         t1_pass_raw(msty, (int32_t)p, 0, nb));
+                        }
+                        for (uint32_t cv = 0; cv < 8; ++cv) {
+                            const uint32_t sty = msty | (cv & 1 ? CBLKSTY_RESET : 0) | (cv & 2 ? CBLKSTY_TERMALL : 0) |
+                                                 (cv & 4 ? CBLKSTY_PTERM : 0);
+                            const uint32_t rule = t1_enc_slab_bytes(w, h, sty, nb);
+                            uint32_t *buf = rule_sized ? (uint32_t *)malloc(16 + ((rule + 3) & ~3u)) : big.data();
+                            uint32_t rate[96], cx[32], slen = 0;
+                            if (sty & CBLKSTY_LAZY) t1_mq_block<true>(nb, sym.data(), slot / 4, scr.cnt, kTab, cx, buf + 4, rate, &slen, sty);
+                            else t1_mq_block<false>(nb, sym.data(), slot / 4, scr.cnt, kTab, cx, buf + 4, rate, &slen, sty);
+                            if (rule_sized) free(buf);
+                            ++blocks;
+                            past_area += slen > w * h * 4 + 64;
+                            if (slen > rule) {
+                                if (fails < 40)
+                                    printf("OVER sty=%u h=%u w=%u nb=%u kind=%s %s len=%u rule=%u\n", sty, h, w, nb, kSweepKinds[kind],
+                                           qmfbid ? "5/3" : "9/7", slen, rule);
+                                ++fails;
+                            }
+                            const double q = (double)slen / rule;
+                            if (q > worst[sty]) {
+                                worst[sty] = q;
+                                const uint32_t c[5] = {h, w, nb, slen, rule};
+                                memcpy(wcase[sty], c, sizeof c);
+                            }
+                        }
+                    }
+                }
+    }
+    for (int s = 0; s < 64; ++s)
+        printf("MAX sty=%d len/rule=%.3f (%ux%u, %u planes: %u of %u)\n", s, worst[s], wcase[s][0], wcase[s][1], wcase[s][2],
+               wcase[s][3], wcase[s][4]);
+    printf("blocks past w*h*4+64: %llu\n", (unsigned long long)past_area);
+    printf("%s: %d over the rule / %llu blocks\n", fails ? "FAIL" : "OK", fails, (unsigned long long)blocks);
+    return fails ? 1 : 0;
+}
+
 static int encode_file(const char *in, const char *outp, uint32_t sty) {
-    static const uint32_t kTab[47] = GRK_MQ_TABLE_INIT;
-    static T1Scratch scr;
     FILE *fi = fopen(in, "rb"), *fo = fopen(outp, "wb");
     uint32_t n = 0;
     if (!fi || !fo || fread(&n, 4, 1, fi) != 1) return 2;
@@ -160,7 +290,7 @@ static int encode_file(const char *in, const char *outp, uint32_t sty) {
                                                          scr.st.neg, tmp, nullptr, sym.data() + (size_t)p * slot / 4,
                                                          scr.cnt + p * 4, sty, t1_pass_raw(sty, (int32_t)p, 0, lnb));
         }
-        const size_t obytes = ((size_t)w * h * 4 + 64 + 15) & ~(size_t)15;
+        const size_t obytes = ((size_t)t1_enc_slab_bytes(w, h, sty, lnb) + 15) & ~(size_t)15;
         std::vector<uint32_t> sbuf((16 + obytes) / 4, 0);
         uint32_t rec[3 + 96] = {0}, cx[32], slen = 0;
         rec[0] = lnb;
@@ -177,6 +307,7 @@ static int encode_file(const char *in, const char *outp, uint32_t sty) {
 
 int main(int argc, char **argv) {
     if (argc == 5 && !strcmp(argv[1], "--encode")) return encode_file(argv[2], argv[3], (uint32_t)atoi(argv[4]));
+    if (argc >= 2 && !strcmp(argv[1], "--sweep")) return sweep(argc > 2 && !strcmp(argv[2], "rule"));
     const int stride = argc > 1 ? atoi(argv[1]) : 1;
     static const int W[] = {1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64};
     static const int H[] = {1, 3, 4, 5, 8, 61, 63, 64};

@@ -16,6 +16,9 @@
 // sample, formed from the oracle's full decode; with the VSC rule off it must
 // reproduce the oracle's truncated decode, and that is checked for every
 // block of every style.
+// At fixed iterations the blocks are 1x1, 1x2, 2x1 and 2x2 of 17 or more
+// planes under TERMALL without PTERM or BYPASS: dozens of segments of a byte
+// or two, more bytes than w * h * 4 + 64 (t1_enc_slab_bytes).
 // Buffers are sized as the GPU path sizes them (codec.cpp), so that an access
 // outside them is a finding in the shared code: built a second time under
 // AddressSanitizer + UBSan by tests/test_host_build.py (no GPU needed).
@@ -126,6 +129,7 @@ int main(int argc, char **argv) {
     for (uint32_t i = 0; i < 256; ++i) sc[i] = sc_lut_entry(i);
     for (uint32_t i = 0; i < 256; ++i) scw[i] = sc_win_entry(i);
     uint32_t seen_w1 = 0, seen_w63 = 0, seen_w64 = 0, seen_hodd = 0, seen_sty[64] = {0}, decoded = 0, multiseg = 0, vsc_cut = 0;
+    uint32_t seen_tiny = 0, tiny_over = 0;  // tiny blocks whose bytes outgrow w * h * 4 + 64 (the terminations decide their size)
     for (int it = 0; it < iters; ++it) {
         // shapes, amplitudes and kinds as test_t1_core.cpp draws them, with the
         // edge widths and stripe-remainder heights at fixed iterations
@@ -139,7 +143,24 @@ int main(int argc, char **argv) {
         int32_t inv_step = 1000 + rnd() % 20000;
         uint32_t amp = 1u << (rnd() % (qmfbid ? 15 : 24));
         int kind = rnd() % 4;
-        const uint32_t sty = 1 + rnd() % 63;
+        uint32_t sty = 1 + rnd() % 63;
+        // blocks of one to four samples, 17 to 19 planes deep, every sample with
+        // the top plane's bit, every pass terminated with the long (not the
+        // predictable) termination: one to two bytes a pass (mqel_flush's two
+        // BYTEOUTs and its bp++ unless the byte is 0xFF, less mqel_restart's
+        // step back) for 48 to 54 passes, against w * h * 4 + 64 <= 80 bytes
+        // for the samples (t1_enc_slab_bytes).  Most, not all, of these blocks
+        // outgrow that figure; the count is checked below.
+        const bool tiny = it % 12 == 10;
+        if (tiny) {
+            static const uint32_t TW[] = {1, 2, 1, 2}, TH[] = {1, 1, 2, 2}, TS[] = {4, 6, 12, 14, 36, 38, 44, 46};
+            const uint32_t q = (uint32_t)it / 12;
+            w = TW[q % 4]; h = TH[q % 4];
+            sty = TS[(q / 4 + q) % 8];
+            qmfbid = 1;
+            amp = 1u << (16 + q % 3);
+            kind = 0;
+        }
         std::vector<int32_t> coef(w * h);
         for (uint32_t i = 0; i < w * h; ++i) {
             int32_t v = (int32_t)(rnd() % (2 * amp + 1)) - (int32_t)amp;
@@ -147,6 +168,8 @@ int main(int argc, char **argv) {
             if (kind == 2) v = (int32_t)(i % w) - (int32_t)(w / 2);  // ramps
             coef[i] = v;
         }
+        if (tiny)  // every sample has the top plane's bit
+            for (uint32_t i = 0; i < w * h; ++i) coef[i] = coef[i] < 0 ? coef[i] - (int32_t)amp : coef[i] + (int32_t)amp;
         seen_w1 += w == 1; seen_w63 += w == 63; seen_w64 += w == 64; seen_hodd += (h & 3) != 0;
         seen_sty[sty]++;
         // oracle: the cblksty == 0 encode
@@ -171,9 +194,10 @@ int main(int argc, char **argv) {
                                                          t1_pass_raw(sty, (int32_t)p, 0, lnb));
         }
         // the MQ output: 16 bytes of headroom (the pad byte's commit lands in
-        // the dword before the output), then w * h * 4 + 64 bytes rounded to 16
+        // the dword before the output), then t1_enc_slab_bytes rounded to 16
         // (codec.cpp out_off / out_total)
-        const size_t obytes = ((size_t)w * h * 4 + 64 + 15) & ~(size_t)15;
+        const uint32_t slab = t1_enc_slab_bytes(w, h, sty, lnb);
+        const size_t obytes = ((size_t)slab + 15) & ~(size_t)15;
         std::vector<uint32_t> sbuf((16 + obytes) / 4, 0);
         uint32_t *sout = sbuf.data() + 4;
         uint32_t srate[100], slen = 0, cx[32];
@@ -186,7 +210,7 @@ int main(int argc, char **argv) {
             continue;
         }
         if (onp == 0) continue;
-        bool mono = slen <= w * h * 4 + 64;
+        bool mono = slen <= slab;
         for (uint32_t k = 0; mono && k < snp; ++k) mono = srate[k] <= slen && (k == 0 || srate[k] >= srate[k - 1]);
         if (!mono) {
             printf("RATES it=%d sty=%u w=%u h=%u len %u\n", it, sty, w, h, slen);
@@ -194,6 +218,12 @@ int main(int argc, char **argv) {
             continue;
         }
         if (onb > T1_MAX_DEC_BPS) continue;  // refused by the decoder's host side
+        if (tiny && (lnb < 17 || !(sty & CBLKSTY_TERMALL))) {
+            printf("TINY it=%d sty=%u w=%u h=%u nb %u\n", it, sty, w, h, lnb);
+            fails++;
+        }
+        seen_tiny += tiny;
+        tiny_over += tiny && slen > w * h * 4 + 64;
         ++decoded;
         const uint8_t *bytes = (const uint8_t *)sout;
         const uint32_t tnp = (uint32_t)(1 + rnd() % onp);  // the truncated pass count
@@ -292,13 +322,14 @@ int main(int argc, char **argv) {
     if (iters >= 300) {
         uint32_t nsty = 0;
         for (int s = 1; s < 64; ++s) nsty += seen_sty[s] != 0;
-        if (!seen_w1 || !seen_w63 || !seen_w64 || !seen_hodd || nsty < 60 || decoded * 2 < (uint32_t)iters || !multiseg || !vsc_cut) {
-            printf("COVERAGE w1 %u w63 %u w64 %u h%%4 %u styles %u decoded %u multi-segment %u\n", seen_w1, seen_w63,
-                   seen_w64, seen_hodd, nsty, decoded, multiseg);
+        if (!seen_w1 || !seen_w63 || !seen_w64 || !seen_hodd || nsty < 60 || decoded * 2 < (uint32_t)iters || !multiseg || !vsc_cut ||
+            seen_tiny < 24 || tiny_over * 2 < seen_tiny) {
+            printf("COVERAGE w1 %u w63 %u w64 %u h%%4 %u styles %u decoded %u multi-segment %u tiny blocks past w*h*4+64 %u / %u\n", seen_w1,
+                   seen_w63, seen_w64, seen_hodd, nsty, decoded, multiseg, tiny_over, seen_tiny);
             fails++;
         }
     }
-    printf("%s: %d failures / %d blocks (%u decoded, %u decodes over several segments)\n", fails ? "FAIL" : "OK", fails, iters,
-           decoded, multiseg);
+    printf("%s: %d failures / %d blocks (%u decoded, %u decodes over several segments, %u tiny blocks past w*h*4+64)\n",
+           fails ? "FAIL" : "OK", fails, iters, decoded, multiseg, tiny_over);
     return fails ? 1 : 0;
 }

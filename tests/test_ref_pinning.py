@@ -138,6 +138,14 @@ def test_many_block_fixtures_regenerate():
     assert "mismatches 0" in out
 
 
+def test_tiny_block_fixtures_regenerate():
+    """tests/golden/manifest_tiny.json: TERMALL on code-blocks of one to a few
+    samples (oracle/make_golden.py TINY; hashes only), regenerated by the
+    reference -- it encodes every one of them."""
+    out = _check("--tiny")
+    assert "mismatches 0" in out
+
+
 def test_plugin_abi_layout_matches_reference_headers():
     """include/grk_plugin_abi.h re-declares grok.h's plugin-boundary structs;
     oracle/abi/ compiles one offset/size table over the reference's headers
