@@ -207,9 +207,10 @@ class OutPlanes(ctypes.Structure):
                 ("on_device", ctypes.c_int32), ("pad_", ctypes.c_uint32)]
 
 
-COLOUR_NONE, COLOUR_SYCC = 0, 1
+COLOUR_NONE, COLOUR_SYCC, COLOUR_EYCC, COLOUR_CMYK = 0, 1, 3, 4
+COLOUR_FORCE_RGB = 0x100  # flag or'ed into a colour value: gray (+ alpha) -> R = G = B (+ alpha)
 PREC_CLIP, PREC_SCALE = 0, 1
-_COLOURS = {None: COLOUR_NONE, "sycc": COLOUR_SYCC}
+_COLOURS = {None: COLOUR_NONE, "sycc": COLOUR_SYCC, "eycc": COLOUR_EYCC, "cmyk": COLOUR_CMYK}
 _PREC_MODES = {"clip": PREC_CLIP, "scale": PREC_SCALE}
 
 
@@ -221,20 +222,39 @@ class OutOps(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
-def _out_ops(colour, out_prec, prec_mode):
+def _out_channels(colour, force_rgb, prec, sgnd, out_prec=None):
+    """The output channels [(prec, sgnd), ...] the colour / precision /
+    force-RGB steps leave of components (prec[k], sgnd[k]) -- what shapes and
+    dtype checks follow (the library refuses the shapes a step does not take;
+    they pass through here unchanged)."""
+    ch = [(int(p), bool(s)) for p, s in zip(prec, sgnd)]
+    if colour == "eycc" and len(ch) == 3:
+        ch = [(p, False) for p, _ in ch]
+    elif colour == "cmyk" and len(ch) >= 4:
+        ch = [(8, False)] * 3 + ch[4:]
+    if out_prec:
+        ch = [(int(out_prec), s) for _, s in ch]
+    if force_rgb and 1 <= len(ch) <= 2:
+        ch = [ch[0]] * 3 + ch[1:]
+    return ch
+
+
+def _out_ops(colour, out_prec, prec_mode, force_rgb=False):
     """OutOps of decompress / convert_to's arguments (None: no conversion asked for)."""
     if colour not in _COLOURS:
-        raise GrkGpuError("colour must be None or 'sycc' (got %r)" % (colour,))
+        raise GrkGpuError("colour must be None, 'sycc', 'eycc' or 'cmyk' (got %r)" % (colour,))
     if prec_mode not in _PREC_MODES:
         raise GrkGpuError("prec_mode must be 'clip' or 'scale' (got %r)" % (prec_mode,))
     if out_prec is not None and not 1 <= int(out_prec) <= 16:
         raise GrkGpuError("out_prec must be 1 .. 16 (got %r)" % (out_prec,))
-    if colour is None and out_prec is None:
+    if colour is None and out_prec is None and not force_rgb:
         return None
-    return OutOps(colour=_COLOURS[colour], prec=int(out_prec or 0), prec_mode=_PREC_MODES[prec_mode])
+    return OutOps(colour=_COLOURS[colour] | (COLOUR_FORCE_RGB if force_rgb else 0), prec=int(out_prec or 0),
+                  prec_mode=_PREC_MODES[prec_mode])
 
 
 COLOUR_AUTO = 2  # grkgpu_jp2_decompress only: sYCC -> RGB when the file's colr box says sYCC
+COLOUR_AUTO_RGB = 5  # grkgpu_jp2_decompress only: sYCC / eYCC / CMYK -> RGB by the file's colr box
 JP2_MAX_CDEF = 64
 # GRKGPU_CS_* (GRK_CLRSPC_*): the colour space a JP2 file signals / is written with
 COLOUR_SPACES = {"unknown": 0, "unspecified": 1, "srgb": 2, "gray": 3, "sycc": 4, "eycc": 5, "cmyk": 6,
@@ -973,7 +993,8 @@ class Codec:
                                                    ctypes.byref(op), ctypes.byref(ops)))
 
     def decompress(self, buf, device_out=False, out=None, reduce=0, window=None, layers=0, dtype=None, layout="chw",
-                   upsample=False, colour=None, out_prec=None, prec_mode="clip", custom_mct=False):
+                   upsample=False, colour=None, out_prec=None, prec_mode="clip", custom_mct=False,
+                   force_rgb=False):
         """Decode a .j2k codestream -> (c,h,w) int32 (numpy, or torch.cuda when
         device_out / out is a cuda tensor).  dtype = uint8 / int8 / uint16 /
         int16: samples of that type, stored by the last decode kernel (the
@@ -1000,13 +1021,22 @@ class Codec:
         then have to hold the output precision, so a 12-bit stream decodes to
         uint8 with out_prec=8.  Both run in the last decode kernel's store
         (grkgpu_decompress_convert, include/grk_mi355x.h has the closed forms).
+        colour="eycc" (color_esycc_to_rgb): 3 components on one grid, one
+        precision, component 0 unsigned -> unsigned R, G, B.  colour="cmyk"
+        (color_cmyk_to_rgb): 4 or more components on one grid, unsigned inks ->
+        c - 1 channels, 8-bit unsigned R, G, B (so dtype=uint8 holds them) and
+        the components behind the black ink unchanged.  Neither implies
+        upsample.  force_rgb=True (grk_decompress --force-rgb): a 1- or
+        2-component image comes back with its first component three times,
+        (3,h,w) / (4,h,w); 3 or more channels are left alone after a colour
+        conversion and refused without one.
         custom_mct=True (grkgpu_decompress_mct): a stream written with a custom
         array-based MCT (CParams.set_mct; COD MCT = 2) is decoded -- the inverse
         matrix and offsets read_mct returns, applied by the last decode kernel
         -- where every other decode refuses it as the reference does; every
         other keyword keeps its meaning, and any other stream decodes as
         without it."""
-        ops = _out_ops(colour, out_prec, prec_mode)
+        ops = _out_ops(colour, out_prec, prec_mode, force_rgb)
         d = _read_mct(buf)[0] if custom_mct else read_header(buf)
         if window is not None:  # the window (reference grid) clipped to the image
             wx0, wy0, wx1, wy1 = window
@@ -1026,6 +1056,14 @@ class Codec:
             return cd(cd(a1, s) - cd(a0, s), R)
         c = d.numcomps
         h, w = extent(d.y0, d.y1, 1), extent(d.x0, d.x1, 1)
+        subsampled = any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c))
+        # the output channels: the components, unless a colour step or force_rgb changes their number
+        chans = _out_channels(colour, force_rgb, [d.prec[k] for k in range(c)], [d.sgnd[k] for k in range(c)],
+                              out_prec)
+        grid = [(d.dx[k], d.dy[k]) for k in range(c)]
+        if len(chans) != c:  # (CMYK: the black ink's plane goes; one grid either way)
+            grid = [grid[0]] * len(chans)
+        c = len(chans)
         # the sample format: dtype, or the dtype of `out` (an `out` no decode
         # writes is refused below as "not int32")
         dt, fmt = _out_format(dtype)
@@ -1035,20 +1073,20 @@ class Codec:
             dt, fmt = _out_format(_out_dtype(out))
         shape = _layout_shape((c, h, w), layout)
         if ops is not None:  # the output's precision, not the stream's, is what the samples must hold
-            oprec = [ops.prec or d.prec[k] for k in range(c)]
-            if not _fmt_fits(fmt, oprec, [d.sgnd[k] for k in range(c)]):
+            oprec = [p for p, _ in chans]
+            if not _fmt_fits(fmt, oprec, [s for _, s in chans]):
                 raise GrkGpuError("%s samples do not hold the output precision / signedness (%s bits)"
                                   % (dt.name, "/".join(str(v) for v in oprec)))
         # grkgpu_decompress_to / _convert; else today's entry points
         narrow = fmt != SAMPLE_I32 or layout != "chw" or ops is not None or bool(custom_mct)
-        up = (bool(upsample) or colour == "sycc") and any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c))
-        if not up and any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)):
+        up = (bool(upsample) or colour == "sycc") and subsampled
+        if not up and subsampled:
             # subsampled components: a list of host planes, each on its grid
             if out is not None or device_out:
                 raise GrkGpuError("subsampled components decode to host planes only")
-            if layout != "chw" and all(d.dx[k] == d.dx[0] and d.dy[k] == d.dy[0] for k in range(c)):
+            if layout != "chw" and all(g == grid[0] for g in grid):
                 raise GrkGpuError("subsampled components decode to host planes only")
-            outs = [np.empty((extent(d.y0, d.y1, d.dy[k]), extent(d.x0, d.x1, d.dx[k])), dtype=dt)
+            outs = [np.empty((extent(d.y0, d.y1, grid[k][1]), extent(d.x0, d.x1, grid[k][0])), dtype=dt)
                     for k in range(c)]
             ptrs = (ctypes.c_void_p * c)(*[a.ctypes.data for a in outs])
             bp, bn, keep = _buf_ptr(buf)
@@ -1109,7 +1147,7 @@ class Codec:
         return out
 
     def decompress_jp2(self, buf, dtype=None, layout="chw", colour="auto", out_prec=None, prec_mode="clip",
-                       window=None, reduce=0, layers=0, device_out=False):
+                       window=None, reduce=0, layers=0, device_out=False, force_rgb=False):
         """Decode a .jp2 file (grkgpu_jp2_decompress) -> (array, info): the
         output CHANNELS as a (c,h,w) / (h,w,c) array -- numpy, or a cuda tensor
         with device_out -- and jp2_info(buf).  A palette (pclr + cmap) and the
@@ -1121,18 +1159,27 @@ class Codec:
         has to hold the channels' precision (the palette's column sizes, or
         out_prec).  dtype / layout / out_prec / prec_mode / window / reduce /
         layers / device_out as decompress.  A file with subsampled components
-        and no sYCC conversion decodes to a list of host planes, as there."""
-        if colour not in ("auto", None):
-            raise GrkGpuError("colour must be 'auto' or None (got %r)" % (colour,))
+        and no sYCC conversion decodes to a list of host planes, as there.
+        colour="auto_rgb": sYCC, eYCC (EnumCS 24) and CMYK (EnumCS 12) -> RGB
+        by what the file says, with decompress's rules for each (CMYK: one
+        channel fewer, R, G, B of 8 bits).  force_rgb=True: 1 or 2 channels
+        come back with the first one three times; 3 or more are left alone
+        after a conversion or when the file says sRGB, refused otherwise, and
+        a file with an ICC profile is refused."""
+        if colour not in ("auto", "auto_rgb", None):
+            raise GrkGpuError("colour must be 'auto', 'auto_rgb' or None (got %r)" % (colour,))
         ji, d, info = _jp2_read(buf)
         c = d.numcomps
-        sycc = colour == "auto" and info["colour_space"] == "sycc"
+        sycc = colour in ("auto", "auto_rgb") and info["colour_space"] == "sycc"
+        conv = info["colour_space"] if colour == "auto_rgb" and info["colour_space"] in ("eycc", "cmyk") else None
         if any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)) and not sycc:
             mv = memoryview(buf)[ji.cs_offset:ji.cs_offset + ji.cs_length]
             return self.decompress(np.frombuffer(mv, dtype=np.uint8), dtype=dtype, layout=layout, out_prec=out_prec,
-                                   prec_mode=prec_mode, window=window, reduce=reduce, layers=layers), info
+                                   prec_mode=prec_mode, window=window, reduce=reduce, layers=layers, colour=conv,
+                                   force_rgb=force_rgb), info
         _out_ops(None, out_prec, prec_mode)  # (argument checks)
-        ops = OutOps(colour=COLOUR_AUTO if colour == "auto" else COLOUR_NONE, prec=int(out_prec or 0),
+        ops = OutOps(colour={"auto": COLOUR_AUTO, "auto_rgb": COLOUR_AUTO_RGB, None: COLOUR_NONE}[colour]
+                     | (COLOUR_FORCE_RGB if force_rgb else 0), prec=int(out_prec or 0),
                      prec_mode=_PREC_MODES[prec_mode])
         if window is not None:
             wx0, wy0, wx1, wy1 = window
@@ -1146,8 +1193,10 @@ class Codec:
             return cd(a1, R) - cd(a0, R) if window is not None else cd(a1 - a0, R)
         h, w = extent(d.y0, d.y1), extent(d.x0, d.x1)
         dt, fmt = _out_format(dtype)
-        oprec = [ops.prec or d.prec[k] for k in range(c)]
-        if not _fmt_fits(fmt, oprec, [d.sgnd[k] for k in range(c)]):
+        chans = _out_channels(conv, force_rgb, [d.prec[k] for k in range(c)], [d.sgnd[k] for k in range(c)], out_prec)
+        c = len(chans)
+        oprec = [p for p, _ in chans]
+        if not _fmt_fits(fmt, oprec, [s for _, s in chans]):
             raise GrkGpuError("%s samples do not hold the output precision / signedness (%s bits)"
                               % (dt.name, "/".join(str(v) for v in oprec)))
         if layers < 0:
@@ -1328,15 +1377,18 @@ def upsample_to(src, dst, rect, subsampling, layout="chw", dst_stride=None):
 
 
 def convert_to(src, dst, rect, subsampling, prec, sgnd=False, layout="chw", dst_stride=None, colour=None,
-               out_prec=None, prec_mode="clip"):
+               out_prec=None, prec_mode="clip", force_rgb=False):
     """grkgpu_convert_to: upsample_to with the colour / precision steps of
     Codec.decompress(colour=, out_prec=, prec_mode=) in its store.  src: one 2-D
     cuda tensor per component on its grid (as upsample_to), all of one dtype
     that holds every (prec, sgnd) -- it may differ from dst's, which has to hold
-    the output precision.  prec / sgnd: one value, or one per component."""
+    the output precision.  prec / sgnd: one value, or one per component.
+    colour="eycc" / "cmyk" and force_rgb as decompress: dst then holds the
+    output channels (CMYK: one fewer than src; force_rgb on one or two int32
+    planes at (1,1): three or four)."""
     x0, y0, x1, y1 = rect
     c, w, h = len(src), x1 - x0, y1 - y0
-    ops = _out_ops(colour, out_prec, prec_mode)
+    ops = _out_ops(colour, out_prec, prec_mode, force_rgb)
     dt, fmt = _out_format(_out_dtype(dst))
     _layout_shape((c, h, w), layout)  # refuses an unknown layout
     cd = lambda v, s: -(-v // s)  # noqa: E731
@@ -1345,9 +1397,10 @@ def convert_to(src, dst, rect, subsampling, prec, sgnd=False, layout="chw", dst_
     precs, sgnds = _per_comp(prec, c), _per_comp(sgnd, c)
     sdt, sfmt = _out_format(_out_dtype(src[0]))
     il = layout == "hwc"
-    row = w * c if il else w
+    co = len(_out_channels(colour, force_rgb, precs, sgnds, out_prec))  # the channels dst holds
+    row = w * co if il else w
     stride = row if dst_stride is None else dst_stride
-    need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
+    need = (h - 1) * stride + row if il else (co * h - 1) * stride + row
     if dst.dim() != 1 or not dst.is_contiguous() or not dst.is_cuda or stride < row or dst.numel() < need:
         raise GrkGpuError("convert_to: dst flat, %d samples, on a cuda device" % need)
     for a, (dx, dy) in zip(src, subsampling):
@@ -1359,7 +1412,7 @@ def convert_to(src, dst, rect, subsampling, prec, sgnd=False, layout="chw", dst_
             raise GrkGpuError("convert_to: component plane %s %s, its grid needs %s %s on dst's device"
                               % (tuple(a.shape), a.dtype, shape, src[0].dtype))
     op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout] | LAYOUT_UPSAMPLE, on_device=1)
-    for k in range(1 if il else c):
+    for k in range(1 if il else co):
         op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
     ptrs = (ctypes.c_void_p * c)(*[a.data_ptr() for a in src])
     ss = (ctypes.c_uint32 * c)(*[a.stride(0) if a.shape[0] > 1 and a.numel() else max(1, a.shape[1]) for a in src])

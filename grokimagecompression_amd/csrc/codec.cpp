@@ -2463,6 +2463,7 @@ struct DecodeOut {
     const grkgpu_out_ops *ops;  // grkgpu_decompress_convert: colour / precision in the last store (null: none)
     int custom_mct;  // grkgpu_decompress_mct: a COD with MCT = 2 (Part 2 array-based) is decoded, not refused
     const struct ChanMap *chan;  // grkgpu_jp2_decompress: the output channels where they are not the components in order
+    int is_rgb;  // grkgpu_jp2_decompress: the file says sRGB (GRKGPU_COLOUR_FORCE_RGB leaves 3+ channels alone)
 };
 // The output channels of a JP2 file with a palette or a channel swap
 // (jp2_resolve_channels): channel c takes component comp[c]'s sample, or entry
@@ -2483,9 +2484,12 @@ static DecodeOut i32_planes(int32_t *const *planes, int on_device) {
 
 // grkgpu_out_ops' own rules, checked before anything touches a device; fmt = the
 // output's sample format
+static uint32_t colour_of(const grkgpu_out_ops *o) { return o->colour & ~GRKGPU_COLOUR_FORCE_RGB; }
 static int check_out_ops(const grkgpu_out_ops *o, uint32_t fmt) {
     if (!o) return GRKGPU_OK;
-    if (o->colour > GRKGPU_COLOUR_SYCC) return set_err(GRKGPU_EINVAL, "unknown colour conversion");
+    const uint32_t col = colour_of(o);  // (2 and 5 are GRKGPU_COLOUR_AUTO / _AUTO_RGB, resolved by the JP2 entry point)
+    if (col != GRKGPU_COLOUR_NONE && col != GRKGPU_COLOUR_SYCC && col != GRKGPU_COLOUR_EYCC && col != GRKGPU_COLOUR_CMYK)
+        return set_err(GRKGPU_EINVAL, "unknown colour conversion");
     if (o->prec > 16) return set_err(GRKGPU_EINVAL, "output precision must be 1 .. 16 (0: the component's own)");
     if (o->prec && o->prec_mode > GRKGPU_PREC_SCALE) return set_err(GRKGPU_EINVAL, "unknown precision mode");
     if (o->reserved) return set_err(GRKGPU_EINVAL, "reserved field of the output ops must be 0");
@@ -2496,13 +2500,54 @@ static int check_out_ops(const grkgpu_out_ops *o, uint32_t fmt) {
 static bool out_ops_active(const grkgpu_out_ops *o) { return o && (o->colour || o->prec); }
 
 // The device form of checked ops for components of (prec, sgnd, dx, dy): the
-// sYCC shape rules (color_sycc_to_rgb, color.cpp:384-418) and each component's
-// precision op (clip_component / scale_component, convert.cpp:82-161).
-// oprec[k] = the output precision.
-static int resolve_out_ops(const grkgpu_out_ops *o, uint32_t nc, const uint32_t *prec, const int32_t *sgnd,
-                           const uint32_t *dx, const uint32_t *dy, OutOps &dev, uint32_t *oprec) {
+// shape rules of the colour step (color_sycc_to_rgb, color.cpp:384-418;
+// color_esycc_to_rgb / color_cmyk_to_rgb, :881-995, and grk_decompress's own
+// checks around them) and each output channel's precision op (clip_component
+// / scale_component, convert.cpp:82-161).  no = the output channels (the
+// components, one fewer after CMYK), oprec[c] / osgnd[c] = what channel c
+// leaves with.
+static int resolve_out_ops(const grkgpu_out_ops *o, uint32_t nc, const uint32_t *prec_in, const int32_t *sgnd_in,
+                           const uint32_t *dx, const uint32_t *dy, OutOps &dev, uint32_t &no, uint32_t *oprec,
+                           int32_t *osgnd) {
     dev = OutOps{};
-    if (o->colour == GRKGPU_COLOUR_SYCC) {
+    no = nc;
+    // the channels the precision step sees
+    uint32_t prec[GRKGPU_MAX_COMPS];
+    int32_t sgnd[GRKGPU_MAX_COMPS];
+    for (uint32_t k = 0; k < nc; ++k) { prec[k] = prec_in[k]; sgnd[k] = sgnd_in[k]; }
+    const uint32_t col = colour_of(o);
+    if (col == GRKGPU_COLOUR_EYCC || col == GRKGPU_COLOUR_CMYK) {
+        const bool cmyk = col == GRKGPU_COLOUR_CMYK;
+        if (cmyk ? nc < 4 : nc != 3)
+            return set_err(GRKGPU_EINVAL, cmyk ? "CMYK conversion needs at least 4 components"
+                                               : "eYCC conversion needs exactly 3 components");
+        for (uint32_t k = 1; k < nc; ++k)
+            if (dx[k] != dx[0] || dy[k] != dy[0])
+                return set_err(GRKGPU_EINVAL, cmyk ? "CMYK conversion needs every component on one grid"
+                                                   : "eYCC conversion needs every component on one grid");
+        if (cmyk) {
+            for (uint32_t k = 0; k < 4; ++k) {
+                if (sgnd[k] || prec[k] < 1 || prec[k] > 16)
+                    return set_err(GRKGPU_EINVAL, "CMYK conversion needs unsigned inks of precision 1 .. 16");
+                dev.sc[k] = 1.0f / (float)((1 << prec[k]) - 1);
+            }
+            dev.col = COL_CMYK;
+            no = nc - 1;
+            for (uint32_t c = 0; c < no; ++c) {
+                prec[c] = c < 3 ? 8 : prec_in[c + 1];
+                sgnd[c] = c < 3 ? 0 : sgnd_in[c + 1];
+            }
+        } else {
+            if (sgnd[0] || prec[0] < 1 || prec[0] > 16 || prec[1] != prec[0] || prec[2] != prec[0])
+                return set_err(GRKGPU_EINVAL, "eYCC conversion needs an unsigned component 0 and one precision (1 .. 16)");
+            dev.col = COL_EYCC;
+            dev.coff[0] = sgnd[1] ? 0 : 1 << (prec[0] - 1);
+            dev.coff[1] = sgnd[2] ? 0 : 1 << (prec[0] - 1);
+            dev.upb = (int32_t)((1u << prec[0]) - 1);
+            sgnd[0] = sgnd[1] = sgnd[2] = 0;  // R, G, B in [0, upb]: reported, and scaled or clipped, as unsigned
+        }
+    }
+    if (col == GRKGPU_COLOUR_SYCC) {
         if (nc != 3) return set_err(GRKGPU_EINVAL, "sYCC conversion needs exactly 3 components");
         for (uint32_t k = 0; k < 3; ++k)
             if (sgnd[k] || prec[k] != prec[0] || prec[k] < 1 || prec[k] > 16)
@@ -2514,10 +2559,11 @@ static int resolve_out_ops(const grkgpu_out_ops *o, uint32_t nc, const uint32_t 
         dev.off = 1 << (prec[0] - 1);
         dev.upb = (int32_t)((1u << prec[0]) - 1);
     }
-    for (uint32_t k = 0; k < nc; ++k) {
+    for (uint32_t k = 0; k < no; ++k) {
         const uint32_t q = prec[k], p = o->prec;
         PrecOp &op = dev.pc[k];
         oprec[k] = p ? p : q;
+        osgnd[k] = sgnd[k];
         if (!p || p == q) continue;
         if (o->prec_mode == GRKGPU_PREC_CLIP) {
             if (p > q) continue;  // every value is inside the wider range
@@ -2654,22 +2700,61 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     // form, oprec the precision the samples leave with.  sYCC needs every
     // component of the pixel, so it implies the upsampled output.
     const bool conv = out_ops_active(od.ops);
-    const bool sycc = conv && od.ops->colour == GRKGPU_COLOUR_SYCC;
+    const uint32_t colour = conv ? colour_of(od.ops) : GRKGPU_COLOUR_NONE;
+    const bool sycc = colour == GRKGPU_COLOUR_SYCC;
+    // eYCC / CMYK -> RGB sit where sYCC sits, on components of one grid (they
+    // do not imply the upsampled output); CMYK leaves nc - 1 channels
+    const bool colconv = colour != GRKGPU_COLOUR_NONE;
+    const bool force_rgb = conv && (od.ops->colour & GRKGPU_COLOUR_FORCE_RGB);
     OutOps dops{};
     uint32_t oprec[GRKGPU_MAX_COMPS];
-    for (uint32_t k = 0; k < nc; ++k) oprec[k] = cp.prec[k];
+    int32_t osgnd[GRKGPU_MAX_COMPS];
+    for (uint32_t k = 0; k < nc; ++k) { oprec[k] = cp.prec[k]; osgnd[k] = cp.sgnd[k]; }
+    // the shape rules, on the codestream's components: ahead of what force-RGB
+    // makes of the channel count, and of the refusal behind a channel map
+    if (colconv && (!sycc || !od.chan)) {
+        uint32_t n_;
+        int rc = resolve_out_ops(od.ops, nc, cp.prec, cp.sgnd, cp.dx, cp.dy, dops, n_, oprec, osgnd);
+        if (rc) return rc;
+    }
     // od.chan (grkgpu_jp2_decompress): `no` output channels instead of the nc
     // components -- what the planes, the format and the ops describe from here on
-    const ChanMap *const cm = od.chan;
-    const uint32_t no = cm ? cm->nch : nc;
+    const ChanMap *cm = od.chan;
+    // GRKGPU_COLOUR_FORCE_RGB (convert_gray_to_rgb, grk_decompress.cpp:805-890)
+    // on the one or two channels the steps before it leave: channel 0 three
+    // times and the second one behind it -- a channel map without a table,
+    // stored by the palette kernels
+    ChanMap fcm{};
+    {
+        const uint32_t nbefore = cm ? cm->nch : (colour == GRKGPU_COLOUR_CMYK ? nc - 1 : nc);
+        if (force_rgb && nbefore >= 1 && nbefore <= 2) {
+            if (subs) return set_err(GRKGPU_EUNSUPPORTED, "force-RGB over subsampled components");
+            if (cp.mct == 2) return set_err(GRKGPU_EUNSUPPORTED, "force-RGB behind a custom MCT");
+            fcm.nch = nbefore + 2;
+            for (uint32_t ch = 0; ch < fcm.nch; ++ch) {
+                const uint32_t from = ch < 3 ? 0 : 1;
+                fcm.comp[ch] = cm ? cm->comp[from] : from;
+                fcm.pcol[ch] = cm ? cm->pcol[from] : -1;
+                fcm.prec[ch] = cm ? cm->prec[from] : cp.prec[from];
+                fcm.sgnd[ch] = cm ? cm->sgnd[from] : cp.sgnd[from];
+            }
+            if (cm) { fcm.ne = cm->ne; fcm.npc = cm->npc; fcm.table = cm->table; }
+            cm = &fcm;
+        } else if (force_rgb && !colconv && !od.is_rgb) {
+            return set_err(GRKGPU_EINVAL, "force-RGB: don't know how to convert these channels to RGB");
+        }
+    }
+    uint32_t no = cm ? cm->nch : nc;
     if (cm) {
         if (subs) return set_err(GRKGPU_EUNSUPPORTED, "JP2 palette / channel order over subsampled components");
         if (sycc) return set_err(GRKGPU_EUNSUPPORTED, "sYCC conversion behind a JP2 palette or channel swap");
+        if (colconv) return set_err(GRKGPU_EUNSUPPORTED, "eYCC / CMYK conversion behind a JP2 palette or channel swap");
         if (no < 1 || no > GRKGPU_MAX_COMPS) return set_err(GRKGPU_EINVAL, "bad channel map");
         for (uint32_t ch = 0; ch < no; ++ch) {
             if (cm->comp[ch] >= nc || (cm->pcol[ch] >= 0 && (!cm->table || !cm->ne || (uint32_t)cm->pcol[ch] >= cm->npc)))
                 return set_err(GRKGPU_EINVAL, "bad channel map");
             oprec[ch] = cm->prec[ch];
+            osgnd[ch] = cm->sgnd[ch];
         }
         if (img) {
             img->numcomps = no;
@@ -2682,11 +2767,12 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         if (conv) {
             uint32_t one[GRKGPU_MAX_COMPS];
             for (uint32_t ch = 0; ch < GRKGPU_MAX_COMPS; ++ch) one[ch] = 1;
-            int rc = resolve_out_ops(od.ops, no, cm->prec, cm->sgnd, one, one, dops, oprec);
+            uint32_t n_;
+            int rc = resolve_out_ops(od.ops, no, cm->prec, cm->sgnd, one, one, dops, n_, oprec, osgnd);
             if (rc) return rc;
         }
     } else if (conv) {
-        int rc = resolve_out_ops(od.ops, nc, cp.prec, cp.sgnd, cp.dx, cp.dy, dops, oprec);
+        int rc = resolve_out_ops(od.ops, nc, cp.prec, cp.sgnd, cp.dx, cp.dy, dops, no, oprec, osgnd);
         if (rc) return rc;
     }
     const bool up = (od.upsample || sycc) && subs;
@@ -2696,9 +2782,16 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         for (uint32_t k = 0; k < nc; ++k) img->dx[k] = img->dy[k] = 1;
     if (img && conv)
         for (uint32_t k = 0; k < no; ++k) img->prec[k] = oprec[k];
+    if (img && colconv && !sycc) {  // the output channels: unsigned R, G, B, and CMYK's one fewer
+        img->numcomps = no;
+        for (uint32_t k = 0; k < no; ++k) {
+            img->sgnd[k] = osgnd[k];
+            if (no != nc && k >= 3) { img->dx[k] = img->dx[k + 1]; img->dy[k] = img->dy[k + 1]; }
+        }
+    }
     for (uint32_t k = 0; od.fmt != SMP_I32 && k < no; ++k) {
         const bool sg = od.fmt == SMP_I8 || od.fmt == SMP_I16;
-        if (((cm ? cm->sgnd[k] : cp.sgnd[k]) != 0) != sg || oprec[k] > 8 * sb)
+        if ((osgnd[k] != 0) != sg || oprec[k] > 8 * sb)
             return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
         // a channel used directly carries its component's samples whatever the palette box says of its size
         if (cm && cm->pcol[k] < 0 && (cm->prec[k] != cp.prec[cm->comp[k]] || (cm->sgnd[k] != 0) != (cp.sgnd[cm->comp[k]] != 0)))
@@ -3183,7 +3276,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     // (upsampled: every component has the output rectangle's iw x (oy1 - iy0) samples)
     const uint64_t opix = (uint64_t)iw * (oy1 - iy0);
     auto region_bytes = [&](uint32_t k) {
-        if (up) return (size_t)(opix * (il ? nc : 1)) * sb;
+        if (up) return (size_t)(opix * (il ? no : 1)) * sb;
         return (size_t)(il ? ooff[no] : ooff[k + 1] - ooff[k]) * sb;
     };
     // upsampled: which components go through a staging plane -- all when they
@@ -3236,7 +3329,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         DstPlanes fdst{};
         for (uint32_t k = 0; k < nout; ++k)
             fdst.p[k] = at(k, (uint64_t)(o.y0 - orect[0].y0) * ow + (o.x0 - orect[0].x0));
-        return launch_upsample_ops(zero, nc, o.x0, o.y0, o.w(), o.h(), fdst, od.fmt, il, il ? ow * nc : ow, dops, s);
+        return launch_upsample_ops(zero, nc, o.x0, o.y0, o.w(), o.h(), fdst, od.fmt, il, il ? ow * no : ow, dops, s);
     };
     // a channel map's fills: the palette store run over zero samples -- entry 0
     // of each looked-up channel, then the precision op -- since the
@@ -3261,12 +3354,12 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                                       ceil_pow2(cr.y1, reduce)}, orect[0]);
             if (!o.empty()) HIPCHK(fill_mapped(o));
         }
-    } else if (sycc && !up && opad) {
+    } else if (colconv && !up && opad) {
         HIPCHK(fill_converted(orect[0]));
-    } else if (sycc && !up && missing) {
+    } else if (colconv && !up && missing) {
         for (uint32_t t = tb; t < te; ++t) {
             if (walk.decoded[t] || wskip[t]) continue;
-            const Rect cr = tile_rect(cp, t);
+            const Rect cr = comp_rect(tile_rect(cp, t), cp.dx[0], cp.dy[0]);  // (one grid; sYCC: the image's)
             const Rect o = intersect({ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
                                       ceil_pow2(cr.y1, reduce)}, orect[0]);
             if (!o.empty()) HIPCHK(fill_converted(o));
@@ -3348,10 +3441,10 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
             HIPCHK(launch_palette(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * no : ow, nc, sh, mn, mx,
                                   tmct[tile.index - tb], wmask, pmap, ptable, conv ? &dops : nullptr, s));
         else if (tmct[tile.index - tb] == 2)  // (every component at (1,1): never upsampled)
-            HIPCHK(launch_mct_inv_custom(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * nc : ow, nc, minv,
+            HIPCHK(launch_mct_inv_custom(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * no : ow, nc, minv,
                                          moff, mn, mx, conv ? &dops : nullptr, s));
         else if (conv && !up)
-            HIPCHK(launch_mct_inv_dcshift_ops(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * nc : ow, nc,
+            HIPCHK(launch_mct_inv_dcshift_ops(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, il, il ? ow * no : ow, nc,
                                               sh, mn, mx, tmct[tile.index - tb], wmask, dops, s));
         else
             HIPCHK(launch_mct_inv_dcshift_to(tsrc, tr.w(), out.w(), out.h(), tdst, up ? sfmt : od.fmt, il && !up,
@@ -3394,7 +3487,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         DstPlanes tdst{};
         for (uint32_t k = 0; k < nout; ++k) tdst.p[k] = at(k, (uint64_t)(out.y0 - iy0) * iw + (out.x0 - ix0));
         if (conv)
-            HIPCHK(launch_upsample_ops(pl, nc, out.x0, out.y0, out.w(), out.h(), tdst, od.fmt, il, il ? iw * nc : iw,
+            HIPCHK(launch_upsample_ops(pl, nc, out.x0, out.y0, out.w(), out.h(), tdst, od.fmt, il, il ? iw * no : iw,
                                        dops, s));
         else
             HIPCHK(launch_upsample_to(pl, nc, out.x0, out.y0, out.w(), out.h(), tdst, od.fmt, il, il ? iw * nc : iw,
@@ -3491,7 +3584,7 @@ static int check_out_planes(const grkgpu_out_planes *out) {
 static int decompress_to_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
                               uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
                               const grkgpu_out_planes *out, const grkgpu_out_ops *ops, bool custom_mct = false,
-                              const ChanMap *chan = nullptr) {
+                              const ChanMap *chan = nullptr, bool is_rgb = false) {
     int rc = check_out_planes(out);
     if (rc) return rc;
     rc = check_out_ops(ops, out->sample_fmt);
@@ -3499,7 +3592,7 @@ static int decompress_to_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, con
     const DecodeOut od{out->planes, (int32_t)out->sample_fmt,
                        (out->layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED, out->on_device,
                        (out->layout & GRKGPU_LAYOUT_UPSAMPLE) != 0, out_ops_active(ops) ? ops : nullptr,
-                       custom_mct ? 1 : 0, chan};
+                       custom_mct ? 1 : 0, chan, is_rgb ? 1 : 0};
     if (!dp) return decompress_impl(c, csb, len, img, od, tile_begin, tile_end);
     const bool win = dp->DA_x0 || dp->DA_y0 || dp->DA_x1 || dp->DA_y1;
     const Rect w{dp->DA_x0, dp->DA_y0, dp->DA_x1, dp->DA_y1};
@@ -3641,12 +3734,25 @@ extern "C" int grkgpu_jp2_decompress(grkgpu_ctx *c, const uint8_t *file, size_t 
     grkgpu_out_ops o{};
     if (ops) {
         o = *ops;
-        if (o.colour == GRKGPU_COLOUR_AUTO)
-            o.colour = j.ch.colour_space == JP2_CS_SYCC ? GRKGPU_COLOUR_SYCC : GRKGPU_COLOUR_NONE;
+        const uint32_t force = o.colour & GRKGPU_COLOUR_FORCE_RGB, col = o.colour & ~GRKGPU_COLOUR_FORCE_RGB;
+        const uint32_t space = j.ch.colour_space;
+        if (col == GRKGPU_COLOUR_AUTO)
+            o.colour = force | (space == JP2_CS_SYCC ? GRKGPU_COLOUR_SYCC : GRKGPU_COLOUR_NONE);
+        else if (col == GRKGPU_COLOUR_AUTO_RGB)
+            o.colour = force | (space == JP2_CS_SYCC   ? GRKGPU_COLOUR_SYCC
+                                : space == JP2_CS_EYCC ? GRKGPU_COLOUR_EYCC
+                                : space == JP2_CS_CMYK ? GRKGPU_COLOUR_CMYK
+                                                       : GRKGPU_COLOUR_NONE);
+        // grk_decompress --force-rgb on a file with a profile goes through its colour management library
+        if (force && (j.boxes.icc_len || space == JP2_CS_ICC))
+            return set_err(GRKGPU_EUNSUPPORTED, "JP2: force-RGB on a file with an ICC profile");
     }
+    const bool is_rgb = j.ch.colour_space == JP2_CS_SRGB;
     const uint8_t *cs = file + j.boxes.cs_off;
     const size_t cslen = (size_t)j.boxes.cs_len;
-    if (!j.ch.mapped) return decompress_to_impl(c, cs, cslen, dp, tile_begin, tile_end, img, out, ops ? &o : nullptr);
+    if (!j.ch.mapped)
+        return decompress_to_impl(c, cs, cslen, dp, tile_begin, tile_end, img, out, ops ? &o : nullptr, false, nullptr,
+                                  is_rgb);
     ChanMap cm{};
     cm.nch = (uint32_t)j.ch.ch.size();
     for (uint32_t i = 0; i < cm.nch; ++i) {
@@ -3660,7 +3766,7 @@ extern "C" int grkgpu_jp2_decompress(grkgpu_ctx *c, const uint8_t *file, size_t 
         cm.npc = j.boxes.npc;
         cm.table = j.table.data();
     }
-    return decompress_to_impl(c, cs, cslen, dp, tile_begin, tile_end, img, out, ops ? &o : nullptr, false, &cm);
+    return decompress_to_impl(c, cs, cslen, dp, tile_begin, tile_end, img, out, ops ? &o : nullptr, false, &cm, is_rgb);
 }
 
 static int jp2_wparams_of(const grkgpu_image_desc *img, const grkgpu_jp2_wparams *wp, Jp2WriteParams &w) {
@@ -3977,7 +4083,16 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
     if (!src || !src_stride || !dx || !dy || !prec || !sgnd || numcomps < 1 || numcomps > 16 || x1 <= x0 ||
         y1 <= y0 || x1 > 0x7fffffffu || y1 > 0x7fffffffu)
         return set_err(GRKGPU_EINVAL, "bad arguments");
-    if ((uint64_t)dst_stride < (uint64_t)(x1 - x0) * (il ? numcomps : 1))
+    // the channels dst describes: the components, one fewer after CMYK, and
+    // channel 0 three times where force-RGB finds one or two
+    const bool force_rgb = ops && (ops->colour & GRKGPU_COLOUR_FORCE_RGB);
+    const bool colconv = ops && colour_of(ops) != GRKGPU_COLOUR_NONE;
+    const uint32_t nbefore = ops && colour_of(ops) == GRKGPU_COLOUR_CMYK && numcomps >= 4 ? numcomps - 1 : numcomps;
+    const bool forced = force_rgb && nbefore <= 2;
+    const uint32_t nch = forced ? nbefore + 2 : nbefore;
+    if (force_rgb && !forced && !colconv)
+        return set_err(GRKGPU_EINVAL, "force-RGB: don't know how to convert these channels to RGB");
+    if ((uint64_t)dst_stride < (uint64_t)(x1 - x0) * (il ? nch : 1))
         return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
     bool full = true;  // every component at (1,1)
     for (uint32_t k = 0; k < numcomps; ++k) {
@@ -3991,15 +4106,29 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
     }
     const grkgpu_out_ops none{};
     OutOps dops{};
-    uint32_t oprec[GRKGPU_MAX_COMPS];
-    rc = resolve_out_ops(ops ? ops : &none, numcomps, prec, sgnd, dx, dy, dops, oprec);
+    uint32_t oprec[GRKGPU_MAX_COMPS], no = numcomps;
+    int32_t osgnd[GRKGPU_MAX_COMPS];
+    uint32_t fprec[4] = {prec[0], prec[0], prec[0], numcomps > 1 ? prec[1] : 0};  // (forced: the channels)
+    int32_t fsgnd[4] = {sgnd[0], sgnd[0], sgnd[0], numcomps > 1 ? sgnd[1] : 0};
+    if (forced) {
+        const uint32_t one[4] = {1, 1, 1, 1};
+        if (colconv) {  // (no conversion takes one or two components: its own refusal)
+            rc = resolve_out_ops(ops, numcomps, prec, sgnd, dx, dy, dops, no, oprec, osgnd);
+            return rc ? rc : set_err(GRKGPU_EINVAL, "bad arguments");
+        }
+        rc = resolve_out_ops(ops, nch, fprec, fsgnd, one, one, dops, no, oprec, osgnd);
+    } else {
+        rc = resolve_out_ops(ops ? ops : &none, numcomps, prec, sgnd, dx, dy, dops, no, oprec, osgnd);
+    }
     if (rc) return rc;
     UpPlan pl{};
     DstPlanes d{};
-    for (uint32_t k = 0; k < numcomps; ++k) {
+    for (uint32_t k = 0; k < no; ++k) {
         const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
-        if (fmt != SMP_I32 && ((sgnd[k] != 0) != sg || oprec[k] > 8 * sb))
+        if (fmt != SMP_I32 && ((osgnd[k] != 0) != sg || oprec[k] > 8 * sb))
             return set_err(GRKGPU_EINVAL, "sample format does not hold the output precision / signedness");
+    }
+    for (uint32_t k = 0; k < numcomps; ++k) {
         const Rect cr = comp_rect({x0, y0, x1, y1}, dx[k], dy[k]);
         if (src_stride[k] < cr.w()) return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
         // (a grid without a sample inside the rectangle has no plane: every index is negative)
@@ -4008,10 +4137,32 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
         pl.c[k] = UpComp{src[k], src_stride[k], (int32_t)cr.x0, (int32_t)cr.y0, (int32_t)cr.x0, (int32_t)cr.y0,
                          (uint8_t)dx[k], (uint8_t)dy[k], (uint8_t)(UPCOMP_FIN + sfmt), 0, 0, 0, 0};
     }
-    for (uint32_t k = 0; k < (il ? 1u : numcomps); ++k) {
+    for (uint32_t k = 0; k < (il ? 1u : no); ++k) {
         if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
             return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
         d.p[k] = dst->planes[k];
+    }
+    if (forced) {
+        // channel 0 three times, a second one behind it: the palette kernels' direct map on finished int32 planes
+        for (uint32_t k = 0; k < numcomps; ++k) full = full && src_stride[k] == src_stride[0];
+        if (!full || sfmt != SMP_I32)
+            return set_err(GRKGPU_EUNSUPPORTED, "force-RGB needs int32 sources at (1,1) with one row stride");
+        rc = check_device(-1);
+        if (rc) return rc;
+        PlanePtrs p{};
+        ShiftArr sh{}, mn{}, mx{};
+        PalMap map{};
+        map.nch = no;
+        for (uint32_t ch = 0; ch < no; ++ch) { map.comp[ch] = ch < 3 ? 0 : 1; map.pcol[ch] = -1; }
+        set_pal_used(map);
+        for (uint32_t k = 0; k < numcomps; ++k) {
+            p.p[k] = (int32_t *)const_cast<void *>(src[k]);
+            if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
+            else { mn.v[k] = 0; mx.v[k] = (int32_t)((1u << prec[k]) - 1); }
+        }
+        HIPCHK(launch_palette(p, src_stride[0], x1 - x0, y1 - y0, d, fmt, il, dst_stride, numcomps, sh, mn, mx, 0, 0, map,
+                              nullptr, &dops, (hipStream_t)stream));
+        return GRKGPU_OK;
     }
     rc = check_device(-1);
     if (rc) return rc;

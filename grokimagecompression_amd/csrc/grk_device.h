@@ -133,16 +133,38 @@ hipError_t launch_upsample_to(const UpPlan &src, uint32_t ncomp, uint32_t X0, ui
 //   POP_MULDIV  (uint32) v * a / b, the unsigned scale-up (the product fits 32 bits)
 //   POP_MUL     v * a, the signed scale-up by a power of two
 // Everything here is uniform over a launch.
+//
+// col (COL_*; never together with sycc) is one of the two other conversions
+// of grk_decompress's colour step (color.cpp:881-995), which sit where sycc
+// sits:
+//   COL_EYCC  color_esycc_to_rgb on the three components: cb = v1 - coff[0],
+//             cr = v2 - coff[1] (2^(P-1) for an unsigned chroma component, 0
+//             for a signed one), then in IEEE double, every operation rounded
+//             on its own, left to right, truncating, clamped to [0, upb]
+//               R = (y - 0.0000368 * cb + 1.40199 * cr + 0.5)
+//               G = (1.0003 * y - 0.344125 * cb - 0.7141128 * cr + 0.5)
+//               B = (0.999823 * y + 1.77204 * cb - 0.000008 * cr + 0.5)
+//   COL_CMYK  color_cmyk_to_rgb on components 0 .. 3 of ncomp >= 4: in
+//             float32, every operation rounded on its own, truncating,
+//               C = 1.0f - (float)v0 * sc[0]   (likewise M, Y, K)
+//               R = (int32)(255.0f * C * K), G = ... M ..., B = ... Y ...
+//             sc[k] = 1.0f / (float)(2^prec_k - 1), divided on the host.  The
+//             ncomp components leave as ncomp - 1 CHANNELS: R, G, B, then
+//             components 4 .. as channels 3 ..; pc[], the destination planes,
+//             dstride and the run ownership of the stores describe channels.
 enum : int32_t { POP_NONE = 0, POP_CLIP = 1, POP_SHR = 2, POP_MULDIV = 3, POP_MUL = 4 };
+enum : int32_t { COL_NONE = 0, COL_EYCC = 1, COL_CMYK = 2 };
 struct PrecOp { int32_t mode, a, b; };
 struct OutOps {
     int32_t sycc, off, upb;
     PrecOp pc[GRK_MAX_COMPS];
+    int32_t col, coff[2];
+    float sc[4];
 };
 // launch_mct_inv_dcshift_to / launch_upsample_to with the conversions in their
 // stores (the same kernels, instantiated with the ops; int32 planes run
-// k_mct_inv_dcshift_planar<int32_t>).  sycc needs ncomp == 3 and an unsigned
-// or int32 format.  A finished (not raw) UpComp of launch_upsample_ops carries
+// k_mct_inv_dcshift_planar<int32_t>).  sycc / COL_EYCC need ncomp == 3,
+// COL_CMYK ncomp >= 4, all three an unsigned or int32 format.  A finished (not raw) UpComp of launch_upsample_ops carries
 // its samples' own format f, which may differ from the destination's, as
 // raw = UPCOMP_FIN + f: a staging plane keeps the stream's precision when the
 // output is narrower.

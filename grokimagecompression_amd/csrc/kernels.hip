@@ -286,9 +286,15 @@ __device__ __forceinline__ void inv_plain_run(int32_t (&a)[N], int32_t irrev_c, 
 // them as the template parameter OP: 0 = none (the instantiations every decode
 // without ops runs: no ops argument, the code as it was), OP_PREC = the
 // precision op of each component, OP_SYCC = sYCC -> RGB on the three
-// components, then their precision ops.
+// components, then their precision ops; OP_EYCC = eYCC -> RGB in their place;
+// OP_CMYK = CMYK -> RGB on components 0 .. 3, which leaves one channel fewer
+// than there are components (OutOps: COL_EYCC / COL_CMYK).
 // ---------------------------------------------------------------------------
-constexpr int OP_PREC = 1, OP_SYCC = 2;
+constexpr int OP_PREC = 1, OP_SYCC = 2, OP_EYCC = 3, OP_CMYK = 4;
+// a conversion of exactly three components, with or without an MCT
+constexpr bool op_ycc(int op) { return op == OP_SYCC || op == OP_EYCC; }
+// the component output channel c carries: c, or behind CMYK's black ink c + 1
+constexpr int chan_comp(int op, int c) { return op == OP_CMYK && c >= 3 ? c + 1 : c; }
 
 // clip_component / scale_component (convert.cpp:82-161); o is uniform over the
 // launch, so the switch does not diverge
@@ -350,11 +356,109 @@ __device__ __forceinline__ void sycc_run(int32_t (&a)[N], int32_t (&b)[N], int32
     }
 }
 
+// color_esycc_to_rgb (color.cpp:936-995): IEEE double, the source line's
+// operations one by one from the left, each rounded on its own (no
+// contraction, as in sycc_terms), the conversion truncating
+__device__ __forceinline__ void eycc_pixel(int32_t &y, int32_t &u, int32_t &v, const OutOps &ops) {
+#pragma clang fp contract(off)
+    const double yv = (double)y, cb = (double)(u - ops.coff[0]), cr = (double)(v - ops.coff[1]);
+    const int32_t r = (int32_t)(yv - 0.0000368 * cb + 1.40199 * cr + 0.5);
+    const int32_t g = (int32_t)(1.0003 * yv - 0.344125 * cb - 0.7141128 * cr + 0.5);
+    const int32_t b = (int32_t)(0.999823 * yv + 1.77204 * cb - 0.000008 * cr + 0.5);
+    y = clamp_upb(r, ops.upb);
+    u = clamp_upb(g, ops.upb);
+    v = clamp_upb(b, ops.upb);
+}
+template <int N>
+__device__ __forceinline__ void eycc_run(int32_t (&a)[N], int32_t (&b)[N], int32_t (&c)[N], const OutOps &ops) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        eycc_pixel(a[i], b[i], c[i], ops);
+        // One pixel's doubles at a time: left to itself the compiler converts a 16-pixel run to doubles
+        // first and spills (800 scratch instructions).  The empty statement makes the next pixel's inputs
+        // depend on this pixel's results, which is an order instruction selection has to keep.
+        if constexpr (N > 4) {
+            if (i + 1 < N)
+                asm volatile("" : "+v"(a[i]), "+v"(b[i]), "+v"(c[i]), "+v"(a[i + 1]), "+v"(b[i + 1]), "+v"(c[i + 1]));
+        }
+    }
+}
+// the conversion of a three-component OP
+template <int OP, int N>
+__device__ __forceinline__ void ycc_run(int32_t (&a)[N], int32_t (&b)[N], int32_t (&c)[N], const OutOps &ops) {
+    if constexpr (OP == OP_SYCC) sycc_run<N>(a, b, c, ops);
+    else eycc_run<N>(a, b, c, ops);
+}
+
+// color_cmyk_to_rgb (color.cpp:881-933): float32, every operation rounded on
+// its own, the conversion truncating; the scales come divided from the host.
+// In-range unsigned inks give 0 .. 255, so nothing is clamped.
+__device__ __forceinline__ void cmyk_pixel(int32_t &c, int32_t &m, int32_t &y, int32_t k, const OutOps &ops) {
+#pragma clang fp contract(off)
+    const float C = 1.0f - (float)c * ops.sc[0], M = 1.0f - (float)m * ops.sc[1];
+    const float Y = 1.0f - (float)y * ops.sc[2], K = 1.0f - (float)k * ops.sc[3];
+    c = (int32_t)(255.0f * C * K);
+    m = (int32_t)(255.0f * M * K);
+    y = (int32_t)(255.0f * Y * K);
+}
+template <int N>
+__device__ __forceinline__ void cmyk_run(int32_t (&a)[N], int32_t (&b)[N], int32_t (&c)[N], const int32_t (&k)[N],
+                                         const OutOps &ops) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) cmyk_pixel(a[i], b[i], c[i], k[i], ops);
+}
+
 // The kernels take the ops as a trailing parameter pack O: empty for OP = 0, so
 // those instantiations keep the parameters and the code they always had, and
 // one OutOps otherwise.
 __device__ __forceinline__ const OutOps *ops_ptr() { return nullptr; }
 __device__ __forceinline__ const OutOps *ops_ptr(const OutOps &o) { return &o; }
+
+template <typename T>
+__device__ __forceinline__ void store_packed(T *p, const uint32_t (&w)[4], int n);  // (below)
+// 4 samples packed behind the ones a run's 16 bytes already hold (k_mct_inv_custom_planar's push)
+template <typename T>
+__device__ __forceinline__ void push_packed(uint32_t (&p)[4], const int32_t (&v)[4]) {
+    constexpr int W = (int)sizeof(T);
+#pragma unroll
+    for (int w = 0; w + W < 4; ++w) p[w] = p[w + W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) p[4 - W + w] = pack_word<T>(v, w);
+}
+
+// OP_CMYK, planar: the run's R, G, B planes from its four ink planes, walked
+// in sub-runs of 4 pixels as k_mct_inv_custom_planar walks its run, so that an
+// 8-bit run never holds its 4 x 16 inks as floats at once
+template <typename T>
+__device__ __forceinline__ void cmyk_planar_run(const PlanePtrs &src, size_t si, const DstPlanes &dst, size_t di, int n,
+                                                const ShiftArr &shift, const ShiftArr &minv, const ShiftArr &maxv,
+                                                int32_t mct, int32_t irrev, const OutOps &ops) {
+    constexpr int N = NarrowRun<T>::N;
+    uint32_t pk[3][4];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) pk[j][w] = 0;
+#pragma unroll 1
+    for (int s = 0; s < N / 4; ++s) {
+        const int left = n - 4 * s, ms = left < 0 ? 0 : (left > 4 ? 4 : left);
+        int32_t v[4][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) load_run<4>(src.p[k] + si + 4 * s, ms, v[k]);
+        if (mct) inv_mct_run<4>(v[0], v[1], v[2], irrev, shift, minv, maxv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (!mct || k == 3) inv_plain_run<4>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        cmyk_run<4>(v[0], v[1], v[2], v[3], ops);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            prec_run<4>(v[j], ops.pc[j]);
+            push_packed<T>(pk[j], v[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) store_packed<T>((T *)dst.p[j] + di, pk[j], n);
+}
 
 // planar: dst.p[c] = plane c (samples T), rows dstride samples apart
 template <typename T, int OP = 0, typename... O>
@@ -372,19 +476,30 @@ __global__ void k_mct_inv_dcshift_planar(PlanePtrs src, uint32_t sstride, uint32
     if (n <= 0) return;
     const size_t si = (size_t)y * sstride + x0, di = drow + x0;
     uint32_t c0 = 0;
-    if (OP == OP_SYCC || (mct && ncomp >= 3)) {  // (sYCC: exactly three components, with or without an MCT)
+    if constexpr (OP == OP_CMYK) {  // four or more components: channels R, G, B, then components 4 ..
+        cmyk_planar_run<T>(src, si, dst, di, n, shift, minv, maxv, mct, irrev, *ops);
+        for (uint32_t k = 4; k < ncomp; ++k) {
+            int32_t a[N];
+            load_run<N>(src.p[k] + si, n, a);
+            inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+            prec_run<N>(a, ops->pc[k - 1]);
+            store_samples<T, N>((T *)dst.p[k - 1] + di, a, n);
+        }
+        return;
+    }
+    if (op_ycc(OP) || (mct && ncomp >= 3)) {  // (sYCC / eYCC: exactly three components, with or without an MCT)
         int32_t a[N], b[N], c[N];
         load_run<N>(src.p[0] + si, n, a);
         load_run<N>(src.p[1] + si, n, b);
         load_run<N>(src.p[2] + si, n, c);
-        if (OP != OP_SYCC || mct) {
+        if (!op_ycc(OP) || mct) {
             inv_mct_run<N>(a, b, c, irrev, shift, minv, maxv);
         } else {
             inv_plain_run<N>(a, irrev & 1, shift.v[0], minv.v[0], maxv.v[0]);
             inv_plain_run<N>(b, (irrev >> 1) & 1, shift.v[1], minv.v[1], maxv.v[1]);
             inv_plain_run<N>(c, (irrev >> 2) & 1, shift.v[2], minv.v[2], maxv.v[2]);
         }
-        if constexpr (OP == OP_SYCC) sycc_run<N>(a, b, c, *ops);
+        if constexpr (op_ycc(OP)) ycc_run<OP, N>(a, b, c, *ops);
         if constexpr (OP != 0) {
             prec_run<N>(a, ops->pc[0]);
             prec_run<N>(b, ops->pc[1]);
@@ -411,12 +526,16 @@ __global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32
                                          int32_t irrev, O... o) {
     static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
     [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
+    static_assert(!op_ycc(OP) || NC == 3, "sYCC / eYCC: three components");
+    static_assert(OP != OP_CMYK || NC >= 4, "CMYK: four inks");
     constexpr int N = NarrowRun<T>::N;
+    // the pixels stored: NCH channels each (OP_CMYK: one fewer than the components read)
+    constexpr int NCH = OP == OP_CMYK ? NC - 1 : NC;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (y >= th) return;
     T *const drow = (T *)dst.p[0] + (size_t)y * dstride;
     uint32_t x0;
-    const int n = run_of<N>((uintptr_t)drow, NC * sizeof(T), t, tw, x0);
+    const int n = run_of<N>((uintptr_t)drow, NCH * sizeof(T), t, tw, x0);
     if (n <= 0) return;
     const size_t si = (size_t)y * sstride + x0;
     int32_t v[NC][N];
@@ -426,17 +545,18 @@ __global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32
 #pragma unroll
     for (int k = 0; k < NC; ++k)
         if (!mct || k >= 3) inv_plain_run<N>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-    if constexpr (OP == OP_SYCC) sycc_run<N>(v[0], v[1], v[2], *ops);
+    if constexpr (op_ycc(OP)) ycc_run<OP, N>(v[0], v[1], v[2], *ops);
+    if constexpr (OP == OP_CMYK) cmyk_run<N>(v[0], v[1], v[2], v[3], *ops);
     if constexpr (OP != 0) {
 #pragma unroll
-        for (int k = 0; k < NC; ++k) prec_run<N>(v[k], ops->pc[k]);
+        for (int c = 0; c < NCH; ++c) prec_run<N>(v[chan_comp(OP, c)], ops->pc[c]);
     }
-    int32_t px[N * NC];
+    int32_t px[N * NCH];
 #pragma unroll
     for (int i = 0; i < N; ++i)
 #pragma unroll
-        for (int k = 0; k < NC; ++k) px[i * NC + k] = v[k][i];
-    store_samples<T, N * NC>(drow + (size_t)x0 * NC, px, n * NC);
+        for (int c = 0; c < NCH; ++c) px[i * NCH + c] = v[chan_comp(OP, c)][i];
+    store_samples<T, N * NCH>(drow + (size_t)x0 * NCH, px, n * NCH);
 }
 
 // interleaved, any other component count: one thread per pixel, one store per sample
@@ -449,6 +569,29 @@ __global__ void k_mct_inv_dcshift_pixels_any(PlanePtrs src, uint32_t sstride, ui
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= tw || y >= th) return;
     const size_t si = (size_t)y * sstride + x;
+    if constexpr (OP == OP_CMYK) {  // ncomp >= 4 components, pixels of ncomp - 1 channels
+        T *const d = (T *)dst.p[0] + (size_t)y * dstride + (size_t)x * (ncomp - 1);
+        int32_t v[4][1];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k][0] = src.p[k][si];
+        if (mct) inv_mct_run<1>(v[0], v[1], v[2], irrev, shift, minv, maxv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (!mct || k == 3) inv_plain_run<1>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        cmyk_run<1>(v[0], v[1], v[2], v[3], *ops);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            prec_run<1>(v[j], ops->pc[j]);
+            __builtin_nontemporal_store((T)v[j][0], d + j);
+        }
+        for (uint32_t k = 4; k < ncomp; ++k) {
+            int32_t a[1] = {src.p[k][si]};
+            inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+            prec_run<1>(a, ops->pc[k - 1]);
+            __builtin_nontemporal_store((T)a[0], d + (k - 1));
+        }
+        return;
+    }
     T *const d = (T *)dst.p[0] + (size_t)y * dstride + (size_t)x * ncomp;
     uint32_t c0 = 0;
     if (mct && ncomp >= 3) {
@@ -546,7 +689,8 @@ __global__ void __launch_bounds__(256) k_mct_inv_custom_planar(PlanePtrs src, ui
                                         uint32_t dstride, uint32_t ncomp, MctInv m, ShiftArr off, ShiftArr minv,
                                         ShiftArr maxv, O... o) {
     static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
-    static_assert(OP != OP_SYCC || NC == 3, "sYCC: three components");
+    static_assert(!op_ycc(OP) || NC == 3, "sYCC / eYCC: three components");
+    static_assert(OP != OP_CMYK || NC == 0, "CMYK: the any-count form");
     [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
     constexpr int N = NarrowRun<T>::N, KM = NC ? NC : GRK_MAX_COMPS;
     constexpr int W = (int)sizeof(T);  // packed words of a sub-run
@@ -588,11 +732,31 @@ __global__ void __launch_bounds__(256) k_mct_inv_custom_planar(PlanePtrs src, ui
 #pragma unroll
             for (int j = 0; j < NC; ++j)
                 custom_out<KM, 4>(x, m.d + j * GRK_MAX_COMPS, nc, off.v[j], minv.v[j], maxv.v[j], v[j]);
-            if constexpr (OP == OP_SYCC) sycc_run<4>(v[0], v[1], v[2], *ops);
+            if constexpr (op_ycc(OP)) ycc_run<OP, 4>(v[0], v[1], v[2], *ops);
 #pragma unroll
             for (int j = 0; j < NC; ++j) {
                 if constexpr (OP != 0) prec_run<4>(v[j], ops->pc[j]);
                 push(pk[j], v[j]);
+            }
+        } else if constexpr (OP == OP_CMYK) {  // (nc >= 4) the four inks together, then channel j - 1 from output j
+            int32_t q[4][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                custom_out<KM, 4>(x, m.d + j * GRK_MAX_COMPS, nc, off.v[j], minv.v[j], maxv.v[j], q[j]);
+            cmyk_run<4>(q[0], q[1], q[2], q[3], *ops);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                prec_run<4>(q[j], ops->pc[j]);
+                push(pk[j], q[j]);
+            }
+#pragma unroll
+            for (int j = 4; j < KM; ++j) {
+                if ((uint32_t)j < nc) {
+                    int32_t v[4];
+                    custom_out<KM, 4>(x, m.d + j * GRK_MAX_COMPS, nc, off.v[j], minv.v[j], maxv.v[j], v);
+                    prec_run<4>(v, ops->pc[j - 1]);
+                    push(pk[j - 1], v);
+                }
             }
         } else {
 #pragma unroll
@@ -606,9 +770,10 @@ __global__ void __launch_bounds__(256) k_mct_inv_custom_planar(PlanePtrs src, ui
             }
         }
     }
+    const uint32_t nch = OP == OP_CMYK ? nc - 1 : nc;  // channels stored
 #pragma unroll
     for (int j = 0; j < KM; ++j) {
-        if (NC || (uint32_t)j < nc) store_packed<T>((T *)dst.p[j] + di, pk[j], n);
+        if (NC || (uint32_t)j < nch) store_packed<T>((T *)dst.p[j] + di, pk[j], n);
     }
 }
 
@@ -620,7 +785,8 @@ __global__ void __launch_bounds__(256) k_mct_inv_custom_pixels(PlanePtrs src, ui
                                         uint32_t dstride, uint32_t ncomp, MctInv m, ShiftArr off, ShiftArr minv,
                                         ShiftArr maxv, O... o) {
     static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
-    static_assert(OP != OP_SYCC || NC == 3, "sYCC: three components");
+    static_assert(!op_ycc(OP) || NC == 3, "sYCC / eYCC: three components");
+    static_assert(OP != OP_CMYK || NC == 0, "CMYK: the any-count form");
     [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (y >= th) return;
@@ -637,7 +803,7 @@ __global__ void __launch_bounds__(256) k_mct_inv_custom_pixels(PlanePtrs src, ui
 #pragma unroll
         for (int j = 0; j < NC; ++j)
             custom_out<NC, N>(x, m.d + j * GRK_MAX_COMPS, NC, off.v[j], minv.v[j], maxv.v[j], v[j]);
-        if constexpr (OP == OP_SYCC) sycc_run<N>(v[0], v[1], v[2], *ops);
+        if constexpr (op_ycc(OP)) ycc_run<OP, N>(v[0], v[1], v[2], *ops);
         if constexpr (OP != 0) {
 #pragma unroll
             for (int k = 0; k < NC; ++k) prec_run<N>(v[k], ops->pc[k]);
@@ -656,6 +822,29 @@ __global__ void __launch_bounds__(256) k_mct_inv_custom_pixels(PlanePtrs src, ui
         int32_t x[KM][1];
 #pragma unroll
         for (int k = 0; k < KM; ++k) x[k][0] = (uint32_t)k < ncomp ? src.p[k][si] : 0;
+        if constexpr (OP == OP_CMYK) {  // (ncomp >= 4) pixels of ncomp - 1 channels
+            T *const dc = (T *)dst.p[0] + (size_t)y * dstride + (size_t)t * (ncomp - 1);
+            int32_t q[4][1];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                custom_out<KM, 1>(x, m.d + j * GRK_MAX_COMPS, ncomp, off.v[j], minv.v[j], maxv.v[j], q[j]);
+            cmyk_run<1>(q[0], q[1], q[2], q[3], *ops);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                prec_run<1>(q[j], ops->pc[j]);
+                __builtin_nontemporal_store((T)q[j][0], dc + j);
+            }
+#pragma unroll
+            for (int j = 4; j < KM; ++j) {
+                if ((uint32_t)j < ncomp) {
+                    int32_t v[1];
+                    custom_out<KM, 1>(x, m.d + j * GRK_MAX_COMPS, ncomp, off.v[j], minv.v[j], maxv.v[j], v);
+                    prec_run<1>(v, ops->pc[j - 1]);
+                    __builtin_nontemporal_store((T)v[0], dc + (j - 1));
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < KM; ++j) {
             if ((uint32_t)j < ncomp) {
@@ -1065,6 +1254,40 @@ __global__ void k_upsample_any(UpPlan p, uint32_t ncomp, uint32_t X0, uint32_t Y
                 prec_run<1>(v[k], ops->pc[k]);
                 T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * 3 + k : (T *)dst.p[k] + drow + x;
                 __builtin_nontemporal_store((T)v[k][0], d);
+            }
+            return;
+        }
+        if (ops->col == COL_EYCC) {  // (three components, one grid)
+            int32_t v[3][1];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                v[k][0] = up_sample<T, OP>(p.c[k], (int32_t)(X / p.c[k].dx), (int32_t)(Y / p.c[k].dy));
+            eycc_run<1>(v[0], v[1], v[2], *ops);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                prec_run<1>(v[k], ops->pc[k]);
+                T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * 3 + k : (T *)dst.p[k] + drow + x;
+                __builtin_nontemporal_store((T)v[k][0], d);
+            }
+            return;
+        }
+        if (ops->col == COL_CMYK) {  // (ncomp >= 4 components, ncomp - 1 channels)
+            int32_t v[4][1];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                v[k][0] = up_sample<T, OP>(p.c[k], (int32_t)(X / p.c[k].dx), (int32_t)(Y / p.c[k].dy));
+            cmyk_run<1>(v[0], v[1], v[2], v[3], *ops);
+            for (uint32_t ch = 0; ch + 1 < ncomp; ++ch) {
+                int32_t a[1];
+                if (ch < 3) {
+                    a[0] = ch == 0 ? v[0][0] : (ch == 1 ? v[1][0] : v[2][0]);
+                } else {
+                    const UpComp &c = p.c[ch + 1];
+                    a[0] = up_sample<T, OP>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy));
+                }
+                prec_run<1>(a, ops->pc[ch]);
+                T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * (ncomp - 1) + ch : (T *)dst.p[ch] + drow + x;
+                __builtin_nontemporal_store((T)a[0], d);
             }
             return;
         }
@@ -2145,6 +2368,30 @@ static void launch_inv_ops(const PlanePtrs &src, uint32_t sstride, uint32_t tw, 
     const dim3 grid((runs + 255) / 256, th);
     mct = mct && ncomp >= 3;
     if constexpr (SY) {
+        if (ops.col == COL_EYCC) {  // three components (checked by the caller)
+            if (!interleaved)
+                hipLaunchKernelGGL((k_mct_inv_dcshift_planar<T, OP_EYCC>), grid, dim3(256), 0, s, src, sstride, tw,
+                                   th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
+            else
+                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 3, OP_EYCC>), grid, dim3(256), 0, s, src, sstride,
+                                   tw, th, dst, dstride, shift, mn, mx, mct, irrev, ops);
+            return;
+        }
+        if (ops.col == COL_CMYK) {  // four or more components (checked by the caller), one channel fewer
+            if (!interleaved)
+                hipLaunchKernelGGL((k_mct_inv_dcshift_planar<T, OP_CMYK>), grid, dim3(256), 0, s, src, sstride, tw,
+                                   th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
+            else if (ncomp == 4)
+                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 4, OP_CMYK>), grid, dim3(256), 0, s, src, sstride,
+                                   tw, th, dst, dstride, shift, mn, mx, mct, irrev, ops);
+            else if (ncomp == 5)
+                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 5, OP_CMYK>), grid, dim3(256), 0, s, src, sstride,
+                                   tw, th, dst, dstride, shift, mn, mx, mct, irrev, ops);
+            else
+                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels_any<T, OP_CMYK>), dim3((tw + 255) / 256, th), dim3(256),
+                                   0, s, src, sstride, tw, th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
+            return;
+        }
         if (ops.sycc) {  // three components (checked by the caller)
             if (!interleaved)
                 hipLaunchKernelGGL((k_mct_inv_dcshift_planar<T, OP_SYCC>), grid, dim3(256), 0, s, src, sstride, tw,
@@ -2169,9 +2416,11 @@ static void launch_inv_ops(const PlanePtrs &src, uint32_t sstride, uint32_t tw, 
                            sstride, tw, th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
 }
 
-// sYCC output is unsigned: its formats are U8 / U16 / I32
+// sYCC / eYCC / CMYK output is unsigned: its formats are U8 / U16 / I32
 static bool sycc_launchable(const OutOps &ops, uint32_t ncomp, int32_t fmt) {
-    return !ops.sycc || (ncomp == 3 && (fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16));
+    if (ops.col != COL_NONE && (ops.sycc || (ops.col != COL_EYCC && ops.col != COL_CMYK))) return false;
+    if (!ops.sycc && ops.col == COL_NONE) return true;
+    return (ops.col == COL_CMYK ? ncomp >= 4 : ncomp == 3) && (fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16);
 }
 
 hipError_t launch_mct_inv_dcshift_ops(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th,
@@ -2206,9 +2455,12 @@ static void launch_custom(const PlanePtrs &src, uint32_t sstride, uint32_t tw, u
 #define GRK_CUSTOM(KERNEL, NC, GRID) \
     hipLaunchKernelGGL((KERNEL<T, OP, NC>), GRID, dim3(256), 0, s, src, sstride, tw, th, dst, dstride, ncomp, m, off, \
                        mn, mx, ops...)
-    if constexpr (OP == OP_SYCC) {  // three components (checked by the caller)
+    if constexpr (op_ycc(OP)) {  // three components (checked by the caller)
         if (!interleaved) GRK_CUSTOM(k_mct_inv_custom_planar, 3, grid);
         else GRK_CUSTOM(k_mct_inv_custom_pixels, 3, grid);
+    } else if constexpr (OP == OP_CMYK) {  // four or more components: the any-count forms
+        if (!interleaved) GRK_CUSTOM(k_mct_inv_custom_planar, 0, grid);
+        else GRK_CUSTOM(k_mct_inv_custom_pixels, 0, dim3((tw + 255) / 256, th));
     } else if (!interleaved || ncomp == 1) {
         if (ncomp == 3) GRK_CUSTOM(k_mct_inv_custom_planar, 3, grid);
         else if (ncomp == 4) GRK_CUSTOM(k_mct_inv_custom_planar, 4, grid);
@@ -2235,6 +2487,12 @@ hipError_t launch_mct_inv_custom(const PlanePtrs &src, uint32_t sstride, uint32_
         if (!ops) launch_custom<T, 0>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, mn, mx, s); \
         else if (SY && ops->sycc) \
             launch_custom<T, SY ? OP_SYCC : OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, \
+                                                     mn, mx, s, *ops); \
+        else if (SY && ops->col == COL_EYCC) \
+            launch_custom<T, SY ? OP_EYCC : OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, \
+                                                     mn, mx, s, *ops); \
+        else if (SY && ops->col == COL_CMYK) \
+            launch_custom<T, SY ? OP_CMYK : OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, \
                                                      mn, mx, s, *ops); \
         else launch_custom<T, OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, mn, mx, s, *ops); \
     } while (0)
@@ -2276,7 +2534,7 @@ hipError_t launch_palette(const PlanePtrs &src, uint32_t sstride, uint32_t tw, u
                           const ShiftArr &mn, const ShiftArr &mx, int32_t mct, int32_t irrev, const PalMap &map,
                           const uint16_t *table, const OutOps *ops, hipStream_t s) {
     if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS || map.nch < 1 || map.nch > (uint32_t)GRK_MAX_COMPS ||
-        map.ne > 1024 || map.npc > (uint32_t)GRK_MAX_COMPS || (ops && ops->sycc))
+        map.ne > 1024 || map.npc > (uint32_t)GRK_MAX_COMPS || (ops && (ops->sycc || ops->col)))
         return hipErrorInvalidValue;
     for (uint32_t c = 0; c < map.nch; ++c) {  // every index the kernel forms stays inside the table and the planes
         if (map.comp[c] >= ncomp || !((map.used >> map.comp[c]) & 1)) return hipErrorInvalidValue;
@@ -2308,8 +2566,9 @@ static void launch_up_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32
                           hipStream_t s) {
     const UpComp *c = src.c;
     if constexpr (FAST) {
-        if (ncomp == 3 && c[0].dx == 1 && c[0].dy == 1 && c[1].dx == 2 && c[2].dx == 2 && c[1].dy == c[2].dy &&
-            (c[1].dy == 1 || c[1].dy == 2)) {
+        // (eYCC / CMYK need one grid, which this shape is not: k_upsample_any's)
+        if (!ops.col && ncomp == 3 && c[0].dx == 1 && c[0].dy == 1 && c[1].dx == 2 && c[2].dx == 2 &&
+            c[1].dy == c[2].dy && (c[1].dy == 1 || c[1].dy == 2)) {
             const uint32_t runs = (uint32_t)(((uint64_t)w + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
             const dim3 grid((runs + 255) / 256, h);
 #define GRK_420(IL, OP) \

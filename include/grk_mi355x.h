@@ -640,11 +640,66 @@ int grkgpu_decompress_to(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, const g
  * each plane on its own grid.  Samples nothing decoded (the zero margin of a
  * reduced decode at an odd origin, tiles a cut stream never reached) are
  * converted like any other, as the reference's colour step does with them:
- * with SYCC they come out as the conversion of (0, 0, 0). */
-enum { GRKGPU_COLOUR_NONE = 0, GRKGPU_COLOUR_SYCC = 1 };
+ * with SYCC they come out as the conversion of (0, 0, 0).
+ *
+ * The other per-sample colour steps of grk_decompress (grk_decompress.cpp:
+ * 1585-1749: colour -> precision -> upsample -> force-RGB; computed here as
+ * forcergb(precision(colour(upsample(decode)))), replication commuting with a
+ * per-sample map) sit in the same store.  Neither implies the upsample flag:
+ * components all subsampled alike stay on their grid without it.
+ *
+ * colour = GRKGPU_COLOUR_EYCC (color_esycc_to_rgb, bin/common/color.cpp:936-995):
+ * exactly 3 components on one grid, one precision P in 1 .. 16, component 0
+ * unsigned; anything else is GRKGPU_EINVAL.  With flip = 2^(P-1),
+ * max = 2^P - 1, y = U_0, cb = U_1 - (sgnd_1 ? 0 : flip),
+ * cr = U_2 - (sgnd_2 ? 0 : flip):
+ *   R = clamp(trunc(((y - 0.0000368 * cb) + 1.40199 * cr) + 0.5), 0, max)
+ *   G = clamp(trunc(((1.0003 * y - 0.344125 * cb) - 0.7141128 * cr) + 0.5), 0, max)
+ *   B = clamp(trunc(((0.999823 * y + 1.77204 * cb) - 0.000008 * cr) + 0.5), 0, max)
+ * in IEEE double, every product, sum and difference rounded on its own, left
+ * to right (no FMA), the conversion to int32 truncating.  Deviations from the
+ * reference: the three output channels are reported UNSIGNED and the
+ * precision step treats them so (the reference leaves sgnd = 1 on a signed
+ * chroma component that now holds [0, max], and its -p clip would cut G and B
+ * at 2^(p-1) - 1); a signed component 0, on which the reference's "assuming
+ * unsigned" loop computes regardless, is refused.
+ *
+ * colour = GRKGPU_COLOUR_CMYK (color_cmyk_to_rgb, color.cpp:881-933): n >= 4
+ * components on one grid, components 0 .. 3 unsigned with precisions q_k in
+ * 1 .. 16; anything else is GRKGPU_EINVAL (signed inks, from which the
+ * reference makes negative garbage, included).  With
+ * s_k = 1.0f / (float)(2^q_k - 1), one correctly rounded float32 division:
+ *   C = 1.0f - (float)U_0 * s_0      (likewise M, Y, K)
+ *   R = (int32)((255.0f * C) * K),  G = ... M ...,  B = ... Y ...
+ * in float32, every operation rounded on its own (no FMA), the conversions
+ * truncating.  The output has n - 1 CHANNELS: R, G, B unsigned of precision 8
+ * (every result lies in 0 .. 255), then components 4 .. as channels 3 .. with
+ * their own precision and sign.
+ *
+ * GRKGPU_COLOUR_FORCE_RGB, or'ed into colour (grk_decompress --force-rgb,
+ * convert_gray_to_rgb, grk_decompress.cpp:805-890), looks at the channels left
+ * by the steps above: 1 or 2 -> channel 0 three times (R = G = B, its
+ * precision and sign), a second channel following as channel 3 (k_palette_*'s
+ * store with a direct map); every component must be at (1,1) and the stream
+ * carry no custom MCT, else GRKGPU_EUNSUPPORTED.  3 or more: nothing when this
+ * call converted (SYCC / EYCC / CMYK), else GRKGPU_EINVAL ("don't know how to
+ * convert to RGB": a raw codestream has no colour space).
+ *
+ * With any of these, out->sample_fmt has to hold the precision and sign of
+ * the OUTPUT CHANNELS (R, G, B: 8 bits after CMYK), planar out->planes[] has
+ * one entry per output channel, an interleaved pixel that many samples, and
+ * img receives the output channels: count, precision, sign.  Samples nothing
+ * decoded are converted like any other: CMYK of zeros is (255, 255, 255) and
+ * zero extras, EYCC of zeros the formula at (0, 0, 0).  EYCC or CMYK behind a
+ * JP2 palette or channel swap is GRKGPU_EUNSUPPORTED.  Value 2 is
+ * GRKGPU_COLOUR_AUTO and 5 GRKGPU_COLOUR_AUTO_RGB, both for
+ * grkgpu_jp2_decompress only (GRKGPU_EINVAL elsewhere).  Not taken: ICC and
+ * CIELab (they need a colour management library), per-component -p lists. */
+enum { GRKGPU_COLOUR_NONE = 0, GRKGPU_COLOUR_SYCC = 1, GRKGPU_COLOUR_EYCC = 3, GRKGPU_COLOUR_CMYK = 4 };
+#define GRKGPU_COLOUR_FORCE_RGB 0x100u
 enum { GRKGPU_PREC_CLIP = 0, GRKGPU_PREC_SCALE = 1 };
 typedef struct {
-    uint32_t colour;     /* GRKGPU_COLOUR_* */
+    uint32_t colour;     /* GRKGPU_COLOUR_* [| GRKGPU_COLOUR_FORCE_RGB] */
     uint32_t prec;       /* 0: keep each component's precision; 1..16: output precision of every component */
     uint32_t prec_mode;  /* GRKGPU_PREC_*; read only when prec != 0 */
     uint32_t reserved;   /* 0 */
@@ -776,8 +831,17 @@ int grkgpu_jp2_read_palette(const uint8_t *file, size_t len, uint16_t *entries, 
  * space -- CMYK, eYCC, CIELab and ICC are reported in info and not converted.
  * SYCC together with a palette or a channel swap is GRKGPU_EUNSUPPORTED.  A
  * file without palette or swap takes grkgpu_decompress_convert's launches,
- * launch for launch.  info (may be NULL) as grkgpu_jp2_read_info. */
+ * launch for launch.  info (may be NULL) as grkgpu_jp2_read_info.
+ * ops->colour = GRKGPU_COLOUR_AUTO_RGB (valid only here): SYCC for EnumCS 18,
+ * EYCC for 24, CMYK for 12 (each with its shape rules), NONE for every other
+ * space.  EYCC or CMYK together with a palette or a channel swap is
+ * GRKGPU_EUNSUPPORTED.  GRKGPU_COLOUR_FORCE_RGB may be or'ed into any value:
+ * as above, on the file's channels (behind a palette too); 3 or more channels
+ * are also left alone when the file says sRGB (EnumCS 16); a file with an ICC
+ * profile and the flag is GRKGPU_EUNSUPPORTED (the reference would run its
+ * colour management library). */
 #define GRKGPU_COLOUR_AUTO 2u
+#define GRKGPU_COLOUR_AUTO_RGB 5u
 int grkgpu_jp2_decompress(grkgpu_ctx *ctx, const uint8_t *file, size_t len, const grkgpu_dparams *p,
                           uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
                           const grkgpu_out_planes *out, const grkgpu_out_ops *ops, grkgpu_jp2_info *info);
@@ -878,7 +942,11 @@ int grkgpu_upsample_to(const void *const *src, const uint32_t *src_stride, uint3
  * must hold the output precision and signedness.  ops as above (NULL: no
  * conversion -- the samples replicated and stored in dst's format).  Int32
  * sources with every component at (1,1) run the inverse-MCT kernels' stores,
- * every other shape the upsampling kernels'. */
+ * every other shape the upsampling kernels'.  EYCC and CMYK as there (CMYK:
+ * dst describes numcomps - 1 channels, dst_stride interleaved >= (x1 - x0) *
+ * (numcomps - 1)).  GRKGPU_COLOUR_FORCE_RGB on 1 or 2 components: int32
+ * sources at (1,1) with one row stride (dst: 3 or 4 channels), every other
+ * shape GRKGPU_EUNSUPPORTED; on 3 or more as there. */
 int grkgpu_convert_to(const void *const *src, const uint32_t *src_stride, uint32_t src_fmt, uint32_t numcomps,
                       const uint32_t *dx, const uint32_t *dy, const uint32_t *prec, const int32_t *sgnd,
                       uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
