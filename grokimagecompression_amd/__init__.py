@@ -207,6 +207,30 @@ class OutPlanes(ctypes.Structure):
                 ("on_device", ctypes.c_int32), ("pad_", ctypes.c_uint32)]
 
 
+class BatchItem(ctypes.Structure):
+    """grkgpu_batch_item: one codestream of grkgpu_decompress_batch / grkgpu_batch_plan."""
+    _fields_ = [("cs", ctypes.c_void_p), ("len", ctypes.c_size_t), ("out", OutPlanes), ("img", ImageDesc),
+                ("status", ctypes.c_int32), ("pad_", ctypes.c_uint32)]
+
+
+class BatchInfo(ctypes.Structure):
+    """grkgpu_batch_info: items decoded, code-blocks, job-table store records, kernel launches + fills."""
+    _fields_ = [("n_ok", ctypes.c_uint32), ("n_blocks", ctypes.c_uint32), ("n_store_jobs", ctypes.c_uint32),
+                ("n_launches", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class StoreJob(ctypes.Structure):
+    """grkgpu_store_job: one tile of grkgpu_mct_inv_dcshift_jobs_to."""
+    _fields_ = [("src", ctypes.c_void_p * 4), ("dst", ctypes.c_void_p * 4), ("src_stride", ctypes.c_uint32),
+                ("dst_stride", ctypes.c_uint32), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32),
+                ("numcomps", ctypes.c_uint32), ("mct", ctypes.c_int32), ("wavelet_mask", ctypes.c_uint32),
+                ("pad_", ctypes.c_uint32), ("shift", ctypes.c_int32 * 4), ("min", ctypes.c_int32 * 4),
+                ("max", ctypes.c_int32 * 4)]
+
+
 COLOUR_NONE, COLOUR_SYCC, COLOUR_EYCC, COLOUR_CMYK = 0, 1, 3, 4
 COLOUR_FORCE_RGB = 0x100  # flag or'ed into a colour value: gray (+ alpha) -> R = G = B (+ alpha)
 PREC_CLIP, PREC_SCALE = 0, 1
@@ -397,6 +421,10 @@ def lib():
                                                ctypes.c_int]
         L.grkgpu_decompress_ex.argtypes = [VP, VP, ctypes.c_size_t, P(DParams), P(ImageDesc), P(VP), ctypes.c_int]
         L.grkgpu_decompress_to.argtypes = [VP, VP, ctypes.c_size_t, P(DParams), U32, U32, P(ImageDesc), P(OutPlanes)]
+        if hasattr(L, "grkgpu_decompress_batch"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_decompress_batch.argtypes = [VP, P(BatchItem), U32, P(DParams), P(BatchInfo)]
+            L.grkgpu_batch_plan.argtypes = [P(BatchItem), U32, P(DParams), P(BatchInfo)]
+            L.grkgpu_mct_inv_dcshift_jobs_to.argtypes = [P(StoreJob), U32, U32, U32, VP]
         L.grkgpu_mct_inv_dcshift_to.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), I32, I32, P(OutPlanes), U32,
                                                 VP]
         if hasattr(L, "grkgpu_upsample_to"):  # not in an older library given by GRKGPU_LIB (A/B runs)
@@ -603,6 +631,35 @@ def read_header(buf):
     ptr, n, keep = _buf_ptr(buf)
     _check(lib().grkgpu_read_header(ptr, n, ctypes.byref(d)))
     return d
+
+
+def _batch_items(bufs):
+    """The grkgpu_batch_item array of a list of codestreams (+ what keeps their bytes alive)."""
+    items = (BatchItem * max(len(bufs), 1))()
+    keep = []
+    for i, buf in enumerate(bufs):
+        ptr, n, k = _buf_ptr(buf)
+        items[i].cs, items[i].len = ptr.value, n
+        keep.append(k)
+    return items, keep
+
+
+def plan_batch(bufs, reduce=0, layers=0):
+    """grkgpu_batch_plan: the host half of Codec.decompress_batch -- no device
+    call.  Returns a dict: "status" (one grkgpu code per stream, 0 = it would
+    decode), "img" (one ImageDesc per stream: the decoded geometry), "rc" (0, or
+    the first failing stream's code), "error" (its message, "item <i>: ...") and
+    the grkgpu_batch_info fields n_ok / n_blocks / n_store_jobs (n_launches = 0)."""
+    bufs = list(bufs)
+    items, keep = _batch_items(bufs)
+    info = BatchInfo()
+    dp = DParams(cp_reduce=reduce, cp_layer=layers)
+    rc = lib().grkgpu_batch_plan(items, len(bufs), ctypes.byref(dp), ctypes.byref(info))
+    res = info.as_dict()
+    res.update(rc=rc, error=lib().grkgpu_last_error().decode() if rc else "",
+               status=[items[i].status for i in range(len(bufs))],
+               img=[ImageDesc.from_buffer_copy(items[i].img) for i in range(len(bufs))])
+    return res
 
 
 def _read_mct(buf):
@@ -1146,6 +1203,110 @@ class Codec:
             _check(lib().grkgpu_decompress(self._ctx, bp, bn, None, ptrs, 1 if on_dev else 0))
         return out
 
+    def decompress_batch(self, bufs, dtype=None, layout="chw", device_out=False, out=None, reduce=0, layers=0,
+                         stack=False, errors="raise"):
+        """Decode a list of .j2k codestreams in one launch set
+        (grkgpu_decompress_batch) -> a list with one array / cuda tensor per
+        stream, each what decompress(buf, dtype=, layout=, device_out=, out=,
+        reduce=, layers=) returns, bit for bit.  dtype, layout and device_out
+        apply to every stream, or are lists with one entry per stream; out is
+        None or a list of outputs (entries may be None).  Streams with
+        subsampled components or a custom MCT are refused item by item, as is
+        anything decompress refuses; the other streams are still decoded and a
+        failing stream's `out` is left untouched.  errors="raise": raise
+        GrkGpuError naming the first failing item after the call;
+        errors="return": the GrkGpuError in that item's slot.  stack=True: the
+        streams must decode to one shape; the result is one (n, ...) array or
+        tensor whose slices are the items' destinations, so a host result
+        leaves the device in one copy.  self.batch_info holds the call's
+        grkgpu_batch_info afterwards."""
+        if errors not in ("raise", "return"):
+            raise GrkGpuError("errors must be 'raise' or 'return'")
+        bufs = list(bufs)
+        n = len(bufs)
+
+        def per_item(v, name):
+            if isinstance(v, (list, tuple)):
+                if len(v) != n:
+                    raise GrkGpuError("%s: one entry per stream (got %d for %d)" % (name, len(v), n))
+                return list(v)
+            return [v] * n
+        dtypes, layouts, devs = per_item(dtype, "dtype"), per_item(layout, "layout"), per_item(device_out, "device_out")
+        outs = per_item(None, "out") if out is None else per_item(list(out), "out")
+        if layers < 0 or reduce < 0:
+            raise GrkGpuError("reduce and layers must be >= 0")
+        if stack and out is not None:
+            raise GrkGpuError("stack=True allocates the output itself")
+        items, keep = _batch_items(bufs)
+        cd = lambda v, s: -(-v // s)  # noqa: E731
+        R = 1 << reduce
+        shapes, any_dev = [None] * n, False
+        for i, buf in enumerate(bufs):
+            # geometry from the main header alone (the library checks everything
+            # else); a stream whose header does not read gets no destination and
+            # fails inside the call with its own code
+            d = ImageDesc()
+            hdr_ok = lib().grkgpu_read_header(ctypes.c_void_p(items[i].cs), items[i].len, ctypes.byref(d)) == 0
+            dt, fmt = _out_format(dtypes[i])
+            o = outs[i]
+            if o is not None and _out_dtype(o) is not None:
+                if dtypes[i] is not None and _out_dtype(o) != dt:
+                    raise GrkGpuError("item %d: out holds %s samples, dtype asks for %s"
+                                      % (i, _out_dtype(o).name, dt.name))
+                dt, fmt = _out_format(_out_dtype(o))
+            _layout_shape((1, 1, 1), layouts[i])
+            items[i].out.sample_fmt, items[i].out.layout = fmt, _LAYOUTS[layouts[i]]
+            if not hdr_ok:
+                continue
+            c = d.numcomps
+            if any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)):
+                continue  # refused by the call
+            shp = (c, cd(d.y1 - d.y0, R), cd(d.x1 - d.x0, R))
+            shapes[i] = (_layout_shape(shp, layouts[i]), dt)
+            if stack:
+                continue
+            if o is not None:
+                on_dev = _check_out(o, shp, self.device, dt, layouts[i])
+            else:
+                on_dev = bool(devs[i])
+                if on_dev:
+                    o = _torch().empty(shapes[i][0], dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
+                else:
+                    o = np.empty(shapes[i][0], dtype=dt)
+                outs[i] = o
+            any_dev = any_dev or on_dev
+            items[i].out = self._out_planes(o, c, fmt, layouts[i], on_dev)
+        stacked = None
+        if stack and n:
+            if any(sh is None for sh in shapes) or any(sh != shapes[0] for sh in shapes) or len(set(devs)) != 1:
+                raise GrkGpuError("stack=True needs streams of one shape, dtype, layout and destination")
+            shp, dt = shapes[0]
+            any_dev = bool(devs[0])
+            if any_dev:
+                stacked = _torch().empty((n,) + tuple(shp), dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
+            else:
+                stacked = np.empty((n,) + tuple(shp), dtype=dt)
+            c = shp[0] if layouts[0] == "chw" else shp[2]
+            for i in range(n):
+                outs[i] = stacked[i]
+                items[i].out = self._out_planes(stacked[i], c, _out_format(dt)[1], layouts[i], any_dev)
+        if any_dev:
+            lib().grkgpu_set_stream(self._ctx, _stream_handle(self.device))
+        info = BatchInfo()
+        dp = DParams(cp_reduce=reduce, cp_layer=layers)
+        rc = lib().grkgpu_decompress_batch(self._ctx, items, n, ctypes.byref(dp), ctypes.byref(info))
+        self.batch_info = info.as_dict()
+        msg = lib().grkgpu_last_error().decode() if rc else ""
+        failed = [i for i in range(n) if items[i].status]
+        if rc and (errors == "raise" or not failed):
+            raise GrkGpuError("grkgpu error %d: %s" % (rc, msg))
+        if stacked is not None:
+            return stacked
+        for i in failed:
+            outs[i] = GrkGpuError("grkgpu error %d: item %d failed%s" % (items[i].status, i,
+                                                                         msg[msg.index(":"):] if failed[0] == i else ""))
+        return outs
+
     def decompress_jp2(self, buf, dtype=None, layout="chw", colour="auto", out_prec=None, prec_mode="clip",
                        window=None, reduce=0, layers=0, device_out=False, force_rgb=False):
         """Decode a .jp2 file (grkgpu_jp2_decompress) -> (array, info): the
@@ -1550,6 +1711,47 @@ def mct_inv_dcshift_to(src, dst, w, prec, sgnd, mct, irreversible, layout="chw",
     _check(lib().grkgpu_mct_inv_dcshift_to(ptrs, c, w, h, sstride, pr, sg, mct, 1 if irreversible else 0,
                                            ctypes.byref(op), stride, _stream_handle(src.device)))
     return dst
+
+
+def mct_inv_dcshift_jobs_to(jobs, layout="chw"):
+    """grkgpu_mct_inv_dcshift_jobs_to: mct_inv_dcshift_to for a list of tiles
+    in one launch.  jobs: dicts with mct_inv_dcshift_to's arguments -- src, dst,
+    w, prec, sgnd, mct, irreversible and (optionally) dst_stride -- of 1 .. 4
+    components each, every dst of one dtype and on one device.  wavelet_mask
+    (optional; bit k: component k holds 9/7 samples) stands in for
+    irreversible where the components differ.  Returns the dsts."""
+    _layout_shape((1, 1, 1), layout)
+    il = layout == "hwc"
+    if not jobs:
+        return []
+    dt, fmt = _out_format(_out_dtype(jobs[0]["dst"]))
+    arr = (StoreJob * len(jobs))()
+    for i, q in enumerate(jobs):
+        src, dst, w = q["src"], q["dst"], int(q["w"])
+        c, h, sstride = src.shape
+        row = w * c if il else w
+        stride = row if q.get("dst_stride") is None else int(q["dst_stride"])
+        need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
+        if (src.dtype != _torch_dtype(np.int32) or not src.is_contiguous() or not src.is_cuda or dst.dim() != 1
+                or not dst.is_contiguous() or dst.device != src.device or w > sstride or stride < row
+                or dst.numel() < need or _out_dtype(dst) != dt or c > 4):
+            raise GrkGpuError("mct_inv_dcshift_jobs_to: job %d: src (c <= 4,h,stride >= w) int32, dst flat %s, %d "
+                              "samples, on src's device" % (i, dt.name, need))
+        j = arr[i]
+        prec, sgnd = _per_comp(q["prec"], c), _per_comp(q["sgnd"], c)
+        for k in range(c):
+            j.src[k] = src[k].data_ptr()
+            j.shift[k] = 0 if sgnd[k] else 1 << (prec[k] - 1)
+            j.min[k] = -(1 << (prec[k] - 1)) if sgnd[k] else 0
+            j.max[k] = (1 << (prec[k] - 1)) - 1 if sgnd[k] else (1 << prec[k]) - 1
+        for k in range(1 if il else c):
+            j.dst[k] = dst.data_ptr() + k * h * stride * dt.itemsize
+        j.src_stride, j.dst_stride, j.w, j.h, j.numcomps = sstride, stride, w, h, c
+        j.mct = int(q["mct"])
+        j.wavelet_mask = int(q["wavelet_mask"]) if "wavelet_mask" in q else ((1 << c) - 1 if q["irreversible"] else 0)
+    _check(lib().grkgpu_mct_inv_dcshift_jobs_to(arr, len(jobs), fmt, _LAYOUTS[layout],
+                                                _stream_handle(jobs[0]["src"].device)))
+    return [q["dst"] for q in jobs]
 
 
 def mct_inv_custom_to(src, dst, w, matrix, offsets, prec, sgnd, layout="chw", dst_stride=None):

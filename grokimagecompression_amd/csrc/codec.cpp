@@ -101,6 +101,7 @@ struct CtxDevBufs {
     // (in), its summary and records (out)
     DevBuf pinfo, precs;
     DevBuf pal;  // JP2 decode: the palette table, uploaded again by every call that looks up
+    DevBuf storejobs;  // batch decode: the StoreJob table and its first-workgroup arrays, uploaded by every batch
 };
 struct CtxHostBufs {
     HostBuf h_results, h_packed, h_gather, h_blocks, h_out, h_symoff, h_dwtjobs, h_segs;
@@ -108,6 +109,8 @@ struct CtxHostBufs {
     HostBuf h_dwtjobs53;
     // grkgpu_encode_blocks output (valid until the next call on the context)
     HostBuf h_slab;
+    // batch decode: the items' codestreams packed for one H2D, and the store-job table's staging
+    HostBuf h_cs, h_storejobs;
 };
 
 struct grkgpu_ctx : CtxDevBufs, CtxHostBufs {
@@ -237,15 +240,16 @@ int grkgpu_set_stream(grkgpu_ctx *c, void *stream) {
 // Every buffer of CtxDevBufs / CtxHostBufs, for grkgpu_debug_fill.
 namespace {
 struct CtxBuffers {
-    DevBuf *dev[21];
-    HostBuf *host[13];
+    DevBuf *dev[22];
+    HostBuf *host[15];
 };
 CtxBuffers ctx_buffers(grkgpu_ctx *c) {
     CtxBuffers b{{&c->img, &c->work, &c->coef, &c->ll, &c->scratch, &c->mqout, &c->blocks, &c->results, &c->gather,
                   &c->packed, &c->cs, &c->sym, &c->symoff, &c->dwtjobs, &c->ubuf, &c->segs, &c->dwtjobs53, &c->t1order,
-                  &c->pinfo, &c->precs, &c->pal},
+                  &c->pinfo, &c->precs, &c->pal, &c->storejobs},
                  {&c->h_results, &c->h_packed, &c->h_gather, &c->h_blocks, &c->h_out, &c->h_symoff, &c->h_dwtjobs,
-                  &c->h_segs, &c->h_pinfo, &c->h_psum, &c->h_precs, &c->h_dwtjobs53, &c->h_slab}};
+                  &c->h_segs, &c->h_pinfo, &c->h_psum, &c->h_precs, &c->h_dwtjobs53, &c->h_slab, &c->h_cs,
+                  &c->h_storejobs}};
     static_assert(sizeof(CtxDevBufs) == sizeof(b.dev) / sizeof(b.dev[0]) * sizeof(DevBuf),
                   "a DevBuf was added to CtxDevBufs: list it in ctx_buffers()");
     static_assert(sizeof(CtxHostBufs) == sizeof(b.host) / sizeof(b.host[0]) * sizeof(HostBuf),
@@ -2636,19 +2640,85 @@ static int32_t holding_fmt(uint32_t nc, const uint32_t *prec, const int32_t *sgn
 // tile (tile-component x0 = ceil(tx0 / dx): `staged` below), and one launch
 // per tile (launch_upsample_to) writes the output: the other components
 // straight from the tile buffer, the staged ones replicated from their planes.
-static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu_image_desc *img,
-                           const DecodeOut &od, uint32_t tb, uint32_t te,
-                           uint32_t reduce = 0, const Rect *win = nullptr, uint32_t max_layers = 0,
-                           bool host_only = false, std::vector<uint8_t> *decoded_out = nullptr) {
-    void *const *const planes = od.planes;
-    const int planes_on_device = od.on_device;
-    if ((!c && !host_only) || !csb || (!planes && !host_only)) return set_err(GRKGPU_EINVAL, "null argument");
-    if (od.fmt < SMP_I32 || od.fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
-    const uint32_t sb = sample_bytes(od.fmt);  // bytes per output sample
-    const bool il = od.interleaved != 0;
-    ActiveCall active;
-    double t_start = now_ms();
+//
+// The host half of a decode is DecHost: begin() (main header, geometry, the
+// refusals, the tile-part walk), parse_tiles() (packet headers, tile by tile,
+// safe to run for different tiles on different threads) and finish() (arenas
+// and the DecBlock / DecSeg tables, offsets counted from the stream's own
+// zero).  decompress_impl runs them for its one stream; the batch decode runs
+// them for every item and rebases the tables into the merged ones.
+struct DecHost {
+    // in
+    const uint8_t *csb = nullptr;
+    size_t len = 0;
+    grkgpu_image_desc *img = nullptr;
+    DecodeOut od{};
+    uint32_t tb = 0, te = 0xffffffffu, reduce = 0, max_layers = 0;
+    const Rect *win = nullptr;
+    bool host_only = false;
+    bool batch = false;  // an item of a batch decode: a stream with a subsampled component is refused
+    // begin()
+    void *const *planes = nullptr;
+    int planes_on_device = 0;
+    uint32_t sb = 4;
+    bool il = false;
     CodingParams cp;
+    Rect wr{};
+    uint32_t ix0 = 0, iy0 = 0, ix1 = 0, iy1 = 0, ox1 = 0, oy1 = 0, nc = 0, ntiles = 0, iw = 0;
+    bool whole = true, subs = false, mixed = false, conv = false, sycc = false, colconv = false;
+    uint32_t colour = 0;
+    OutOps dops{};
+    uint32_t oprec[GRKGPU_MAX_COMPS];
+    int32_t osgnd[GRKGPU_MAX_COMPS];
+    const ChanMap *cm = nullptr;
+    ChanMap fcm{};  // (cm may point here: a DecHost is never copied after begin())
+    uint32_t no = 0;
+    bool up = false;
+    int32_t sfmt = SMP_I32;
+    uint32_t ssb = 4;
+    Rect orect[GRKGPU_MAX_COMPS];
+    uint64_t ooff[GRKGPU_MAX_COMPS + 1];
+    bool opad = false;
+    Rect cwin[GRKGPU_MAX_COMPS];
+    std::vector<uint8_t> wskip;
+    TileWalk walk;
+    bool missing = false;
+    std::vector<uint8_t> ppm_buf;
+    std::vector<std::pair<size_t, size_t>> ppm_chunk;  // (offset in ppm_buf, Nppm)
+    uint32_t nsh = 0;
+    std::vector<Tile> tiles;
+    std::vector<std::vector<uint8_t>> tbufs;    // tiles of several tile-parts: their data concatenated
+    std::vector<std::vector<uint8_t>> tpacked;  // packed packet headers (PPM / PPT) of each tile
+    std::vector<uint8_t> tpacked_on;
+    std::vector<size_t> ppm_from;  // PPM: where each tile's packet headers start in ppm_buf
+    std::vector<uint8_t> contig;
+    std::vector<int> terr;
+    std::vector<std::array<uint8_t, 16>> troi;  // per tile: ROI shift of each component
+    std::vector<std::array<uint8_t, 16>> tsty;  // per tile: code-block style of each component
+    std::vector<int32_t> tmct;                  // per tile: MCT (a tile COD may change it)
+    // finish()
+    uint64_t arena = 0, llarena = 0;
+    std::vector<uint64_t> lloff;
+    std::vector<DecBlock> db;
+    std::vector<DecSeg> dsegs;        // codeword segments of all blocks
+    std::vector<uint8_t> droi;        // per-block ROI shift (empty: no ROI)
+    std::vector<uint8_t> dsty;        // per-block code-block style (COD / COC of its tile-component)
+    std::vector<uint32_t> seg_first;  // per block: first segment
+    std::vector<uint8_t> extra;       // concatenated multi-chunk segments
+    bool too_deep = false;
+
+    int begin();
+    void parse_tiles(size_t l0, size_t l1);
+    int finish();
+};
+
+int DecHost::begin() {
+    planes = od.planes;
+    planes_on_device = od.on_device;
+    if (!csb || (!planes && !host_only)) return set_err(GRKGPU_EINVAL, "null argument");
+    if (od.fmt < SMP_I32 || od.fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    sb = sample_bytes(od.fmt);  // bytes per output sample
+    il = od.interleaved != 0;
     size_t pos = 0;
     std::string err;
     bool hdr_corrupt = false;
@@ -2657,7 +2727,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     if (img) image_desc_of(cp, img);
     if (reduce >= cp.numres)  // j2k.cpp:6994
         return set_err(GRKGPU_EINVAL, "reduce must be smaller than the number of resolutions");
-    Rect wr{};  // window, clipped to the image
+    // the window, clipped to the image
     if (win) {
         wr = intersect(*win, cp.image);
         if (wr.empty()) return set_err(GRKGPU_EINVAL, "decode window outside the image");
@@ -2665,50 +2735,49 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     // output image geometry: the image or the window (reference grid), at the
     // decoded resolution ceil(x / 2^reduce) (j2k_set_decode_area, j2k.cpp:1464-1476)
     const Rect full = win ? wr : cp.image;
-    const uint32_t ix0 = ceil_pow2(full.x0, reduce), iy0 = ceil_pow2(full.y0, reduce);
-    const uint32_t ix1 = ceil_pow2(full.x1, reduce), iy1 = ceil_pow2(full.y1, reduce);
+    ix0 = ceil_pow2(full.x0, reduce), iy0 = ceil_pow2(full.y0, reduce);
+    ix1 = ceil_pow2(full.x1, reduce), iy1 = ceil_pow2(full.y1, reduce);
     if (win && (ix1 <= ix0 || iy1 <= iy0)) return set_err(GRKGPU_EINVAL, "decode window empty at this resolution");
     // Without a window the planes take grk_image_comp_header_update's sizes,
     // ceil(size / 2^reduce) (image.cpp:124-155), while the tiles land from
     // ceil(x0 / 2^reduce) (TileProcessor.cpp:1729-1734): with an odd origin
     // that is one row / column more than the decoded samples, left zero.
     // A window takes update_image_dimensions' (image.cpp:207-246) exact extent.
-    const uint32_t ox1 = win ? ix1 : ix0 + ceil_pow2(full.w(), reduce);
-    const uint32_t oy1 = win ? iy1 : iy0 + ceil_pow2(full.h(), reduce);
+    ox1 = win ? ix1 : ix0 + ceil_pow2(full.w(), reduce);
+    oy1 = win ? iy1 : iy0 + ceil_pow2(full.h(), reduce);
     if (img && (reduce || win)) {
         img->x0 = ix0; img->y0 = iy0;
         img->x1 = ox1; img->y1 = oy1;
     }
-    const uint32_t nc = cp.numcomps, ntiles = cp.tw * cp.th;
-    const uint32_t iw = ox1 - ix0;
+    nc = cp.numcomps, ntiles = cp.tw * cp.th;
+    iw = ox1 - ix0;
     if (te > ntiles) te = ntiles;
     if (tb > te) return set_err(GRKGPU_EINVAL, "bad tile range");
-    const bool whole = tb == 0 && te == ntiles;
+    whole = tb == 0 && te == ntiles;
     if (reduce && !whole) return set_err(GRKGPU_EINVAL, "reduced decode of a tile range is not supported");
     // subsampled components: component k's output plane is the output
     // rectangle on its grid (ceil(x / dx), the nested ceilings of a reduced
     // decode commute), rows of its own width
-    bool subs = false, mixed = false;  // mixed: components on different grids
+    subs = false, mixed = false;  // mixed: components on different grids
     for (uint32_t k = 0; k < nc; ++k) {
         subs = subs || cp.dx[k] != 1 || cp.dy[k] != 1;
         mixed = mixed || cp.dx[k] != cp.dx[0] || cp.dy[k] != cp.dy[0];
     }
     if (subs && !whole) return set_err(GRKGPU_EUNSUPPORTED, "tile-range decode of subsampled images is not supported");
+    if (subs && batch) return set_err(GRKGPU_EUNSUPPORTED, "subsampled components are not supported in a batch");
     if (win && !whole) return set_err(GRKGPU_EINVAL, "window decode of a tile range is not supported");
     // od.ops (grkgpu_decompress_convert): the colour and precision steps of
     // grk_decompress in the store of the last kernel -- dops their device
     // form, oprec the precision the samples leave with.  sYCC needs every
     // component of the pixel, so it implies the upsampled output.
-    const bool conv = out_ops_active(od.ops);
-    const uint32_t colour = conv ? colour_of(od.ops) : GRKGPU_COLOUR_NONE;
-    const bool sycc = colour == GRKGPU_COLOUR_SYCC;
+    conv = out_ops_active(od.ops);
+    colour = conv ? colour_of(od.ops) : GRKGPU_COLOUR_NONE;
+    sycc = colour == GRKGPU_COLOUR_SYCC;
     // eYCC / CMYK -> RGB sit where sYCC sits, on components of one grid (they
     // do not imply the upsampled output); CMYK leaves nc - 1 channels
-    const bool colconv = colour != GRKGPU_COLOUR_NONE;
+    colconv = colour != GRKGPU_COLOUR_NONE;
     const bool force_rgb = conv && (od.ops->colour & GRKGPU_COLOUR_FORCE_RGB);
-    OutOps dops{};
-    uint32_t oprec[GRKGPU_MAX_COMPS];
-    int32_t osgnd[GRKGPU_MAX_COMPS];
+    dops = OutOps{};
     for (uint32_t k = 0; k < nc; ++k) { oprec[k] = cp.prec[k]; osgnd[k] = cp.sgnd[k]; }
     // the shape rules, on the codestream's components: ahead of what force-RGB
     // makes of the channel count, and of the refusal behind a channel map
@@ -2719,12 +2788,12 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     }
     // od.chan (grkgpu_jp2_decompress): `no` output channels instead of the nc
     // components -- what the planes, the format and the ops describe from here on
-    const ChanMap *cm = od.chan;
+    cm = od.chan;
     // GRKGPU_COLOUR_FORCE_RGB (convert_gray_to_rgb, grk_decompress.cpp:805-890)
     // on the one or two channels the steps before it leave: channel 0 three
     // times and the second one behind it -- a channel map without a table,
     // stored by the palette kernels
-    ChanMap fcm{};
+    fcm = ChanMap{};
     {
         const uint32_t nbefore = cm ? cm->nch : (colour == GRKGPU_COLOUR_CMYK ? nc - 1 : nc);
         if (force_rgb && nbefore >= 1 && nbefore <= 2) {
@@ -2744,7 +2813,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
             return set_err(GRKGPU_EINVAL, "force-RGB: don't know how to convert these channels to RGB");
         }
     }
-    uint32_t no = cm ? cm->nch : nc;
+    no = cm ? cm->nch : nc;
     if (cm) {
         if (subs) return set_err(GRKGPU_EUNSUPPORTED, "JP2 palette / channel order over subsampled components");
         if (sycc) return set_err(GRKGPU_EUNSUPPORTED, "sYCC conversion behind a JP2 palette or channel swap");
@@ -2775,7 +2844,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         int rc = resolve_out_ops(od.ops, nc, cp.prec, cp.sgnd, cp.dx, cp.dy, dops, no, oprec, osgnd);
         if (rc) return rc;
     }
-    const bool up = (od.upsample || sycc) && subs;
+    up = (od.upsample || sycc) && subs;
     if (up && reduce)  // grk_decompress refuses -u with -r
         return set_err(GRKGPU_EINVAL, "upsampled output of a reduced decode is not supported");
     if (img && up)
@@ -2801,18 +2870,16 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     // the staging planes of an upsampled decode keep the stream's precision:
     // the ops run in the replicating launch, which reads one sample type and
     // writes another (12 bits staged, 8 stored)
-    const int32_t sfmt = conv ? holding_fmt(nc, cp.prec, cp.sgnd) : od.fmt;
-    const uint32_t ssb = sample_bytes(sfmt);
+    sfmt = conv ? holding_fmt(nc, cp.prec, cp.sgnd) : od.fmt;
+    ssb = sample_bytes(sfmt);
     if (il && mixed && !up)
         return set_err(GRKGPU_EUNSUPPORTED, "interleaved output needs every component on one grid");
     if (il && (uint64_t)iw * no > 0xffffffffull)  // the kernel's row stride is 32 bits of samples
         return set_err(GRKGPU_EUNSUPPORTED, "image too wide for interleaved output");
     for (uint32_t k = 0; !host_only && k < (il ? 1u : no); ++k)
         if (!planes[k] || (uintptr_t)planes[k] % sb) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
-    Rect orect[GRKGPU_MAX_COMPS];
-    uint64_t ooff[GRKGPU_MAX_COMPS + 1];
     ooff[0] = 0;
-    bool opad = false;  // planes extending past the decoded samples (zero filled)
+    opad = false;  // planes extending past the decoded samples (zero filled)
     for (uint32_t k = 0; k < std::max(nc, no); ++k) {  // (a channel map: every component at (1,1))
         const uint32_t kdx = k < nc ? cp.dx[k] : 1, kdy = k < nc ? cp.dy[k] : 1;
         orect[k] = comp_rect({ix0, iy0, ix1, iy1}, kdx, kdy);
@@ -2826,7 +2893,6 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         ooff[k + 1] = ooff[k] + (uint64_t)orect[k].w() * orect[k].h();
     }
     // the window on each component's grid at the decoded resolution
-    Rect cwin[GRKGPU_MAX_COMPS];
     for (uint32_t k = 0; k < nc; ++k) cwin[k] = comp_rect({ix0, iy0, ix1, iy1}, cp.dx[k], cp.dy[k]);
 
     // tile-parts: the reference's walk (walk_tile_parts) -- which tiles are
@@ -2834,22 +2900,16 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     // coding-parameter markers of the tile-part headers (COD / COC / QCD / QCC
     // / RGN / POC / PPT, j2k.cpp:3829-4990) are applied to the tile's own copy
     // of the parameters below
-    std::vector<uint8_t> wskip(ntiles, 0);
+    wskip.assign(ntiles, 0);
     if (win)
         for (uint32_t t = 0; t < ntiles; ++t)
             wskip[t] = !overlap(comp_rect(tile_rect(cp, t), 1u << reduce, 1u << reduce), {ix0, iy0, ix1, iy1});
-    TileWalk walk;
     if (!walk_tile_parts(csb, len, pos, ntiles, wskip, walk, err)) return set_err(GRKGPU_ECORRUPT, err);
-    const auto &tparts = walk.parts;
-    const auto &tmarks = walk.marks;
-    const auto &tpseq = walk.seq;
-    bool missing = false;  // tiles the walk did not decode: zero in the output
+    missing = false;  // tiles the walk did not decode: zero in the output
     for (uint32_t t = tb; t < te; ++t) missing = missing || (!walk.decoded[t] && !wskip[t]);
     // PPM (j2k_merge_ppm, j2k.cpp:4766-4900): the main header's packed packet
     // headers, Zppm order, as Nppm / Ippm pairs -- the i-th pair holds the
     // headers of the codestream's i-th tile-part
-    std::vector<uint8_t> ppm_buf;
-    std::vector<std::pair<size_t, size_t>> ppm_chunk;  // (offset in ppm_buf, Nppm)
     if (!cp.ppm.empty()) {
         std::vector<uint8_t> raw;
         for (auto &q : cp.ppm) raw.insert(raw.end(), csb + q.off, csb + q.off + q.len);
@@ -2866,35 +2926,34 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     }
 
     // host Tier-2 over every tile of the shard; code-block segments -> DecBlock table
-    const uint32_t nsh = te - tb;
-    std::vector<Tile> tiles(nsh);
-    uint64_t arena = 0, llarena = 0;
-    std::vector<uint64_t> lloff(nsh * nc);
-    std::vector<DecBlock> db;
-    std::vector<DecSeg> dsegs;        // codeword segments of all blocks
-    std::vector<uint8_t> droi;        // per-block ROI shift (empty: no ROI)
-    std::vector<uint8_t> dsty;        // per-block code-block style (COD / COC of its tile-component)
-    std::vector<uint32_t> seg_first;  // per block: first segment (+ the total at the end)
-    std::vector<uint8_t> extra;  // concatenated multi-chunk segments
-    bool too_deep = false;
-    // Packet headers of the tiles, parsed in parallel on the host pool (each
-    // tile's geometry, tag trees and code-block segments are its own); then
-    // the arenas and the DecBlock table in tile order.
-    std::vector<std::vector<uint8_t>> tbufs(nsh);  // tiles of several tile-parts: their data concatenated
-    std::vector<std::vector<uint8_t>> tpacked(nsh);  // packed packet headers (PPM / PPT) of each tile
-    std::vector<uint8_t> tpacked_on(nsh, 0);
-    std::vector<size_t> ppm_from(nsh, 0);  // PPM: where each tile's packet headers start in ppm_buf
-    std::vector<uint8_t> contig(nsh, 1);
+    nsh = te - tb;
+    tiles.assign(nsh, Tile());
+    tbufs.assign(nsh, {});
+    tpacked.assign(nsh, {});
+    tpacked_on.assign(nsh, 0);
+    ppm_from.assign(nsh, 0);
+    contig.assign(nsh, 1);
     // 1: bad POC marker, 2: corrupt packet header, 3: bad tile-part COD / COC
     // / QCD / QCC / RGN / PPT, 4: tile-component parameters this decoder does
     // not take (code-block style, wavelet or MCT other than the main header's,
     // reduce >= its resolutions), 6: a custom MCT the tile-part headers touch
     // (MCT / MCC / MCO there, a tile COD with another MCT, a 5/3 component)
-    std::vector<int> terr(nsh, 0);
-    std::vector<std::array<uint8_t, 16>> troi(nsh);  // per tile: ROI shift of each component
-    std::vector<std::array<uint8_t, 16>> tsty(nsh);  // per tile: code-block style of each component
-    std::vector<int32_t> tmct(nsh, cp.mct);            // per tile: MCT (a tile COD may change it)
-    host_parallel_for(nsh, 1, [&](size_t l0, size_t l1) {
+    terr.assign(nsh, 0);
+    troi.assign(nsh, {});
+    tsty.assign(nsh, {});
+    tmct.assign(nsh, cp.mct);
+    return GRKGPU_OK;
+}
+
+// Packet headers of tiles [l0, l1) of the shard (each tile's geometry, tag
+// trees and code-block segments are its own, so tiles parse in parallel on
+// the host pool); finish() then lays out the arenas and the DecBlock table in
+// tile order.
+void DecHost::parse_tiles(size_t l0, size_t l1) {
+    const auto &tparts = walk.parts;
+    const auto &tmarks = walk.marks;
+    const auto &tpseq = walk.seq;
+    {
         for (size_t lt = l0; lt < l1; ++lt) {
             const uint32_t t = tb + (uint32_t)lt;
             Tile &tile = tiles[lt];
@@ -3028,7 +3087,13 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                 off += (size_t)used;
             }
         }
-    });
+    }
+}
+
+// The tiles' errors in tile order, then the arenas and the block table.
+int DecHost::finish() {
+    arena = llarena = 0;
+    lloff.assign((size_t)nsh * nc, 0);
     for (uint32_t lt = 0; lt < nsh; ++lt) {
         if (terr[lt] == 1) return set_err(GRKGPU_ECORRUPT, "Error reading POC marker");
         if (terr[lt] == 2) return set_err(GRKGPU_ECORRUPT, "corrupt packet header");
@@ -3113,15 +3178,20 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         }
     }
     if (too_deep) return set_err(GRKGPU_ECORRUPT, "unsupported bpno_plus_one >= 31 (code-block bit-planes + ROI shift)");
-    if (decoded_out) *decoded_out = walk.decoded;
-    if (host_only) return GRKGPU_OK;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
+    return GRKGPU_OK;
+}
+
+// The Tier-1 launch plan over a block table (seg_first with its total at the
+// end): blocks grouped by code-block style -- a launch range each, returned in
+// sranges -- and, by t1_dec_sort, in decreasing order of expected work; the
+// T1Scratch records the ranges need are returned.
+struct StyRange { uint32_t b0, n, sty; uint64_t scr0; };
+static uint64_t order_dec_tables(std::vector<DecBlock> &db, std::vector<DecSeg> &dsegs, std::vector<uint32_t> &seg_first,
+                                 std::vector<uint8_t> &droi, std::vector<uint8_t> &dsty, bool lone,
+                                 std::vector<StyRange> &sranges) {
     const uint32_t nblk = (uint32_t)db.size();
-    seg_first.push_back((uint32_t)dsegs.size());
     bool mixed_sty = false;  // tile-components of different code-block styles: one decode launch per style
     for (uint32_t i = 1; i < nblk; ++i) mixed_sty = mixed_sty || dsty[i] != dsty[0];
-    const bool lone = lone_call();
     const bool sort_work = (dwt_options().t1_dec_sort == 1 || (dwt_options().t1_dec_sort < 0 && lone)) && nblk > 64;
     if (sort_work || mixed_sty) {
         // blocks grouped by style (a launch each), and -- t1_dec_sort -- since
@@ -3168,8 +3238,6 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     }
     // launch ranges: one per code-block style, each with its own scratch
     // groups (64 blocks each) so the ranges need no alignment
-    struct StyRange { uint32_t b0, n, sty; uint64_t scr0; };
-    std::vector<StyRange> sranges;
     uint64_t scr_records = 0;
     for (uint32_t i = 0; i < nblk;) {
         uint32_t j = i;
@@ -3178,6 +3246,58 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         scr_records += t1_scratch_records(j - i);
         i = j;
     }
+    return scr_records;
+}
+
+static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu_image_desc *img,
+                           const DecodeOut &od, uint32_t tb, uint32_t te,
+                           uint32_t reduce = 0, const Rect *win = nullptr, uint32_t max_layers = 0,
+                           bool host_only = false, std::vector<uint8_t> *decoded_out = nullptr) {
+    if ((!c && !host_only) || !csb || (!od.planes && !host_only)) return set_err(GRKGPU_EINVAL, "null argument");
+    if (od.fmt < SMP_I32 || od.fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    ActiveCall active;
+    double t_start = now_ms();
+    DecHost H;
+    H.csb = csb; H.len = len; H.img = img; H.od = od;
+    H.tb = tb; H.te = te; H.reduce = reduce; H.win = win; H.max_layers = max_layers; H.host_only = host_only;
+    int hrc = H.begin();
+    if (hrc) return hrc;
+    host_parallel_for(H.nsh, 1, [&](size_t l0, size_t l1) { H.parse_tiles(l0, l1); });
+    hrc = H.finish();
+    if (hrc) return hrc;
+    if (decoded_out) *decoded_out = H.walk.decoded;
+    if (host_only) return GRKGPU_OK;
+    // the host half's results, under the names the device half below uses
+    void *const *const planes = H.planes;
+    const int planes_on_device = H.planes_on_device;
+    const uint32_t sb = H.sb, ssb = H.ssb, nc = H.nc, no = H.no, iw = H.iw;
+    const uint32_t ix0 = H.ix0, iy0 = H.iy0, ix1 = H.ix1, iy1 = H.iy1, oy1 = H.oy1;
+    const bool il = H.il, whole = H.whole, mixed = H.mixed, conv = H.conv, colconv = H.colconv, up = H.up;
+    const bool opad = H.opad, missing = H.missing;
+    const int32_t sfmt = H.sfmt;
+    const CodingParams &cp = H.cp;
+    const OutOps &dops = H.dops;
+    const ChanMap *const cm = H.cm;
+    const Rect *const orect = H.orect, *const cwin = H.cwin;
+    const uint64_t *const ooff = H.ooff;
+    const std::vector<uint8_t> &wskip = H.wskip;
+    const TileWalk &walk = H.walk;
+    std::vector<Tile> &tiles = H.tiles;
+    const std::vector<int32_t> &tmct = H.tmct;
+    const uint64_t arena = H.arena, llarena = H.llarena;
+    const std::vector<uint64_t> &lloff = H.lloff;
+    std::vector<DecBlock> &db = H.db;
+    std::vector<DecSeg> &dsegs = H.dsegs;
+    std::vector<uint8_t> &droi = H.droi, &dsty = H.dsty, &extra = H.extra;
+    std::vector<uint32_t> &seg_first = H.seg_first;
+    tb = H.tb; te = H.te;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const uint32_t nblk = (uint32_t)db.size();
+    seg_first.push_back((uint32_t)dsegs.size());
+    const bool lone = lone_call();
+    std::vector<StyRange> sranges;
+    const uint64_t scr_records = order_dec_tables(db, dsegs, seg_first, droi, dsty, lone, sranges);
     double t_t2 = now_ms();
     HIPCHK(c->cs.ensure(len + extra.size() + 256));
     HIPCHK(c->coef.ensure(arena * 4 + 256));
@@ -3620,6 +3740,466 @@ extern "C" int grkgpu_decompress_mct(grkgpu_ctx *c, const uint8_t *csb, size_t l
 }
 
 // ---------------------------------------------------------------------------
+// Batch decode (grkgpu_decompress_batch): the host half of decompress_impl
+// (DecHost) per item, items and tiles in parallel on the host pool; the
+// items' tables rebased into one DecBlock / DecSeg table and one DwtPlan per
+// wavelet -- codestreams back to back in ctx->cs, each on a 16-byte boundary
+// with its multi-chunk bytes behind it, the coef / work / ll arenas item
+// after item -- then the device half once: one H2D of the packed streams, the
+// Tier-1 launches of a single call of that many blocks, the inverse DWT, and
+// the last store from a StoreJob table, one launch per (sample format,
+// layout) present.
+// ---------------------------------------------------------------------------
+static_assert(sizeof(grkgpu_store_job) == sizeof(StoreJob) && offsetof(grkgpu_store_job, dst) == offsetof(StoreJob, dst) &&
+                  offsetof(grkgpu_store_job, src_stride) == offsetof(StoreJob, sstride) &&
+                  offsetof(grkgpu_store_job, numcomps) == offsetof(StoreJob, ncomp) &&
+                  offsetof(grkgpu_store_job, wavelet_mask) == offsetof(StoreJob, irrev) &&
+                  offsetof(grkgpu_store_job, shift) == offsetof(StoreJob, shift) &&
+                  offsetof(grkgpu_store_job, max) == offsetof(StoreJob, mx),
+              "grkgpu_store_job is StoreJob");
+
+// the launches and copies dwt_launch issues for a plan
+static uint32_t dwt_launch_count(const DwtPlan &P, bool inverse) {
+    uint32_t nl = (uint32_t)P.copies2d.size();
+    for (auto &cp : P.copies) nl += cp.elems != 0;
+    for (size_t li = 0; li < P.levels.size(); ++li) {
+        ++nl;
+        if ((li < P.f01.size() && P.f01[li]) || (inverse && P.i01 && li + 2 == P.levels.size())) ++li;  // a level pair
+    }
+    return nl;
+}
+
+// The StoreJob tables of a launch set, one group per (sample format, layout):
+// jobs in table order, `first` their first-workgroup numbers.
+struct StoreGroup {
+    int32_t fmt = 0;
+    bool il = false;
+    std::vector<StoreJob> jobs;
+    std::vector<uint32_t> first;
+};
+// a tile the job table does not take (more than four components, or too many
+// workgroups for one job): launch_mct_inv_dcshift_to's arguments
+struct TileStore {
+    PlanePtrs src;
+    DstPlanes dst;
+    uint32_t sstride, w, h, dstride, nc;
+    int32_t fmt, mct, wmask;
+    bool il;
+    ShiftArr sh, mn, mx;
+};
+static bool store_group_add(StoreGroup (&groups)[10], int32_t fmt, bool il, const StoreJob &j) {
+    const uint64_t wgs = store_job_wgs(j, sample_bytes(fmt), il);
+    StoreGroup &g = groups[fmt * 2 + (il ? 1 : 0)];
+    if (wgs > STORE_JOB_MAX_WGS || (g.first.empty() ? 0 : g.first.back()) + wgs > 0x7fffffffull) return false;
+    g.fmt = fmt;
+    g.il = il;
+    if (g.first.empty()) g.first.push_back(0);
+    g.jobs.push_back(j);
+    g.first.push_back(g.first.back() + (uint32_t)wgs);
+    return true;
+}
+// The groups' tables in one device buffer (jobs of every group, then their
+// first arrays), uploaded through `stage`, and their launches.
+static size_t store_groups_bytes(const StoreGroup (&groups)[10]) {
+    size_t b = 0;
+    for (const StoreGroup &g : groups) b += g.jobs.size() * sizeof(StoreJob) + g.first.size() * 4;
+    return b;
+}
+static hipError_t store_groups_upload(const StoreGroup (&groups)[10], uint8_t *stage, void *dev, hipStream_t s) {
+    size_t o = 0;
+    for (const StoreGroup &g : groups) {
+        if (g.jobs.empty()) continue;
+        memcpy(stage + o, g.jobs.data(), g.jobs.size() * sizeof(StoreJob));
+        o += g.jobs.size() * sizeof(StoreJob);
+    }
+    for (const StoreGroup &g : groups) {
+        if (g.jobs.empty()) continue;
+        memcpy(stage + o, g.first.data(), g.first.size() * 4);
+        o += g.first.size() * 4;
+    }
+    return o ? hipMemcpyAsync(dev, stage, o, hipMemcpyHostToDevice, s) : hipSuccess;
+}
+static hipError_t store_groups_launch(const StoreGroup (&groups)[10], const void *dev, hipStream_t s, uint32_t *nl) {
+    size_t njobs = 0;
+    for (const StoreGroup &g : groups) njobs += g.jobs.size();
+    size_t jo = 0, fo = njobs * sizeof(StoreJob);
+    for (const StoreGroup &g : groups) {
+        if (g.jobs.empty()) continue;
+        if (g.first.back()) {
+            hipError_t e = launch_store_jobs((const StoreJob *)((const uint8_t *)dev + jo),
+                                             (const uint32_t *)((const uint8_t *)dev + fo), (uint32_t)g.jobs.size(),
+                                             g.first.back(), g.fmt, g.il, s);
+            if (e != hipSuccess) return e;
+            if (nl) ++*nl;
+        }
+        jo += g.jobs.size() * sizeof(StoreJob);
+        fo += g.first.size() * 4;
+    }
+    return hipSuccess;
+}
+
+static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
+                      grkgpu_batch_info *info, bool host_only) {
+    if (info) *info = grkgpu_batch_info{};
+    if ((!c && !host_only) || (n && !items)) return set_err(GRKGPU_EINVAL, "null argument");
+    if (p && (p->DA_x0 || p->DA_y0 || p->DA_x1 || p->DA_y1))
+        return set_err(GRKGPU_EINVAL, "a decode area is not supported in a batch");
+    if (!n) return GRKGPU_OK;
+    ActiveCall active;
+    const double t_start = now_ms();
+    const uint32_t reduce = p ? p->cp_reduce : 0, layers = p ? p->cp_layer : 0;
+    std::vector<DecHost> H(n);
+    std::vector<std::string> emsg(n);
+    // (called on the thread whose check failed: the message is thread-local)
+    auto fail = [&](size_t i, int rc) { items[i].status = rc; emsg[i] = g_err; };
+    host_parallel_for(n, 1, [&](size_t a, size_t b) {
+        for (size_t i = a; i < b; ++i) {
+            grkgpu_batch_item &it = items[i];
+            it.status = GRKGPU_OK;
+            it.img = grkgpu_image_desc{};
+            DecHost &h = H[i];
+            int rc = it.cs ? check_out_planes(&it.out) : set_err(GRKGPU_EINVAL, "null argument");
+            if (!rc && (it.out.layout & GRKGPU_LAYOUT_UPSAMPLE))
+                rc = set_err(GRKGPU_EUNSUPPORTED, "upsampled output is not supported in a batch");
+            if (!rc) {
+                h.csb = it.cs; h.len = it.len; h.img = &it.img;
+                h.od = DecodeOut{it.out.planes, (int32_t)it.out.sample_fmt, it.out.layout == GRKGPU_LAYOUT_INTERLEAVED,
+                                 it.out.on_device, 0, nullptr, 0, nullptr, 0};
+                h.reduce = reduce; h.max_layers = layers; h.host_only = host_only; h.batch = true;
+                rc = h.begin();
+            }
+            if (rc) fail(i, rc);
+        }
+    });
+    // packet headers over every (item, tile), then each item's tables
+    std::vector<std::pair<uint32_t, uint32_t>> todo;
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t lt = 0; !items[i].status && lt < H[i].nsh; ++lt) todo.push_back({i, lt});
+    host_parallel_for(todo.size(), 1, [&](size_t a, size_t b) {
+        for (size_t q = a; q < b; ++q) H[todo[q].first].parse_tiles(todo[q].second, todo[q].second + 1);
+    });
+    host_parallel_for(n, 1, [&](size_t a, size_t b) {
+        for (size_t i = a; i < b; ++i) {
+            if (items[i].status) continue;
+            const int rc = H[i].finish();
+            if (rc) fail(i, rc);
+        }
+    });
+    int first_rc = GRKGPU_OK;
+    std::string first_msg;
+    for (uint32_t i = 0; i < n && !first_rc; ++i)
+        if (items[i].status) { first_rc = items[i].status; first_msg = "item " + std::to_string(i) + ": " + emsg[i]; }
+    auto result = [&]() { return first_rc ? set_err(first_rc, first_msg) : GRKGPU_OK; };
+
+    // the merged tables: item i's stream at cs_off[i], its arenas from abase[i] / llbase[i]
+    std::vector<uint64_t> cs_off(n, 0), abase(n, 0), llbase(n, 0);
+    uint64_t cs_total = 0, cs_sum = 0, arena = 0, llarena = 0, nblk64 = 0, nseg64 = 0;
+    uint32_t n_ok = 0;
+    bool any_roi = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (items[i].status) continue;
+        const DecHost &h = H[i];
+        cs_off[i] = cs_total;
+        cs_total = (cs_total + h.len + h.extra.size() + 15) & ~(uint64_t)15;
+        abase[i] = arena;
+        arena += h.arena;
+        llbase[i] = llarena;
+        llarena += h.llarena;
+        nblk64 += h.db.size();
+        nseg64 += h.dsegs.size();
+        cs_sum += h.len;
+        any_roi = any_roi || !h.droi.empty();
+        ++n_ok;
+    }
+    uint64_t uwords = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        for (size_t q = 0; !items[i].status && q < H[i].dsegs.size(); ++q)
+            uwords += t1_unstuff_region_words(H[i].dsegs[q].len);
+    if (nblk64 > 0xffffffffull || nseg64 > 0xffffffffull || uwords / 4 > 0xffffffffull)
+        return set_err(GRKGPU_EUNSUPPORTED, "batch too large for one call");
+    const uint32_t nblk = (uint32_t)nblk64;
+    std::vector<DecBlock> db;
+    std::vector<DecSeg> dsegs;
+    std::vector<uint8_t> droi, dsty;
+    std::vector<uint32_t> seg_first;
+    db.reserve(nblk);
+    dsegs.reserve(nseg64);
+    dsty.reserve(nblk);
+    seg_first.reserve((size_t)nblk + 1);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (items[i].status) continue;
+        DecHost &h = H[i];
+        const uint32_t s0 = (uint32_t)dsegs.size();
+        for (DecBlock d : h.db) {
+            d.dst_off += abase[i];
+            d.data_off += cs_off[i];
+            db.push_back(d);
+        }
+        for (DecSeg sg : h.dsegs) {
+            sg.data_off += cs_off[i];
+            dsegs.push_back(sg);
+        }
+        for (uint32_t f : h.seg_first) seg_first.push_back(s0 + f);
+        dsty.insert(dsty.end(), h.dsty.begin(), h.dsty.end());
+        if (any_roi) {
+            if (h.droi.empty()) droi.insert(droi.end(), h.db.size(), 0);
+            else droi.insert(droi.end(), h.droi.begin(), h.droi.end());
+        }
+        for (Tile &tile : h.tiles)
+            for (TileComp &tc : tile.comps) tc.arena_off += abase[i];
+        for (uint64_t &o : h.lloff) o += llbase[i];
+    }
+    seg_first.push_back((uint32_t)dsegs.size());
+
+    // where the items' samples go on the device: their own planes, or the
+    // staging image.  Host regions adjacent in the caller's memory are
+    // adjacent there too and leave in one copy; every other region starts on
+    // a 16-byte boundary (the store's packed writes).
+    struct Region { uint8_t *host; size_t off, bytes; };
+    std::vector<Region> regions;
+    std::vector<std::array<size_t, GRKGPU_MAX_COMPS>> roff(n);
+    size_t img_bytes = 0;
+    auto region_bytes = [&](const DecHost &h, uint32_t k) {
+        return (size_t)(h.il ? h.ooff[h.nc] : h.ooff[k + 1] - h.ooff[k]) * h.sb;
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+        const DecHost &h = H[i];
+        if (items[i].status || h.planes_on_device || host_only) continue;
+        for (uint32_t k = 0; k < (h.il ? 1u : h.nc); ++k) {
+            Region r{(uint8_t *)h.planes[k], 0, region_bytes(h, k)};
+            const bool adj = !regions.empty() && regions.back().host + regions.back().bytes == r.host &&
+                             (regions.back().off + regions.back().bytes) % h.sb == 0;
+            r.off = adj ? regions.back().off + regions.back().bytes : (img_bytes + 15) & ~(size_t)15;
+            img_bytes = r.off + r.bytes;
+            roff[i][k] = r.off;
+            regions.push_back(r);
+        }
+    }
+    if (!host_only) {
+        HIPCHK(hipSetDevice(c->device));
+        if (img_bytes) HIPCHK(c->img.ensure(img_bytes + 256));
+        HIPCHK(c->work.ensure(arena * 4 + 256));
+    }
+    // the last store: a StoreJob per tile of every item of up to four
+    // components, per-tile launches for the others
+    StoreGroup groups[10];
+    std::vector<TileStore> singles;
+    uint32_t n_store_jobs = 0;
+    const uintptr_t work0 = host_only ? 0 : (uintptr_t)c->work.p, img0 = host_only ? 0 : (uintptr_t)c->img.p;
+    auto dst_of = [&](uint32_t i, uint32_t k) {
+        return H[i].planes_on_device ? (uintptr_t)H[i].planes[k] : img0 + roff[i][k];
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+        if (items[i].status) continue;
+        const DecHost &h = H[i];
+        const uint32_t nc = h.nc, nout = h.il ? 1 : nc, ow = h.orect[0].w();
+        const size_t eb = h.il ? (size_t)nc * h.sb : h.sb;
+        for (uint32_t lt = 0; lt < h.nsh; ++lt) {
+            const Tile &tile = h.tiles[lt];
+            if (tile.comps.empty()) continue;
+            const Rect tr = tile.comps[0].res[tile.comps[0].numres - 1 - reduce].r;  // the tile at the decoded resolution
+            const Rect out = intersect(tr, h.orect[0]);                            // its part of the output
+            if (out.empty()) continue;
+            const uint64_t soff = (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0);
+            const uint64_t doff = ((uint64_t)(out.y0 - h.orect[0].y0) * ow + (out.x0 - h.orect[0].x0)) * eb;
+            int32_t wmask = 0;  // components holding 9/7 (float) samples
+            for (uint32_t k = 0; k < nc; ++k) wmask |= tile.comps[k].irrev << k;
+            TileStore ts{};
+            for (uint32_t k = 0; k < nc; ++k) {
+                ts.src.p[k] = (int32_t *)(work0 + (tile.comps[k].arena_off + soff) * 4);
+                ts.sh.v[k] = h.cp.shift[k];
+                if (h.cp.sgnd[k]) { ts.mn.v[k] = -(1 << (h.cp.prec[k] - 1)); ts.mx.v[k] = (1 << (h.cp.prec[k] - 1)) - 1; }
+                else { ts.mn.v[k] = 0; ts.mx.v[k] = (1 << h.cp.prec[k]) - 1; }
+            }
+            for (uint32_t k = 0; k < nout; ++k) ts.dst.p[k] = (void *)(dst_of(i, k) + doff);
+            ts.sstride = tr.w(); ts.w = out.w(); ts.h = out.h();
+            ts.dstride = h.il ? ow * nc : ow;  // (h.il: ow * nc fits 32 bits, checked by begin())
+            ts.nc = nc; ts.fmt = h.od.fmt; ts.il = h.il; ts.mct = h.tmct[lt]; ts.wmask = wmask;
+            bool tabled = false;
+            if (nc <= 4) {
+                StoreJob j{};
+                for (uint32_t k = 0; k < nc; ++k) {
+                    j.src[k] = ts.src.p[k];
+                    j.dst[k] = ts.dst.p[k];
+                    j.shift[k] = ts.sh.v[k]; j.mn[k] = ts.mn.v[k]; j.mx[k] = ts.mx.v[k];
+                }
+                j.sstride = ts.sstride; j.dstride = ts.dstride; j.w = ts.w; j.h = ts.h;
+                j.ncomp = nc; j.mct = ts.mct; j.irrev = (uint32_t)wmask;
+                tabled = store_group_add(groups, ts.fmt, ts.il, j);
+            }
+            if (tabled) ++n_store_jobs;
+            else singles.push_back(ts);
+        }
+    }
+    if (info) {
+        info->n_ok = n_ok;
+        info->n_blocks = nblk;
+        info->n_store_jobs = n_store_jobs;
+    }
+    if (host_only || !n_ok) return result();
+
+    hipStream_t s = c->stream;
+    uint32_t nl = 0;  // kernel launches and fills of this call
+    const int drc = [&]() -> int {
+        const bool lone = lone_call();
+        std::vector<StyRange> sranges;
+        const uint64_t scr_records = order_dec_tables(db, dsegs, seg_first, droi, dsty, lone, sranges);
+        const double t_t2 = now_ms();
+        HIPCHK(c->cs.ensure(cs_total + 256));
+        HIPCHK(c->h_cs.ensure(cs_total + 256));
+        HIPCHK(c->coef.ensure(arena * 4 + 256));
+        HIPCHK(c->ll.ensure(llarena * 4 + 256));
+        HIPCHK(c->scratch.ensure((size_t)scr_records * sizeof(T1Scratch) + 256));
+        uint64_t uw = 0;  // per-segment unstuffed-stream regions (16-byte units)
+        for (auto &sg : dsegs) {
+            sg.ub_off = (uint32_t)(uw / 4);
+            uw += t1_unstuff_region_words(sg.len);
+        }
+        const size_t segbytes = dsegs.size() * sizeof(DecSeg), sfbytes = seg_first.size() * 4, roibytes = droi.size();
+        HIPCHK(c->segs.ensure(segbytes + sfbytes + roibytes + 256));
+        HIPCHK(c->h_segs.ensure(segbytes + sfbytes + roibytes + 256));
+        memcpy(c->h_segs.p, dsegs.data(), segbytes);
+        memcpy((uint8_t *)c->h_segs.p + segbytes, seg_first.data(), sfbytes);
+        if (roibytes) memcpy((uint8_t *)c->h_segs.p + segbytes + sfbytes, droi.data(), roibytes);
+        HIPCHK(c->ubuf.ensure(uw * 4 + 256));
+        HIPCHK(c->blocks.ensure((size_t)nblk * sizeof(DecBlock) + 256));
+        HIPCHK(c->h_blocks.ensure((size_t)nblk * sizeof(DecBlock) + 256));
+        memcpy(c->h_blocks.p, db.data(), (size_t)nblk * sizeof(DecBlock));
+        const size_t sjbytes = store_groups_bytes(groups);
+        HIPCHK(c->storejobs.ensure(sjbytes + 256));
+        HIPCHK(c->h_storejobs.ensure(sjbytes + 256));
+        // the streams packed into the pinned buffer, on the host pool: the
+        // bytes between them are never addressed by a segment
+        host_parallel_for(n, 1, [&](size_t a, size_t b) {
+            for (size_t i = a; i < b; ++i) {
+                if (items[i].status) continue;
+                uint8_t *d = c->h_cs.as<uint8_t>() + cs_off[i];
+                memcpy(d, H[i].csb, H[i].len);
+                if (!H[i].extra.empty()) memcpy(d + H[i].len, H[i].extra.data(), H[i].extra.size());
+            }
+        });
+
+        HIPCHK(hipEventRecord(c->ev[0], s));
+        HIPCHK(hipMemcpyAsync(c->cs.p, c->h_cs.p, cs_total, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, (size_t)nblk * sizeof(DecBlock), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->segs.p, c->h_segs.p, segbytes + sfbytes + roibytes, hipMemcpyHostToDevice, s));
+        HIPCHK(store_groups_upload(groups, c->h_storejobs.as<uint8_t>(), c->storejobs.p, s));
+        DwtPlan dplan[2];  // one plan per wavelet over every item's tile-components
+        for (uint32_t i = 0; i < n; ++i) {
+            if (items[i].status) continue;
+            const DecHost &h = H[i];
+            for (uint32_t lt = 0; lt < h.nsh; ++lt)
+                for (uint32_t k = 0; k < h.tiles[lt].comps.size(); ++k) {
+                    const TileComp &tc = h.tiles[lt].comps[k];
+                    dwt_plan_tc(dplan[tc.irrev], tc, c->work.as<int32_t>() + tc.arena_off,
+                                c->coef.as<int32_t>() + tc.arena_off, c->ll.as<int32_t>() + h.lloff[lt * h.nc + k],
+                                tc.irrev, true, tc.numres - reduce, nullptr);
+                }
+        }
+        HIPCHK(dwt_upload(dplan[1], c->dwtjobs, c->h_dwtjobs, 1, s));
+        HIPCHK(dwt_upload(dplan[0], c->dwtjobs53, c->h_dwtjobs53, 0, s));
+        HIPCHK(hipEventRecord(c->ev[1], s));
+        for (const StyRange &g : sranges) {
+            HIPCHK(launch_t1_decode(c->blocks.as<DecBlock>() + g.b0, g.n, c->cs.as<uint8_t>(),
+                                    c->scratch.as<T1Scratch>() + g.scr0, c->coef.as<int32_t>(), s,
+                                    c->ubuf.as<uint32_t>(), 0, c->segs.as<DecSeg>(),
+                                    (const uint32_t *)(c->segs.as<uint8_t>() + segbytes) + g.b0, g.sty,
+                                    roibytes ? c->segs.as<uint8_t>() + segbytes + sfbytes + g.b0 : nullptr,
+                                    lone ? lone_bpw(nblk) : 0));
+            ++nl;
+        }
+        HIPCHK(hipEventRecord(c->ev[2], s));
+        c->ltimes.clear();
+        c->lidx.clear();
+        LaunchLog llog{&c->lev, &c->ltimes, &c->lidx};
+        HIPCHK(dwt_launch(dplan[1], c->dwtjobs, 1, true, s, c->launch_timing ? &llog : nullptr));
+        HIPCHK(dwt_launch(dplan[0], c->dwtjobs53, 0, true, s, c->launch_timing ? &llog : nullptr));
+        nl += dwt_launch_count(dplan[1], true) + dwt_launch_count(dplan[0], true);
+        HIPCHK(hipEventRecord(c->ev[3], s));
+        // samples nothing decodes are zero: the margin of a reduced decode at
+        // an odd origin (the whole region), the tiles a cut stream never reached
+        for (uint32_t i = 0; i < n; ++i) {
+            if (items[i].status) continue;
+            const DecHost &h = H[i];
+            const uint32_t nout = h.il ? 1 : h.nc;
+            const size_t eb = h.il ? (size_t)h.nc * h.sb : h.sb;
+            if (h.opad) {
+                for (uint32_t k = 0; k < nout; ++k, ++nl)
+                    HIPCHK(hipMemsetAsync((void *)dst_of(i, k), 0, region_bytes(h, k), s));
+            } else if (h.missing) {
+                for (uint32_t t = 0; t < h.nsh; ++t) {
+                    if (h.walk.decoded[t]) continue;
+                    for (uint32_t k = 0; k < nout; ++k) {
+                        const Rect cr = tile_rect(h.cp, t);
+                        const Rect rr{ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
+                                      ceil_pow2(cr.y1, reduce)};
+                        const Rect o = intersect(rr, h.orect[k]);
+                        if (o.empty()) continue;
+                        const uint32_t ow = h.orect[k].w();
+                        const uint64_t e0 = (uint64_t)(o.y0 - h.orect[k].y0) * ow + (o.x0 - h.orect[k].x0);
+                        HIPCHK(hipMemset2DAsync((void *)(dst_of(i, k) + e0 * eb), (size_t)ow * eb, 0, (size_t)o.w() * eb,
+                                                o.h(), s));
+                        ++nl;
+                    }
+                }
+            }
+        }
+        HIPCHK(store_groups_launch(groups, c->storejobs.p, s, &nl));
+        for (const TileStore &ts : singles) {
+            HIPCHK(launch_mct_inv_dcshift_to(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc,
+                                             ts.sh, ts.mn, ts.mx, ts.mct, ts.wmask, s));
+            ++nl;
+        }
+        HIPCHK(hipEventRecord(c->ev[4], s));
+        for (size_t r = 0; r < regions.size();) {  // one copy per run of adjacent regions
+            size_t e = r + 1, bytes = regions[r].bytes;
+            while (e < regions.size() && regions[e].off == regions[r].off + bytes &&
+                   regions[e].host == regions[r].host + bytes)
+                bytes += regions[e++].bytes;
+            if (bytes)
+                HIPCHK(hipMemcpyAsync(regions[r].host, c->img.as<uint8_t>() + regions[r].off, bytes,
+                                      hipMemcpyDeviceToHost, s));
+            r = e;
+        }
+        HIPCHK(hipEventRecord(c->ev[5], s));
+        HIPCHK(hipStreamSynchronize(s));
+        const double t_end = now_ms();
+        grkgpu_stats &st = c->stats;
+        memset(&st, 0, sizeof(st));
+        hipEventElapsedTime(&st.h2d_ms, c->ev[0], c->ev[1]);
+        hipEventElapsedTime(&st.t1_ms, c->ev[1], c->ev[2]);
+        hipEventElapsedTime(&st.dwt_ms, c->ev[2], c->ev[3]);
+        hipEventElapsedTime(&st.dcshift_mct_ms, c->ev[3], c->ev[4]);
+        hipEventElapsedTime(&st.d2h_ms, c->ev[4], c->ev[5]);
+        log_collect(c);
+        st.host_t2_ms = (float)(t_t2 - t_start);
+        st.total_ms = (float)(t_end - t_start);
+        st.num_cblks = nblk;
+        st.cs_bytes = cs_sum;
+        return GRKGPU_OK;
+    }();
+    if (drc) {  // a device error leaves no item decoded
+        const std::string msg = g_err;
+        for (uint32_t i = 0; i < n; ++i)
+            if (!items[i].status) items[i].status = drc;
+        if (info) info->n_ok = 0;
+        return set_err(drc, msg);
+    }
+    if (info) info->n_launches = nl;
+    return result();
+}
+
+extern "C" int grkgpu_decompress_batch(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
+                                       grkgpu_batch_info *info) {
+    return batch_impl(c, items, n, p, info, false);
+}
+
+extern "C" int grkgpu_batch_plan(grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
+                                 grkgpu_batch_info *info) {
+    return batch_impl(nullptr, items, n, p, info, true);
+}
+
+// ---------------------------------------------------------------------------
 // JP2 files: the box layer (jp2.cpp) around the entry points above
 // ---------------------------------------------------------------------------
 namespace {
@@ -3931,6 +4511,68 @@ extern "C" int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t num
     if (rc) return rc;
     HIPCHK(launch_mct_inv_dcshift_to(p, src_stride, w, h, d, fmt, il, dst_stride, numcomps, sh, mn, mx, mct,
                                      irreversible ? 0xFFFF : 0, (hipStream_t)stream));
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_mct_inv_dcshift_jobs_to(const grkgpu_store_job *jobs, uint32_t n, uint32_t sample_fmt,
+                                              uint32_t layout, void *stream) {
+    if (sample_fmt > GRKGPU_SAMPLE_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if (layout > GRKGPU_LAYOUT_INTERLEAVED) return set_err(GRKGPU_EINVAL, "unknown layout");
+    if (!n) return GRKGPU_OK;
+    if (!jobs) return set_err(GRKGPU_EINVAL, "null argument");
+    const int32_t fmt = (int32_t)sample_fmt;
+    const bool il = layout == GRKGPU_LAYOUT_INTERLEAVED;
+    const uint32_t sb = sample_bytes(fmt);
+    const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
+    const int64_t lo = fmt == SMP_I32 ? INT32_MIN : (sg ? -((int64_t)1 << (8 * sb - 1)) : 0);
+    const int64_t hi = fmt == SMP_I32 ? INT32_MAX : (sg ? ((int64_t)1 << (8 * sb - 1)) - 1 : ((int64_t)1 << (8 * sb)) - 1);
+    StoreGroup groups[10];
+    std::vector<TileStore> singles;
+    for (uint32_t i = 0; i < n; ++i) {
+        const grkgpu_store_job &q = jobs[i];
+        const uint32_t nc = q.numcomps;
+        if (nc < 1 || nc > 4 || q.src_stride < q.w || (uint64_t)q.dst_stride < (uint64_t)q.w * (il ? nc : 1))
+            return set_err(GRKGPU_EINVAL, "bad arguments (1 .. 4 components, strides must hold a row)");
+        if (q.wavelet_mask >> nc) return set_err(GRKGPU_EINVAL, "wavelet mask names a component the job does not have");
+        StoreJob j;
+        static_assert(sizeof(j) == sizeof(q), "grkgpu_store_job is StoreJob");
+        memcpy(&j, &q, sizeof(j));
+        for (uint32_t k = nc; k < 4; ++k) j.src[k] = nullptr;
+        TileStore ts{};
+        for (uint32_t k = 0; k < nc; ++k) {
+            if (!q.src[k] || (uintptr_t)q.src[k] % 4) return set_err(GRKGPU_EINVAL, "null or misaligned source plane");
+            if (q.min[k] > q.max[k] || q.min[k] < lo || q.max[k] > hi)
+                return set_err(GRKGPU_EINVAL, "sample format does not hold the component's range");
+            ts.src.p[k] = const_cast<int32_t *>(q.src[k]);
+            ts.sh.v[k] = q.shift[k]; ts.mn.v[k] = q.min[k]; ts.mx.v[k] = q.max[k];
+        }
+        for (uint32_t k = 0; k < (il ? 1u : nc); ++k) {
+            if (!q.dst[k] || (uintptr_t)q.dst[k] % sb) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+            ts.dst.p[k] = q.dst[k];
+        }
+        if (store_group_add(groups, fmt, il, j)) continue;
+        ts.sstride = q.src_stride; ts.w = q.w; ts.h = q.h; ts.dstride = q.dst_stride; ts.nc = nc;
+        ts.fmt = fmt; ts.il = il; ts.mct = q.mct; ts.wmask = (int32_t)q.wavelet_mask;
+        singles.push_back(ts);
+    }
+    int rc = check_device(-1);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = store_groups_bytes(groups);
+    std::vector<uint8_t> stage(bytes);
+    void *dev = nullptr;
+    if (bytes) HIPCHK(hipMalloc(&dev, bytes));
+    hipError_t e = bytes ? store_groups_upload(groups, stage.data(), dev, s) : hipSuccess;
+    if (e == hipSuccess) e = store_groups_launch(groups, dev, s, nullptr);
+    for (size_t i = 0; e == hipSuccess && i < singles.size(); ++i) {
+        const TileStore &ts = singles[i];
+        e = launch_mct_inv_dcshift_to(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc, ts.sh,
+                                      ts.mn, ts.mx, ts.mct, ts.wmask, s);
+    }
+    const hipError_t es = hipStreamSynchronize(s);  // the table and its staging are freed below
+    if (dev) hipFree(dev);
+    HIPCHK(e);
+    HIPCHK(es);
     return GRKGPU_OK;
 }
 

@@ -97,6 +97,37 @@ hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uin
                                      const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
                                      uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn, const ShiftArr &mx,
                                      int32_t mct, int32_t irrev, hipStream_t s);
+// launch_mct_inv_dcshift_to for a table of tiles in one launch (the batch
+// decode, grkgpu_mct_inv_dcshift_jobs_to): each tile's arguments as a record
+// in device memory (grkgpu_store_job's layout; static_assert in codec.cpp),
+// 1 .. 4 components, all jobs of a launch in one sample format and layout.
+// irrev: bit k set = component k holds 9/7 samples.
+struct StoreJob {
+    const int32_t *src[4];  // component k's coefficients at the tile's first stored sample
+    void *dst[4];           // planar: plane k there; interleaved: dst[0]
+    uint32_t sstride, dstride, w, h;
+    uint32_t ncomp;
+    int32_t mct;
+    uint32_t irrev, pad_;
+    int32_t shift[4], mn[4], mx[4];
+};
+// threads along a row of a job: the lead run and the runs of 16 bytes
+// (launch_inv_to's), or the pixels of a two-component interleaved tile
+__host__ __device__ inline uint32_t store_job_row_threads(uint32_t w, uint32_t ncomp, uint32_t sb, bool interleaved) {
+    if (interleaved && ncomp == 2) return w;
+    const uint32_t n = 16 / sb;
+    return (uint32_t)(((uint64_t)w + n - 1) / n + 1);
+}
+// a job's workgroups of 256 threads (0: nothing to store); more than 2^24 do
+// not fit the kernel's 32-bit thread index: such a tile takes the launch of its own
+inline uint64_t store_job_wgs(const StoreJob &j, uint32_t sb, bool interleaved) {
+    if (!j.w || !j.h) return 0;
+    return ((uint64_t)store_job_row_threads(j.w, j.ncomp, sb, interleaved) * j.h + 255) / 256;
+}
+constexpr uint64_t STORE_JOB_MAX_WGS = (uint64_t)1 << 24;
+// first: njobs + 1 first-workgroup numbers (prefix sums of store_job_wgs), nwg = first[njobs]
+hipError_t launch_store_jobs(const StoreJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg, int32_t fmt,
+                             bool interleaved, hipStream_t s);
 // The decoded image with its subsampled components replicated to the image
 // grid (GRKGPU_LAYOUT_UPSAMPLE, grk_decompress -u): output pixel (X, Y) of the
 // reference grid takes component k's sample at column floor(X / dx), row

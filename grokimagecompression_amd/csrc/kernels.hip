@@ -2319,6 +2319,127 @@ hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uin
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// The same store for a table of tiles (StoreJob, grk_device.h) in one launch:
+// the batch decode's last stage, where one launch per tile would cost more
+// than the tiles' samples.  Workgroup wg belongs to the last job j with
+// first[j] <= wg (first: the jobs' first workgroup numbers, njobs + 1 entries,
+// an empty job's equal to its successor's, so it is never found).  The search
+// depends on blockIdx alone: it and the record's fields are uniform over the
+// workgroup, read with scalar loads before the first store and kept in scalar
+// registers.  Thread g of a job -- g counted over its workgroups -- owns run
+// (g % rpr) of row (g / rpr), rpr = store_job_row_threads: the runs
+// k_mct_inv_dcshift_planar / _pixels lay on the destination's 16-byte grid
+// (IL with two components: k_mct_inv_dcshift_pixels_any's thread per pixel),
+// finished and stored by the same helpers, statement for statement.  No LDS,
+// no atomics, nothing shared between workgroups.
+// ---------------------------------------------------------------------------
+template <typename T, int NC>
+__device__ __forceinline__ void store_job_pixels(const StoreJob &J, uint32_t y, uint32_t t, const ShiftArr &shift,
+                                                 const ShiftArr &minv, const ShiftArr &maxv, int32_t mct,
+                                                 int32_t irrev) {
+    constexpr int N = NarrowRun<T>::N;
+    T *const drow = (T *)J.dst[0] + (size_t)y * J.dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)drow, NC * sizeof(T), t, J.w, x0);
+    if (n <= 0) return;
+    const size_t si = (size_t)y * J.sstride + x0;
+    int32_t v[NC][N];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) load_run<N>(J.src[k] + si, n, v[k]);
+    if (mct) inv_mct_run<N>(v[0], v[1], v[2], irrev, shift, minv, maxv);
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+        if (!mct || k >= 3) inv_plain_run<N>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+    int32_t px[N * NC];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) px[i * NC + c] = v[c][i];
+    store_samples<T, N * NC>(drow + (size_t)x0 * NC, px, n * NC);
+}
+
+template <typename T, bool IL>
+__global__ void __launch_bounds__(256) k_store_jobs(const StoreJob *__restrict__ jobs,
+                                                    const uint32_t *__restrict__ first, uint32_t njobs) {
+    constexpr int N = NarrowRun<T>::N;
+    const uint32_t wg = blockIdx.x;
+    uint32_t lo = 0, hi = njobs;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first[mid] <= wg) lo = mid; else hi = mid;
+    }
+    const StoreJob J = jobs[lo];
+    const uint32_t ncomp = J.ncomp, tw = J.w, th = J.h;
+    const int32_t mct = J.mct && ncomp >= 3, irrev = (int32_t)J.irrev;
+    ShiftArr shift{}, minv{}, maxv{};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { shift.v[k] = J.shift[k]; minv.v[k] = J.mn[k]; maxv.v[k] = J.mx[k]; }
+    const uint32_t rpr = store_job_row_threads(tw, ncomp, (uint32_t)sizeof(T), IL);
+    const uint32_t g = (wg - first[lo]) * 256u + threadIdx.x;
+    const uint32_t y = g / rpr, t = g - y * rpr;
+    if (y >= th) return;
+    if constexpr (IL) {
+        if (ncomp == 3) { store_job_pixels<T, 3>(J, y, t, shift, minv, maxv, mct, irrev); return; }
+        if (ncomp == 4) { store_job_pixels<T, 4>(J, y, t, shift, minv, maxv, mct, irrev); return; }
+        if (ncomp == 2) {  // a thread per pixel, a store per sample
+            const size_t si = (size_t)y * J.sstride + t;
+            T *const d = (T *)J.dst[0] + (size_t)y * J.dstride + (size_t)t * 2;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                int32_t a[1] = {J.src[k][si]};
+                inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+                __builtin_nontemporal_store((T)a[0], d + k);
+            }
+            return;
+        }
+    }
+    // planar (one interleaved component is a plane)
+    const size_t drow = (size_t)y * J.dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)((T *)J.dst[0] + drow), sizeof(T), t, tw, x0);
+    if (n <= 0) return;
+    const size_t si = (size_t)y * J.sstride + x0, di = drow + x0;
+    if (mct) {
+        int32_t a[N], b[N], c[N];
+        load_run<N>(J.src[0] + si, n, a);
+        load_run<N>(J.src[1] + si, n, b);
+        load_run<N>(J.src[2] + si, n, c);
+        inv_mct_run<N>(a, b, c, irrev, shift, minv, maxv);
+        store_samples<T, N>((T *)J.dst[0] + di, a, n);
+        store_samples<T, N>((T *)J.dst[1] + di, b, n);
+        store_samples<T, N>((T *)J.dst[2] + di, c, n);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if ((uint32_t)k >= ncomp || (mct && k < 3)) continue;
+        int32_t a[N];
+        load_run<N>(J.src[k] + si, n, a);
+        inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        store_samples<T, N>((T *)J.dst[k] + di, a, n);
+    }
+}
+
+hipError_t launch_store_jobs(const StoreJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg, int32_t fmt,
+                             bool interleaved, hipStream_t s) {
+    if (!njobs || !nwg) return hipSuccess;
+#define GRK_JOBS(T)                                                                                                   \
+    do {                                                                                                              \
+        if (interleaved) hipLaunchKernelGGL((k_store_jobs<T, true>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs); \
+        else hipLaunchKernelGGL((k_store_jobs<T, false>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs);            \
+    } while (0)
+    switch (fmt) {
+        case SMP_I32: GRK_JOBS(int32_t); break;
+        case SMP_U8: GRK_JOBS(uint8_t); break;
+        case SMP_I8: GRK_JOBS(int8_t); break;
+        case SMP_U16: GRK_JOBS(uint16_t); break;
+        case SMP_I16: GRK_JOBS(int16_t); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_JOBS
+    return hipGetLastError();
+}
+
 template <typename T, bool FAST>
 static void launch_up(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
                       const DstPlanes &dst, bool interleaved, uint32_t dstride, hipStream_t s) {

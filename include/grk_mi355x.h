@@ -732,6 +732,54 @@ int grkgpu_decompress_convert(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, co
 int grkgpu_decompress_mct(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, const grkgpu_dparams *p,
                           uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
                           const grkgpu_out_planes *out, const grkgpu_out_ops *ops);
+/* Decode a batch of codestreams in one launch set: item i is the whole-image
+ * decode grkgpu_decompress_to(ctx, cs, len, p, 0, 0xffffffff, &img, &out) and
+ * receives that call's samples bit for bit, but the n items share one upload
+ * of their codestreams, one Tier-1 launch per code-block style, one inverse
+ * DWT launch sequence and one store launch per (sample format, layout) present
+ * -- the way a few dozen code-blocks per image fill the device.  Items may
+ * differ in everything grkgpu_decompress_to takes: geometry, tile grid,
+ * components (1 .. 16; more than four go through per-tile store launches),
+ * precision, sign, wavelet, code-block size and style, layers, progression,
+ * tile-part markers, sample format, layout and host / device destination.
+ * p (NULL: defaults) applies to every item: cp_reduce and cp_layer; a decode
+ * area is GRKGPU_EINVAL for the call, as are a NULL ctx or items with n > 0;
+ * n = 0 is GRKGPU_OK.
+ *
+ * Every check that can refuse a stream runs on the host before the first
+ * device call.  An item that fails gets its code in `status` -- what the
+ * single call would have returned, and GRKGPU_EUNSUPPORTED for a stream with a
+ * subsampled component, GRKGPU_LAYOUT_UPSAMPLE in out.layout and a custom-MCT
+ * stream, which this call does not take -- and its destination is left
+ * untouched; the other items are decoded.  The call returns GRKGPU_OK when
+ * every item succeeded, else the first failing item's code with
+ * grkgpu_last_error() = "item <i>: <its message>".  A cut stream the single
+ * call accepts is accepted, its missing tiles zero.  Merged tables beyond the
+ * 32-bit limits of one call (blocks, passes, unstuffed words): the whole call
+ * is GRKGPU_EUNSUPPORTED "batch too large for one call" before any device
+ * work; the caller splits.  grkgpu_get_stats reports the batch (num_cblks and
+ * cs_bytes are sums); the call is one call in progress for the Tier-1 plan,
+ * chosen on the merged block count.
+ *
+ * info (may be NULL): items decoded, code-blocks, job-table store records and
+ * n_launches, the call's kernel launches and fills (the DWT plan's device
+ * copies included, the H2D / D2H copies not): 64 copies of a stream take the
+ * launches of one.
+ * grkgpu_batch_plan is the host half alone -- no device call, no ctx, the
+ * items' `out` planes not read: status / img of every item and info with
+ * n_launches = 0. */
+typedef struct {
+    const uint8_t *cs;     /* in: one raw codestream */
+    size_t len;
+    grkgpu_out_planes out; /* in: this item's destination (format, layout, host / device) */
+    grkgpu_image_desc img; /* out: geometry, as grkgpu_decompress_to reports it */
+    int32_t status;        /* out: GRKGPU_OK or the code this item alone would have returned */
+    uint32_t pad_;
+} grkgpu_batch_item;
+typedef struct { uint32_t n_ok, n_blocks, n_store_jobs, n_launches; } grkgpu_batch_info;
+int grkgpu_decompress_batch(grkgpu_ctx *ctx, grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
+                            grkgpu_batch_info *info);
+int grkgpu_batch_plan(grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p, grkgpu_batch_info *info);
 /* The custom MCT of a codestream, host only: grkgpu_read_header's img (may be
  * NULL) for a stream with or without MCT = 2, and for the former *n = numcomps,
  * matrix[n * n] and offsets[n] (room for 256 / 16; either may be NULL) as
@@ -902,6 +950,26 @@ int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t numcomps, uint
                               uint32_t src_stride, const uint32_t *prec, const int32_t *sgnd, int32_t mct,
                               int32_t irreversible, const grkgpu_out_planes *dst, uint32_t dst_stride,
                               void *stream);
+/* grkgpu_mct_inv_dcshift_to for a table of n tiles in one launch (the last
+ * kernel of grkgpu_decompress_batch on its own): jobs is a host array whose
+ * src / dst are device pointers (src 4-byte aligned, dst sample aligned;
+ * interleaved: dst[0]), numcomps 1 .. 4, strides as there, the DC shift and
+ * the clamp bounds given per component, wavelet_mask bit k set = component k
+ * holds 9/7 float bit patterns (the MCT follows component 0's).  Every job
+ * has the sample format and layout given; the bounds must fit the format.
+ * Jobs of w = 0 or h = 0 store nothing.  The table is copied to the device
+ * and freed after the launch, so the call synchronises `stream`. */
+typedef struct {
+    const int32_t *src[4];
+    void *dst[4];
+    uint32_t src_stride, dst_stride, w, h;
+    uint32_t numcomps;
+    int32_t mct;
+    uint32_t wavelet_mask, pad_;
+    int32_t shift[4], min[4], max[4];
+} grkgpu_store_job;
+int grkgpu_mct_inv_dcshift_jobs_to(const grkgpu_store_job *jobs, uint32_t n, uint32_t sample_fmt, uint32_t layout,
+                                   void *stream);
 /* The last kernel of grkgpu_decompress_mct on its own, as
  * grkgpu_mct_inv_dcshift_to is grkgpu_decompress_to's: src[c] = float planes
  * (the inverse 9/7 wavelet's output), rows src_stride apart; matrix = numcomps
