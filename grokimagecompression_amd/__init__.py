@@ -231,6 +231,29 @@ class StoreJob(ctypes.Structure):
                 ("max", ctypes.c_int32 * 4)]
 
 
+class CBatchItem(ctypes.Structure):
+    """grkgpu_cbatch_item: one image of grkgpu_compress_batch / grkgpu_compress_batch_plan."""
+    _fields_ = [("img", ImageDesc), ("p", ctypes.POINTER(CParams)), ("in_", Planes), ("cs", ctypes.c_void_p),
+                ("len", ctypes.c_size_t), ("status", ctypes.c_int32), ("pad_", ctypes.c_uint32)]
+
+
+class CBatchInfo(ctypes.Structure):
+    """grkgpu_cbatch_info: items encoded, code-blocks, job-table load records, kernel launches + fills."""
+    _fields_ = [("n_ok", ctypes.c_uint32), ("n_blocks", ctypes.c_uint32), ("n_load_jobs", ctypes.c_uint32),
+                ("n_launches", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class LoadJob(ctypes.Structure):
+    """grkgpu_load_job: one tile of grkgpu_dcshift_mct_fwd_jobs."""
+    _fields_ = [("src", ctypes.c_void_p * 4), ("dst", ctypes.c_void_p * 4), ("src_stride", ctypes.c_uint32),
+                ("dst_stride", ctypes.c_uint32), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32),
+                ("numcomps", ctypes.c_uint32), ("mct", ctypes.c_int32), ("irreversible", ctypes.c_int32),
+                ("pad_", ctypes.c_uint32), ("shift", ctypes.c_int32 * 4)]
+
+
 COLOUR_NONE, COLOUR_SYCC, COLOUR_EYCC, COLOUR_CMYK = 0, 1, 3, 4
 COLOUR_FORCE_RGB = 0x100  # flag or'ed into a colour value: gray (+ alpha) -> R = G = B (+ alpha)
 PREC_CLIP, PREC_SCALE = 0, 1
@@ -425,6 +448,10 @@ def lib():
             L.grkgpu_decompress_batch.argtypes = [VP, P(BatchItem), U32, P(DParams), P(BatchInfo)]
             L.grkgpu_batch_plan.argtypes = [P(BatchItem), U32, P(DParams), P(BatchInfo)]
             L.grkgpu_mct_inv_dcshift_jobs_to.argtypes = [P(StoreJob), U32, U32, U32, VP]
+        if hasattr(L, "grkgpu_compress_batch"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_compress_batch.argtypes = [VP, P(CBatchItem), U32, P(CBatchInfo)]
+            L.grkgpu_compress_batch_plan.argtypes = [P(CBatchItem), U32, P(CBatchInfo)]
+            L.grkgpu_dcshift_mct_fwd_jobs.argtypes = [VP, P(LoadJob), U32, U32]
         L.grkgpu_mct_inv_dcshift_to.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), I32, I32, P(OutPlanes), U32,
                                                 VP]
         if hasattr(L, "grkgpu_upsample_to"):  # not in an older library given by GRKGPU_LIB (A/B runs)
@@ -659,6 +686,52 @@ def plan_batch(bufs, reduce=0, layers=0):
     res.update(rc=rc, error=lib().grkgpu_last_error().decode() if rc else "",
                status=[items[i].status for i in range(len(bufs))],
                img=[ImageDesc.from_buffer_copy(items[i].img) for i in range(len(bufs))])
+    return res
+
+
+def _per_item(v, n, name):
+    """One value for all n items of a batch, or a list with one entry per item."""
+    if isinstance(v, list):
+        if len(v) != n:
+            raise GrkGpuError("%s: one entry per image (got %d for %d)" % (name, len(v), n))
+        return list(v)
+    return [v] * n
+
+
+def plan_compress_batch(descs):
+    """grkgpu_compress_batch_plan: the host half of Codec.compress_batch -- no
+    device call, no samples.  descs: one dict per image with "shape" (c, h, w)
+    and "prec", and optionally "params" (CParams), "offset" (x0, y0), "sgnd",
+    "fmt" (a SAMPLE_* width with its flags; default SAMPLE_I32) and
+    "subsampling" (one (dx, dy) per component).  prec / sgnd: one value or one
+    per component.  Returns a dict: "status" (one grkgpu code per image, 0 = it
+    would encode), "rc" (0, or the first failing image's code), "error" (its
+    message, "item <i>: ...") and the grkgpu_cbatch_info fields n_ok / n_blocks
+    / n_load_jobs (n_launches = 0)."""
+    descs = list(descs)
+    n = len(descs)
+    items = (CBatchItem * max(n, 1))()
+    keep = []
+    for i, q in enumerate(descs):
+        c, h, w = q["shape"]
+        d = items[i].img
+        x0, y0 = q.get("offset", (0, 0))
+        d.x0, d.y0, d.x1, d.y1, d.numcomps = x0, y0, x0 + w, y0 + h, c
+        sub = q.get("subsampling")
+        for k, (pk, sk) in enumerate(zip(_per_comp(q["prec"], c), _per_comp(q.get("sgnd", False), c))):
+            d.prec[k], d.sgnd[k] = pk, 1 if sk else 0
+            if sub is not None:
+                d.dx[k], d.dy[k] = sub[k]
+        p = q.get("params")
+        if p is not None:
+            keep.append(p)
+            items[i].p = ctypes.pointer(p)
+        items[i].in_.sample_fmt = q.get("fmt", SAMPLE_I32)
+    info = CBatchInfo()
+    rc = lib().grkgpu_compress_batch_plan(items, n, ctypes.byref(info))
+    res = info.as_dict()
+    res.update(rc=rc, error=lib().grkgpu_last_error().decode() if rc else "",
+               status=[items[i].status for i in range(n)])
     return res
 
 
@@ -924,6 +997,86 @@ class Codec:
         pinned output buffer, valid for as long as the view lives (_CtxView)."""
         return self.compress_tiles(img, prec, params or CParams.make(), 0, 0xFFFFFFFF, PART_ALL, offset, sgnd,
                                    view=view, layout=layout)
+
+    def compress_batch(self, imgs, prec, params=None, offset=(0, 0), sgnd=False, layout="chw", errors="raise"):
+        """Encode a list of images in one launch set (grkgpu_compress_batch)
+        -> a list of bytes, item i what compress(imgs[i], prec, params, offset,
+        sgnd, layout=) returns, byte for byte.  Images are what compress takes
+        (numpy or torch, host or cuda:<device>, int32 or 8 / 16-bit, '>u2'); an
+        entry may also be a prepared (ImageDesc, Planes, keepalive) triple as
+        _image / _image_subsampled return it.  prec, params, offset, sgnd and
+        layout are one value for all images or a list with one entry per
+        image (a per-component prec / sgnd goes in as a tuple).  Images with subsampled components or a custom MCT are refused
+        item by item, as is anything compress refuses; the others are still
+        encoded.  errors="raise": raise GrkGpuError naming the first failing
+        item after the call; errors="return": the GrkGpuError in that item's
+        slot.  self.cbatch_info holds the call's grkgpu_cbatch_info afterwards."""
+        if errors not in ("raise", "return"):
+            raise GrkGpuError("errors must be 'raise' or 'return'")
+        imgs = list(imgs)
+        n = len(imgs)
+        precs, pars, offs = _per_item(prec, n, "prec"), _per_item(params, n, "params"), _per_item(offset, n, "offset")
+        sgnds, layouts = _per_item(sgnd, n, "sgnd"), _per_item(layout, n, "layout")
+        items = (CBatchItem * max(n, 1))()
+        keep = []
+        default = CParams.make()
+        for i, im in enumerate(imgs):
+            if isinstance(im, tuple):
+                d, pl, k = im
+            else:
+                d, pl, k = self._image(im, precs[i], offs[i], sgnds[i], layouts[i])
+            p = pars[i] if pars[i] is not None else default
+            keep.append((k, p))
+            items[i].img, items[i].in_, items[i].p = d, pl, ctypes.pointer(p)
+        info = CBatchInfo()
+        rc = lib().grkgpu_compress_batch(self._ctx, items, n, ctypes.byref(info))
+        self.cbatch_info = info.as_dict()
+        msg = lib().grkgpu_last_error().decode() if rc else ""
+        failed = [i for i in range(n) if items[i].status]
+        if rc and (errors == "raise" or not failed):
+            raise GrkGpuError("grkgpu error %d: %s" % (rc, msg))
+        outs = [None if items[i].status else ctypes.string_at(items[i].cs, items[i].len) for i in range(n)]
+        for i in failed:
+            outs[i] = GrkGpuError("grkgpu error %d: item %d failed%s" % (items[i].status, i,
+                                                                         msg[msg.index(":"):] if failed[0] == i else ""))
+        return outs
+
+    def dcshift_mct_fwd_jobs(self, jobs, fmt):
+        """grkgpu_dcshift_mct_fwd_jobs: dcshift_mct_fwd_from for a list of tiles
+        in one launch, on this codec's stream.  jobs: dicts with
+        dcshift_mct_fwd_from's arguments -- src (flat uint8 cuda tensor),
+        byte_offset, dst ((c <= 4, h, dst_stride) int32 cuda tensor), w, h,
+        shifts, mct, irreversible and (optionally) src_stride -- every src in
+        format fmt (a SAMPLE_* width | SAMPLE_INTERLEAVED | SAMPLE_BIG_ENDIAN).
+        Returns the dsts."""
+        il = bool(fmt & SAMPLE_INTERLEAVED)
+        sb = 4 if fmt & 0xFF == SAMPLE_I32 else (1 if fmt & 0xFF in (SAMPLE_U8, SAMPLE_I8) else 2)
+        if not jobs:
+            return []
+        arr = (LoadJob * len(jobs))()
+        for i, q in enumerate(jobs):
+            src, dst, w, h, off = q["src"], q["dst"], int(q["w"]), int(q["h"]), int(q["byte_offset"])
+            c, dstride = dst.shape[0], dst.shape[2]
+            row = w * c if il else w
+            stride = row if q.get("src_stride") is None else int(q["src_stride"])
+            need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
+            if (src.dtype != _torch_dtype(np.uint8) or src.dim() != 1 or not src.is_contiguous() or not src.is_cuda
+                    or dst.dtype != _torch_dtype(np.int32) or dst.dim() != 3 or tuple(dst.stride()[1:]) != (dstride, 1)
+                    or dst.device != src.device or src.device.index != self.device or dst.shape[1] != h or w > dstride
+                    or stride < row or off < 0 or src.numel() < off + need * sb or c > 4):
+                raise GrkGpuError("dcshift_mct_fwd_jobs: job %d: src flat uint8 holding %d samples from byte_offset, "
+                                  "dst (c <= 4,h,stride >= w) int32 on the codec's device" % (i, need))
+            j = arr[i]
+            for k in range(1 if il else c):
+                j.src[k] = src.data_ptr() + off + k * h * stride * sb
+            for k in range(c):
+                j.dst[k] = dst[k].data_ptr()
+                j.shift[k] = int(q["shifts"][k])
+            j.src_stride, j.dst_stride, j.w, j.h, j.numcomps = stride, dstride, w, h, c
+            j.mct, j.irreversible = int(q["mct"]), 1 if q["irreversible"] else 0
+        lib().grkgpu_set_stream(self._ctx, _stream_handle(jobs[0]["src"].device))
+        _check(lib().grkgpu_dcshift_mct_fwd_jobs(self._ctx, arr, len(jobs), fmt))
+        return [q["dst"] for q in jobs]
 
     def compress_subsampled(self, planes, prec, size, subsampling, params=None, offset=(0, 0), sgnd=False):
         """Subsampled components (SIZ XRsiz / YRsiz): planes[k] is component

@@ -102,6 +102,7 @@ struct CtxDevBufs {
     DevBuf pinfo, precs;
     DevBuf pal;  // JP2 decode: the palette table, uploaded again by every call that looks up
     DevBuf storejobs;  // batch decode: the StoreJob table and its first-workgroup arrays, uploaded by every batch
+    DevBuf loadjobs;   // batch encode: the LoadJob table and its first-workgroup arrays, uploaded by every batch
 };
 struct CtxHostBufs {
     HostBuf h_results, h_packed, h_gather, h_blocks, h_out, h_symoff, h_dwtjobs, h_segs;
@@ -111,6 +112,8 @@ struct CtxHostBufs {
     HostBuf h_slab;
     // batch decode: the items' codestreams packed for one H2D, and the store-job table's staging
     HostBuf h_cs, h_storejobs;
+    // batch encode: the load-job table's staging, and the items' host samples packed for one H2D
+    HostBuf h_loadjobs, h_img;
 };
 
 struct grkgpu_ctx : CtxDevBufs, CtxHostBufs {
@@ -240,16 +243,16 @@ int grkgpu_set_stream(grkgpu_ctx *c, void *stream) {
 // Every buffer of CtxDevBufs / CtxHostBufs, for grkgpu_debug_fill.
 namespace {
 struct CtxBuffers {
-    DevBuf *dev[22];
-    HostBuf *host[15];
+    DevBuf *dev[23];
+    HostBuf *host[17];
 };
 CtxBuffers ctx_buffers(grkgpu_ctx *c) {
     CtxBuffers b{{&c->img, &c->work, &c->coef, &c->ll, &c->scratch, &c->mqout, &c->blocks, &c->results, &c->gather,
                   &c->packed, &c->cs, &c->sym, &c->symoff, &c->dwtjobs, &c->ubuf, &c->segs, &c->dwtjobs53, &c->t1order,
-                  &c->pinfo, &c->precs, &c->pal, &c->storejobs},
+                  &c->pinfo, &c->precs, &c->pal, &c->storejobs, &c->loadjobs},
                  {&c->h_results, &c->h_packed, &c->h_gather, &c->h_blocks, &c->h_out, &c->h_symoff, &c->h_dwtjobs,
                   &c->h_segs, &c->h_pinfo, &c->h_psum, &c->h_precs, &c->h_dwtjobs53, &c->h_slab, &c->h_cs,
-                  &c->h_storejobs}};
+                  &c->h_storejobs, &c->h_loadjobs, &c->h_img}};
     static_assert(sizeof(CtxDevBufs) == sizeof(b.dev) / sizeof(b.dev[0]) * sizeof(DevBuf),
                   "a DevBuf was added to CtxDevBufs: list it in ctx_buffers()");
     static_assert(sizeof(CtxHostBufs) == sizeof(b.host) / sizeof(b.host[0]) * sizeof(HostBuf),
@@ -1198,28 +1201,110 @@ static BandNeed window_need(const TileComp &tc, const Rect &win, std::vector<Rec
 // ---------------------------------------------------------------------------
 // encode
 // ---------------------------------------------------------------------------
-// Encode tiles [tb, te) (a tile shard: j2k_encode's per-tile loop,
-// j2k.cpp:2088-2111) and emit [main header][their tile-parts][EOC] per `parts`.
-// export_blocks: stop after Tier-1 and hand the per-code-block results to the
-// caller instead of writing a codestream (grkgpu_encode_blocks).
-//
-// row0 / nrows: the planes hold only image rows [row0, row0 + nrows) (a tile-
-// row shard: a rank loads just the rows of its tiles); nrows = 0: all rows.
-static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkgpu_cparams *p,
-                         const void *const *planes, int planes_on_device, int32_t fmt, const uint8_t **view,
-                         size_t *outlen,
-                         uint32_t tb = 0, uint32_t te = 0xffffffffu, uint32_t parts = GRKGPU_PART_ALL,
-                         bool export_blocks = false, int force_dist = 0, uint32_t row0 = 0, uint32_t nrows = 0,
-                         uint32_t col0 = 0, uint32_t ncols = 0, const std::vector<uint8_t> *jp2_boxes = nullptr) {
-    if (!c || !planes) return set_err(GRKGPU_EINVAL, "null argument");
-    ActiveCall active;
+// The host half of an encode is EncHost: begin() (parameter and format checks,
+// tile geometry, the code-block tables with their slab offsets, the tile-part
+// counts -- everything that can refuse an image before a device is touched),
+// records() (the coders' results as EncCblkState and pass records, from the
+// device-formed records or from EncResult), finish() (rate allocation and
+// packets per tile on the host pool, the header blob and the PlanItem list).
+// compress_impl runs the three around its device work for one image; the
+// batch encode runs them per item and merges the tables in between.  Offsets
+// in eb (coef_off, out_off), symoff and the tiles' arena_off / lloff start at
+// zero here; the batch rebases them (EncHost::rebase).
+namespace {
+struct EncHost {
+    // ---- in ----
+    const grkgpu_image_desc *img = nullptr;
+    const grkgpu_cparams *p = nullptr;
+    int32_t fmt_in = 0;  // sample_fmt with its flags
+    uint32_t tb = 0, te = 0xffffffffu, parts = GRKGPU_PART_ALL;
+    uint32_t row0 = 0, nrows = 0, col0 = 0, ncols = 0;
+    bool export_blocks = false, batch = false;
+    int force_dist = 0;
+
+    // ---- begin() ----
     CodingParams cp;
+    int32_t fmt = 0, lfmt = 0;  // the width; the width with the flags the loader kernels take
+    bool il = false, big = false, mixed = false;
+    uint32_t sb = 4, nc = 0, iw = 0, ih = 0, pw = 0;
+    uint64_t plane = 0;
+    Rect prect[GRKGPU_MAX_COMPS];
+    uint64_t poff[GRKGPU_MAX_COMPS + 1];
+    uint32_t ntiles = 0;
+    std::vector<Tile> tiles;
+    uint64_t arena = 0, llarena = 0;
+    std::vector<uint64_t> lloff;
+    std::vector<EncBlock> eb;
+    struct BlkInfo {  // position + distortion weights (t1_getwmsedec)
+        uint32_t compno, level, orient;
+        float stepsize;
+        uint32_t tileno, resno, precno, cblkno;
+        Rect r;
+    };
+    std::vector<BlkInfo> binfo;
+    std::vector<uint64_t> symoff;  // per-block symbol-stream slots, sized by the band's numbps bound (nblk + 1)
+    std::vector<uint32_t> pcap;    // per-block pass-record slots (3 numbps - 2 of that bound)
+    uint64_t sym_total = 0, out_total = 0, ptotal = 0;
+    uint32_t maxdepth = 1, nblk = 0;
+    bool need_rc = false;
+    const double *mct_norms = nullptr;
+    uint32_t mct_numcomps = 0;
+    std::vector<std::vector<uint32_t>> tp_counts;  // [tile][poc entry]
+    uint32_t total_tile_parts = 0;
+
+    // ---- records ----
+    std::vector<EncCblkState> cst;
+    EncPass *precs = nullptr;  // the records Tier-2 reads (cst[i].pass0 counts from here)
+    uint64_t npass = 0, nsym = 0;
+    std::vector<EncLayer> layers;
+    std::vector<double> blk_disto;
+    std::vector<uint32_t> blen;  // each block's MQ bytes
+
+    // ---- finish ----
+    struct TileOut {
+        ByteBuf hdr;
+        std::vector<PlanItem> plan;
+        std::vector<uint8_t> tlm;
+        double rate_ms = 0, packet_ms = 0;
+        RateStats rs;
+        bool ok = true;
+    };
+    std::vector<TileOut> touts;
+    ByteBuf hdr, mainhdr;
+    std::vector<PlanItem> plan;
+    size_t tlm_at = 0;
+    uint64_t tile_bound = 0;
+    double t_rate = 0, t_packets = 0;  // summed over tiles (host CPU time)
+    RateStats rsum;
+
+    int begin();
+    // element offset of tile-component tc's first sample in plane k
+    uint64_t plane_org(uint32_t k, const TileComp &tc) const {
+        return (uint64_t)(tc.r.y0 - prect[k].y0) * prect[k].w() + (tc.r.x0 - prect[k].x0);
+    }
+    double wfac(uint32_t i) const {
+        const BlkInfo &bi = binfo[i];
+        return t1_wmsedec_factor(bi.compno, bi.level, bi.orient, cp.irrev ? 0 : 1, (double)bi.stepsize, mct_norms,
+                                 mct_numcomps);
+    }
+    void rebase(uint64_t abase, uint64_t llbase, uint64_t obase, uint64_t sbase);
+    void records_alloc();
+    int records_dev(const PassSum *sm, const uint64_t *p0, EncPass *recs);
+    int records_host_count(const EncResult *res);
+    void records_host_fill(const EncResult *res, EncPass *out);
+    int finish_begin();
+    void finish_tile(size_t ti);
+    int finish_end();
+    void tile_rates(const Rect &tr, uint32_t ntp, double *rates) const;
+};
+
+int EncHost::begin() {
     int rc = setup_params(img, p, cp);
     if (rc) return rc;
     // sample_fmt = width | flags (GRKGPU_SAMPLE_INTERLEAVED / _BIG_ENDIAN), all
     // checked before the context or a device is touched
-    const int32_t fflags = fmt & ~0xff;
-    fmt &= 0xff;
+    const int32_t fflags = fmt_in & ~0xff;
+    fmt = fmt_in & 0xff;
     if (fflags & ~(SMP_INTERLEAVED | SMP_BIG_ENDIAN)) return set_err(GRKGPU_EINVAL, "unknown sample format flags");
     if (fmt < SMP_I32 || fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
     if ((fflags & SMP_BIG_ENDIAN) && fmt != SMP_U16 && fmt != SMP_I16)
@@ -1229,24 +1314,23 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
         if ((img->sgnd[k] != 0) != sg || img->prec[k] > 8 * sample_bytes(fmt))
             return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
     }
-    const uint32_t sb = sample_bytes(fmt);  // bytes per input sample
+    sb = sample_bytes(fmt);  // bytes per input sample
     for (uint32_t k = 1; (fflags & SMP_INTERLEAVED) && k < cp.numcomps; ++k)
         if (cp.dx[k] != cp.dx[0] || cp.dy[k] != cp.dy[0])
             return set_err(GRKGPU_EUNSUPPORTED, "interleaved samples need every component on one grid");
     // pixels in planes[0] (one component's pixels are its plane), and the
     // format as the loader kernels take it
-    const bool il = (fflags & SMP_INTERLEAVED) && cp.numcomps > 1;
-    const bool big = (fflags & SMP_BIG_ENDIAN) != 0;
-    const int32_t lfmt = fmt | (il ? SMP_INTERLEAVED : 0) | (big ? SMP_BIG_ENDIAN : 0);
+    il = (fflags & SMP_INTERLEAVED) && cp.numcomps > 1;
+    big = (fflags & SMP_BIG_ENDIAN) != 0;
+    lfmt = fmt | (il ? SMP_INTERLEAVED : 0) | (big ? SMP_BIG_ENDIAN : 0);
     {
         const uint32_t nt = cp.tw * cp.th;
         if (te > nt) te = nt;
         if (tb > te) return set_err(GRKGPU_EINVAL, "bad tile range");
     }
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    double t_start = now_ms();
-    const uint32_t nc = cp.numcomps, iw = cp.image.w(), ih = cp.image.h();
+    nc = cp.numcomps;
+    iw = cp.image.w();
+    ih = cp.image.h();
     if (nrows == 0) {
         if (row0) return set_err(GRKGPU_EINVAL, "row0 without nrows");
         nrows = ih;
@@ -1257,50 +1341,33 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
         ncols = iw;
     }
     if ((uint64_t)col0 + ncols > iw) return set_err(GRKGPU_EINVAL, "column range outside the image");
-    const uint32_t pw = ncols;                    // row stride of the caller's planes (samples)
-    const uint64_t plane = (uint64_t)pw * nrows;  // samples per plane held by the caller
+    pw = ncols;                    // row stride of the caller's planes (samples)
+    plane = (uint64_t)pw * nrows;  // samples per plane held by the caller
     // subsampled components (SIZ XRsiz / YRsiz): each plane on its own grid
-    bool subs = false, mixed = false;  // mixed: components on different grids
+    bool subs = false;
+    mixed = false;  // components on different grids
     for (uint32_t k = 0; k < nc; ++k) {
         subs = subs || cp.dx[k] != 1 || cp.dy[k] != 1;
         mixed = mixed || cp.dx[k] != cp.dx[0] || cp.dy[k] != cp.dy[0];
     }
+    if (batch && subs) return set_err(GRKGPU_EUNSUPPORTED, "a subsampled component is not supported in a batch");
+    if (batch && cp.mct == 2) return set_err(GRKGPU_EUNSUPPORTED, "a custom MCT is not supported in a batch");
     // the rectangle each caller plane covers (the rows / columns held, on the
     // component's grid: ceil(x / dx), TileComponent.cpp:150-196 -- a tile's
     // plane holds its tile-component, as grk_write_tile's data does,
     // TileProcessor.cpp:1923-1972), its stride, and its offset in the staging
     // buffer (samples)
-    Rect prect[GRKGPU_MAX_COMPS];
-    uint64_t poff[GRKGPU_MAX_COMPS + 1];
     poff[0] = 0;
     const Rect held{cp.image.x0 + col0, cp.image.y0 + row0, cp.image.x0 + col0 + ncols, cp.image.y0 + row0 + nrows};
     for (uint32_t k = 0; k < nc; ++k) {
         prect[k] = comp_rect(held, cp.dx[k], cp.dy[k]);
         poff[k + 1] = poff[k] + (uint64_t)prect[k].w() * prect[k].h();
     }
-    (void)subs;
-    // element offset of tile-component tc's first sample in plane k
-    auto plane_org = [&](uint32_t k, const TileComp &tc) {
-        return (uint64_t)(tc.r.y0 - prect[k].y0) * prect[k].w() + (tc.r.x0 - prect[k].x0);
-    };
 
     // geometry for every tile of the shard, arena offsets, block table
-    const uint32_t ntiles = te - tb;
-    std::vector<Tile> tiles(ntiles);
-    uint64_t arena = 0, llarena = 0;
-    std::vector<uint64_t> lloff(ntiles * nc);
-    std::vector<EncBlock> eb;
-    struct BlkInfo {  // position + distortion weights (t1_getwmsedec)
-        uint32_t compno, level, orient;
-        float stepsize;
-        uint32_t tileno, resno, precno, cblkno;
-        Rect r;
-    };
-    std::vector<BlkInfo> binfo;
-    std::vector<uint64_t> symoff;  // per-block symbol-stream slots, sized by the band's numbps bound
-    std::vector<uint32_t> pcap;    // per-block pass-record slots (3 numbps - 2 of that bound)
-    uint64_t sym_total = 0;
-    uint32_t maxdepth = 1;
+    ntiles = te - tb;
+    tiles.resize(ntiles);
+    lloff.resize((size_t)ntiles * nc);
     // tile geometry (independent per tile) on the host pool, then the block
     // table in tile order
     for (uint32_t t = 0; t < ntiles; ++t) {
@@ -1360,14 +1427,429 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
             });
         }
     }
-    const uint32_t nblk = (uint32_t)eb.size();
-    uint64_t out_total = 0;
+    nblk = (uint32_t)eb.size();
+    out_total = 0;
+    ptotal = 0;
     for (uint32_t i = 0; i < nblk; ++i) {  // MQ output slab: t1_enc_slab_bytes at the band's bound (+ the zero pad byte before)
         EncBlock &b = eb[i];
         out_total += 16;
         b.out_off = out_total;
         out_total += ((uint64_t)t1_enc_slab_bytes(b.w, b.h, cp.cblksty, (pcap[i] + 2) / 3) + 15) & ~15ull;
+        ptotal += pcap[i];
     }
+    symoff.push_back(sym_total);
+    // per-pass distortion only when some layer is rate-controlled
+    // (TileProcessor::needs_rate_control, TileProcessor.cpp:260-266)
+    need_rc = force_dist != 0;
+    for (uint32_t l = 0; l < cp.numlayers; ++l)
+        need_rc = need_rc || (cp.disto_alloc && cp.rates[l] > 0.0) || (cp.fixed_quality && cp.distoratio[l] > 0.0f);
+    if (cp.mct == 1) {  // TileProcessor::t1_encode (TileProcessor.cpp:1535-1551), mct.cpp:65-79
+        static const double kRev[3] = {1.732, .8292, .8292}, kIrrev[3] = {1.732, 1.805, 1.573};
+        mct_norms = cp.irrev ? kIrrev : kRev;
+        mct_numcomps = 3;
+    } else {  // custom MCT: the inverse's column norms (TileProcessor.cpp:1548-1551); else none
+        mct_numcomps = nc;
+        if (cp.mct == 2) mct_norms = cp.mct_norms;  // (cp is a member: an EncHost is never copied after begin())
+    }
+    if (export_blocks) return GRKGPU_OK;
+    // tile-parts of every tile (j2k_calculate_tp, j2k.cpp:2990-3048): needed
+    // for the TLM marker and the rate bookkeeping even outside the shard
+    const uint32_t ntot = cp.tw * cp.th;
+    tp_counts.resize(ntot);
+    total_tile_parts = 0;
+    for (uint32_t t = 0; t < ntot; ++t) {
+        Tile tmp;
+        const Tile *tp = nullptr;
+        if (t >= tb && t < te) tp = &tiles[t - tb];
+        else if (cp.tp_on) {
+            tmp.index = t;
+            tmp.r = tile_rect(cp, t);
+            tmp.comps.resize(nc);
+            for (uint32_t k = 0; k < nc; ++k) build_tilecomp(tmp.comps[k], tmp.r, cp, k, true);
+            tp = &tmp;
+        }
+        if (tp) tp_counts[t] = tile_part_counts(cp, *tp);
+        else tp_counts[t].assign(num_poc_entries(cp), 1);
+        uint32_t n = 0;
+        for (uint32_t v : tp_counts[t]) n += v;
+        if (n > 255) return set_err(GRKGPU_EUNSUPPORTED, "more than 255 tile-parts in a tile");
+        total_tile_parts += n;
+    }
+    return GRKGPU_OK;
+}
+
+// the item's place in the merged tables of a batch: coefficient arena, LL
+// arena, MQ slab and symbol arena bases
+void EncHost::rebase(uint64_t abase, uint64_t llbase, uint64_t obase, uint64_t sbase) {
+    for (EncBlock &b : eb) {
+        b.coef_off += abase;
+        b.out_off += obase;
+    }
+    for (uint64_t &o : symoff) o += sbase;
+    for (Tile &tile : tiles)
+        for (TileComp &tc : tile.comps) tc.arena_off += abase;
+    for (uint64_t &o : lloff) o += llbase;
+}
+
+void EncHost::records_alloc() {
+    cst.assign(nblk, EncCblkState{});
+    layers.assign((size_t)nblk * cp.numlayers, EncLayer{0, 0, 0, 0.0});
+    blk_disto.assign(nblk, 0.0);
+    blen.assign(nblk, 0);
+    npass = 0;
+    nsym = 0;
+}
+
+// the device-formed records (launch_pass_records): sm = this image's block
+// summaries, p0 = its blocks' record slots (nblk + 1), recs = the record at
+// slot p0[0]
+int EncHost::records_dev(const PassSum *sm, const uint64_t *p0, EncPass *recs) {
+    records_alloc();
+    for (uint32_t i = 0; i < nblk; ++i) {
+        const PassSum &q = sm[i];
+        if (q.bad & 1u) return set_err(GRKGPU_EUNSUPPORTED, "code-block numbps exceeds its band's bound");
+        if (q.bad & 2u) return set_err(GRKGPU_EUNSUPPORTED, "too many coding passes");
+        if (q.bad & 4u) return set_err(GRKGPU_EUNSUPPORTED, "MQ slab overflow");
+        nsym += q.nsym;
+        EncCblkState &st = cst[i];
+        st.numbps = q.numbps;
+        st.numpasses = q.numpasses;
+        st.pass0 = (uint32_t)(p0[i] - p0[0]);
+        st.dev_off = eb[i].out_off;
+        st.smin = q.smin;
+        st.smax = q.smax;
+        st.s0max = q.s0max;
+        st.z0 = q.z0 != 0;
+        blk_disto[i] = q.disto;
+        blen[i] = q.len;
+    }
+    if (ptotal > 0xffffffffu) return set_err(GRKGPU_EUNSUPPORTED, "too many coding passes");
+    npass = ptotal;
+    precs = recs;
+    return GRKGPU_OK;
+}
+
+// the host-formed records: validate and lay the blocks' passes out (prefix
+// sum; npass records), then -- records_host_fill -- fill them on the host
+// pool (blocks are independent)
+int EncHost::records_host_count(const EncResult *res) {
+    records_alloc();
+    for (uint32_t i = 0; i < nblk; ++i) {
+        const EncResult &r = res[i];
+        if (r.pad) return set_err(GRKGPU_EUNSUPPORTED, "code-block numbps exceeds its band's bound");
+        if (r.numpasses > GRK_MAX_PASSES) return set_err(GRKGPU_EUNSUPPORTED, "too many coding passes");
+        const uint32_t np = r.numpasses;
+        if (np && r.rate[np - 1] > t1_enc_slab_bytes(eb[i].w, eb[i].h, cp.cblksty, r.numbps)) return set_err(GRKGPU_EUNSUPPORTED, "MQ slab overflow");
+        nsym += r.nsym;
+        EncCblkState &st = cst[i];
+        st.numbps = r.numbps;
+        st.numpasses = np;
+        st.pass0 = (uint32_t)npass;
+        st.dev_off = eb[i].out_off;
+        npass += np;
+    }
+    return GRKGPU_OK;
+}
+
+void EncHost::records_host_fill(const EncResult *res, EncPass *out0) {
+    host_parallel_for(nblk, 1024, [&](size_t b0, size_t b1) {
+        for (size_t i = b0; i < b1; ++i) {
+            const EncResult &r = res[i];
+            const uint32_t np = r.numpasses;
+            EncPass *out = out0 + cst[i].pass0;
+            double cum = 0.0;
+            const double wf = need_rc ? wfac((uint32_t)i) : 0.0;
+            for (uint32_t k = 0; k < np; ++k) {
+                EncPass ps;
+                ps.rate = r.rate[k];
+                ps.len = r.rate[k] - (k ? r.rate[k - 1] : 0);
+                // t1_enc_is_term_pass (t1.cpp:1131-1151)
+                {
+                    const int32_t bp = k == 0 ? (int32_t)r.numbps - 1 : (int32_t)r.numbps - 2 - (int32_t)((k - 1) / 3);
+                    const int pt = k == 0 ? 2 : (int)((k - 1) % 3);
+                    ps.term = t1_pass_term(cp.cblksty, bp, pt, r.numbps);
+                }
+                ps.slope = 0;
+                if (need_rc) {  // t1_encode_cblk's cumulative distortion (t1.cpp:1249-1254)
+                    const int32_t bpno = k == 0 ? (int32_t)r.numbps - 1 : (int32_t)r.numbps - 2 - (int32_t)((k - 1) / 3);
+                    cum += t1_wmsedec_at(wf, r.nmsedec[k], bpno);
+                }
+                ps.dd = cum;
+                out[k] = ps;
+            }
+            // the simple PCRD's slope range over this block's passes, from
+            // the records just written (pcrd_simple's own loop, TileEnc::slopes)
+            block_slopes(cst[i], out);
+            blk_disto[i] = cum;
+        }
+    });
+    precs = out0;
+    for (uint32_t i = 0; i < nblk; ++i) blen[i] = res[i].len;
+}
+
+// j2k_update_rates (j2k.cpp:2806-2926): layer ratios -> byte budgets per tile
+void EncHost::tile_rates(const Rect &tr, uint32_t ntp, double *rates) const {
+    const uint32_t L = cp.numlayers;
+    const double header_size = (double)mainhdr.size();
+    const double bits_empty = 8.0 * cp.dx[0] * cp.dy[0], size_pixel = (double)nc * cp.prec[0];
+    const uint32_t width = iw, height = ih;
+    const double offset = (double)(cp.tp_on ? (float)((ntp - 1) * 14) : 0.0f) / L;
+    const uint64_t npix = (uint64_t)tr.w() * tr.h();
+    for (uint32_t k = 0; k < L; ++k) {
+        rates[k] = cp.rates[k];
+        if (rates[k] > 0.0f) rates[k] = (size_pixel * (double)npix) / (rates[k] * bits_empty) - offset;
+    }
+    rates[L] = 0;
+    const double sot_adjust = ((double)npix * header_size) / ((double)width * height);
+    double *r = rates;
+    if (*r > 0.0) {
+        *r -= sot_adjust;
+        if (*r < 30.0f) *r = 30.0f;
+    }
+    ++r;
+    const uint32_t last_res = L - 1;
+    for (uint32_t k = 1; k < last_res; ++k) {
+        if (*r > 0.0) {
+            *r -= sot_adjust;
+            if (*r < *(r - 1) + 10.0) *r = (*(r - 1)) + 20.0;
+        }
+        ++r;
+    }
+    if (*r > 0.0) {
+        *r -= (sot_adjust + 2.0);
+        if (*r < *(r - 1) + 10.0) *r = (*(r - 1)) + 20.0;
+    }
+}
+
+// Tier-2 + headers on the host (j2k_encode :2059, j2k_post_write_tile
+// :2196, T2::encode_packets): only header BITS are produced here; the
+// code-block bytes never visit the host -- a gather kernel assembles the
+// codestream in HBM and one D2H copies it into the pinned output buffer.
+// finish_begin(): the main header and the rate allocator's tile bound;
+// finish_tile(ti): one tile's tile-parts into its own header blob and plan;
+// finish_end(): those appended in tile order, TLM and EOC.
+int EncHost::finish_begin() {
+    hdr.v.reserve(batch ? 4096 : 1 << 20);
+    plan.reserve(nblk + 64);
+    write_main_header(mainhdr, cp, &tlm_at, total_tile_parts);
+    if (parts & GRKGPU_PART_HEADER) {
+        hdr.putn(mainhdr.v.data(), mainhdr.size());
+        plan.push_back({0, (uint32_t)hdr.size(), 0});
+    }
+    // tile buffer bound for the rate allocator (j2k_post_write_tile :2196-2222,
+    // j2k_get_specific_header_sizes :4346-4366, then SOT / POC / SOD / EOC room)
+    const bool cinema = cp.rsiz == RSIZ_CINEMA_2K || cp.rsiz == RSIZ_CINEMA_4K;
+    {
+        uint64_t ts = 0;
+        for (uint32_t k = 0; k < nc; ++k) ts += (uint64_t)cp.tdx * cp.tdy * cp.prec[k];
+        ts = (uint64_t)((double)ts * 0.1625);
+        uint32_t max_tp = 0;
+        for (auto &v : tp_counts) {
+            uint32_t n = 0;
+            for (uint32_t x : v) n += x;
+            max_tp = std::max(max_tp, n);
+        }
+        uint64_t spec = 12ull * max_tp;
+        if (!cinema) {
+            const uint64_t coc = 6 + ((cp.csty & CSTY_PRT) ? 5 + cp.numres : 5);
+            spec += (uint64_t)(nc - 1) * coc * 2;
+        }
+        spec += 4 + 9ull * num_poc_entries(cp);
+        ts += spec;
+        if (ts < 256ull * nc) ts = 256ull * nc;
+        const uint64_t pocsz = (!cinema && cp.numpocs) ? 4 + (5 + 2 * (nc <= 256 ? 1 : 2)) * cp.numpocs : 0;
+        tile_bound = ts - 12 - pocsz - 4;
+    }
+    // Tiles are independent in rate control and Tier-2 (their blocks, layer
+    // records and packet state are disjoint): each tile's tile-parts are
+    // formed on the host pool into its own header blob and plan, then
+    // appended in tile order (header runs rebased onto the shared blob).
+    touts.clear();
+    touts.resize(tiles.size());
+    return GRKGPU_OK;
+}
+
+void EncHost::finish_tile(size_t ti) {
+    const uint32_t L = cp.numlayers;
+    const bool cinema = cp.rsiz == RSIZ_CINEMA_2K || cp.rsiz == RSIZ_CINEMA_4K;
+    Tile &tile = tiles[ti];
+    TileOut &to = touts[ti];
+    TileEnc tenc;
+    tenc.tile = &tile;
+    tenc.cblk = &cst;
+    tenc.passes = precs;
+    tenc.layers = &layers;
+    tenc.slopes = true;  // the pass-record fill above computed every block's slope range
+    init_enc_pocs(cp, tenc);
+    CodingParams cpt = cp;
+    uint32_t ntp = 0;
+    for (uint32_t v : tp_counts[tile.index]) ntp += v;
+    tile_rates(tile.r, ntp, cpt.rates);
+    tenc.distotile = 0;
+    for (auto &tc : tile.comps) for_each_cblk(tc, [&](Band &, Cblk &cb) { tenc.distotile += blk_disto[cb.gidx]; });
+    const double tr0 = now_ms();
+    if (!rate_allocate(cpt, tenc, tile_bound, &to.rs)) { to.ok = false; return; }
+    const double tp0 = now_ms();
+    to.rate_ms = tp0 - tr0;
+    // The tile-parts' packets (T2::encode_packets per tile-part,
+    // T2.cpp:64-125).  Tile-parts whose packets touch disjoint
+    // precincts (tile-parts split by component or resolution, no POC
+    // revisiting a precinct: the cinema profiles) are independent --
+    // a packet header's state is its precinct's tag trees and its
+    // code-blocks' inclusion records -- and are written in parallel,
+    // each from its own SOP packet number; the bytes are the same.
+    struct TpOut {
+        uint32_t pino, tpn, packno0 = 0;
+        std::vector<PacketId> order;
+        ByteBuf hdr;
+        std::vector<PlanItem> plan;
+    };
+    std::vector<TpOut> tps;
+    for (uint32_t pino = 0; pino < tenc.pocs.size(); ++pino)
+        for (uint32_t tpn = 0; tpn < tp_counts[tile.index][pino]; ++tpn) {
+            tps.push_back(TpOut{pino, tpn});
+            encode_packet_order(cpt, tenc, pino, tpn, tps.back().order);
+        }
+    bool disjoint = tps.size() > 1;
+    {
+        std::vector<int32_t> owner;  // precinct -> tile-part
+        std::vector<std::vector<uint32_t>> pb(nc);  // first precinct index of (component, resolution)
+        uint32_t np = 0;
+        for (uint32_t k = 0; k < nc; ++k) {
+            pb[k].resize(tile.comps[k].numres);
+            for (uint32_t r = 0; r < tile.comps[k].numres; ++r) {
+                pb[k][r] = np;
+                np += tile.comps[k].res[r].pw * tile.comps[k].res[r].ph;
+            }
+        }
+        owner.assign(np, -1);
+        uint32_t packno = 0;
+        for (size_t j = 0; j < tps.size() && disjoint; ++j) {
+            tps[j].packno0 = packno;
+            for (auto &pk : tps[j].order) {
+                if (pk.layno >= L) continue;
+                ++packno;
+                int32_t &o = owner[pb[pk.compno][pk.resno] + pk.precno];
+                if (o >= 0 && o != (int32_t)j) { disjoint = false; break; }
+                o = (int32_t)j;
+            }
+        }
+    }
+    auto write_tp = [&](TpOut &t, TileEnc &te) {
+        for (auto &pk : t.order)
+            if (pk.layno < L) write_packet(cpt, te, pk, t.hdr, t.plan);
+    };
+    if (disjoint) {
+        host_parallel_for(tps.size(), 1, [&](size_t j0, size_t j1) {
+            for (size_t j = j0; j < j1; ++j) {
+                TileEnc te = tenc;  // shares the tile's state; its own packet counter
+                te.packno = tps[j].packno0;
+                write_tp(tps[j], te);
+            }
+        });
+    } else {
+        for (auto &t : tps) write_tp(t, tenc);
+    }
+    uint32_t tpno = 0;
+    ByteBuf &th = to.hdr;
+    for (auto &t : tps) {
+        const size_t sot = th.size();
+        th.put16(0xFF90); th.put16(10); th.put16(tile.index); th.put32(0); th.put8(tpno); th.put8(ntp);
+        if (tpno == 0 && !cinema && cp.numpocs) write_poc(th, cpt);
+        th.put16(0xFF93);
+        to.plan.push_back({sot, (uint32_t)(th.size() - sot), 0});
+        const size_t first = to.plan.size() - 1;
+        const uint64_t base = th.size();
+        th.putn(t.hdr.v.data(), t.hdr.size());
+        for (PlanItem it : t.plan) {
+            if (it.kind == 0) it.src += base;
+            to.plan.push_back(it);
+        }
+        uint64_t psot = 0;
+        for (size_t i = first; i < to.plan.size(); ++i) psot += to.plan[i].len;
+        th.set32(sot + 6, (uint32_t)psot);  // Psot (j2k.cpp:2418-2426)
+        if (cinema) {
+            to.tlm.push_back((uint8_t)tile.index);
+            for (int b = 3; b >= 0; --b) to.tlm.push_back((uint8_t)(psot >> (8 * b)));
+        }
+        ++tpno;
+    }
+    to.packet_ms = now_ms() - tp0;
+}
+
+int EncHost::finish_end() {
+    std::vector<uint8_t> tlm;  // TLM records (j2k_update_tlm, j2k.cpp:6649-6660)
+    for (auto &to : touts) {
+        if (!to.ok) return set_err(GRKGPU_EINVAL, "rate allocation failed");
+        t_rate += to.rate_ms;
+        t_packets += to.packet_ms;
+        rsum.probes += to.rs.probes;
+        rsum.skipped += to.rs.skipped;
+        rsum.evals += to.rs.evals;
+        rsum.sims += to.rs.sims;
+        rsum.form_ms += to.rs.form_ms;
+        rsum.sim_ms += to.rs.sim_ms;
+        const uint64_t base = hdr.size();
+        hdr.putn(to.hdr.v.data(), to.hdr.size());
+        for (PlanItem it : to.plan) {
+            if (it.kind == 0) it.src += base;
+            plan.push_back(it);
+        }
+        tlm.insert(tlm.end(), to.tlm.begin(), to.tlm.end());
+    }
+    if ((parts & GRKGPU_PART_HEADER) && tlm_at && tlm.size() == 5ull * total_tile_parts)
+        memcpy(hdr.v.data() + tlm_at, tlm.data(), tlm.size());  // j2k_write_updated_tlm (:2555-2577)
+    if (parts & GRKGPU_PART_EOC) {
+        size_t eoc = hdr.size();
+        hdr.put16(0xFFD9);
+        plan.push_back({eoc, 2, 0});
+    }
+    return GRKGPU_OK;
+}
+}  // namespace
+
+// Encode tiles [tb, te) (a tile shard: j2k_encode's per-tile loop,
+// j2k.cpp:2088-2111) and emit [main header][their tile-parts][EOC] per `parts`.
+// export_blocks: stop after Tier-1 and hand the per-code-block results to the
+// caller instead of writing a codestream (grkgpu_encode_blocks).
+//
+// row0 / nrows: the planes hold only image rows [row0, row0 + nrows) (a tile-
+// row shard: a rank loads just the rows of its tiles); nrows = 0: all rows.
+static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkgpu_cparams *p,
+                         const void *const *planes, int planes_on_device, int32_t fmt_in, const uint8_t **view,
+                         size_t *outlen,
+                         uint32_t tb = 0, uint32_t te = 0xffffffffu, uint32_t parts = GRKGPU_PART_ALL,
+                         bool export_blocks = false, int force_dist = 0, uint32_t row0 = 0, uint32_t nrows = 0,
+                         uint32_t col0 = 0, uint32_t ncols = 0, const std::vector<uint8_t> *jp2_boxes = nullptr) {
+    if (!c || !planes) return set_err(GRKGPU_EINVAL, "null argument");
+    ActiveCall active;
+    // the host half (EncHost): every check that needs no device, the tile
+    // geometry and the block tables
+    EncHost H;
+    H.img = img; H.p = p; H.fmt_in = fmt_in;
+    H.tb = tb; H.te = te; H.parts = parts;
+    H.row0 = row0; H.nrows = nrows; H.col0 = col0; H.ncols = ncols;
+    H.export_blocks = export_blocks; H.force_dist = force_dist;
+    double t_start = now_ms();
+    int rc = H.begin();
+    if (rc) return rc;
+    const CodingParams &cp = H.cp;
+    tb = H.tb; te = H.te;
+    const int32_t fmt = H.fmt, lfmt = H.lfmt;
+    const bool il = H.il, big = H.big, mixed = H.mixed, need_rc = H.need_rc;
+    const uint32_t sb = H.sb, nc = H.nc, pw = H.pw, nblk = H.nblk, maxdepth = H.maxdepth;
+    const uint64_t plane = H.plane, arena = H.arena, llarena = H.llarena, sym_total = H.sym_total,
+                   out_total = H.out_total;
+    const Rect *prect = H.prect;
+    const uint64_t *poff = H.poff;
+    std::vector<Tile> &tiles = H.tiles;
+    const std::vector<uint64_t> &lloff = H.lloff, &symoff = H.symoff;
+    const std::vector<EncBlock> &eb = H.eb;
+    const std::vector<EncHost::BlkInfo> &binfo = H.binfo;
+    const std::vector<uint32_t> &pcap = H.pcap;
+    auto plane_org = [&](uint32_t k, const TileComp &tc) { return H.plane_org(k, tc); };
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
     HIPCHK(c->work.ensure(arena * 4 + 256));
     HIPCHK(c->coef.ensure(arena * 4 + 256));
     HIPCHK(c->ll.ensure(llarena * 4 + 256));
@@ -1378,7 +1860,6 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
     HIPCHK(c->results.ensure((size_t)nblk * sizeof(EncResult) + 256));
     HIPCHK(c->h_results.ensure((size_t)nblk * sizeof(EncResult) + 256));
     HIPCHK(c->h_blocks.ensure((size_t)nblk * sizeof(EncBlock) + 256));
-    symoff.push_back(sym_total);
     HIPCHK(c->sym.ensure(sym_total + 256));
     HIPCHK(c->symoff.ensure(symoff.size() * 8 + 256));
     HIPCHK(c->h_symoff.ensure(symoff.size() * 8 + 256));
@@ -1510,21 +1991,6 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
                             c->sym.as<uint8_t>(), c->symoff.as<uint64_t>(), maxdepth, c->mqout.as<uint8_t>(),
                             c->results.as<EncResult>(), s, cp.cblksty, lone_call() ? lone_bpw(nblk) : 0,
                             c->t1order.as<uint32_t>()));
-    // per-pass distortion only when some layer is rate-controlled
-    // (TileProcessor::needs_rate_control, TileProcessor.cpp:260-266)
-    bool need_rc = force_dist != 0;
-    for (uint32_t l = 0; l < cp.numlayers; ++l)
-        need_rc = need_rc || (cp.disto_alloc && cp.rates[l] > 0.0) || (cp.fixed_quality && cp.distoratio[l] > 0.0f);
-    const double *mct_norms = nullptr;
-    uint32_t mct_numcomps = 0;
-    if (cp.mct == 1) {  // TileProcessor::t1_encode (TileProcessor.cpp:1535-1551), mct.cpp:65-79
-        static const double kRev[3] = {1.732, .8292, .8292}, kIrrev[3] = {1.732, 1.805, 1.573};
-        mct_norms = cp.irrev ? kIrrev : kRev;
-        mct_numcomps = 3;
-    } else {  // custom MCT: the inverse's column norms (TileProcessor.cpp:1548-1551); else none
-        mct_numcomps = nc;
-        if (cp.mct == 2) mct_norms = cp.mct_norms;
-    }
     // With rate control the pass records are formed on the device
     // (launch_pass_records): the host fills each block's distortion factor
     // and record slots while the GPU codes, and after the coders only the
@@ -1537,9 +2003,7 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
         double *wf = c->h_pinfo.as<double>();
         uint64_t *p0 = (uint64_t *)(wf + nblk);
         for (uint32_t i = 0; i < nblk; ++i) {
-            const BlkInfo &bi = binfo[i];
-            wf[i] = t1_wmsedec_factor(bi.compno, bi.level, bi.orient, cp.irrev ? 0 : 1, (double)bi.stepsize, mct_norms,
-                                      mct_numcomps);
+            wf[i] = H.wfac(i);
             p0[i] = ptotal;
             ptotal += pcap[i];
         }
@@ -1576,96 +2040,21 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
     // code-block bytes never visit the host -- a gather kernel assembles the
     // codestream in HBM and one D2H copies it into the pinned output buffer.
     double t_t2 = now_ms();
-    const uint32_t L = cp.numlayers;
-    std::vector<EncCblkState> cst(nblk);
-    std::vector<EncPass> &passes = c->enc_passes;  // host-formed records: [0, npass) filled below
-    EncPass *precs = nullptr;                      // the records Tier-2 reads: these, or the device's
-    uint64_t npass = 0;
-    std::vector<EncLayer> layers((size_t)nblk * L, EncLayer{0, 0, 0, 0.0});
-    std::vector<double> blk_disto(nblk, 0.0);
-    std::vector<uint32_t> blen(nblk, 0);  // each block's MQ bytes
-    uint64_t nsym = 0;
     if (dev_rec) {
-        const PassSum *sm = c->h_psum.as<PassSum>();
-        const uint64_t *p0 = (const uint64_t *)(c->h_pinfo.as<double>() + nblk);
-        for (uint32_t i = 0; i < nblk; ++i) {
-            const PassSum &q = sm[i];
-            if (q.bad & 1u) return set_err(GRKGPU_EUNSUPPORTED, "code-block numbps exceeds its band's bound");
-            if (q.bad & 2u) return set_err(GRKGPU_EUNSUPPORTED, "too many coding passes");
-            if (q.bad & 4u) return set_err(GRKGPU_EUNSUPPORTED, "MQ slab overflow");
-            nsym += q.nsym;
-            EncCblkState &st = cst[i];
-            st.numbps = q.numbps;
-            st.numpasses = q.numpasses;
-            st.pass0 = (uint32_t)p0[i];
-            st.dev_off = eb[i].out_off;
-            st.smin = q.smin;
-            st.smax = q.smax;
-            st.s0max = q.s0max;
-            st.z0 = q.z0 != 0;
-            blk_disto[i] = q.disto;
-            blen[i] = q.len;
-        }
-        if (ptotal > 0xffffffffu) return set_err(GRKGPU_EUNSUPPORTED, "too many coding passes");
-        npass = ptotal;
-        precs = c->h_precs.as<EncPass>();
+        rc = H.records_dev(c->h_psum.as<PassSum>(), (const uint64_t *)(c->h_pinfo.as<double>() + nblk),
+                           c->h_precs.as<EncPass>());
+        if (rc) return rc;
     } else {
-        // per-block pass records: validate and lay the blocks' passes out (prefix
-        // sum), then fill them on the host pool (blocks are independent)
-        {
-            for (uint32_t i = 0; i < nblk; ++i) {
-                const EncResult &r = res[i];
-                if (r.pad) return set_err(GRKGPU_EUNSUPPORTED, "code-block numbps exceeds its band's bound");
-                if (r.numpasses > GRK_MAX_PASSES) return set_err(GRKGPU_EUNSUPPORTED, "too many coding passes");
-                const uint32_t np = r.numpasses;
-                if (np && r.rate[np - 1] > t1_enc_slab_bytes(eb[i].w, eb[i].h, cp.cblksty, r.numbps)) return set_err(GRKGPU_EUNSUPPORTED, "MQ slab overflow");
-                nsym += r.nsym;
-                EncCblkState &st = cst[i];
-                st.numbps = r.numbps;
-                st.numpasses = np;
-                st.pass0 = (uint32_t)npass;
-                st.dev_off = eb[i].out_off;
-                npass += np;
-            }
-            if (passes.size() < npass) passes.resize(npass);
-        }
-        host_parallel_for(nblk, 1024, [&](size_t b0, size_t b1) {
-            for (size_t i = b0; i < b1; ++i) {
-                const EncResult &r = res[i];
-                const uint32_t np = r.numpasses;
-                EncPass *out = passes.data() + cst[i].pass0;
-                double cum = 0.0;
-                const BlkInfo &bi = binfo[i];
-                const double wfac = need_rc ? t1_wmsedec_factor(bi.compno, bi.level, bi.orient, cp.irrev ? 0 : 1,
-                                                                (double)bi.stepsize, mct_norms, mct_numcomps)
-                                            : 0.0;
-                for (uint32_t k = 0; k < np; ++k) {
-                    EncPass ps;
-                    ps.rate = r.rate[k];
-                    ps.len = r.rate[k] - (k ? r.rate[k - 1] : 0);
-                    // t1_enc_is_term_pass (t1.cpp:1131-1151)
-                    {
-                        const int32_t bp = k == 0 ? (int32_t)r.numbps - 1 : (int32_t)r.numbps - 2 - (int32_t)((k - 1) / 3);
-                        const int pt = k == 0 ? 2 : (int)((k - 1) % 3);
-                        ps.term = t1_pass_term(cp.cblksty, bp, pt, r.numbps);
-                    }
-                    ps.slope = 0;
-                    if (need_rc) {  // t1_encode_cblk's cumulative distortion (t1.cpp:1249-1254)
-                        const int32_t bpno = k == 0 ? (int32_t)r.numbps - 1 : (int32_t)r.numbps - 2 - (int32_t)((k - 1) / 3);
-                        cum += t1_wmsedec_at(wfac, r.nmsedec[k], bpno);
-                    }
-                    ps.dd = cum;
-                    out[k] = ps;
-                }
-                // the simple PCRD's slope range over this block's passes, from
-                // the records just written (pcrd_simple's own loop, TileEnc::slopes)
-                block_slopes(cst[i], out);
-                blk_disto[i] = cum;
-            }
-        });
-        precs = passes.data();
-        for (uint32_t i = 0; i < nblk; ++i) blen[i] = res[i].len;
+        rc = H.records_host_count(res);
+        if (rc) return rc;
+        std::vector<EncPass> &passes = c->enc_passes;  // host-formed records: [0, npass) filled below
+        if (passes.size() < H.npass) passes.resize(H.npass);
+        H.records_host_fill(res, passes.data());
     }
+    const std::vector<EncCblkState> &cst = H.cst;
+    const std::vector<uint32_t> &blen = H.blen;
+    const EncPass *precs = H.precs;  // the records Tier-2 reads: the host-formed ones, or the device's
+    const uint64_t npass = H.npass, nsym = H.nsym;
     const double t_passrec = now_ms() - t_t2;
     if (export_blocks) {
         // the MQ slab to pinned host memory, then one record per block
@@ -1681,7 +2070,7 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
         }
         for (uint32_t i = 0; i < nblk; ++i) {
             grkgpu_block_info &o = c->bexp[i];
-            const BlkInfo &bi = binfo[i];
+            const EncHost::BlkInfo &bi = binfo[i];
             o.tileno = bi.tileno; o.compno = bi.compno; o.resno = bi.resno; o.bandno = bi.orient;
             o.precno = bi.precno; o.cblkno = bi.cblkno;
             o.x0 = bi.r.x0; o.y0 = bi.r.y0; o.x1 = bi.r.x1; o.y1 = bi.r.y1;
@@ -1709,246 +2098,17 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
         st0.total_ms = (float)(now_ms() - t_start);
         return GRKGPU_OK;
     }
-    // tile-parts of every tile (j2k_calculate_tp, j2k.cpp:2990-3048): needed
-    // for the TLM marker and the rate bookkeeping even outside the shard
-    const uint32_t ntot = cp.tw * cp.th;
-    std::vector<std::vector<uint32_t>> tp_counts(ntot);  // [tile][poc entry]
-    uint32_t total_tile_parts = 0;
-    for (uint32_t t = 0; t < ntot; ++t) {
-        Tile tmp;
-        const Tile *tp = nullptr;
-        if (t >= tb && t < te) tp = &tiles[t - tb];
-        else if (cp.tp_on) {
-            tmp.index = t;
-            tmp.r = tile_rect(cp, t);
-            tmp.comps.resize(nc);
-            for (uint32_t k = 0; k < nc; ++k) build_tilecomp(tmp.comps[k], tmp.r, cp, k, true);
-            tp = &tmp;
-        }
-        if (tp) tp_counts[t] = tile_part_counts(cp, *tp);
-        else tp_counts[t].assign(num_poc_entries(cp), 1);
-        uint32_t n = 0;
-        for (uint32_t v : tp_counts[t]) n += v;
-        if (n > 255) return set_err(GRKGPU_EUNSUPPORTED, "more than 255 tile-parts in a tile");
-        total_tile_parts += n;
-    }
-    ByteBuf hdr;
-    hdr.v.reserve(1 << 20);
-    std::vector<PlanItem> plan;
-    plan.reserve(nblk + 64);
-    size_t tlm_at = 0;
-    ByteBuf mainhdr;
-    write_main_header(mainhdr, cp, &tlm_at, total_tile_parts);
-    if (parts & GRKGPU_PART_HEADER) {
-        hdr.putn(mainhdr.v.data(), mainhdr.size());
-        plan.push_back({0, (uint32_t)hdr.size(), 0});
-    }
-    // j2k_update_rates (j2k.cpp:2806-2926): layer ratios -> byte budgets per tile
-    const double header_size = (double)mainhdr.size();
-    const double bits_empty = 8.0 * cp.dx[0] * cp.dy[0], size_pixel = (double)nc * cp.prec[0];
-    const uint32_t width = iw, height = ih;
-    auto tile_rates = [&](const Rect &tr, uint32_t ntp, double *rates) {
-        const double offset = (double)(cp.tp_on ? (float)((ntp - 1) * 14) : 0.0f) / L;
-        const uint64_t npix = (uint64_t)tr.w() * tr.h();
-        for (uint32_t k = 0; k < L; ++k) {
-            rates[k] = cp.rates[k];
-            if (rates[k] > 0.0f) rates[k] = (size_pixel * (double)npix) / (rates[k] * bits_empty) - offset;
-        }
-        rates[L] = 0;
-        const double sot_adjust = ((double)npix * header_size) / ((double)width * height);
-        double *r = rates;
-        if (*r > 0.0) {
-            *r -= sot_adjust;
-            if (*r < 30.0f) *r = 30.0f;
-        }
-        ++r;
-        const uint32_t last_res = L - 1;
-        for (uint32_t k = 1; k < last_res; ++k) {
-            if (*r > 0.0) {
-                *r -= sot_adjust;
-                if (*r < *(r - 1) + 10.0) *r = (*(r - 1)) + 20.0;
-            }
-            ++r;
-        }
-        if (*r > 0.0) {
-            *r -= (sot_adjust + 2.0);
-            if (*r < *(r - 1) + 10.0) *r = (*(r - 1)) + 20.0;
-        }
-    };
-    // tile buffer bound for the rate allocator (j2k_post_write_tile :2196-2222,
-    // j2k_get_specific_header_sizes :4346-4366, then SOT / POC / SOD / EOC room)
-    const bool cinema = cp.rsiz == RSIZ_CINEMA_2K || cp.rsiz == RSIZ_CINEMA_4K;
-    uint64_t tile_bound;
-    {
-        uint64_t ts = 0;
-        for (uint32_t k = 0; k < nc; ++k) ts += (uint64_t)cp.tdx * cp.tdy * cp.prec[k];
-        ts = (uint64_t)((double)ts * 0.1625);
-        uint32_t max_tp = 0;
-        for (auto &v : tp_counts) {
-            uint32_t n = 0;
-            for (uint32_t x : v) n += x;
-            max_tp = std::max(max_tp, n);
-        }
-        uint64_t spec = 12ull * max_tp;
-        if (!cinema) {
-            const uint64_t coc = 6 + ((cp.csty & CSTY_PRT) ? 5 + cp.numres : 5);
-            spec += (uint64_t)(nc - 1) * coc * 2;
-        }
-        spec += 4 + 9ull * num_poc_entries(cp);
-        ts += spec;
-        if (ts < 256ull * nc) ts = 256ull * nc;
-        const uint64_t pocsz = (!cinema && cp.numpocs) ? 4 + (5 + 2 * (nc <= 256 ? 1 : 2)) * cp.numpocs : 0;
-        tile_bound = ts - 12 - pocsz - 4;
-    }
-    std::vector<uint8_t> tlm;  // TLM records (j2k_update_tlm, j2k.cpp:6649-6660)
-    // Tiles are independent in rate control and Tier-2 (their blocks, layer
-    // records and packet state are disjoint): each tile's tile-parts are
-    // formed on the host pool into its own header blob and plan, then
-    // appended in tile order (header runs rebased onto the shared blob).
-    struct TileOut {
-        ByteBuf hdr;
-        std::vector<PlanItem> plan;
-        std::vector<uint8_t> tlm;
-        double rate_ms = 0, packet_ms = 0;
-        RateStats rs;
-        bool ok = true;
-    };
-    std::vector<TileOut> touts(tiles.size());
-    double t_rate = 0;  // summed over tiles (host CPU time of the rate allocation)
+    rc = H.finish_begin();
+    if (rc) return rc;
     host_parallel_for(tiles.size(), 1, [&](size_t t0, size_t t1) {
-        for (size_t ti = t0; ti < t1; ++ti) {
-            Tile &tile = tiles[ti];
-            TileOut &to = touts[ti];
-            TileEnc tenc;
-            tenc.tile = &tile;
-            tenc.cblk = &cst;
-            tenc.passes = precs;
-            tenc.layers = &layers;
-            tenc.slopes = true;  // the pass-record fill above computed every block's slope range
-            init_enc_pocs(cp, tenc);
-            CodingParams cpt = cp;
-            uint32_t ntp = 0;
-            for (uint32_t v : tp_counts[tile.index]) ntp += v;
-            tile_rates(tile.r, ntp, cpt.rates);
-            tenc.distotile = 0;
-            for (auto &tc : tile.comps) for_each_cblk(tc, [&](Band &, Cblk &cb) { tenc.distotile += blk_disto[cb.gidx]; });
-            const double tr0 = now_ms();
-            if (!rate_allocate(cpt, tenc, tile_bound, &to.rs)) { to.ok = false; continue; }
-            const double tp0 = now_ms();
-            to.rate_ms = tp0 - tr0;
-            // The tile-parts' packets (T2::encode_packets per tile-part,
-            // T2.cpp:64-125).  Tile-parts whose packets touch disjoint
-            // precincts (tile-parts split by component or resolution, no POC
-            // revisiting a precinct: the cinema profiles) are independent --
-            // a packet header's state is its precinct's tag trees and its
-            // code-blocks' inclusion records -- and are written in parallel,
-            // each from its own SOP packet number; the bytes are the same.
-            struct TpOut {
-                uint32_t pino, tpn, packno0 = 0;
-                std::vector<PacketId> order;
-                ByteBuf hdr;
-                std::vector<PlanItem> plan;
-            };
-            std::vector<TpOut> tps;
-            for (uint32_t pino = 0; pino < tenc.pocs.size(); ++pino)
-                for (uint32_t tpn = 0; tpn < tp_counts[tile.index][pino]; ++tpn) {
-                    tps.push_back(TpOut{pino, tpn});
-                    encode_packet_order(cpt, tenc, pino, tpn, tps.back().order);
-                }
-            bool disjoint = tps.size() > 1;
-            {
-                std::vector<int32_t> owner;  // precinct -> tile-part
-                std::vector<std::vector<uint32_t>> pb(nc);  // first precinct index of (component, resolution)
-                uint32_t np = 0;
-                for (uint32_t k = 0; k < nc; ++k) {
-                    pb[k].resize(tile.comps[k].numres);
-                    for (uint32_t r = 0; r < tile.comps[k].numres; ++r) {
-                        pb[k][r] = np;
-                        np += tile.comps[k].res[r].pw * tile.comps[k].res[r].ph;
-                    }
-                }
-                owner.assign(np, -1);
-                uint32_t packno = 0;
-                for (size_t j = 0; j < tps.size() && disjoint; ++j) {
-                    tps[j].packno0 = packno;
-                    for (auto &pk : tps[j].order) {
-                        if (pk.layno >= L) continue;
-                        ++packno;
-                        int32_t &o = owner[pb[pk.compno][pk.resno] + pk.precno];
-                        if (o >= 0 && o != (int32_t)j) { disjoint = false; break; }
-                        o = (int32_t)j;
-                    }
-                }
-            }
-            auto write_tp = [&](TpOut &t, TileEnc &te) {
-                for (auto &pk : t.order)
-                    if (pk.layno < L) write_packet(cpt, te, pk, t.hdr, t.plan);
-            };
-            if (disjoint) {
-                host_parallel_for(tps.size(), 1, [&](size_t j0, size_t j1) {
-                    for (size_t j = j0; j < j1; ++j) {
-                        TileEnc te = tenc;  // shares the tile's state; its own packet counter
-                        te.packno = tps[j].packno0;
-                        write_tp(tps[j], te);
-                    }
-                });
-            } else {
-                for (auto &t : tps) write_tp(t, tenc);
-            }
-            uint32_t tpno = 0;
-            ByteBuf &th = to.hdr;
-            for (auto &t : tps) {
-                const size_t sot = th.size();
-                th.put16(0xFF90); th.put16(10); th.put16(tile.index); th.put32(0); th.put8(tpno); th.put8(ntp);
-                if (tpno == 0 && !cinema && cp.numpocs) write_poc(th, cpt);
-                th.put16(0xFF93);
-                to.plan.push_back({sot, (uint32_t)(th.size() - sot), 0});
-                const size_t first = to.plan.size() - 1;
-                const uint64_t base = th.size();
-                th.putn(t.hdr.v.data(), t.hdr.size());
-                for (PlanItem it : t.plan) {
-                    if (it.kind == 0) it.src += base;
-                    to.plan.push_back(it);
-                }
-                uint64_t psot = 0;
-                for (size_t i = first; i < to.plan.size(); ++i) psot += to.plan[i].len;
-                th.set32(sot + 6, (uint32_t)psot);  // Psot (j2k.cpp:2418-2426)
-                if (cinema) {
-                    to.tlm.push_back((uint8_t)tile.index);
-                    for (int b = 3; b >= 0; --b) to.tlm.push_back((uint8_t)(psot >> (8 * b)));
-                }
-                ++tpno;
-            }
-            to.packet_ms = now_ms() - tp0;
-        }
+        for (size_t ti = t0; ti < t1; ++ti) H.finish_tile(ti);
     });
-    double t_packets = 0;
-    RateStats rsum;
-    for (auto &to : touts) {
-        if (!to.ok) return set_err(GRKGPU_EINVAL, "rate allocation failed");
-        t_rate += to.rate_ms;
-        t_packets += to.packet_ms;
-        rsum.probes += to.rs.probes;
-        rsum.skipped += to.rs.skipped;
-        rsum.evals += to.rs.evals;
-        rsum.sims += to.rs.sims;
-        rsum.form_ms += to.rs.form_ms;
-        rsum.sim_ms += to.rs.sim_ms;
-        const uint64_t base = hdr.size();
-        hdr.putn(to.hdr.v.data(), to.hdr.size());
-        for (PlanItem it : to.plan) {
-            if (it.kind == 0) it.src += base;
-            plan.push_back(it);
-        }
-        tlm.insert(tlm.end(), to.tlm.begin(), to.tlm.end());
-    }
-    if ((parts & GRKGPU_PART_HEADER) && tlm_at && tlm.size() == 5ull * total_tile_parts)
-        memcpy(hdr.v.data() + tlm_at, tlm.data(), tlm.size());  // j2k_write_updated_tlm (:2555-2577)
-    if (parts & GRKGPU_PART_EOC) {
-        size_t eoc = hdr.size();
-        hdr.put16(0xFFD9);
-        plan.push_back({eoc, 2, 0});
-    }
+    rc = H.finish_end();
+    if (rc) return rc;
+    ByteBuf &hdr = H.hdr;
+    std::vector<PlanItem> &plan = H.plan;
+    const double t_rate = H.t_rate, t_packets = H.t_packets;
+    const RateStats &rsum = H.rsum;
     if (jp2_boxes) {
         // grkgpu_jp2_compress: the file's boxes (ending in the jp2c box header)
         // are one more run of the header blob, gathered ahead of everything
@@ -4200,6 +4360,581 @@ extern "C" int grkgpu_batch_plan(grkgpu_batch_item *items, uint32_t n, const grk
 }
 
 // ---------------------------------------------------------------------------
+// Batch encode (grkgpu_compress_batch): the host half of compress_impl
+// (EncHost) per item on the host pool; the items' tables rebased into one
+// EncBlock / symoff table, one MQ slab, one coef / work / ll arena and one
+// DwtPlan per wavelet -- then the device half once: one H2D of the host
+// samples (staged into h_img, each plane on a 16-byte boundary), the DC shift
+// + MCT from a LoadJob table, one launch per (sample format, mode) present,
+// the forward DWT, one Tier-1 launch set per code-block style, the pass
+// records and Tier-2 per item over (item, tile) pairs on the host pool, one
+// gather and one D2H.
+//
+// Merged block order: style groups in order of first appearance; inside a
+// group the items with rate control first, then the others, each in call
+// order, so k_pass_records runs over a contiguous prefix of the group.
+// k_t1_dist runs over the whole group when that prefix is not empty (the
+// coders' scratch layout is the group's, t1_lane.h enc_scratch); the sums it
+// leaves for blocks without rate control are not read.
+// ---------------------------------------------------------------------------
+static_assert(sizeof(grkgpu_load_job) == sizeof(LoadJob) && offsetof(grkgpu_load_job, dst) == offsetof(LoadJob, dst) &&
+                  offsetof(grkgpu_load_job, src_stride) == offsetof(LoadJob, sstride) &&
+                  offsetof(grkgpu_load_job, numcomps) == offsetof(LoadJob, ncomp) &&
+                  offsetof(grkgpu_load_job, irreversible) == offsetof(LoadJob, irrev) &&
+                  offsetof(grkgpu_load_job, shift) == offsetof(LoadJob, shift),
+              "grkgpu_load_job is LoadJob");
+static_assert(sizeof(DevPass) == sizeof(EncPass), "DevPass is EncPass");
+
+// The LoadJob tables of a launch set, one group per (sample format, mode):
+// jobs in table order, `first` their first-workgroup numbers.
+struct LoadGroup {
+    int32_t fmt = 0;
+    int mode = 0;
+    std::vector<LoadJob> jobs;
+    std::vector<uint32_t> first;
+};
+constexpr int LOAD_GROUPS = 20;  // 5 widths x 4 modes
+// a tile the job table does not take (more than four components, or too many
+// workgroups for one job): launch_dcshift_mct_fwd's arguments
+struct TileLoad {
+    SrcPlanes src;
+    PlanePtrs dst;
+    uint32_t sstride, w, h, dstride, nc;
+    int32_t lfmt, mct, irrev;
+    ShiftArr sh;
+};
+static int load_mode(int32_t lfmt) { return ((lfmt & SMP_BIG_ENDIAN) ? 1 : 0) | ((lfmt & SMP_INTERLEAVED) ? 2 : 0); }
+static bool load_group_add(LoadGroup (&groups)[LOAD_GROUPS], int32_t lfmt, const LoadJob &j) {
+    const int mode = load_mode(lfmt);
+    const uint64_t wgs = load_job_wgs(j, (mode & 2) != 0);
+    LoadGroup &g = groups[(lfmt & 0xff) * 4 + mode];
+    if (wgs > STORE_JOB_MAX_WGS || (g.first.empty() ? 0 : g.first.back()) + wgs > 0x7fffffffull) return false;
+    g.fmt = lfmt & 0xff;
+    g.mode = mode;
+    if (g.first.empty()) g.first.push_back(0);
+    g.jobs.push_back(j);
+    g.first.push_back(g.first.back() + (uint32_t)wgs);
+    return true;
+}
+// The groups' tables in one device buffer (jobs of every group, then their
+// first arrays), uploaded through `stage`, and their launches.
+static size_t load_groups_bytes(const LoadGroup (&groups)[LOAD_GROUPS]) {
+    size_t b = 0;
+    for (const LoadGroup &g : groups) b += g.jobs.size() * sizeof(LoadJob) + g.first.size() * 4;
+    return b;
+}
+static hipError_t load_groups_upload(const LoadGroup (&groups)[LOAD_GROUPS], uint8_t *stage, void *dev, hipStream_t s) {
+    size_t o = 0;
+    for (const LoadGroup &g : groups) {
+        if (g.jobs.empty()) continue;
+        memcpy(stage + o, g.jobs.data(), g.jobs.size() * sizeof(LoadJob));
+        o += g.jobs.size() * sizeof(LoadJob);
+    }
+    for (const LoadGroup &g : groups) {
+        if (g.jobs.empty()) continue;
+        memcpy(stage + o, g.first.data(), g.first.size() * 4);
+        o += g.first.size() * 4;
+    }
+    return o ? hipMemcpyAsync(dev, stage, o, hipMemcpyHostToDevice, s) : hipSuccess;
+}
+static hipError_t load_groups_launch(const LoadGroup (&groups)[LOAD_GROUPS], const void *dev, hipStream_t s, uint32_t *nl) {
+    size_t njobs = 0;
+    for (const LoadGroup &g : groups) njobs += g.jobs.size();
+    size_t jo = 0, fo = njobs * sizeof(LoadJob);
+    for (const LoadGroup &g : groups) {
+        if (g.jobs.empty()) continue;
+        if (g.first.back()) {
+            hipError_t e = launch_load_jobs((const LoadJob *)((const uint8_t *)dev + jo),
+                                            (const uint32_t *)((const uint8_t *)dev + fo), (uint32_t)g.jobs.size(),
+                                            g.first.back(), g.fmt, g.mode, s);
+            if (e != hipSuccess) return e;
+            if (nl) ++*nl;
+        }
+        jo += g.jobs.size() * sizeof(LoadJob);
+        fo += g.first.size() * 4;
+    }
+    return hipSuccess;
+}
+static hipError_t tile_load_launch(const TileLoad &t, hipStream_t s) {
+    if (t.dstride == t.w)
+        return launch_dcshift_mct_fwd(t.src, t.lfmt, t.sstride, t.dst, t.w, t.h, t.nc, t.sh, t.mct, t.irrev, s);
+    return launch_dcshift_mct_fwd_from(t.src, t.lfmt, t.sstride, t.dst, t.dstride, t.w, t.h, t.nc, t.sh, t.mct, t.irrev, s);
+}
+
+// the kernel launches and fills launch_t1_encode issues for n blocks
+static uint32_t t1_encode_launch_count(uint32_t n) {
+    if (!n) return 0;
+    return 3 + (dwt_options().t1_enc_sort && n > 64 ? 4 : 0);
+}
+
+static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grkgpu_cbatch_info *info, bool host_only) {
+    if (info) *info = grkgpu_cbatch_info{};
+    if ((!c && !host_only) || (n && !items)) return set_err(GRKGPU_EINVAL, "null argument");
+    if (!n) return GRKGPU_OK;
+    ActiveCall active;
+    const double t_start = now_ms();
+    grkgpu_cparams defp;
+    grkgpu_default_cparams(&defp);
+    std::vector<EncHost> H(n);
+    std::vector<std::string> emsg(n);
+    // (called on the thread whose check failed: the message is thread-local)
+    auto fail = [&](size_t i, int rc) {
+        items[i].status = rc;
+        items[i].cs = nullptr;
+        items[i].len = 0;
+        emsg[i] = g_err;
+    };
+    host_parallel_for(n, 1, [&](size_t a, size_t b) {
+        for (size_t i = a; i < b; ++i) {
+            grkgpu_cbatch_item &it = items[i];
+            it.status = GRKGPU_OK;
+            it.cs = nullptr;
+            it.len = 0;
+            EncHost &h = H[i];
+            h.img = &it.img; h.p = it.p ? it.p : &defp; h.fmt_in = (int32_t)it.in.sample_fmt;
+            h.row0 = it.in.row0; h.nrows = it.in.nrows; h.col0 = it.in.col0; h.ncols = it.in.ncols;
+            h.batch = true;
+            int rc = h.begin();
+            for (uint32_t k = 0; !rc && !host_only && k < (h.il ? 1u : h.nc); ++k)
+                if (!it.in.planes[k]) rc = set_err(GRKGPU_EINVAL, "null argument");
+            if (rc) fail(i, rc);
+        }
+    });
+    int first_rc = GRKGPU_OK;
+    std::string first_msg;
+    auto result = [&]() {
+        for (uint32_t i = 0; i < n && !first_rc; ++i)
+            if (items[i].status) { first_rc = items[i].status; first_msg = "item " + std::to_string(i) + ": " + emsg[i]; }
+        return first_rc ? set_err(first_rc, first_msg) : GRKGPU_OK;
+    };
+
+    // the merged order (style groups; rate-controlled items first in each)
+    // and the items' places in the merged tables
+    struct StyGroup {
+        uint32_t sty = 0, b0 = 0, n = 0, nrc = 0, maxdepth = 1, rc0 = 0;
+        uint64_t scr0 = 0, ord0 = 0;
+        std::vector<uint32_t> items;
+    };
+    std::vector<StyGroup> sg;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (items[i].status) continue;
+        size_t g = 0;
+        while (g < sg.size() && sg[g].sty != H[i].cp.cblksty) ++g;
+        if (g == sg.size()) { sg.emplace_back(); sg[g].sty = H[i].cp.cblksty; }
+        sg[g].items.push_back(i);
+    }
+    std::vector<uint32_t> order;
+    std::vector<uint64_t> mb0(n, 0), rcb0(n, 0), slot0(n, 0);  // first merged block / rc block / pass-record slot
+    uint64_t arena = 0, llarena = 0, out_total = 0, sym_total = 0, nblk64 = 0, nrc64 = 0, slots = 0, slots_all = 0,
+             runs_bound = 0, scr_bytes = 0, ord_words = 0;
+    for (StyGroup &g : sg) {
+        std::stable_partition(g.items.begin(), g.items.end(), [&](uint32_t i) { return H[i].need_rc; });
+        g.b0 = (uint32_t)std::min<uint64_t>(nblk64, 0xffffffffu);
+        g.rc0 = (uint32_t)std::min<uint64_t>(nrc64, 0xffffffffu);
+        for (uint32_t i : g.items) {
+            EncHost &h = H[i];
+            h.rebase(arena, llarena, out_total, sym_total);
+            mb0[i] = nblk64;
+            arena += h.arena;
+            llarena += h.llarena;
+            out_total += h.out_total;
+            sym_total += h.sym_total;
+            nblk64 += h.nblk;
+            slots_all += h.ptotal;
+            runs_bound += (uint64_t)h.nblk * h.cp.numlayers;
+            g.maxdepth = std::max(g.maxdepth, h.maxdepth);
+            if (h.need_rc) {
+                rcb0[i] = nrc64;
+                slot0[i] = slots;
+                nrc64 += h.nblk;
+                slots += h.ptotal;
+            }
+            order.push_back(i);
+        }
+        g.n = (uint32_t)std::min<uint64_t>(nblk64 - g.b0, 0xffffffffu);
+        g.nrc = (uint32_t)std::min<uint64_t>(nrc64 - g.rc0, 0xffffffffu);
+        g.scr0 = scr_bytes;
+        scr_bytes += t1e_scratch_bytes(g.n, g.maxdepth);
+        g.ord0 = ord_words;
+        ord_words += t1_order_words(g.n);
+    }
+    // the 32-bit limits compress_impl relies on: the block count, the
+    // pass-record slots (EncCblkState::pass0) and the gather runs (at least a
+    // run per block and layer; the exact count is checked again before the launch)
+    if (nblk64 > 0xffffffffull || slots_all > 0xffffffffull || runs_bound > 0x7fffffffull)
+        return set_err(GRKGPU_EUNSUPPORTED, "batch too large for one call");
+    const uint32_t nblk = (uint32_t)nblk64, nrc = (uint32_t)nrc64, n_ok = (uint32_t)order.size();
+
+    // host samples: each plane (interleaved: the pixels) at a 16-byte-aligned
+    // offset of the staging image
+    struct Region { const uint8_t *host; size_t off, bytes; };
+    std::vector<Region> regions;
+    std::vector<std::array<size_t, GRKGPU_MAX_COMPS>> roff(n);
+    size_t img_bytes = 0;
+    for (uint32_t i : order) {
+        const EncHost &h = H[i];
+        if (items[i].in.on_device || host_only) continue;
+        for (uint32_t k = 0; k < (h.il ? 1u : h.nc); ++k) {
+            Region r{(const uint8_t *)items[i].in.planes[k], (img_bytes + 15) & ~(size_t)15,
+                     (size_t)(h.il ? h.poff[h.nc] : h.poff[k + 1] - h.poff[k]) * h.sb};
+            img_bytes = r.off + r.bytes;
+            roff[i][k] = r.off;
+            regions.push_back(r);
+        }
+    }
+    if (!host_only) {
+        HIPCHK(hipSetDevice(c->device));
+        if (img_bytes) {
+            HIPCHK(c->img.ensure(img_bytes + 256));
+            HIPCHK(c->h_img.ensure(img_bytes + 256));
+        }
+        HIPCHK(c->work.ensure(arena * 4 + 256));
+    }
+    // the DC shift + MCT: a LoadJob per tile of every item of up to four
+    // components, per-tile launches for the others
+    LoadGroup groups[LOAD_GROUPS];
+    std::vector<TileLoad> singles;
+    uint32_t n_load_jobs = 0;
+    const uintptr_t work0 = host_only ? 0 : (uintptr_t)c->work.p, img0 = host_only ? 0 : (uintptr_t)c->img.p;
+    for (uint32_t i : order) {
+        const EncHost &h = H[i];
+        const uint32_t nc = h.nc;
+        auto src_at = [&](uint32_t k, uint64_t off) {  // sample `off` of component k's plane (compress_impl's src_at)
+            const uintptr_t p0 = items[i].in.on_device ? (uintptr_t)items[i].in.planes[h.il ? 0 : k]
+                                                       : img0 + roff[i][h.il ? 0 : k];
+            return (const void *)(h.il ? p0 + (off * nc + k) * h.sb : p0 + off * h.sb);
+        };
+        for (const Tile &tile : h.tiles) {
+            const Rect &tcr = tile.comps[0].r;
+            TileLoad tl{};
+            for (uint32_t k = 0; k < nc; ++k) {
+                tl.src.p[k] = src_at(k, h.plane_org(k, tile.comps[k]));
+                tl.dst.p[k] = (int32_t *)(work0 + tile.comps[k].arena_off * 4);
+                tl.sh.v[k] = h.cp.shift[k];
+            }
+            tl.sstride = h.prect[0].w() * (h.il ? nc : 1);  // interleaved: src.p[0] = the tile's first pixel
+            tl.w = tcr.w(); tl.h = tcr.h(); tl.dstride = tcr.w(); tl.nc = nc;
+            tl.lfmt = h.lfmt; tl.mct = h.cp.mct; tl.irrev = h.cp.irrev;
+            bool tabled = false;
+            if (nc <= 4) {
+                LoadJob j{};
+                for (uint32_t k = 0; k < nc; ++k) {
+                    j.src[k] = tl.src.p[k];
+                    j.dst[k] = tl.dst.p[k];
+                    j.shift[k] = tl.sh.v[k];
+                }
+                j.sstride = tl.sstride; j.dstride = tl.dstride; j.w = tl.w; j.h = tl.h;
+                j.ncomp = nc; j.mct = tl.mct; j.irrev = tl.irrev;
+                tabled = load_group_add(groups, h.lfmt, j);
+            }
+            if (tabled) ++n_load_jobs;
+            else singles.push_back(tl);
+        }
+    }
+    if (info) {
+        info->n_ok = n_ok;
+        info->n_blocks = nblk;
+        info->n_load_jobs = n_load_jobs;
+    }
+    if (host_only || !n_ok) return result();
+
+    hipStream_t s = c->stream;
+    uint32_t nl = 0;  // kernel launches and fills of this call
+    const int drc = [&]() -> int {
+        const bool lone = lone_call();
+        HIPCHK(c->coef.ensure(arena * 4 + 256));
+        HIPCHK(c->ll.ensure(llarena * 4 + 256));
+        HIPCHK(c->scratch.ensure((size_t)scr_bytes + 256));
+        HIPCHK(c->t1order.ensure((size_t)ord_words * 4 + 256));
+        HIPCHK(c->mqout.ensure(out_total + 256));
+        HIPCHK(c->blocks.ensure((size_t)nblk * sizeof(EncBlock) + 256));
+        HIPCHK(c->results.ensure((size_t)nblk * sizeof(EncResult) + 256));
+        HIPCHK(c->h_results.ensure((size_t)nblk * sizeof(EncResult) + 256));
+        HIPCHK(c->h_blocks.ensure((size_t)nblk * sizeof(EncBlock) + 256));
+        HIPCHK(c->sym.ensure(sym_total + 256));
+        HIPCHK(c->symoff.ensure(((size_t)nblk + 1) * 8 + 256));
+        HIPCHK(c->h_symoff.ensure(((size_t)nblk + 1) * 8 + 256));
+        const size_t ljbytes = load_groups_bytes(groups);
+        HIPCHK(c->loadjobs.ensure(ljbytes + 256));
+        HIPCHK(c->h_loadjobs.ensure(ljbytes + 256));
+        // the samples packed into the pinned buffer, on the host pool: the pad
+        // bytes between planes are uploaded as they are and never addressed
+        host_parallel_for(regions.size(), 1, [&](size_t a, size_t b) {
+            for (size_t r = a; r < b; ++r) memcpy(c->h_img.as<uint8_t>() + regions[r].off, regions[r].host, regions[r].bytes);
+        });
+        // the merged block table and symbol-stream offsets
+        {
+            EncBlock *hb = c->h_blocks.as<EncBlock>();
+            uint64_t *hs = c->h_symoff.as<uint64_t>();
+            for (uint32_t i : order) {
+                const EncHost &h = H[i];
+                if (h.nblk) memcpy(hb + mb0[i], h.eb.data(), (size_t)h.nblk * sizeof(EncBlock));
+                if (h.nblk) memcpy(hs + mb0[i], h.symoff.data(), (size_t)h.nblk * 8);
+            }
+            hs[nblk] = sym_total;
+        }
+        HIPCHK(hipEventRecord(c->ev[0], s));
+        if (img_bytes) HIPCHK(hipMemcpyAsync(c->img.p, c->h_img.p, img_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(load_groups_upload(groups, c->h_loadjobs.as<uint8_t>(), c->loadjobs.p, s));
+        HIPCHK(hipEventRecord(c->ev[1], s));
+        HIPCHK(load_groups_launch(groups, c->loadjobs.p, s, &nl));
+        for (const TileLoad &tl : singles) {
+            HIPCHK(tile_load_launch(tl, s));
+            ++nl;
+        }
+        HIPCHK(hipEventRecord(c->ev[2], s));
+        DwtPlan dplan[2];  // one plan per wavelet over every item's tile-components (never fused with the load)
+        for (uint32_t i : order) {
+            const EncHost &h = H[i];
+            for (uint32_t t = 0; t < h.ntiles; ++t)
+                for (uint32_t k = 0; k < h.nc; ++k) {
+                    const TileComp &tc = h.tiles[t].comps[k];
+                    dwt_plan_tc(dplan[h.cp.irrev ? 1 : 0], tc, c->work.as<int32_t>() + tc.arena_off,
+                                c->coef.as<int32_t>() + tc.arena_off, c->ll.as<int32_t>() + h.lloff[t * h.nc + k],
+                                h.cp.irrev, false);
+                }
+        }
+        HIPCHK(dwt_upload(dplan[1], c->dwtjobs, c->h_dwtjobs, 1, s));
+        HIPCHK(dwt_upload(dplan[0], c->dwtjobs53, c->h_dwtjobs53, 0, s));
+        c->ltimes.clear();
+        c->lidx.clear();
+        LaunchLog llog{&c->lev, &c->ltimes, &c->lidx};
+        HIPCHK(dwt_launch(dplan[1], c->dwtjobs, 1, false, s, c->launch_timing ? &llog : nullptr));
+        HIPCHK(dwt_launch(dplan[0], c->dwtjobs53, 0, false, s, c->launch_timing ? &llog : nullptr));
+        nl += dwt_launch_count(dplan[1], false) + dwt_launch_count(dplan[0], false);
+        HIPCHK(hipEventRecord(c->ev[3], s));
+        HIPCHK(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, (size_t)nblk * sizeof(EncBlock), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->symoff.p, c->h_symoff.p, ((size_t)nblk + 1) * 8, hipMemcpyHostToDevice, s));
+        for (const StyGroup &g : sg) {
+            HIPCHK(launch_t1_encode(c->blocks.as<EncBlock>() + g.b0, g.n, c->coef.as<int32_t>(),
+                                    c->scratch.as<uint8_t>() + g.scr0, c->sym.as<uint8_t>(),
+                                    c->symoff.as<uint64_t>() + g.b0, g.maxdepth, c->mqout.as<uint8_t>(),
+                                    c->results.as<EncResult>() + g.b0, s, g.sty, lone ? lone_bpw(g.n) : 0,
+                                    c->t1order.as<uint32_t>() + g.ord0));
+            nl += t1_encode_launch_count(g.n);
+        }
+        // the rate-controlled blocks' distortion factors and record slots: per
+        // group its factors, then (all groups) the slots, nrc + one end per group
+        const size_t p0_words = (size_t)nrc + sg.size();
+        if (nrc) {
+            HIPCHK(c->h_pinfo.ensure(((size_t)nrc + p0_words) * 8 + 256));
+            HIPCHK(c->pinfo.ensure(((size_t)nrc + p0_words) * 8 + 256));
+            double *wf = c->h_pinfo.as<double>();
+            uint64_t *p0 = (uint64_t *)(wf + nrc);
+            for (size_t gi = 0; gi < sg.size(); ++gi) {
+                const StyGroup &g = sg[gi];
+                uint64_t sl = 0;
+                for (uint32_t i : g.items) {
+                    const EncHost &h = H[i];
+                    if (!h.need_rc) continue;
+                    sl = slot0[i];
+                    for (uint32_t q = 0; q < h.nblk; ++q) {
+                        wf[rcb0[i] + q] = h.wfac(q);
+                        p0[rcb0[i] + gi + q] = sl;
+                        sl += h.pcap[q];
+                    }
+                }
+                if (g.nrc) p0[(size_t)g.rc0 + gi + g.nrc] = sl;
+                else p0[(size_t)g.rc0 + gi] = 0;
+            }
+            HIPCHK(hipMemcpyAsync(c->pinfo.p, c->h_pinfo.p, ((size_t)nrc + p0_words) * 8, hipMemcpyHostToDevice, s));
+        }
+        for (const StyGroup &g : sg) {
+            if (!g.nrc) continue;
+            HIPCHK(launch_t1_dist(c->blocks.as<EncBlock>() + g.b0, g.n, g.maxdepth, c->coef.as<int32_t>(),
+                                  c->scratch.as<uint8_t>() + g.scr0, c->results.as<EncResult>() + g.b0, s));
+            ++nl;
+        }
+        HIPCHK(hipEventRecord(c->ev[4], s));
+        const size_t sum_bytes = ((size_t)nrc * sizeof(PassSum) + 255) & ~(size_t)255;
+        if (nrc) {
+            HIPCHK(c->precs.ensure(sum_bytes + slots * sizeof(DevPass) + 256));
+            HIPCHK(c->h_psum.ensure(sum_bytes + 256));
+            HIPCHK(c->h_precs.ensure(slots * sizeof(DevPass) + 256));
+            PassSum *dsum = c->precs.as<PassSum>();
+            DevPass *dpass = (DevPass *)(c->precs.as<uint8_t>() + sum_bytes);
+            const double *dwf = c->pinfo.as<double>();
+            const uint64_t *dp0 = (const uint64_t *)(dwf + nrc);
+            for (size_t gi = 0; gi < sg.size(); ++gi) {
+                const StyGroup &g = sg[gi];
+                if (!g.nrc) continue;
+                HIPCHK(launch_pass_records(c->blocks.as<EncBlock>() + g.b0, c->results.as<EncResult>() + g.b0,
+                                           dwf + g.rc0, dp0 + g.rc0 + gi, g.nrc, g.sty, dpass, dsum + g.rc0, s));
+                ++nl;
+            }
+            HIPCHK(hipMemcpyAsync(c->h_psum.p, dsum, (size_t)nrc * sizeof(PassSum), hipMemcpyDeviceToHost, s));
+            if (slots) HIPCHK(hipMemcpyAsync(c->h_precs.p, dpass, slots * sizeof(DevPass), hipMemcpyDeviceToHost, s));
+        }
+        for (const StyGroup &g : sg) {  // the other blocks' results, rates only
+            if (g.n == g.nrc) continue;
+            const size_t o = ((size_t)g.b0 + g.nrc) * sizeof(EncResult);
+            HIPCHK(hipMemcpy2DAsync(c->h_results.as<uint8_t>() + o, sizeof(EncResult), c->results.as<uint8_t>() + o,
+                                    sizeof(EncResult), ENC_RESULT_RATE_BYTES, g.n - g.nrc, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+
+        // pass records per item, then rate allocation and packets over
+        // (item, tile) pairs, all on the host pool
+        const double t_t2 = now_ms();
+        const EncResult *res = c->h_results.as<EncResult>();
+        const PassSum *sm = c->h_psum.as<PassSum>();
+        const uint64_t *hp0 = (const uint64_t *)(c->h_pinfo.as<double>() + nrc);
+        std::vector<uint32_t> gidx(n, 0);  // the item's style group
+        for (size_t gi = 0; gi < sg.size(); ++gi)
+            for (uint32_t i : sg[gi].items) gidx[i] = (uint32_t)gi;
+        std::vector<uint64_t> hpass0(n, 0);  // first host-formed record of the items without rate control
+        host_parallel_for(order.size(), 1, [&](size_t a, size_t b) {
+            for (size_t q = a; q < b; ++q) {
+                const uint32_t i = order[q];
+                EncHost &h = H[i];
+                const int rc = h.need_rc ? h.records_dev(sm + rcb0[i], hp0 + rcb0[i] + gidx[i],
+                                                         c->h_precs.as<EncPass>() + slot0[i])
+                                         : h.records_host_count(res + mb0[i]);
+                if (rc) fail(i, rc);
+            }
+        });
+        uint64_t hpasses = 0;
+        for (uint32_t i : order) {
+            if (items[i].status || H[i].need_rc) continue;
+            hpass0[i] = hpasses;
+            hpasses += H[i].npass;
+        }
+        if (c->enc_passes.size() < hpasses) c->enc_passes.resize(hpasses);
+        host_parallel_for(order.size(), 1, [&](size_t a, size_t b) {
+            for (size_t q = a; q < b; ++q) {
+                const uint32_t i = order[q];
+                if (items[i].status) continue;
+                EncHost &h = H[i];
+                if (!h.need_rc) h.records_host_fill(res + mb0[i], c->enc_passes.data() + hpass0[i]);
+                const int rc = h.finish_begin();
+                if (rc) fail(i, rc);
+            }
+        });
+        const double t_passrec = now_ms() - t_t2;
+        std::vector<std::pair<uint32_t, uint32_t>> todo;
+        for (uint32_t i : order)
+            for (uint32_t t = 0; !items[i].status && t < H[i].ntiles; ++t) todo.push_back({i, t});
+        host_parallel_for(todo.size(), 1, [&](size_t a, size_t b) {
+            for (size_t q = a; q < b; ++q) H[todo[q].first].finish_tile(todo[q].second);
+        });
+        // the items' header blobs and plans in call order: header runs rebased
+        // onto the shared blob, each stream's bytes from a 16-byte boundary
+        ByteBuf hdr;
+        std::vector<GatherItem> gi;
+        std::vector<uint64_t> cs_off(n, 0), cs_len(n, 0);
+        uint64_t total = 0, nsym = 0, cs_sum = 0;
+        double t_rate = 0, t_packets = 0;
+        RateStats rsum;
+        uint32_t n_done = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (items[i].status) continue;
+            EncHost &h = H[i];
+            const int rc = h.finish_end();
+            if (rc) { fail(i, rc); continue; }
+            const uint64_t base = hdr.size();
+            hdr.putn(h.hdr.v.data(), h.hdr.size());
+            total = (total + 15) & ~(uint64_t)15;
+            cs_off[i] = total;
+            for (const PlanItem &pi : h.plan) {
+                if (pi.len) gi.push_back({pi.kind == 0 ? pi.src + base : pi.src, total, pi.len, pi.kind});
+                total += pi.len;
+            }
+            cs_len[i] = total - cs_off[i];
+            cs_sum += cs_len[i];
+            nsym += h.nsym;
+            t_rate += h.t_rate;
+            t_packets += h.t_packets;
+            rsum.probes += h.rsum.probes;
+            rsum.skipped += h.rsum.skipped;
+            rsum.evals += h.rsum.evals;
+            rsum.sims += h.rsum.sims;
+            rsum.form_ms += h.rsum.form_ms;
+            rsum.sim_ms += h.rsum.sim_ms;
+            ++n_done;
+        }
+        if (gi.size() > 0x7fffffffull) return set_err(GRKGPU_EUNSUPPORTED, "batch too large for one call");
+        const double t_t2_end = now_ms();
+        HIPCHK(c->gather.ensure(gi.size() * sizeof(GatherItem) + hdr.size() + 512));
+        HIPCHK(c->h_gather.ensure(gi.size() * sizeof(GatherItem) + hdr.size() + 512));
+        HIPCHK(c->packed.ensure(total + 256));
+        std::unique_lock<std::mutex> out_lk(c->out_mu);
+        if (!c->h_out.p && !c->out_spare.empty()) {  // taken by a view: reuse a given-back buffer
+            auto big = std::max_element(c->out_spare.begin(), c->out_spare.end(),
+                                        [](const auto &a, const auto &b) { return a.second < b.second; });
+            c->h_out.p = big->first;
+            c->h_out.cap = big->second;
+            c->out_spare.erase(big);
+        }
+        HIPCHK(c->h_out.ensure(total + 256));
+        const size_t gbytes = gi.size() * sizeof(GatherItem);
+        const size_t hoff = (gbytes + 255) & ~(size_t)255;
+        memcpy(c->h_gather.p, gi.data(), gbytes);
+        memcpy(c->h_gather.as<uint8_t>() + hoff, hdr.v.data(), hdr.size());
+        HIPCHK(hipEventRecord(c->ev[5], s));
+        HIPCHK(hipMemcpyAsync(c->gather.p, c->h_gather.p, hoff + hdr.size(), hipMemcpyHostToDevice, s));
+        if (!gi.empty()) {
+            HIPCHK(launch_gather(c->gather.as<uint8_t>() + hoff, c->mqout.as<uint8_t>(), c->gather.as<GatherItem>(),
+                                 (uint32_t)gi.size(), c->packed.as<uint8_t>(), s));
+            ++nl;
+        }
+        HIPCHK(hipEventRecord(c->ev[6], s));
+        // (the pad bytes before a stream's 16-byte boundary are copied as they are: no item's cs / len covers them)
+        if (total) HIPCHK(hipMemcpyAsync(c->h_out.p, c->packed.p, total, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipEventRecord(c->ev[7], s));
+        HIPCHK(hipStreamSynchronize(s));
+        const double t_end = now_ms();
+        for (uint32_t i = 0; i < n; ++i) {
+            if (items[i].status) continue;
+            items[i].cs = c->h_out.as<uint8_t>() + cs_off[i];
+            items[i].len = (size_t)cs_len[i];
+        }
+        if (info) info->n_ok = n_done;
+
+        grkgpu_stats &st = c->stats;
+        memset(&st, 0, sizeof(st));
+        hipEventElapsedTime(&st.h2d_ms, c->ev[0], c->ev[1]);
+        hipEventElapsedTime(&st.dcshift_mct_ms, c->ev[1], c->ev[2]);
+        hipEventElapsedTime(&st.dwt_ms, c->ev[2], c->ev[3]);
+        hipEventElapsedTime(&st.t1_ms, c->ev[3], c->ev[4]);
+        hipEventElapsedTime(&st.gather_ms, c->ev[5], c->ev[6]);
+        hipEventElapsedTime(&st.d2h_ms, c->ev[6], c->ev[7]);
+        log_collect(c);
+        st.host_t2_ms = (float)(t_t2_end - t_t2);
+        st.total_ms = (float)(t_end - t_start);
+        st.num_cblks = nblk;
+        st.cs_bytes = cs_sum;
+        st.mq_symbols = nsym;
+        st.rate_ms = (float)t_rate;
+        st.packet_ms = (float)t_packets;
+        st.rate_probes = rsum.probes;
+        st.rate_probes_skipped = rsum.skipped;
+        st.rate_block_evals = rsum.evals;
+        st.rate_precinct_sims = rsum.sims;
+        st.rate_form_ms = (float)rsum.form_ms;
+        st.rate_sim_ms = (float)rsum.sim_ms;
+        st.passrec_ms = (float)t_passrec;
+        return GRKGPU_OK;
+    }();
+    if (drc) {  // a device error leaves no item encoded
+        const std::string msg = g_err;
+        for (uint32_t i = 0; i < n; ++i)
+            if (!items[i].status) { items[i].status = drc; items[i].cs = nullptr; items[i].len = 0; }
+        if (info) info->n_ok = 0;
+        return set_err(drc, msg);
+    }
+    if (info) info->n_launches = nl;
+    return result();
+}
+
+extern "C" int grkgpu_compress_batch(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grkgpu_cbatch_info *info) {
+    return cbatch_impl(c, items, n, info, false);
+}
+
+extern "C" int grkgpu_compress_batch_plan(grkgpu_cbatch_item *items, uint32_t n, grkgpu_cbatch_info *info) {
+    return cbatch_impl(nullptr, items, n, info, true);
+}
+
+// ---------------------------------------------------------------------------
 // JP2 files: the box layer (jp2.cpp) around the entry points above
 // ---------------------------------------------------------------------------
 namespace {
@@ -4573,6 +5308,61 @@ extern "C" int grkgpu_mct_inv_dcshift_jobs_to(const grkgpu_store_job *jobs, uint
     if (dev) hipFree(dev);
     HIPCHK(e);
     HIPCHK(es);
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_dcshift_mct_fwd_jobs(grkgpu_ctx *c, const grkgpu_load_job *jobs, uint32_t n,
+                                           uint32_t sample_fmt) {
+    if (!c) return set_err(GRKGPU_EINVAL, "null ctx");
+    const int32_t fflags = (int32_t)sample_fmt & ~0xff, fmt = (int32_t)sample_fmt & 0xff;
+    if (fflags & ~(SMP_INTERLEAVED | SMP_BIG_ENDIAN)) return set_err(GRKGPU_EINVAL, "unknown sample format flags");
+    if (fmt < SMP_I32 || fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if ((fflags & SMP_BIG_ENDIAN) && fmt != SMP_U16 && fmt != SMP_I16)
+        return set_err(GRKGPU_EINVAL, "big-endian samples are 16-bit (U16 / I16)");
+    if (!n) return GRKGPU_OK;
+    if (!jobs) return set_err(GRKGPU_EINVAL, "null argument");
+    const int32_t lfmt = fmt | fflags;
+    const bool il = (fflags & SMP_INTERLEAVED) != 0;
+    const uint32_t sb = sample_bytes(fmt);
+    LoadGroup groups[LOAD_GROUPS];
+    std::vector<TileLoad> singles;
+    for (uint32_t i = 0; i < n; ++i) {
+        const grkgpu_load_job &q = jobs[i];
+        const uint32_t nc = q.numcomps;
+        if (nc < 1 || nc > 4 || q.dst_stride < q.w || (uint64_t)q.src_stride < (uint64_t)q.w * (il ? nc : 1))
+            return set_err(GRKGPU_EINVAL, "bad arguments (1 .. 4 components, strides must hold a row)");
+        LoadJob j;
+        memcpy(&j, &q, sizeof(j));
+        j.pad_ = 0;
+        for (uint32_t k = nc; k < 4; ++k) { j.src[k] = nullptr; j.dst[k] = nullptr; }
+        TileLoad tl{};
+        for (uint32_t k = 0; k < (il ? 1u : nc); ++k) {
+            // planar samples in host byte order are read with typed loads
+            if (!q.src[k] || (!fflags && (uintptr_t)q.src[k] % sb))
+                return set_err(GRKGPU_EINVAL, "null or misaligned source plane");
+            tl.src.p[k] = q.src[k];
+        }
+        for (uint32_t k = 0; k < nc; ++k) {
+            if (!q.dst[k] || (uintptr_t)q.dst[k] % 4) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+            tl.dst.p[k] = q.dst[k];
+            tl.sh.v[k] = q.shift[k];
+        }
+        if (load_group_add(groups, lfmt, j)) continue;
+        tl.sstride = q.src_stride; tl.w = q.w; tl.h = q.h; tl.dstride = q.dst_stride; tl.nc = nc;
+        tl.lfmt = lfmt; tl.mct = q.mct; tl.irrev = q.irreversible;
+        singles.push_back(tl);
+    }
+    int rc = check_device(c->device);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t bytes = load_groups_bytes(groups);
+    HIPCHK(c->loadjobs.ensure(bytes + 256));
+    HIPCHK(c->h_loadjobs.ensure(bytes + 256));
+    HIPCHK(load_groups_upload(groups, c->h_loadjobs.as<uint8_t>(), c->loadjobs.p, s));
+    HIPCHK(load_groups_launch(groups, c->loadjobs.p, s, nullptr));
+    for (const TileLoad &tl : singles) HIPCHK(tile_load_launch(tl, s));
+    HIPCHK(hipStreamSynchronize(s));  // the staging is the context's: free for the next call
     return GRKGPU_OK;
 }
 

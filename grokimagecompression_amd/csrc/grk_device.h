@@ -128,6 +128,35 @@ constexpr uint64_t STORE_JOB_MAX_WGS = (uint64_t)1 << 24;
 // first: njobs + 1 first-workgroup numbers (prefix sums of store_job_wgs), nwg = first[njobs]
 hipError_t launch_store_jobs(const StoreJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg, int32_t fmt,
                              bool interleaved, hipStream_t s);
+// launch_dcshift_mct_fwd / _from for a table of tiles in one launch (the batch
+// encode, grkgpu_dcshift_mct_fwd_jobs): each tile's arguments as a record in
+// device memory (grkgpu_load_job's layout; static_assert in codec.cpp), 1 .. 4
+// components on one grid, all jobs of a launch in one sample format and mode
+// (bit 0 big-endian, bit 1 interleaved).
+struct LoadJob {
+    const void *src[4];  // planar: component k's sample at the tile's origin; interleaved: src[0] = its first pixel
+    int32_t *dst[4];     // component k's tile buffer
+    uint32_t sstride, dstride, w, h;  // sstride in samples (interleaved: of every component)
+    uint32_t ncomp;
+    int32_t mct, irrev;
+    uint32_t pad_;
+    int32_t shift[4];
+};
+// threads along a row of a job: the lead run and the runs of 4 pixels of an
+// interleaved 3 / 4-component source (launch_fwd_from's), else the samples
+__host__ __device__ inline uint32_t load_job_row_threads(uint32_t w, uint32_t ncomp, bool interleaved) {
+    if (interleaved && (ncomp == 3 || ncomp == 4)) return (uint32_t)(((uint64_t)w + 3) / 4 + 1);
+    return w;
+}
+// a job's workgroups of 256 threads (0: nothing to load); more than
+// STORE_JOB_MAX_WGS do not fit the kernel's 32-bit thread index
+inline uint64_t load_job_wgs(const LoadJob &j, bool interleaved) {
+    if (!j.w || !j.h) return 0;
+    return ((uint64_t)load_job_row_threads(j.w, j.ncomp, interleaved) * j.h + 255) / 256;
+}
+// first: njobs + 1 first-workgroup numbers (prefix sums of load_job_wgs), nwg = first[njobs]
+hipError_t launch_load_jobs(const LoadJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg, int32_t fmt,
+                            int mode, hipStream_t s);
 // The decoded image with its subsampled components replicated to the image
 // grid (GRKGPU_LAYOUT_UPSAMPLE, grk_decompress -u): output pixel (X, Y) of the
 // reference grid takes component k's sample at column floor(X / dx), row

@@ -2440,6 +2440,163 @@ hipError_t launch_store_jobs(const StoreJob *jobs, const uint32_t *first, uint32
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// The DC shift + forward MCT of a table of tiles in one launch (the batch
+// encode: a few workgroups per tile, hundreds of tiles) -- the forward mirror
+// of k_store_jobs.  Workgroup wg finds its job by binary search over the
+// jobs' first-workgroup numbers; the search depends on blockIdx alone, so it
+// and the job record are wave-uniform: scalar loads, the record in scalar
+// registers.  Thread g of a job -- g counted over its workgroups -- owns
+// position (g % rpr) of row (g / rpr), rpr = load_job_row_threads: a run of
+// PIX_RUN pixels of an interleaved 3 / 4-component source
+// (k_dcshift_mct_fwd_pixels' runs on the source row's best aligned grid, read
+// and stored by the same helpers), else one sample position
+// (k_dcshift_mct_fwd's typed loads for planar samples in host byte order,
+// k_dcshift_mct_fwd_from's byte-addressed ones otherwise), the arithmetic
+// statement for statement.  Rows are packed into the workgroups, so a 64-wide
+// tile fills its wavefronts where a (tw / 256, th) grid leaves three quarters
+// of each idle.  Stores are non-temporal as there.  No LDS, no atomics,
+// nothing shared between workgroups.
+// M: bit 0 = big-endian samples, bit 1 = interleaved.
+// ---------------------------------------------------------------------------
+template <typename S, int NC, bool BE>
+__device__ __forceinline__ void load_job_pixels(const LoadJob &J, uint32_t y, uint32_t t, const int32_t (&shift)[4],
+                                                int32_t mct, int32_t irrev) {
+    constexpr int N = PIX_RUN;
+    const uint8_t *const srow = (const uint8_t *)J.src[0] + (size_t)y * J.sstride * sizeof(S);
+    uint32_t x0;
+    const int n = src_run_of<N>((uintptr_t)srow, NC * sizeof(S), t, J.w, x0);
+    if (n <= 0) return;
+    int32_t px[N * NC];
+    load_samples<S, N * NC, BE>(srow + (size_t)x0 * NC * sizeof(S), px, n * NC);
+    int32_t v[NC][N];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int k = 0; k < NC; ++k) v[k][i] = px[i * NC + k];
+    if (mct) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            int32_t r = v[0][i] - shift[0], g = v[1][i] - shift[1], b = v[2][i] - shift[2];
+            int32_t o0, o1, o2;
+            if (!irrev) {
+                o0 = (r + (g * 2) + b) >> 2;
+                o1 = b - g;
+                o2 = r - g;
+            } else {
+                o0 = ict_term(r, 2449) + ict_term(g, 4809) + ict_term(b, 934);
+                o1 = -ict_term(r, 1382) - ict_term(g, 2714) + ict_term(b, 4096);
+                o2 = ict_term(r, 4096) - ict_term(g, 3430) - ict_term(b, 666);
+            }
+            v[0][i] = o0; v[1][i] = o1; v[2][i] = o2;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        if (mct && k < 3) continue;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            int32_t s = v[k][i] - shift[k];
+            v[k][i] = irrev ? (int32_t)((uint32_t)s << 11) : s;
+        }
+    }
+    const size_t di = (size_t)y * J.dstride + x0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) store_run<N>(J.dst[k] + di, v[k], n);
+}
+
+template <typename S, int M>
+__global__ void __launch_bounds__(256) k_load_jobs(const LoadJob *__restrict__ jobs,
+                                                   const uint32_t *__restrict__ first, uint32_t njobs) {
+    constexpr bool BE = (M & 1) != 0, IL = (M & 2) != 0;
+    const uint32_t wg = blockIdx.x;
+    uint32_t lo = 0, hi = njobs;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first[mid] <= wg) lo = mid; else hi = mid;
+    }
+    const LoadJob J = jobs[lo];
+    const uint32_t ncomp = J.ncomp, tw = J.w, th = J.h;
+    const int32_t mct = J.mct && ncomp >= 3, irrev = J.irrev;
+    int32_t shift[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) shift[k] = J.shift[k];
+    const uint32_t rpr = load_job_row_threads(tw, ncomp, IL);
+    const uint32_t g = (wg - first[lo]) * 256u + threadIdx.x;
+    const uint32_t y = g / rpr, x = g - y * rpr;
+    if (y >= th) return;
+    if constexpr (IL) {
+        if (ncomp == 3) { load_job_pixels<S, 3, BE>(J, y, x, shift, mct, irrev); return; }
+        if (ncomp == 4) { load_job_pixels<S, 4, BE>(J, y, x, shift, mct, irrev); return; }
+    }
+    // one sample position, one load per component
+    const size_t srow = (size_t)y * J.sstride, di = (size_t)y * J.dstride + x;
+    int32_t v[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if ((uint32_t)k >= ncomp) continue;
+        if constexpr (M == 0) {
+            v[k] = (int32_t)((const S *)J.src[k])[srow + x];
+        } else {
+            const uint8_t *p = IL ? (const uint8_t *)J.src[0] + (srow + (size_t)x * ncomp + k) * sizeof(S)
+                                  : (const uint8_t *)J.src[k] + (srow + x) * sizeof(S);
+            v[k] = ld_sample<S, BE>(p);
+        }
+    }
+    if (mct) {
+        int32_t r = v[0] - shift[0], gg = v[1] - shift[1], b = v[2] - shift[2];
+        int32_t o0, o1, o2;
+        if (!irrev) {
+            o0 = (r + (gg * 2) + b) >> 2;
+            o1 = b - gg;
+            o2 = r - gg;
+        } else {
+            o0 = ict_term(r, 2449) + ict_term(gg, 4809) + ict_term(b, 934);
+            o1 = -ict_term(r, 1382) - ict_term(gg, 2714) + ict_term(b, 4096);
+            o2 = ict_term(r, 4096) - ict_term(gg, 3430) - ict_term(b, 666);
+        }
+        put<true>(&J.dst[0][di], o0); put<true>(&J.dst[1][di], o1); put<true>(&J.dst[2][di], o2);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if ((uint32_t)k >= ncomp || (mct && k < 3)) continue;
+        const int32_t s = v[k] - shift[k];
+        put<true>(&J.dst[k][di], irrev ? (int32_t)((uint32_t)s << 11) : s);
+    }
+}
+
+hipError_t launch_load_jobs(const LoadJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg, int32_t fmt,
+                            int mode, hipStream_t s) {
+    if (!njobs || !nwg) return hipSuccess;
+    if (mode < 0 || mode > 3) return hipErrorInvalidValue;
+#define GRK_LJ(S, MM) hipLaunchKernelGGL((k_load_jobs<S, MM>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs)
+#define GRK_LJ8(S)                         \
+    do {                                   \
+        if (mode & 1) return hipErrorInvalidValue; \
+        if (mode & 2) GRK_LJ(S, 2);        \
+        else GRK_LJ(S, 0);                 \
+    } while (0)
+#define GRK_LJ16(S)                  \
+    do {                             \
+        if (mode == 0) GRK_LJ(S, 0); \
+        else if (mode == 1) GRK_LJ(S, 1); \
+        else if (mode == 2) GRK_LJ(S, 2); \
+        else GRK_LJ(S, 3);           \
+    } while (0)
+    switch (fmt) {
+        case SMP_I32: GRK_LJ8(int32_t); break;
+        case SMP_U8: GRK_LJ8(uint8_t); break;
+        case SMP_I8: GRK_LJ8(int8_t); break;
+        case SMP_U16: GRK_LJ16(uint16_t); break;
+        case SMP_I16: GRK_LJ16(int16_t); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_LJ16
+#undef GRK_LJ8
+#undef GRK_LJ
+    return hipGetLastError();
+}
+
 template <typename T, bool FAST>
 static void launch_up(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
                       const DstPlanes &dst, bool interleaved, uint32_t dstride, hipStream_t s) {

@@ -780,6 +780,61 @@ typedef struct { uint32_t n_ok, n_blocks, n_store_jobs, n_launches; } grkgpu_bat
 int grkgpu_decompress_batch(grkgpu_ctx *ctx, grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
                             grkgpu_batch_info *info);
 int grkgpu_batch_plan(grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p, grkgpu_batch_info *info);
+/* Encode a batch of images in one launch set: item i is the whole-image encode
+ * grkgpu_compress_ex(ctx, &img, p, &in, 0, 0xffffffff, GRKGPU_PART_ALL, ...)
+ * and receives that call's codestream byte for byte, but the n items share
+ * one upload of their host samples (staged into one pinned buffer, each plane
+ * on a 16-byte boundary; device-resident items are read in place), one DC
+ * shift / MCT launch per source format and layout present (a job table,
+ * grkgpu_dcshift_mct_fwd_jobs; tiles of more than four components go through
+ * per-tile launches), one forward DWT launch sequence per wavelet, one Tier-1
+ * launch set per distinct code-block style, one gather launch and one D2H.
+ * Items may differ in everything grkgpu_compress_ex takes for a whole image:
+ * geometry, image and tile offsets, tile grid, components (1 .. 16),
+ * precision, sign, wavelet, resolutions, code-block size and style, precincts,
+ * layers with rate control, progression and POC, SOP / EPH, tile-parts and
+ * TLM, the cinema profiles, ROI, sample format with its flags, host or device
+ * source (in.row0 .. in.ncols as there: the whole image must be held).
+ *
+ * Every check that can refuse an image before a device is touched runs on the
+ * host first (the parameters, the sample-format rules, the 255 tile-part
+ * limit).  Not taken by this call, GRKGPU_EUNSUPPORTED for the item: a
+ * subsampled component, and a custom MCT (tcp_mct == 2 / grkgpu_set_mct).  An
+ * item that fails gets its code in `status` -- what the single call would have
+ * returned -- with cs = NULL and len = 0; the other items are encoded.  A
+ * failure that shows only after Tier-1 ("code-block numbps exceeds its band's
+ * bound", "too many coding passes", "MQ slab overflow", "rate allocation
+ * failed") fails that item alone.  The call returns GRKGPU_OK when every item
+ * succeeded, else the first failing item's code with grkgpu_last_error() =
+ * "item <i>: <its message>".  A NULL ctx, or NULL items with n > 0:
+ * GRKGPU_EINVAL; n = 0 is GRKGPU_OK.  Merged tables beyond the 32-bit limits
+ * of one call (code-blocks, pass-record slots, gather runs): the whole call is
+ * GRKGPU_EUNSUPPORTED "batch too large for one call" before any device work;
+ * the caller splits.
+ *
+ * cs / len point into the context's pinned output buffer, each item's stream
+ * on a 16-byte boundary, valid until the next call on ctx.  grkgpu_get_stats
+ * reports the batch (num_cblks, cs_bytes and mq_symbols are sums); the call is
+ * one call in progress for the Tier-1 plan, chosen on the merged block count
+ * of each style group.  info (may be NULL): items encoded, code-blocks,
+ * job-table load records and n_launches, the call's kernel launches and fills
+ * (the DWT plan's device copies included, the H2D / D2H copies not): 64
+ * copies of an image take the launches of one.
+ * grkgpu_compress_batch_plan is the host half alone -- no device call, no ctx,
+ * the items' planes not read: status of every item and info with
+ * n_launches = 0. */
+typedef struct {
+    grkgpu_image_desc img;   /* in */
+    const grkgpu_cparams *p; /* in; NULL: grkgpu_default_cparams */
+    grkgpu_planes in;        /* in: this item's samples (format + flags, host / device) */
+    const uint8_t *cs;       /* out: this item's codestream, in the context's pinned output buffer */
+    size_t len;              /* out */
+    int32_t status;          /* out: GRKGPU_OK or the code this item alone would have returned */
+    uint32_t pad_;
+} grkgpu_cbatch_item;
+typedef struct { uint32_t n_ok, n_blocks, n_load_jobs, n_launches; } grkgpu_cbatch_info;
+int grkgpu_compress_batch(grkgpu_ctx *ctx, grkgpu_cbatch_item *items, uint32_t n, grkgpu_cbatch_info *info);
+int grkgpu_compress_batch_plan(grkgpu_cbatch_item *items, uint32_t n, grkgpu_cbatch_info *info);
 /* The custom MCT of a codestream, host only: grkgpu_read_header's img (may be
  * NULL) for a stream with or without MCT = 2, and for the former *n = numcomps,
  * matrix[n * n] and offsets[n] (room for 256 / 16; either may be NULL) as
@@ -1031,6 +1086,28 @@ int grkgpu_convert_to(const void *const *src, const uint32_t *src_stride, uint32
 int grkgpu_dcshift_mct_fwd_from(const grkgpu_planes *src, uint32_t numcomps, uint32_t w, uint32_t h,
                                 uint32_t src_stride, const int32_t *shift, int32_t mct, int32_t irreversible,
                                 int32_t *const *dst, uint32_t dst_stride, void *stream);
+/* grkgpu_dcshift_mct_fwd_from for a table of n tiles in one launch (the first
+ * kernel of grkgpu_compress_batch on its own; the counterpart of
+ * grkgpu_mct_inv_dcshift_jobs_to): jobs is a host array whose src / dst are
+ * device pointers -- src[k] component k's sample at the tile's origin
+ * (interleaved: src[0] its first pixel; planar samples in host byte order
+ * sample aligned, else any byte), dst[k] its int32 plane -- numcomps 1 .. 4,
+ * src_stride in samples (>= w, interleaved >= w * numcomps), dst_stride >= w,
+ * the DC shift given per component.  Every job has the sample format given (a
+ * width with its flags, as grkgpu_planes.sample_fmt).  Jobs of w = 0 or h = 0
+ * load nothing.  The values are those grkgpu_dcshift_mct_fwd_from leaves job
+ * by job.  The table goes through the context's buffers and runs on its
+ * stream, which the call synchronises. */
+typedef struct {
+    const void *src[4];
+    int32_t *dst[4];
+    uint32_t src_stride, dst_stride, w, h;
+    uint32_t numcomps;
+    int32_t mct, irreversible;
+    uint32_t pad_;
+    int32_t shift[4];
+} grkgpu_load_job;
+int grkgpu_dcshift_mct_fwd_jobs(grkgpu_ctx *ctx, const grkgpu_load_job *jobs, uint32_t n, uint32_t sample_fmt);
 /* In-place (Mallat layout) forward / inverse DWT of one tile-component with
  * origin (x0,y0), size (x1-x0) x (y1-y0), row stride x1-x0.  scratch must
  * hold grkgpu_dwt_scratch_bytes(...) device bytes.  For 9/7 inverse the buffer
