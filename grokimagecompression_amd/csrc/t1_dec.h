@@ -9,9 +9,11 @@
 //     x-1..x+1) is packed into an 18-bit window P; the zero-coding context of
 //     row r is the LUT entry for (P >> 3r) & 0x1FF and the sign context comes
 //     from the N/W/E/S bits of P and of the matching sign window Q
-//   * the symbols of a column go through ONE decode site (a small state
-//     machine: ZC -> SC, AGG -> UNI -> UNI -> SC), so lanes of a wavefront
-//     that sit in different rows / symbol kinds still share the MQ code
+//   * a column's loop takes one step per sample: its ZC decision or a run
+//     symbol (a small state machine: ZC, AGG -> UNI -> UNI) through one decode
+//     site, so lanes of a wavefront that sit in different rows / symbol kinds
+//     still share the MQ code, and the sign decision of a sample that became
+//     significant through a second site in the same step (one masked region)
 //   * outputs are write-only bit-plane rows (sigafter / refbit, t1_lane.h)
 //     rebuilt into coefficients by k_t1_rebuild.
 //
@@ -118,49 +120,51 @@ GRK_HD bool d3_column(D &d, uint32_t *cxw, const DecTables &T, Stripe &s, uint32
     }
     uint32_t todo = nz & ~sig4 & ~vis4 & rows;
     const uint32_t todo0 = todo;
-    uint32_t kind = 0, p = 0;  // kind: 0 ZC, 1 SC, 2 AGG, 3 UNI(hi), 4 UNI(lo); p = 3 x row
-    // the context of the next symbol when it is not a ZC one: AGG, then UNI
-    // after an aggregation 1, or the SC context read with the sign LUT -- set
-    // at the transitions, so a step only selects between it and the ZC LUT's
-    uint32_t cxn = CX_AGG;
+    uint32_t kind = 0, p = 0;  // kind: 0 ZC (+ SC), 2 AGG, 3 UNI(hi), 4 UNI(lo) (+ SC); p = 3 x row
     if (CUP && nr == 4 && P == 0 && vis4 == 0) {
         kind = 2;
     } else {
         if (!todo) return false;
         p = (uint32_t)__builtin_ctz(todo);
     }
-    // the sign window, read at the column start by every lane: a lane's first
-    // sign symbol comes at almost every decision step of a wavefront, so a
-    // lazy read would be a branch entered at every step
-    uint32_t Q = win18(s.neg, x), si = 0;
+    // the sign window, read at the column start by every lane: the sign
+    // region below is entered at almost every step of a wavefront
+    uint32_t Q = win18(s.neg, x);
+    // One step per SAMPLE: the zero-coding decision (or a run symbol) and,
+    // for the lanes whose sample became significant, its sign decision in the
+    // same step -- a lane's column takes 1..4 steps plus the run symbols, not
+    // 1..9, and a wavefront's column step lasts as long as its slowest lane's.
     // The symbol-kind transitions are selects, not branches: the 64 lanes of
     // a wavefront sit in different kinds, and every branch taken by any lane
     // costs the whole wavefront its exec-mask bookkeeping.
     for (;;) {
         const uint32_t zcx = T.zc[(P >> p) & 0x1FF];  // read for every kind (LDS, in bounds)
         keep_here(zcx);
-        const uint32_t cx = kind == 0 ? zcx : cxn;
+        const uint32_t cx = kind == 0 ? zcx : kind == 2 ? (uint32_t)CX_AGG : (uint32_t)CX_UNI;
         const uint32_t bit = d.decode(cxw, T.mq, cx);
         if (kind == 2 && !bit) break;  // aggregation symbol 0: the column is done
-        const bool k0 = kind == 0, k1 = kind == 1, k3 = kind == 3, k4 = kind == 4;
-        // SC: the sample is significant with sign sg
-        const uint32_t sg = bit ^ ((D::kLazy && d.raw) ? 0u : (si >> 7));  // a raw sign is the sign itself
-        // the new significance and sign go into the windows only: the
-        // column's new rows are read back from them once, after the loop
-        P |= k1 ? 1u << (p + 4) : 0u;
-        Q |= k1 ? sg << (p + 4) : 0u;
-        // the sample below now has a significant neighbour (SPP)
-        todo |= (!CUP && k1) ? (rows & ~(sig4 | vis4)) & (8u << p) : 0u;
+        const bool k0 = kind == 0, k3 = kind == 3, k4 = kind == 4;
         // UNI, UNI: the run position (row 2 bit1 + bit0); the rows after it are plain ZC
         p = k3 ? (bit ? 6u : 0u) : k4 ? p + (bit ? 3u : 0u) : p;
-        todo = k4 ? rows & ~((8u << p) - 1) : todo;
-        const bool advance = k1 || (k0 && !bit);
-        cxn = kind == 2 ? (uint32_t)CX_UNI : cxn;  // aggregation 1: the run position in UNI
-        kind = k0 ? bit : k1 ? 0u : kind == 2 ? 3u : k3 ? 4u : 1u;
-        if (kind == 1 && !advance) {
-            si = T.sc[(((P >> p) & 0xAA) >> 1) | ((Q >> p) & 0xAA)];
-            cxn = si & 0x7fu;
+        todo = k4 ? rows : todo;
+        // the sign of the sample that became significant (a ZC 1, or the row
+        // the run position names): the one region of the step, entered when
+        // any lane of the wavefront needs it, the other lanes masked off
+        if (wave_any(k4 || (k0 && bit))) {
+            if (k4 || (k0 && bit)) {
+                const uint32_t si = T.sc[(((P >> p) & 0xAA) >> 1) | ((Q >> p) & 0xAA)];
+                const uint32_t sb = d.decode(cxw, T.mq, si & 0x7fu);
+                const uint32_t sg = sb ^ ((D::kLazy && d.raw) ? 0u : (si >> 7));  // a raw sign is the sign itself
+                // the new significance and sign go into the windows only: the
+                // column's new rows are read back from them once, after the loop
+                P |= 1u << (p + 4);
+                Q |= sg << (p + 4);
+                // the sample below now has a significant neighbour (SPP)
+                todo |= !CUP ? (rows & ~(sig4 | vis4)) & (8u << p) : 0u;
+            }
         }
+        const bool advance = k0 || k4;  // the sample is done; AGG 1 and the first UNI stay
+        kind = kind == 2 ? 3u : k3 ? 4u : 0u;
         todo = advance ? todo & ~((8u << p) - 1) : todo;
         if (advance && !todo) break;
         p = advance ? (uint32_t)__builtin_ctz(todo | (1u << 12)) : p;

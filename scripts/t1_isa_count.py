@@ -125,6 +125,14 @@ if "--all" in sys.argv:
             if any(x.startswith("v_alignbit_b32") for x in blocks[b]) and blocks[b][-1].startswith("s_cbranch_execz"):
                 tgt = blocks[b][-1].split()[1]
                 i, j = order.index(b) + 1, order.index(tgt)
+                if j < i:
+                    # the join block was laid out before this one (the sign
+                    # decision of a fused column step): the rare region runs
+                    # up to the block that branches back to it
+                    j = i
+                    while not blocks[order[j]] or not blocks[order[j]][-1].startswith("s_branch"):
+                        j += 1
+                    j += 1
                 rare.update(order[i:j])
         t = {"valu": 0, "salu": 0, "lds": 0, "vmem": 0, "other": 0}
         for b in lb:
