@@ -200,9 +200,17 @@ void build_tilecomp(TileComp &tc, const Rect &tile_r, const CodingParams &cp, ui
                 uint32_t cbgy0 = tlcbgy + (precno / res.pw) * (1u << cbgh);
                 pr.r = {std::max(cbgx0, b.r.x0), std::max(cbgy0, b.r.y0), std::min(cbgx0 + (1u << cbgw), b.r.x1),
                         std::min(cbgy0 + (1u << cbgh), b.r.y1)};
-                if (pr.r.x1 <= pr.r.x0 || pr.r.y1 <= pr.r.y0) { pr.cw = pr.ch = 0; continue; }
                 uint32_t tlx = (pr.r.x0 >> cbw) << cbw, tly = (pr.r.y0 >> cbh) << cbh;
                 uint32_t brx = ceildivpow2(pr.r.x1, cbw) << cbw, bry = ceildivpow2(pr.r.y1, cbh) << cbh;
+                if (pr.r.x1 <= pr.r.x0 || pr.r.y1 <= pr.r.y0) {
+                    // no samples, no code-blocks.  The reference still lays its code-block grid over
+                    // the empty rectangle (TileComponent.cpp:378-396, unsigned as there): at a
+                    // coordinate that is no multiple of the code-block size it holds a block without
+                    // samples, which only the rate allocator's packet simulation ever visits
+                    pr.phantom = (uint64_t)((brx - tlx) >> cbw) * ((bry - tly) >> cbh) > 0;
+                    pr.cw = pr.ch = 0;
+                    continue;
+                }
                 pr.cw = (brx - tlx) >> cbw;
                 pr.ch = (bry - tly) >> cbh;
                 pr.cblks.assign(pr.cw * pr.ch, Cblk());

@@ -167,6 +167,7 @@ struct Cblk {
 struct Precinct {
     Rect r;
     uint32_t cw = 0, ch = 0;
+    bool phantom = false;  // empty, but the reference's code-block grid over it has a block (build_tilecomp)
     std::vector<Cblk> cblks;
     TagTree incl, imsb;
 };

@@ -580,7 +580,15 @@ struct BitCount {
 
 // Packet header body shared by the writer and the simulator: inclusion,
 // missing MSBs, pass counts, length indicators.
-template <class W>
+// SIM: the header as T2::encode_packet_simulate counts it.  Unlike
+// encode_packet (T2.cpp:905, :939) it does not skip an empty band, and the
+// reference's precinct of an empty band can hold a code-block without samples
+// (Precinct::phantom): its inclusion tag tree, reset with the layer-0 packet
+// and never given a value, costs one 0 bit a packet -- the root's step from
+// layno to layno + 1; every other node inherits the root's bound.  That bit is
+// in no packet written, but it can carry a simulated header into one more
+// byte and so decide a bisection probe at a budget of a few dozen bytes.
+template <bool SIM = false, class W>
 void packet_header(const CodingParams &cp, TileEnc &te, Resolution &res, uint32_t precno, uint32_t layno, W &w) {
     std::vector<EncCblkState> &cs = *te.cblk;
     std::vector<EncLayer> &lay = *te.layers;
@@ -604,6 +612,7 @@ void packet_header(const CodingParams &cp, TileEnc &te, Resolution &res, uint32_
     w.write(1, 1);  // Grok always signals a non-empty packet (T2.cpp:924-927)
     for (uint32_t bandno = 0; bandno < res.numbands; ++bandno) {
         Band &b = res.bands[bandno];
+        if (SIM && b.empty() && precno < b.precs.size() && b.precs[precno].phantom) w.write(0, 1);
         if (b.empty() || precno >= b.precs.size()) continue;
         Precinct &pr = b.precs[precno];
         if (pr.cblks.empty()) continue;
@@ -695,7 +704,7 @@ bool simulate_packet(const CodingParams &cp, TileEnc &te, const PacketId &pk, ui
     uint64_t written = 0;
     if (cp.csty & CSTY_SOP) { length -= 6; written += 6; }
     BitCount w;
-    packet_header(cp, te, res, pk.precno, pk.layno, w);
+    packet_header<true>(cp, te, res, pk.precno, pk.layno, w);
     if (w.bytes > length) return false;
     written += w.bytes;
     length -= w.bytes;
@@ -776,8 +785,10 @@ struct RateProbe {
     std::vector<int64_t> comp_body;
     // the first layer's packet headers, bounded from above: per block the
     // bits its records cost (tag-tree bits taken as the whole path, the rest
-    // exact), summed per precinct; a packet of B bits is at most B / 7 + 2
-    // bytes (bit stuffing leaves >= 7 bits in every byte, the flush adds <= 2)
+    // exact), summed per precinct, plus the non-empty bit and one bit for each
+    // of up to three bands without samples (packet_header<SIM>); a packet of B
+    // bits is at most B / 7 + 2 bytes (bit stuffing leaves >= 7 bits in every
+    // byte, the flush adds <= 2)
     std::vector<uint8_t> lev;           // per block: its tag trees' path length
     std::vector<uint8_t> bnumbps;       // per block: its band's bit-planes
     std::vector<uint32_t> ub;           // per block: header bits bound of its layer-0 record
@@ -926,7 +937,7 @@ void probe_precinct(CodingParams &cp, TileEnc &te, RateProbe &rp, uint32_t p) {
         const PacketId &pk = rp.order[rp.pos[q]];
         Resolution &res = te.tile->comps[pk.compno].res[pk.resno];
         BitCount w;
-        packet_header(cp, te, res, pk.precno, pk.layno, w);
+        packet_header<true>(cp, te, res, pk.precno, pk.layno, w);
         uint64_t d = 0;
         for (uint32_t bandno = 0; bandno < res.numbands; ++bandno) {
             Band &b = res.bands[bandno];
@@ -944,7 +955,7 @@ void probe_precinct(CodingParams &cp, TileEnc &te, RateProbe &rp, uint32_t p) {
         // the bound body_fits takes for this packet (header_bits_ub summed per precinct)
         if (rp.layers == 1 && rp.body_exact && !(cp.csty & (CSTY_SOP | CSTY_EPH)) && rp.prec_bits[p] < (int64_t)UB_NONE) {
             ++g_ub_checks;
-            if ((uint64_t)w.bytes > (uint64_t)(1 + rp.prec_bits[p]) / 7 + 2) ++g_ub_viol;
+            if ((uint64_t)w.bytes > (uint64_t)(1 + 3 + rp.prec_bits[p]) / 7 + 2) ++g_ub_viol;
         }
 #endif
     }
@@ -1325,7 +1336,7 @@ bool body_fits(CodingParams &cp, TileEnc &te, uint32_t max_layers, uint64_t max_
         const uint32_t npk = rp.head[p + 1] - rp.head[p];
         if (!npk) continue;
         if (rp.prec_bits[p] >= (int64_t)UB_NONE) return false;
-        const uint64_t b = (uint64_t)npk * ((uint64_t)(1 + rp.prec_bits[p]) / 7 + 2);
+        const uint64_t b = (uint64_t)npk * ((uint64_t)(1 + 3 + rp.prec_bits[p]) / 7 + 2);  // + a bit per band without samples
         hb += b;
         chb[rp.prec_comp[p]] += b;
     }

@@ -179,3 +179,29 @@ def test_pcrd_header_bound_holds(tmp_path):
                 m = re.search(r"header_ub checks (\d+) violations (\d+)", r.stdout)
                 assert m, r.stdout
                 assert int(m.group(1)) > 0 and int(m.group(2)) == 0, (algo, budget, terms, r.stdout)
+
+
+# tile -> code-block bytes of its first layer in the reference's codestream
+GEOM_RATE = {"geom_000_t14": 17, "geom_001_t6": 12, "geom_002_t2": 14}
+
+
+def test_rate_allocation_counts_sampleless_blocks_of_empty_bands(tmp_path):
+    """Three tiles of the geometry sweep, 2 or 3 samples wide, under -r a,1:
+    their first layer has 30 bytes, and one bisection probe lands on exactly 30.
+    The reference's packet simulation counts one more header bit there -- the
+    inclusion bit of a code-block without samples that it keeps in a band
+    without samples (t2.cpp packet_header<SIM>) -- so the probe does not fit
+    and the layer ends smaller.  tests/cpp/geom_rate.cpp replays the
+    allocation from the encoder's pass records: the first layer's code-block
+    bytes are those of the reference's codestream (17 / 12 / 14, not 18 / 14 /
+    18), with and without the precomputed slope extremes.  The whole streams:
+    tests/test_gpu_geom.py."""
+    exe = tmp_path / "geom_rate"
+    c = os.path.join(ROOT, "grokimagecompression_amd", "csrc")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I" + c, "-o", str(exe), os.path.join(ROOT, "tests/cpp/geom_rate.cpp"),
+                    os.path.join(c, "t2.cpp"), os.path.join(c, "codestream.cpp"), "-lpthread"], check=True)
+    for name, body in GEOM_RATE.items():
+        for slopes in ("0", "1"):
+            r = subprocess.run([str(exe), os.path.join(ROOT, "tests", "golden", "geom_rate_%s.txt" % name), slopes],
+                               capture_output=True, text=True, check=True)
+            assert "rate0 30.000" in r.stdout and "layer 0 body bytes %d\n" % body in r.stdout, (name, slopes, r.stdout)

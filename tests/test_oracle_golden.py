@@ -4,11 +4,13 @@ tests/golden/*.j2k were written by the reference grk_compress (Grok v5.1.0)
 from tests/golden/synth.py images (oracle/make_golden.py); *.dec.npy are the
 reference grk_decompress outputs.  The oracle must reproduce both exactly.
 """
+import functools
 import hashlib
 
 import numpy as np
 import pytest
 
+import geom_fixtures
 import prec_fixtures
 import synth
 from conftest import GOLD, load_manifest, oracle_supported
@@ -126,3 +128,46 @@ def test_oracle_reduce_is_forward_ll(oracle, name):
         assert np.array_equal(red, exp), (name, r)
     with pytest.raises(RuntimeError):
         oracle.decode(gold, reduce=numres)
+
+
+# ---- the geometry sweep (oracle/make_golden_geom.py): reference == manifest == oracle ----
+GEOM_ORACLE = [m["name"] for m in geom_fixtures.CASES if oracle_supported(m["args"]) and not m["subsampling"]]
+
+
+@functools.lru_cache(maxsize=None)
+def geom_oracle_stream(name):
+    """The oracle's codestream of a sweep case (no stream is committed: the
+    manifest holds the reference's hash of it)."""
+    import pyoracle
+    m = geom_fixtures.BY_NAME[name]
+    p = pyoracle.params_from_args(m["args"], nthreads=4)
+    return pyoracle.encode(geom_fixtures.image(m), m["bits"], p, pyoracle.image_offset_from_args(m["args"]))
+
+
+def test_geom_sweep_reaches_the_oracle():
+    """Enough of the sweep is within the options the oracle restates, and it
+    holds tiled, offset, one-sample and deep-resolution cases."""
+    cl = [set(geom_fixtures.BY_NAME[n]["classes"]) for n in GEOM_ORACLE]
+    assert len(GEOM_ORACLE) >= 30
+    for t in "abcdjk":
+        assert sum(t in c for c in cl) >= 2, t
+
+
+@pytest.mark.parametrize("name", GEOM_ORACLE)
+def test_oracle_matches_reference_on_geom_sweep(oracle, name):
+    """Encode: the recorded length and hash of the reference's codestream.
+    Decode of those bytes: the recorded hash of the reference's decode, and of
+    its -r decode where the case has one (the decoded samples, as
+    oracle.decode returns them)."""
+    m = geom_fixtures.BY_NAME[name]
+    b = geom_oracle_stream(name)
+    assert len(b) == m["j2k_len"]
+    assert hashlib.sha256(b).hexdigest() == m["j2k_sha256"]
+    d = oracle.decode(b, nthreads=4)
+    assert geom_fixtures.planes_sha(list(d)) == m["dec_sha256"]
+    for tag, v in m.get("variants", {}).items():
+        if v["args"][0] != "-r":
+            continue
+        r = oracle.decode(b, nthreads=4, reduce=int(v["args"][1]))
+        assert [list(p.shape) for p in r] == v["shapes"], tag
+        assert geom_fixtures.planes_sha(list(r)) == v["dec_sha256"], tag

@@ -69,6 +69,17 @@ def test_subsampled_fixtures_regenerate():
     assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
 
 
+def test_geometry_sweep_regenerates():
+    """tests/golden/manifest_geom.json: 256 machine-drawn geometries (odd
+    origins, one-sample tiles, empty resolutions, small precincts, position
+    progressions, subsampling), hashes only, drawn and encoded again by the
+    reference (oracle/make_golden_geom.py): the same draws, every edge class
+    with its 8 members, at most 10 % of the draws refused by the reference."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "make_golden_geom.py"), "--check"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
+
+
 def test_precision_fixtures_regenerate():
     """tests/golden/p_*: every precision 1 .. 16, signed samples, 1 .. 5 and
     mixed components, encoded and decoded by the reference
