@@ -1141,6 +1141,36 @@ static hipError_t dwt_launch(DwtPlan &P, DevBuf &djobs, int irrev, bool inverse,
     return dwt_run_levels(P, djobs.as<DwtJob>(), irrev, inverse, s, log);
 }
 
+// the launches and copies dwt_launch issues for a plan
+static uint32_t dwt_launch_count(const DwtPlan &P, bool inverse) {
+    uint32_t nl = (uint32_t)P.copies2d.size();
+    for (auto &cp : P.copies) nl += cp.elems != 0;
+    for (size_t li = 0; li < P.levels.size(); ++li) {
+        ++nl;
+        if ((li < P.f01.size() && P.f01[li]) || (inverse && P.i01 && li + 2 == P.levels.size())) ++li;  // a level pair
+    }
+    return nl;
+}
+
+// The plan pair of a call whose tile-components may mix the wavelets (COC /
+// tile COD, or the items of a batch): P[1] the 9/7 plan through dwtjobs, P[0]
+// the 5/3 plan through dwtjobs53.  Their uploads, and their launches under the
+// call's launch log; *nl grows by the launches and copies issued.
+static hipError_t dwt_upload_plans(grkgpu_ctx *c, DwtPlan (&P)[2]) {
+    const hipError_t e = dwt_upload(P[1], c->dwtjobs, c->h_dwtjobs, 1, c->stream);
+    return e != hipSuccess ? e : dwt_upload(P[0], c->dwtjobs53, c->h_dwtjobs53, 0, c->stream);
+}
+static hipError_t dwt_launch_plans(grkgpu_ctx *c, DwtPlan (&P)[2], bool inverse, uint32_t *nl) {
+    c->ltimes.clear();
+    c->lidx.clear();
+    LaunchLog llog{&c->lev, &c->ltimes, &c->lidx};
+    LaunchLog *log = c->launch_timing ? &llog : nullptr;
+    hipError_t e = dwt_launch(P[1], c->dwtjobs, 1, inverse, c->stream, log);
+    if (e == hipSuccess) e = dwt_launch(P[0], c->dwtjobs53, 0, inverse, c->stream, log);
+    *nl += dwt_launch_count(P[1], inverse) + dwt_launch_count(P[0], inverse);
+    return e;
+}
+
 static bool overlap(const Rect &a, const Rect &b) { return a.x0 < b.x1 && b.x0 < a.x1 && a.y0 < b.y1 && b.y0 < a.y1; }
 static Rect intersect(const Rect &a, const Rect &b) {
     Rect r{std::max(a.x0, b.x0), std::max(a.y0, b.y0), std::min(a.x1, b.x1), std::min(a.y1, b.y1)};
@@ -1251,6 +1281,9 @@ struct EncHost {
     uint32_t mct_numcomps = 0;
     std::vector<std::vector<uint32_t>> tp_counts;  // [tile][poc entry]
     uint32_t total_tile_parts = 0;
+    // the image's place in the merged tables of a batch (zero in a single
+    // call): its first block, first rate-controlled block, first pass-record slot
+    uint64_t mb0 = 0, rcb0 = 0, slot0 = 0;
 
     // ---- records ----
     std::vector<EncCblkState> cst;
@@ -1808,6 +1841,216 @@ int EncHost::finish_end() {
 }
 }  // namespace
 
+// The device stages of an encode: compress_impl runs them over its one
+// image's tables, the batch encode over its merged ones.
+//
+// A run of the block table coded in one style (a Tier-1 launch set each): its
+// images (indices into the caller's EncHost array) in table order, the
+// rate-controlled ones first -- the run's first nrc blocks.  scr0 / ord0: its
+// place in ctx->scratch (bytes) and ctx->t1order (words); rc0: its first
+// block among the rate-controlled ones of all runs.
+struct StyGroup {
+    uint32_t sty = 0, b0 = 0, n = 0, nrc = 0, maxdepth = 1, rc0 = 0;
+    uint64_t scr0 = 0, ord0 = 0;
+    std::vector<uint32_t> items;
+};
+
+// the kernel launches and fills launch_t1_encode issues for n blocks
+static uint32_t t1_encode_launch_count(uint32_t n) {
+    if (!n) return 0;
+    return 3 + (dwt_options().t1_enc_sort && n > 64 ? 4 : 0);
+}
+
+// the buffers of an encode of nblk blocks that both paths size alike
+static int enc_ensure(grkgpu_ctx *c, uint64_t arena, uint64_t llarena, uint64_t scr_bytes, uint64_t ord_words,
+                      uint64_t out_total, uint64_t sym_total, uint32_t nblk) {
+    HIPCHK(c->work.ensure(arena * 4 + 256));
+    HIPCHK(c->coef.ensure(arena * 4 + 256));
+    HIPCHK(c->ll.ensure(llarena * 4 + 256));
+    HIPCHK(c->scratch.ensure((size_t)scr_bytes + 256));
+    HIPCHK(c->t1order.ensure((size_t)ord_words * 4 + 256));
+    HIPCHK(c->mqout.ensure(out_total + 256));
+    HIPCHK(c->blocks.ensure((size_t)nblk * sizeof(EncBlock) + 256));
+    HIPCHK(c->results.ensure((size_t)nblk * sizeof(EncResult) + 256));
+    HIPCHK(c->h_results.ensure((size_t)nblk * sizeof(EncResult) + 256));
+    HIPCHK(c->h_blocks.ensure((size_t)nblk * sizeof(EncBlock) + 256));
+    HIPCHK(c->sym.ensure(sym_total + 256));
+    HIPCHK(c->symoff.ensure(((size_t)nblk + 1) * 8 + 256));
+    HIPCHK(c->h_symoff.ensure(((size_t)nblk + 1) * 8 + 256));
+    return GRKGPU_OK;
+}
+
+// The Tier-1 stage of an encode, from the table uploads to the results on the
+// host (event 4 after the last coder launch).  In: nblk EncBlocks and nblk + 1
+// symbol-stream offsets staged in h_blocks / h_symoff, the runs `sg` over
+// them, H = the images the runs' items index; nrc / slots = the
+// rate-controlled blocks and their pass-record slots over all runs.  *nl
+// grows by the launches and fills issued.
+// With rate control the pass records are formed on the device
+// (launch_pass_records): the host fills each block's distortion factor and
+// record slots while the GPU codes (h_pinfo: nrc factors, then the slots, nrc
+// + one end per run, run g's from rc0 + g), and only the records (h_precs) and
+// per-block summaries (h_psum) come back.  Without it the host forms them
+// from the coders' results (h_results, rates only: no distortion to weigh).
+static int enc_t1_stage(grkgpu_ctx *c, const std::vector<StyGroup> &sg, const EncHost *H, uint32_t nblk, uint32_t nrc,
+                        uint64_t slots, uint32_t *nl) {
+    hipStream_t s = c->stream;
+    const bool lone = lone_call();
+    HIPCHK(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, (size_t)nblk * sizeof(EncBlock), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->symoff.p, c->h_symoff.p, ((size_t)nblk + 1) * 8, hipMemcpyHostToDevice, s));
+    for (const StyGroup &g : sg) {
+        HIPCHK(launch_t1_encode(c->blocks.as<EncBlock>() + g.b0, g.n, c->coef.as<int32_t>(),
+                                c->scratch.as<uint8_t>() + g.scr0, c->sym.as<uint8_t>(), c->symoff.as<uint64_t>() + g.b0,
+                                g.maxdepth, c->mqout.as<uint8_t>(), c->results.as<EncResult>() + g.b0, s, g.sty,
+                                lone ? lone_bpw(g.n) : 0, c->t1order.as<uint32_t>() + g.ord0));
+        *nl += t1_encode_launch_count(g.n);
+    }
+    const size_t p0_words = (size_t)nrc + sg.size();
+    if (nrc) {
+        HIPCHK(c->h_pinfo.ensure(((size_t)nrc + p0_words) * 8 + 256));
+        HIPCHK(c->pinfo.ensure(((size_t)nrc + p0_words) * 8 + 256));
+        double *wf = c->h_pinfo.as<double>();
+        uint64_t *p0 = (uint64_t *)(wf + nrc);
+        for (size_t gi = 0; gi < sg.size(); ++gi) {
+            const StyGroup &g = sg[gi];
+            uint64_t sl = 0;
+            for (uint32_t i : g.items) {
+                const EncHost &h = H[i];
+                if (!h.need_rc) continue;
+                sl = h.slot0;
+                for (uint32_t q = 0; q < h.nblk; ++q) {
+                    wf[h.rcb0 + q] = h.wfac(q);
+                    p0[h.rcb0 + gi + q] = sl;
+                    sl += h.pcap[q];
+                }
+            }
+            p0[(size_t)g.rc0 + gi + g.nrc] = g.nrc ? sl : 0;
+        }
+        HIPCHK(hipMemcpyAsync(c->pinfo.p, c->h_pinfo.p, ((size_t)nrc + p0_words) * 8, hipMemcpyHostToDevice, s));
+    }
+    for (const StyGroup &g : sg) {
+        if (!g.nrc) continue;
+        HIPCHK(launch_t1_dist(c->blocks.as<EncBlock>() + g.b0, g.n, g.maxdepth, c->coef.as<int32_t>(),
+                              c->scratch.as<uint8_t>() + g.scr0, c->results.as<EncResult>() + g.b0, s));
+        ++*nl;
+    }
+    HIPCHK(hipEventRecord(c->ev[4], s));
+    if (nrc) {
+        const size_t sum_bytes = ((size_t)nrc * sizeof(PassSum) + 255) & ~(size_t)255;
+        HIPCHK(c->precs.ensure(sum_bytes + slots * sizeof(DevPass) + 256));
+        HIPCHK(c->h_psum.ensure(sum_bytes + 256));
+        HIPCHK(c->h_precs.ensure(slots * sizeof(DevPass) + 256));
+        PassSum *dsum = c->precs.as<PassSum>();
+        DevPass *dpass = (DevPass *)(c->precs.as<uint8_t>() + sum_bytes);
+        const double *dwf = c->pinfo.as<double>();
+        const uint64_t *dp0 = (const uint64_t *)(dwf + nrc);
+        for (size_t gi = 0; gi < sg.size(); ++gi) {
+            const StyGroup &g = sg[gi];
+            if (!g.nrc) continue;
+            HIPCHK(launch_pass_records(c->blocks.as<EncBlock>() + g.b0, c->results.as<EncResult>() + g.b0, dwf + g.rc0,
+                                       dp0 + g.rc0 + gi, g.nrc, g.sty, dpass, dsum + g.rc0, s));
+            ++*nl;
+        }
+        HIPCHK(hipMemcpyAsync(c->h_psum.p, dsum, (size_t)nrc * sizeof(PassSum), hipMemcpyDeviceToHost, s));
+        if (slots) HIPCHK(hipMemcpyAsync(c->h_precs.p, dpass, slots * sizeof(DevPass), hipMemcpyDeviceToHost, s));
+    }
+    for (const StyGroup &g : sg) {  // the other blocks' results, rates only
+        if (g.n == g.nrc) continue;
+        const size_t o = ((size_t)g.b0 + g.nrc) * sizeof(EncResult);
+        HIPCHK(hipMemcpy2DAsync(c->h_results.as<uint8_t>() + o, sizeof(EncResult), c->results.as<uint8_t>() + o,
+                                sizeof(EncResult), ENC_RESULT_RATE_BYTES, g.n - g.nrc, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return GRKGPU_OK;
+}
+
+// One image's PlanItems appended to a gather list, its bytes from `total` on
+// (advanced), its header runs `hbase` into the blob the list is gathered from.
+static void gather_append(std::vector<GatherItem> &gi, const std::vector<PlanItem> &plan, uint64_t hbase, uint64_t &total) {
+    for (const PlanItem &pi : plan) {
+        if (pi.len) gi.push_back({pi.kind == 0 ? pi.src + hbase : pi.src, total, pi.len, pi.kind});
+        total += pi.len;
+    }
+}
+
+// The output stage of an encode: the gather list and the header blob to the
+// device, the gather kernel (header runs from the blob, code-block bytes from
+// the MQ slab, assembled in HBM) and one D2H of the `total` bytes into the
+// pinned output buffer, events 5..7 around them.  out_lk (not yet locked) is
+// the caller's lock on ctx->out_mu: taken here before h_out is chosen, for
+// the caller to hold while it hands h_out's bytes out.
+static int enc_output_stage(grkgpu_ctx *c, const std::vector<GatherItem> &gi, const ByteBuf &hdr, uint64_t total,
+                            std::unique_lock<std::mutex> &out_lk, uint32_t *nl) {
+    hipStream_t s = c->stream;
+    HIPCHK(c->gather.ensure(gi.size() * sizeof(GatherItem) + hdr.size() + 512));
+    HIPCHK(c->h_gather.ensure(gi.size() * sizeof(GatherItem) + hdr.size() + 512));
+    HIPCHK(c->packed.ensure(total + 256));
+    out_lk.lock();
+    if (!c->h_out.p && !c->out_spare.empty()) {  // taken by a view: reuse a given-back buffer
+        auto big = std::max_element(c->out_spare.begin(), c->out_spare.end(),
+                                    [](const auto &a, const auto &b) { return a.second < b.second; });
+        c->h_out.p = big->first;
+        c->h_out.cap = big->second;
+        c->out_spare.erase(big);
+    }
+    HIPCHK(c->h_out.ensure(total + 256));
+    const size_t gbytes = gi.size() * sizeof(GatherItem);
+    const size_t hoff = (gbytes + 255) & ~(size_t)255;
+    memcpy(c->h_gather.p, gi.data(), gbytes);
+    memcpy(c->h_gather.as<uint8_t>() + hoff, hdr.v.data(), hdr.size());
+    HIPCHK(hipEventRecord(c->ev[5], s));
+    HIPCHK(hipMemcpyAsync(c->gather.p, c->h_gather.p, hoff + hdr.size(), hipMemcpyHostToDevice, s));
+    if (!gi.empty()) {  // (launch_gather issues nothing for an empty list)
+        HIPCHK(launch_gather(c->gather.as<uint8_t>() + hoff, c->mqout.as<uint8_t>(), c->gather.as<GatherItem>(),
+                             (uint32_t)gi.size(), c->packed.as<uint8_t>(), s));
+        ++*nl;
+    }
+    HIPCHK(hipEventRecord(c->ev[6], s));
+    // (a batch's pad bytes before a stream's 16-byte boundary are copied as they are: no item's cs / len covers them)
+    if (total) HIPCHK(hipMemcpyAsync(c->h_out.p, c->packed.p, total, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(c->ev[7], s));
+    HIPCHK(hipStreamSynchronize(s));
+    return GRKGPU_OK;
+}
+
+// The statistics of an encode (grkgpu_get_stats) from the stage events and the
+// host's clock.  tail: what the calls that write a codestream add (null:
+// grkgpu_encode_blocks, which stops after Tier-1 -- those fields stay zero).
+struct EncStatsTail {
+    double t_t2, t_t2_end, t_passrec, t_rate, t_packets;
+    uint64_t cs_bytes;
+    const RateStats &rs;
+};
+static void fill_enc_stats(grkgpu_ctx *c, double t_start, double t_end, uint32_t nblk, uint64_t nsym,
+                           const EncStatsTail *tail) {
+    grkgpu_stats &st = c->stats;
+    memset(&st, 0, sizeof(st));
+    hipEventElapsedTime(&st.h2d_ms, c->ev[0], c->ev[1]);
+    hipEventElapsedTime(&st.dcshift_mct_ms, c->ev[1], c->ev[2]);
+    hipEventElapsedTime(&st.dwt_ms, c->ev[2], c->ev[3]);
+    hipEventElapsedTime(&st.t1_ms, c->ev[3], c->ev[4]);
+    if (tail) {
+        hipEventElapsedTime(&st.gather_ms, c->ev[5], c->ev[6]);
+        hipEventElapsedTime(&st.d2h_ms, c->ev[6], c->ev[7]);
+    }
+    log_collect(c);
+    st.total_ms = (float)(t_end - t_start);
+    st.num_cblks = nblk;
+    st.mq_symbols = nsym;
+    if (!tail) return;
+    st.host_t2_ms = (float)(tail->t_t2_end - tail->t_t2);
+    st.cs_bytes = tail->cs_bytes;
+    st.rate_ms = (float)tail->t_rate;
+    st.packet_ms = (float)tail->t_packets;
+    st.rate_probes = tail->rs.probes;
+    st.rate_probes_skipped = tail->rs.skipped;
+    st.rate_block_evals = tail->rs.evals;
+    st.rate_precinct_sims = tail->rs.sims;
+    st.rate_form_ms = (float)tail->rs.form_ms;
+    st.rate_sim_ms = (float)tail->rs.sim_ms;
+    st.passrec_ms = (float)tail->t_passrec;
+}
+
 // Encode tiles [tb, te) (a tile shard: j2k_encode's per-tile loop,
 // j2k.cpp:2088-2111) and emit [main header][their tile-parts][EOC] per `parts`.
 // export_blocks: stop after Tier-1 and hand the per-code-block results to the
@@ -1846,23 +2089,11 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
     const std::vector<uint64_t> &lloff = H.lloff, &symoff = H.symoff;
     const std::vector<EncBlock> &eb = H.eb;
     const std::vector<EncHost::BlkInfo> &binfo = H.binfo;
-    const std::vector<uint32_t> &pcap = H.pcap;
     auto plane_org = [&](uint32_t k, const TileComp &tc) { return H.plane_org(k, tc); };
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIPCHK(c->work.ensure(arena * 4 + 256));
-    HIPCHK(c->coef.ensure(arena * 4 + 256));
-    HIPCHK(c->ll.ensure(llarena * 4 + 256));
-    HIPCHK(c->scratch.ensure((size_t)t1e_scratch_bytes(nblk, maxdepth) + 256));
-    HIPCHK(c->t1order.ensure((size_t)t1_order_words(nblk) * 4 + 256));
-    HIPCHK(c->mqout.ensure(out_total + 256));
-    HIPCHK(c->blocks.ensure((size_t)nblk * sizeof(EncBlock) + 256));
-    HIPCHK(c->results.ensure((size_t)nblk * sizeof(EncResult) + 256));
-    HIPCHK(c->h_results.ensure((size_t)nblk * sizeof(EncResult) + 256));
-    HIPCHK(c->h_blocks.ensure((size_t)nblk * sizeof(EncBlock) + 256));
-    HIPCHK(c->sym.ensure(sym_total + 256));
-    HIPCHK(c->symoff.ensure(symoff.size() * 8 + 256));
-    HIPCHK(c->h_symoff.ensure(symoff.size() * 8 + 256));
+    rc = enc_ensure(c, arena, llarena, t1e_scratch_bytes(nblk, maxdepth), t1_order_words(nblk), out_total, sym_total, nblk);
+    if (rc) return rc;
 
     HIPCHK(hipEventRecord(c->ev[0], s));
     // input planes on the device, as the caller's samples (widened to int32
@@ -1984,55 +2215,16 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
     HIPCHK(dwt_launch(dplan, c->dwtjobs, cp.irrev, false, s, c->launch_timing ? &llog : nullptr));
     HIPCHK(hipEventRecord(c->ev[3], s));
     memcpy(c->h_blocks.p, eb.data(), (size_t)nblk * sizeof(EncBlock));
-    HIPCHK(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, (size_t)nblk * sizeof(EncBlock), hipMemcpyHostToDevice, s));
     memcpy(c->h_symoff.p, symoff.data(), symoff.size() * 8);
-    HIPCHK(hipMemcpyAsync(c->symoff.p, c->h_symoff.p, symoff.size() * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(launch_t1_encode(c->blocks.as<EncBlock>(), nblk, c->coef.as<int32_t>(), c->scratch.p,
-                            c->sym.as<uint8_t>(), c->symoff.as<uint64_t>(), maxdepth, c->mqout.as<uint8_t>(),
-                            c->results.as<EncResult>(), s, cp.cblksty, lone_call() ? lone_bpw(nblk) : 0,
-                            c->t1order.as<uint32_t>()));
-    // With rate control the pass records are formed on the device
-    // (launch_pass_records): the host fills each block's distortion factor
-    // and record slots while the GPU codes, and after the coders only the
-    // records and per-block summaries come back.  Without it the host forms
-    // them from the coders' results (rates only: no distortion to weigh).
+    // one run of the image's style: all of its blocks rate-controlled, or none
+    // (then, or with no block at all, the host forms the pass records)
     const bool dev_rec = need_rc && nblk;
-    uint64_t ptotal = 0;
-    if (dev_rec) {
-        HIPCHK(c->h_pinfo.ensure((size_t)nblk * 16 + 8 + 256));
-        double *wf = c->h_pinfo.as<double>();
-        uint64_t *p0 = (uint64_t *)(wf + nblk);
-        for (uint32_t i = 0; i < nblk; ++i) {
-            wf[i] = H.wfac(i);
-            p0[i] = ptotal;
-            ptotal += pcap[i];
-        }
-        p0[nblk] = ptotal;
-        HIPCHK(c->pinfo.ensure((size_t)nblk * 16 + 8 + 256));
-        HIPCHK(hipMemcpyAsync(c->pinfo.p, c->h_pinfo.p, (size_t)nblk * 16 + 8, hipMemcpyHostToDevice, s));
-    }
-    if (need_rc)
-        HIPCHK(launch_t1_dist(c->blocks.as<EncBlock>(), nblk, maxdepth, c->coef.as<int32_t>(), c->scratch.p,
-                              c->results.as<EncResult>(), s));
-    HIPCHK(hipEventRecord(c->ev[4], s));
-    if (dev_rec) {
-        const size_t sum_bytes = ((size_t)nblk * sizeof(PassSum) + 255) & ~(size_t)255;
-        HIPCHK(c->precs.ensure(sum_bytes + ptotal * sizeof(DevPass) + 256));
-        HIPCHK(c->h_psum.ensure(sum_bytes + 256));
-        HIPCHK(c->h_precs.ensure(ptotal * sizeof(DevPass) + 256));
-        PassSum *dsum = c->precs.as<PassSum>();
-        DevPass *dpass = (DevPass *)(c->precs.as<uint8_t>() + sum_bytes);
-        const double *dwf = c->pinfo.as<double>();
-        HIPCHK(launch_pass_records(c->blocks.as<EncBlock>(), c->results.as<EncResult>(), dwf,
-                                   (const uint64_t *)(dwf + nblk), nblk, cp.cblksty, dpass, dsum, s));
-        HIPCHK(hipMemcpyAsync(c->h_psum.p, dsum, (size_t)nblk * sizeof(PassSum), hipMemcpyDeviceToHost, s));
-        if (ptotal)
-            HIPCHK(hipMemcpyAsync(c->h_precs.p, dpass, ptotal * sizeof(DevPass), hipMemcpyDeviceToHost, s));
-    } else if (nblk) {
-        HIPCHK(hipMemcpy2DAsync(c->h_results.p, sizeof(EncResult), c->results.p, sizeof(EncResult),
-                                ENC_RESULT_RATE_BYTES, nblk, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
+    std::vector<StyGroup> sg(1);
+    sg[0].sty = cp.cblksty; sg[0].n = nblk; sg[0].nrc = need_rc ? nblk : 0; sg[0].maxdepth = maxdepth;
+    sg[0].items.push_back(0);
+    uint32_t nl = 0;  // (the batch's launch count: not reported by this call)
+    rc = enc_t1_stage(c, sg, &H, nblk, sg[0].nrc, H.ptotal, &nl);
+    if (rc) return rc;
     const EncResult *res = c->h_results.as<EncResult>();
 
     // Tier-2 + headers on the host (j2k_encode :2059, j2k_post_write_tile
@@ -2086,16 +2278,7 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
         for (auto &tile : tiles)
             for (uint32_t k = 0; k < nc; ++k)
                 c->bexp_coef.push_back({tile.index, k, tile.comps[k].r.w(), tile.comps[k].r.h(), tile.comps[k].arena_off});
-        grkgpu_stats &st0 = c->stats;
-        memset(&st0, 0, sizeof(st0));
-        hipEventElapsedTime(&st0.h2d_ms, c->ev[0], c->ev[1]);
-        hipEventElapsedTime(&st0.dcshift_mct_ms, c->ev[1], c->ev[2]);
-        hipEventElapsedTime(&st0.dwt_ms, c->ev[2], c->ev[3]);
-        hipEventElapsedTime(&st0.t1_ms, c->ev[3], c->ev[4]);
-        log_collect(c);
-        st0.num_cblks = nblk;
-        st0.mq_symbols = nsym;
-        st0.total_ms = (float)(now_ms() - t_start);
+        fill_enc_stats(c, t_start, now_ms(), nblk, nsym, nullptr);
         return GRKGPU_OK;
     }
     rc = H.finish_begin();
@@ -2107,8 +2290,6 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
     if (rc) return rc;
     ByteBuf &hdr = H.hdr;
     std::vector<PlanItem> &plan = H.plan;
-    const double t_rate = H.t_rate, t_packets = H.t_packets;
-    const RateStats &rsum = H.rsum;
     if (jp2_boxes) {
         // grkgpu_jp2_compress: the file's boxes (ending in the jp2c box header)
         // are one more run of the header blob, gathered ahead of everything
@@ -2126,62 +2307,16 @@ static int compress_impl(grkgpu_ctx *c, const grkgpu_image_desc *img, const grkg
     std::vector<GatherItem> gi;
     gi.reserve(plan.size());
     uint64_t total = 0;
-    for (auto &pi : plan) {
-        if (pi.len) gi.push_back({pi.src, total, pi.len, pi.kind});
-        total += pi.len;
-    }
+    gather_append(gi, plan, 0, total);
     double t_t2_end = now_ms();
-    HIPCHK(c->gather.ensure(gi.size() * sizeof(GatherItem) + hdr.size() + 512));
-    HIPCHK(c->h_gather.ensure(gi.size() * sizeof(GatherItem) + hdr.size() + 512));
-    HIPCHK(c->packed.ensure(total + 256));
-    std::unique_lock<std::mutex> out_lk(c->out_mu);
-    if (!c->h_out.p && !c->out_spare.empty()) {  // taken by a view: reuse a given-back buffer
-        auto big = std::max_element(c->out_spare.begin(), c->out_spare.end(),
-                                    [](const auto &a, const auto &b) { return a.second < b.second; });
-        c->h_out.p = big->first;
-        c->h_out.cap = big->second;
-        c->out_spare.erase(big);
-    }
-    HIPCHK(c->h_out.ensure(total + 256));
-    const size_t gbytes = gi.size() * sizeof(GatherItem);
-    const size_t hoff = (gbytes + 255) & ~(size_t)255;
-    memcpy(c->h_gather.p, gi.data(), gbytes);
-    memcpy(c->h_gather.as<uint8_t>() + hoff, hdr.v.data(), hdr.size());
-    HIPCHK(hipEventRecord(c->ev[5], s));
-    HIPCHK(hipMemcpyAsync(c->gather.p, c->h_gather.p, hoff + hdr.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(launch_gather(c->gather.as<uint8_t>() + hoff, c->mqout.as<uint8_t>(), c->gather.as<GatherItem>(),
-                         (uint32_t)gi.size(), c->packed.as<uint8_t>(), s));
-    HIPCHK(hipEventRecord(c->ev[6], s));
-    HIPCHK(hipMemcpyAsync(c->h_out.p, c->packed.p, total, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipEventRecord(c->ev[7], s));
-    HIPCHK(hipStreamSynchronize(s));
+    std::unique_lock<std::mutex> out_lk(c->out_mu, std::defer_lock);
+    rc = enc_output_stage(c, gi, hdr, total, out_lk, &nl);
+    if (rc) return rc;
     double t_end = now_ms();
     *view = c->h_out.as<uint8_t>();
     *outlen = total;
-
-    grkgpu_stats &st = c->stats;
-    memset(&st, 0, sizeof(st));
-    hipEventElapsedTime(&st.h2d_ms, c->ev[0], c->ev[1]);
-    hipEventElapsedTime(&st.dcshift_mct_ms, c->ev[1], c->ev[2]);
-    hipEventElapsedTime(&st.dwt_ms, c->ev[2], c->ev[3]);
-    hipEventElapsedTime(&st.t1_ms, c->ev[3], c->ev[4]);
-    hipEventElapsedTime(&st.gather_ms, c->ev[5], c->ev[6]);
-    hipEventElapsedTime(&st.d2h_ms, c->ev[6], c->ev[7]);
-    log_collect(c);
-    st.host_t2_ms = (float)(t_t2_end - t_t2);
-    st.total_ms = (float)(t_end - t_start);
-    st.num_cblks = nblk;
-    st.cs_bytes = total;
-    st.mq_symbols = nsym;
-    st.rate_ms = (float)t_rate;
-    st.packet_ms = (float)t_packets;
-    st.rate_probes = rsum.probes;
-    st.rate_probes_skipped = rsum.skipped;
-    st.rate_block_evals = rsum.evals;
-    st.rate_precinct_sims = rsum.sims;
-    st.rate_form_ms = (float)rsum.form_ms;
-    st.rate_sim_ms = (float)rsum.sim_ms;
-    st.passrec_ms = (float)t_passrec;
+    const EncStatsTail tail{t_t2, t_t2_end, t_passrec, H.t_rate, H.t_packets, total, H.rsum};
+    fill_enc_stats(c, t_start, t_end, nblk, nsym, &tail);
     return GRKGPU_OK;
 }
 
@@ -2868,6 +3003,12 @@ struct DecHost {
     bool too_deep = false;
 
     int begin();
+    // bytes of output region k: a plane, or (interleaved) the one image --
+    // upsampled, every component has the output rectangle's iw x (oy1 - iy0) samples
+    size_t region_bytes(uint32_t k) const {
+        if (up) return (size_t)((uint64_t)iw * (oy1 - iy0) * (il ? no : 1)) * sb;
+        return (size_t)(il ? ooff[no] : ooff[k + 1] - ooff[k]) * sb;
+    }
     void parse_tiles(size_t l0, size_t l1);
     int finish();
 };
@@ -3409,6 +3550,128 @@ static uint64_t order_dec_tables(std::vector<DecBlock> &db, std::vector<DecSeg> 
     return scr_records;
 }
 
+// The Tier-1 stage of a decode, over one stream's block table or a batch's
+// merged one: prepare() orders the tables (in place: order_dec_tables), gives
+// every segment its unstuffed-stream region and stages the tables in h_blocks
+// and h_segs (segs | seg_first | roi); upload() copies the two to the device
+// (after the codestream bytes they point into, inside the caller's H2D
+// interval); launch() runs the decoders over ctx->cs into ctx->coef, a launch
+// set per style range.  too_large: the caller's message for a table past the
+// 32-bit region offsets.
+struct DecT1Stage {
+    std::vector<StyRange> sranges;
+    size_t segbytes = 0, sfbytes = 0, roibytes = 0;
+    uint32_t nblk = 0;
+    bool lone = false;
+    double t_tables = 0;  // the host's clock once the tables are ordered: the end of the stats' host_t2_ms
+
+    int prepare(grkgpu_ctx *c, std::vector<DecBlock> &db, std::vector<DecSeg> &dsegs, std::vector<uint32_t> &seg_first,
+                std::vector<uint8_t> &droi, std::vector<uint8_t> &dsty, const char *too_large) {
+        nblk = (uint32_t)db.size();
+        lone = lone_call();
+        const uint64_t scr_records = order_dec_tables(db, dsegs, seg_first, droi, dsty, lone, sranges);
+        t_tables = now_ms();
+        // the decoder's lane-interleaved groups span 64 records each (t1_lane.h)
+        HIPCHK(c->scratch.ensure((size_t)scr_records * sizeof(T1Scratch) + 256));
+        // per-segment unstuffed-stream regions (16-byte units)
+        uint64_t uwords = 0;
+        for (auto &sg : dsegs) {
+            sg.ub_off = (uint32_t)(uwords / 4);
+            uwords += t1_unstuff_region_words(sg.len);
+        }
+        if (uwords / 4 > 0xffffffffull) return set_err(GRKGPU_EUNSUPPORTED, too_large);
+        segbytes = dsegs.size() * sizeof(DecSeg);
+        sfbytes = seg_first.size() * 4;
+        roibytes = droi.size();
+        HIPCHK(c->segs.ensure(segbytes + sfbytes + roibytes + 256));
+        HIPCHK(c->h_segs.ensure(segbytes + sfbytes + roibytes + 256));
+        memcpy(c->h_segs.p, dsegs.data(), segbytes);
+        memcpy((uint8_t *)c->h_segs.p + segbytes, seg_first.data(), sfbytes);
+        if (roibytes) memcpy((uint8_t *)c->h_segs.p + segbytes + sfbytes, droi.data(), roibytes);
+        HIPCHK(c->ubuf.ensure(uwords * 4 + 256));
+        HIPCHK(c->blocks.ensure((size_t)nblk * sizeof(DecBlock) + 256));
+        HIPCHK(c->h_blocks.ensure((size_t)nblk * sizeof(DecBlock) + 256));
+        memcpy(c->h_blocks.p, db.data(), (size_t)nblk * sizeof(DecBlock));
+        return GRKGPU_OK;
+    }
+    int upload(grkgpu_ctx *c) const {
+        HIPCHK(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, (size_t)nblk * sizeof(DecBlock), hipMemcpyHostToDevice,
+                              c->stream));
+        HIPCHK(hipMemcpyAsync(c->segs.p, c->h_segs.p, segbytes + sfbytes + roibytes, hipMemcpyHostToDevice, c->stream));
+        return GRKGPU_OK;
+    }
+    int launch(grkgpu_ctx *c, uint32_t *nl) const {
+        for (const StyRange &g : sranges) {
+            HIPCHK(launch_t1_decode(c->blocks.as<DecBlock>() + g.b0, g.n, c->cs.as<uint8_t>(),
+                                    c->scratch.as<T1Scratch>() + g.scr0, c->coef.as<int32_t>(), c->stream,
+                                    c->ubuf.as<uint32_t>(), 0, c->segs.as<DecSeg>(),
+                                    (const uint32_t *)(c->segs.as<uint8_t>() + segbytes) + g.b0, g.sty,
+                                    roibytes ? c->segs.as<uint8_t>() + segbytes + sfbytes + g.b0 : nullptr,
+                                    lone ? lone_bpw(nblk) : 0));
+            ++*nl;
+        }
+        return GRKGPU_OK;
+    }
+};
+
+// the sample range a component's decoded values are clamped to
+static void clamp_bounds(const CodingParams &cp, uint32_t k, int32_t &mn, int32_t &mx) {
+    mn = cp.sgnd[k] ? -(1 << (cp.prec[k] - 1)) : 0;
+    mx = cp.sgnd[k] ? (1 << (cp.prec[k] - 1)) - 1 : (1 << cp.prec[k]) - 1;
+}
+
+// Samples nothing decodes are zero (the plain case: no channel map, no colour
+// conversion, no upsampling launch that writes them itself): the margin of a
+// reduced decode at an odd origin -- the whole of every output region -- or
+// the tiles of [tb, te) a cut stream never reached, their regions only (a
+// shard's device planes hold other tiles).  dst[k] = output region k on the
+// device; *nl grows by the fills issued.
+static hipError_t dec_zero_fills(const DecHost &h, void *const *dst, hipStream_t s, uint32_t *nl) {
+    const uint32_t nout = h.il ? 1 : h.no;
+    const size_t eb = h.il ? (size_t)h.no * h.sb : h.sb;
+    if (h.opad) {
+        for (uint32_t k = 0; k < nout; ++k, ++*nl) {
+            const hipError_t e = hipMemsetAsync(dst[k], 0, h.region_bytes(k), s);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    if (!h.missing || h.up) return hipSuccess;
+    for (uint32_t t = h.tb; t < h.te; ++t) {
+        if (h.walk.decoded[t] || h.wskip[t]) continue;
+        for (uint32_t k = 0; k < nout; ++k) {
+            const Rect cr = comp_rect(tile_rect(h.cp, t), h.cp.dx[k], h.cp.dy[k]);
+            const Rect rr{ceil_pow2(cr.x0, h.reduce), ceil_pow2(cr.y0, h.reduce), ceil_pow2(cr.x1, h.reduce),
+                          ceil_pow2(cr.y1, h.reduce)};
+            const Rect o = intersect(rr, h.orect[k]);
+            if (o.empty()) continue;
+            const uint32_t ow = h.orect[k].w();
+            const uint64_t e0 = (uint64_t)(o.y0 - h.orect[k].y0) * ow + (o.x0 - h.orect[k].x0);
+            const hipError_t e = hipMemset2DAsync((uint8_t *)dst[k] + e0 * eb, (size_t)ow * eb, 0, (size_t)o.w() * eb,
+                                                  o.h(), s);
+            if (e != hipSuccess) return e;
+            ++*nl;
+        }
+    }
+    return hipSuccess;
+}
+
+// the statistics of a decode (grkgpu_get_stats) from the stage events and the host's clock
+static void fill_dec_stats(grkgpu_ctx *c, double t_start, double t_tables, double t_end, uint32_t nblk, uint64_t cs_bytes) {
+    grkgpu_stats &st = c->stats;
+    memset(&st, 0, sizeof(st));
+    hipEventElapsedTime(&st.h2d_ms, c->ev[0], c->ev[1]);
+    hipEventElapsedTime(&st.t1_ms, c->ev[1], c->ev[2]);
+    hipEventElapsedTime(&st.dwt_ms, c->ev[2], c->ev[3]);
+    hipEventElapsedTime(&st.dcshift_mct_ms, c->ev[3], c->ev[4]);
+    hipEventElapsedTime(&st.d2h_ms, c->ev[4], c->ev[5]);
+    log_collect(c);
+    st.host_t2_ms = (float)(t_tables - t_start);
+    st.total_ms = (float)(t_end - t_start);
+    st.num_cblks = nblk;
+    st.cs_bytes = cs_bytes;
+}
+
 static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu_image_desc *img,
                            const DecodeOut &od, uint32_t tb, uint32_t te,
                            uint32_t reduce = 0, const Rect *win = nullptr, uint32_t max_layers = 0,
@@ -3431,7 +3694,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     void *const *const planes = H.planes;
     const int planes_on_device = H.planes_on_device;
     const uint32_t sb = H.sb, ssb = H.ssb, nc = H.nc, no = H.no, iw = H.iw;
-    const uint32_t ix0 = H.ix0, iy0 = H.iy0, ix1 = H.ix1, iy1 = H.iy1, oy1 = H.oy1;
+    const uint32_t ix0 = H.ix0, iy0 = H.iy0, ix1 = H.ix1, iy1 = H.iy1;
     const bool il = H.il, whole = H.whole, mixed = H.mixed, conv = H.conv, colconv = H.colconv, up = H.up;
     const bool opad = H.opad, missing = H.missing;
     const int32_t sfmt = H.sfmt;
@@ -3453,35 +3716,15 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     tb = H.tb; te = H.te;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const uint32_t nblk = (uint32_t)db.size();
     seg_first.push_back((uint32_t)dsegs.size());
-    const bool lone = lone_call();
-    std::vector<StyRange> sranges;
-    const uint64_t scr_records = order_dec_tables(db, dsegs, seg_first, droi, dsty, lone, sranges);
-    double t_t2 = now_ms();
+    DecT1Stage t1;
+    uint32_t nl = 0;  // (the batch's launch count: not reported by this call)
+    hrc = t1.prepare(c, db, dsegs, seg_first, droi, dsty, "codestream too large for one call");
+    if (hrc) return hrc;
     HIPCHK(c->cs.ensure(len + extra.size() + 256));
     HIPCHK(c->coef.ensure(arena * 4 + 256));
     HIPCHK(c->work.ensure(arena * 4 + 256));
     HIPCHK(c->ll.ensure(llarena * 4 + 256));
-    // the decoder's lane-interleaved groups span 64 records each (t1_lane.h)
-    HIPCHK(c->scratch.ensure((size_t)scr_records * sizeof(T1Scratch) + 256));
-    // per-segment unstuffed-stream regions (16-byte units)
-    uint64_t uwords = 0;
-    for (auto &sg : dsegs) {
-        sg.ub_off = (uint32_t)(uwords / 4);
-        uwords += t1_unstuff_region_words(sg.len);
-    }
-    if (uwords / 4 > 0xffffffffull) return set_err(GRKGPU_EUNSUPPORTED, "codestream too large for one call");
-    const size_t segbytes = dsegs.size() * sizeof(DecSeg), sfbytes = seg_first.size() * 4, roibytes = droi.size();
-    HIPCHK(c->segs.ensure(segbytes + sfbytes + roibytes + 256));
-    HIPCHK(c->h_segs.ensure(segbytes + sfbytes + roibytes + 256));
-    memcpy(c->h_segs.p, dsegs.data(), segbytes);
-    memcpy((uint8_t *)c->h_segs.p + segbytes, seg_first.data(), sfbytes);
-    if (roibytes) memcpy((uint8_t *)c->h_segs.p + segbytes + sfbytes, droi.data(), roibytes);
-    HIPCHK(c->ubuf.ensure(uwords * 4 + 256));
-    HIPCHK(c->blocks.ensure((size_t)nblk * sizeof(DecBlock) + 256));
-    HIPCHK(c->h_blocks.ensure((size_t)nblk * sizeof(DecBlock) + 256));
-    memcpy(c->h_blocks.p, db.data(), (size_t)nblk * sizeof(DecBlock));
 
     HIPCHK(hipEventRecord(c->ev[0], s));
     HIPCHK(hipMemcpyAsync(c->cs.p, csb, len, hipMemcpyHostToDevice, s));
@@ -3490,8 +3733,8 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         memcpy(c->h_packed.p, extra.data(), extra.size());
         HIPCHK(hipMemcpyAsync(c->cs.as<uint8_t>() + len, c->h_packed.p, extra.size(), hipMemcpyHostToDevice, s));
     }
-    HIPCHK(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, (size_t)nblk * sizeof(DecBlock), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->segs.p, c->h_segs.p, segbytes + sfbytes + roibytes, hipMemcpyHostToDevice, s));
+    hrc = t1.upload(c);
+    if (hrc) return hrc;
     // one plan per wavelet (COC / tile COD may mix 5/3 and 9/7 components)
     DwtPlan dplan[2];
     for (auto &tile : tiles)
@@ -3505,8 +3748,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                         c->ll.as<int32_t>() + lloff[(tile.index - tb) * nc + k], tc.irrev, true, tc.numres - reduce,
                         win ? &rn : nullptr);
         }
-    HIPCHK(dwt_upload(dplan[1], c->dwtjobs, c->h_dwtjobs, 1, s));
-    HIPCHK(dwt_upload(dplan[0], c->dwtjobs53, c->h_dwtjobs53, 0, s));
+    HIPCHK(dwt_upload_plans(c, dplan));
     // window decode: the coefficients of the code-blocks left undecoded are
     // zero (they lie outside every window sample's support; zero keeps the
     // 9/7 float lifting free of stale NaNs)
@@ -3533,19 +3775,10 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         }
     }
     HIPCHK(hipEventRecord(c->ev[1], s));
-    for (const StyRange &g : sranges)
-        HIPCHK(launch_t1_decode(c->blocks.as<DecBlock>() + g.b0, g.n, c->cs.as<uint8_t>(),
-                                c->scratch.as<T1Scratch>() + g.scr0, c->coef.as<int32_t>(), s, c->ubuf.as<uint32_t>(),
-                                0, c->segs.as<DecSeg>(),
-                                (const uint32_t *)(c->segs.as<uint8_t>() + segbytes) + g.b0, g.sty,
-                                roibytes ? c->segs.as<uint8_t>() + segbytes + sfbytes + g.b0 : nullptr,
-                                lone ? lone_bpw(nblk) : 0));
+    hrc = t1.launch(c, &nl);
+    if (hrc) return hrc;
     HIPCHK(hipEventRecord(c->ev[2], s));
-    c->ltimes.clear();
-    c->lidx.clear();
-    LaunchLog llog{&c->lev, &c->ltimes, &c->lidx};
-    HIPCHK(dwt_launch(dplan[1], c->dwtjobs, 1, true, s, c->launch_timing ? &llog : nullptr));
-    HIPCHK(dwt_launch(dplan[0], c->dwtjobs53, 0, true, s, c->launch_timing ? &llog : nullptr));
+    HIPCHK(dwt_launch_plans(c, dplan, true, &nl));
     HIPCHK(hipEventRecord(c->ev[3], s));
     // the output as the copies and fills see it: `nout` regions (the planes,
     // or the one interleaved image) of elements `eb` bytes wide (a sample, or
@@ -3553,12 +3786,6 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     // (interleaved: all ooff[nc] of them)
     const uint32_t nout = il ? 1 : no;
     const size_t eb = il ? (size_t)no * sb : sb;
-    // (upsampled: every component has the output rectangle's iw x (oy1 - iy0) samples)
-    const uint64_t opix = (uint64_t)iw * (oy1 - iy0);
-    auto region_bytes = [&](uint32_t k) {
-        if (up) return (size_t)(opix * (il ? no : 1)) * sb;
-        return (size_t)(il ? ooff[no] : ooff[k + 1] - ooff[k]) * sb;
-    };
     // upsampled: which components go through a staging plane -- all when they
     // share one subsampled grid (their MCT runs first); otherwise those with a
     // tile boundary that is no multiple of dx / dy, where the tile's first
@@ -3578,7 +3805,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         // whatever the sample width
         size_t off[GRKGPU_MAX_COMPS + 1] = {0}, soff[GRKGPU_MAX_COMPS + 1];
         if (!planes_on_device)
-            for (uint32_t k = 0; k < nout; ++k) off[k + 1] = (off[k] + region_bytes(k) + 15) & ~(size_t)15;
+            for (uint32_t k = 0; k < nout; ++k) off[k + 1] = (off[k] + H.region_bytes(k) + 15) & ~(size_t)15;
         soff[0] = planes_on_device ? 0 : off[nout];
         for (uint32_t k = 0; k < nc; ++k)
             soff[k + 1] = soff[k] + (staged(k) ? ((size_t)(ooff[k + 1] - ooff[k]) * ssb + 15) & ~(size_t)15 : 0);
@@ -3644,28 +3871,13 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                                       ceil_pow2(cr.y1, reduce)}, orect[0]);
             if (!o.empty()) HIPCHK(fill_converted(o));
         }
-    } else if (opad)
-        for (uint32_t k = 0; k < nout; ++k) HIPCHK(hipMemsetAsync(dst.p[k], 0, region_bytes(k), s));
-    else if (missing && !up)  // tiles the tile-part walk never reached: zero (their regions only -- a shard's
-                       // device planes hold other tiles)
-        for (uint32_t t = tb; t < te; ++t) {
-            if (walk.decoded[t] || wskip[t]) continue;
-            for (uint32_t k = 0; k < nout; ++k) {
-                const Rect cr = comp_rect(tile_rect(cp, t), cp.dx[k], cp.dy[k]);
-                const Rect rr{ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
-                              ceil_pow2(cr.y1, reduce)};
-                const Rect o = intersect(rr, orect[k]);
-                if (o.empty()) continue;
-                const uint32_t ow = orect[k].w();
-                HIPCHK(hipMemset2DAsync(at(k, (uint64_t)(o.y0 - orect[k].y0) * ow + (o.x0 - orect[k].x0)),
-                                        (size_t)ow * eb, 0, (size_t)o.w() * eb, o.h(), s));
-            }
-        }
+    } else {
+        HIPCHK(dec_zero_fills(H, dst.p, s, &nl));
+    }
     ShiftArr sh{}, mn{}, mx{};
     for (uint32_t k = 0; k < nc; ++k) {
         sh.v[k] = cp.shift[k];
-        if (cp.sgnd[k]) { mn.v[k] = -(1 << (cp.prec[k] - 1)); mx.v[k] = (1 << (cp.prec[k] - 1)) - 1; }
-        else { mn.v[k] = 0; mx.v[k] = (1 << cp.prec[k]) - 1; }
+        clamp_bounds(cp, k, mn.v[k], mx.v[k]);
     }
     MctInv minv{};  // custom MCT (cp.mct == 2): the stream's matrix and offsets instead of the DC shifts
     ShiftArr moff{};
@@ -3777,7 +3989,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     if (!planes_on_device) {
         if (whole) {
             for (uint32_t k = 0; k < nout; ++k)
-                HIPCHK(hipMemcpyAsync(planes[k], dst.p[k], region_bytes(k), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipMemcpyAsync(planes[k], dst.p[k], H.region_bytes(k), hipMemcpyDeviceToHost, s));
         } else {  // only the shard's tiles
             for (auto &tile : tiles)
                 for (uint32_t k = 0; k < nout; ++k) {
@@ -3790,19 +4002,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
     }
     HIPCHK(hipEventRecord(c->ev[5], s));
     HIPCHK(hipStreamSynchronize(s));
-    double t_end = now_ms();
-    grkgpu_stats &st = c->stats;
-    memset(&st, 0, sizeof(st));
-    hipEventElapsedTime(&st.h2d_ms, c->ev[0], c->ev[1]);
-    hipEventElapsedTime(&st.t1_ms, c->ev[1], c->ev[2]);
-    hipEventElapsedTime(&st.dwt_ms, c->ev[2], c->ev[3]);
-    hipEventElapsedTime(&st.dcshift_mct_ms, c->ev[3], c->ev[4]);
-    hipEventElapsedTime(&st.d2h_ms, c->ev[4], c->ev[5]);
-    log_collect(c);
-    st.host_t2_ms = (float)(t_t2 - t_start);
-    st.total_ms = (float)(t_end - t_start);
-    st.num_cblks = nblk;
-    st.cs_bytes = len;
+    fill_dec_stats(c, t_start, t1.t_tables, now_ms(), t1.nblk, len);
     return GRKGPU_OK;
 }
 
@@ -3917,17 +4117,6 @@ static_assert(sizeof(grkgpu_store_job) == sizeof(StoreJob) && offsetof(grkgpu_st
                   offsetof(grkgpu_store_job, shift) == offsetof(StoreJob, shift) &&
                   offsetof(grkgpu_store_job, max) == offsetof(StoreJob, mx),
               "grkgpu_store_job is StoreJob");
-
-// the launches and copies dwt_launch issues for a plan
-static uint32_t dwt_launch_count(const DwtPlan &P, bool inverse) {
-    uint32_t nl = (uint32_t)P.copies2d.size();
-    for (auto &cp : P.copies) nl += cp.elems != 0;
-    for (size_t li = 0; li < P.levels.size(); ++li) {
-        ++nl;
-        if ((li < P.f01.size() && P.f01[li]) || (inverse && P.i01 && li + 2 == P.levels.size())) ++li;  // a level pair
-    }
-    return nl;
-}
 
 // The StoreJob tables of a launch set, one group per (sample format, layout):
 // jobs in table order, `first` their first-workgroup numbers.
@@ -4119,14 +4308,11 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
     std::vector<Region> regions;
     std::vector<std::array<size_t, GRKGPU_MAX_COMPS>> roff(n);
     size_t img_bytes = 0;
-    auto region_bytes = [&](const DecHost &h, uint32_t k) {
-        return (size_t)(h.il ? h.ooff[h.nc] : h.ooff[k + 1] - h.ooff[k]) * h.sb;
-    };
     for (uint32_t i = 0; i < n; ++i) {
         const DecHost &h = H[i];
         if (items[i].status || h.planes_on_device || host_only) continue;
         for (uint32_t k = 0; k < (h.il ? 1u : h.nc); ++k) {
-            Region r{(uint8_t *)h.planes[k], 0, region_bytes(h, k)};
+            Region r{(uint8_t *)h.planes[k], 0, h.region_bytes(k)};
             const bool adj = !regions.empty() && regions.back().host + regions.back().bytes == r.host &&
                              (regions.back().off + regions.back().bytes) % h.sb == 0;
             r.off = adj ? regions.back().off + regions.back().bytes : (img_bytes + 15) & ~(size_t)15;
@@ -4168,8 +4354,7 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
             for (uint32_t k = 0; k < nc; ++k) {
                 ts.src.p[k] = (int32_t *)(work0 + (tile.comps[k].arena_off + soff) * 4);
                 ts.sh.v[k] = h.cp.shift[k];
-                if (h.cp.sgnd[k]) { ts.mn.v[k] = -(1 << (h.cp.prec[k] - 1)); ts.mx.v[k] = (1 << (h.cp.prec[k] - 1)) - 1; }
-                else { ts.mn.v[k] = 0; ts.mx.v[k] = (1 << h.cp.prec[k]) - 1; }
+                clamp_bounds(h.cp, k, ts.mn.v[k], ts.mx.v[k]);
             }
             for (uint32_t k = 0; k < nout; ++k) ts.dst.p[k] = (void *)(dst_of(i, k) + doff);
             ts.sstride = tr.w(); ts.w = out.w(); ts.h = out.h();
@@ -4201,30 +4386,13 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
     hipStream_t s = c->stream;
     uint32_t nl = 0;  // kernel launches and fills of this call
     const int drc = [&]() -> int {
-        const bool lone = lone_call();
-        std::vector<StyRange> sranges;
-        const uint64_t scr_records = order_dec_tables(db, dsegs, seg_first, droi, dsty, lone, sranges);
-        const double t_t2 = now_ms();
+        DecT1Stage t1;
+        int rc = t1.prepare(c, db, dsegs, seg_first, droi, dsty, "batch too large for one call");
+        if (rc) return rc;
         HIPCHK(c->cs.ensure(cs_total + 256));
         HIPCHK(c->h_cs.ensure(cs_total + 256));
         HIPCHK(c->coef.ensure(arena * 4 + 256));
         HIPCHK(c->ll.ensure(llarena * 4 + 256));
-        HIPCHK(c->scratch.ensure((size_t)scr_records * sizeof(T1Scratch) + 256));
-        uint64_t uw = 0;  // per-segment unstuffed-stream regions (16-byte units)
-        for (auto &sg : dsegs) {
-            sg.ub_off = (uint32_t)(uw / 4);
-            uw += t1_unstuff_region_words(sg.len);
-        }
-        const size_t segbytes = dsegs.size() * sizeof(DecSeg), sfbytes = seg_first.size() * 4, roibytes = droi.size();
-        HIPCHK(c->segs.ensure(segbytes + sfbytes + roibytes + 256));
-        HIPCHK(c->h_segs.ensure(segbytes + sfbytes + roibytes + 256));
-        memcpy(c->h_segs.p, dsegs.data(), segbytes);
-        memcpy((uint8_t *)c->h_segs.p + segbytes, seg_first.data(), sfbytes);
-        if (roibytes) memcpy((uint8_t *)c->h_segs.p + segbytes + sfbytes, droi.data(), roibytes);
-        HIPCHK(c->ubuf.ensure(uw * 4 + 256));
-        HIPCHK(c->blocks.ensure((size_t)nblk * sizeof(DecBlock) + 256));
-        HIPCHK(c->h_blocks.ensure((size_t)nblk * sizeof(DecBlock) + 256));
-        memcpy(c->h_blocks.p, db.data(), (size_t)nblk * sizeof(DecBlock));
         const size_t sjbytes = store_groups_bytes(groups);
         HIPCHK(c->storejobs.ensure(sjbytes + 256));
         HIPCHK(c->h_storejobs.ensure(sjbytes + 256));
@@ -4241,8 +4409,8 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
 
         HIPCHK(hipEventRecord(c->ev[0], s));
         HIPCHK(hipMemcpyAsync(c->cs.p, c->h_cs.p, cs_total, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, (size_t)nblk * sizeof(DecBlock), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->segs.p, c->h_segs.p, segbytes + sfbytes + roibytes, hipMemcpyHostToDevice, s));
+        rc = t1.upload(c);
+        if (rc) return rc;
         HIPCHK(store_groups_upload(groups, c->h_storejobs.as<uint8_t>(), c->storejobs.p, s));
         DwtPlan dplan[2];  // one plan per wavelet over every item's tile-components
         for (uint32_t i = 0; i < n; ++i) {
@@ -4256,53 +4424,18 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
                                 tc.irrev, true, tc.numres - reduce, nullptr);
                 }
         }
-        HIPCHK(dwt_upload(dplan[1], c->dwtjobs, c->h_dwtjobs, 1, s));
-        HIPCHK(dwt_upload(dplan[0], c->dwtjobs53, c->h_dwtjobs53, 0, s));
+        HIPCHK(dwt_upload_plans(c, dplan));
         HIPCHK(hipEventRecord(c->ev[1], s));
-        for (const StyRange &g : sranges) {
-            HIPCHK(launch_t1_decode(c->blocks.as<DecBlock>() + g.b0, g.n, c->cs.as<uint8_t>(),
-                                    c->scratch.as<T1Scratch>() + g.scr0, c->coef.as<int32_t>(), s,
-                                    c->ubuf.as<uint32_t>(), 0, c->segs.as<DecSeg>(),
-                                    (const uint32_t *)(c->segs.as<uint8_t>() + segbytes) + g.b0, g.sty,
-                                    roibytes ? c->segs.as<uint8_t>() + segbytes + sfbytes + g.b0 : nullptr,
-                                    lone ? lone_bpw(nblk) : 0));
-            ++nl;
-        }
+        rc = t1.launch(c, &nl);
+        if (rc) return rc;
         HIPCHK(hipEventRecord(c->ev[2], s));
-        c->ltimes.clear();
-        c->lidx.clear();
-        LaunchLog llog{&c->lev, &c->ltimes, &c->lidx};
-        HIPCHK(dwt_launch(dplan[1], c->dwtjobs, 1, true, s, c->launch_timing ? &llog : nullptr));
-        HIPCHK(dwt_launch(dplan[0], c->dwtjobs53, 0, true, s, c->launch_timing ? &llog : nullptr));
-        nl += dwt_launch_count(dplan[1], true) + dwt_launch_count(dplan[0], true);
+        HIPCHK(dwt_launch_plans(c, dplan, true, &nl));
         HIPCHK(hipEventRecord(c->ev[3], s));
-        // samples nothing decodes are zero: the margin of a reduced decode at
-        // an odd origin (the whole region), the tiles a cut stream never reached
         for (uint32_t i = 0; i < n; ++i) {
             if (items[i].status) continue;
-            const DecHost &h = H[i];
-            const uint32_t nout = h.il ? 1 : h.nc;
-            const size_t eb = h.il ? (size_t)h.nc * h.sb : h.sb;
-            if (h.opad) {
-                for (uint32_t k = 0; k < nout; ++k, ++nl)
-                    HIPCHK(hipMemsetAsync((void *)dst_of(i, k), 0, region_bytes(h, k), s));
-            } else if (h.missing) {
-                for (uint32_t t = 0; t < h.nsh; ++t) {
-                    if (h.walk.decoded[t]) continue;
-                    for (uint32_t k = 0; k < nout; ++k) {
-                        const Rect cr = tile_rect(h.cp, t);
-                        const Rect rr{ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
-                                      ceil_pow2(cr.y1, reduce)};
-                        const Rect o = intersect(rr, h.orect[k]);
-                        if (o.empty()) continue;
-                        const uint32_t ow = h.orect[k].w();
-                        const uint64_t e0 = (uint64_t)(o.y0 - h.orect[k].y0) * ow + (o.x0 - h.orect[k].x0);
-                        HIPCHK(hipMemset2DAsync((void *)(dst_of(i, k) + e0 * eb), (size_t)ow * eb, 0, (size_t)o.w() * eb,
-                                                o.h(), s));
-                        ++nl;
-                    }
-                }
-            }
+            void *dst[GRKGPU_MAX_COMPS];
+            for (uint32_t k = 0; k < (H[i].il ? 1u : H[i].nc); ++k) dst[k] = (void *)dst_of(i, k);
+            HIPCHK(dec_zero_fills(H[i], dst, s, &nl));
         }
         HIPCHK(store_groups_launch(groups, c->storejobs.p, s, &nl));
         for (const TileStore &ts : singles) {
@@ -4323,19 +4456,7 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
         }
         HIPCHK(hipEventRecord(c->ev[5], s));
         HIPCHK(hipStreamSynchronize(s));
-        const double t_end = now_ms();
-        grkgpu_stats &st = c->stats;
-        memset(&st, 0, sizeof(st));
-        hipEventElapsedTime(&st.h2d_ms, c->ev[0], c->ev[1]);
-        hipEventElapsedTime(&st.t1_ms, c->ev[1], c->ev[2]);
-        hipEventElapsedTime(&st.dwt_ms, c->ev[2], c->ev[3]);
-        hipEventElapsedTime(&st.dcshift_mct_ms, c->ev[3], c->ev[4]);
-        hipEventElapsedTime(&st.d2h_ms, c->ev[4], c->ev[5]);
-        log_collect(c);
-        st.host_t2_ms = (float)(t_t2 - t_start);
-        st.total_ms = (float)(t_end - t_start);
-        st.num_cblks = nblk;
-        st.cs_bytes = cs_sum;
+        fill_dec_stats(c, t_start, t1.t_tables, now_ms(), nblk, cs_sum);
         return GRKGPU_OK;
     }();
     if (drc) {  // a device error leaves no item decoded
@@ -4461,12 +4582,6 @@ static hipError_t tile_load_launch(const TileLoad &t, hipStream_t s) {
     return launch_dcshift_mct_fwd_from(t.src, t.lfmt, t.sstride, t.dst, t.dstride, t.w, t.h, t.nc, t.sh, t.mct, t.irrev, s);
 }
 
-// the kernel launches and fills launch_t1_encode issues for n blocks
-static uint32_t t1_encode_launch_count(uint32_t n) {
-    if (!n) return 0;
-    return 3 + (dwt_options().t1_enc_sort && n > 64 ? 4 : 0);
-}
-
 static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grkgpu_cbatch_info *info, bool host_only) {
     if (info) *info = grkgpu_cbatch_info{};
     if ((!c && !host_only) || (n && !items)) return set_err(GRKGPU_EINVAL, "null argument");
@@ -4509,12 +4624,7 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
     };
 
     // the merged order (style groups; rate-controlled items first in each)
-    // and the items' places in the merged tables
-    struct StyGroup {
-        uint32_t sty = 0, b0 = 0, n = 0, nrc = 0, maxdepth = 1, rc0 = 0;
-        uint64_t scr0 = 0, ord0 = 0;
-        std::vector<uint32_t> items;
-    };
+    // and the items' places in the merged tables (EncHost::mb0 / rcb0 / slot0)
     std::vector<StyGroup> sg;
     for (uint32_t i = 0; i < n; ++i) {
         if (items[i].status) continue;
@@ -4524,7 +4634,6 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
         sg[g].items.push_back(i);
     }
     std::vector<uint32_t> order;
-    std::vector<uint64_t> mb0(n, 0), rcb0(n, 0), slot0(n, 0);  // first merged block / rc block / pass-record slot
     uint64_t arena = 0, llarena = 0, out_total = 0, sym_total = 0, nblk64 = 0, nrc64 = 0, slots = 0, slots_all = 0,
              runs_bound = 0, scr_bytes = 0, ord_words = 0;
     for (StyGroup &g : sg) {
@@ -4534,7 +4643,7 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
         for (uint32_t i : g.items) {
             EncHost &h = H[i];
             h.rebase(arena, llarena, out_total, sym_total);
-            mb0[i] = nblk64;
+            h.mb0 = nblk64;
             arena += h.arena;
             llarena += h.llarena;
             out_total += h.out_total;
@@ -4544,8 +4653,8 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
             runs_bound += (uint64_t)h.nblk * h.cp.numlayers;
             g.maxdepth = std::max(g.maxdepth, h.maxdepth);
             if (h.need_rc) {
-                rcb0[i] = nrc64;
-                slot0[i] = slots;
+                h.rcb0 = nrc64;
+                h.slot0 = slots;
                 nrc64 += h.nblk;
                 slots += h.ptotal;
             }
@@ -4641,19 +4750,8 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
     hipStream_t s = c->stream;
     uint32_t nl = 0;  // kernel launches and fills of this call
     const int drc = [&]() -> int {
-        const bool lone = lone_call();
-        HIPCHK(c->coef.ensure(arena * 4 + 256));
-        HIPCHK(c->ll.ensure(llarena * 4 + 256));
-        HIPCHK(c->scratch.ensure((size_t)scr_bytes + 256));
-        HIPCHK(c->t1order.ensure((size_t)ord_words * 4 + 256));
-        HIPCHK(c->mqout.ensure(out_total + 256));
-        HIPCHK(c->blocks.ensure((size_t)nblk * sizeof(EncBlock) + 256));
-        HIPCHK(c->results.ensure((size_t)nblk * sizeof(EncResult) + 256));
-        HIPCHK(c->h_results.ensure((size_t)nblk * sizeof(EncResult) + 256));
-        HIPCHK(c->h_blocks.ensure((size_t)nblk * sizeof(EncBlock) + 256));
-        HIPCHK(c->sym.ensure(sym_total + 256));
-        HIPCHK(c->symoff.ensure(((size_t)nblk + 1) * 8 + 256));
-        HIPCHK(c->h_symoff.ensure(((size_t)nblk + 1) * 8 + 256));
+        int rc = enc_ensure(c, arena, llarena, scr_bytes, ord_words, out_total, sym_total, nblk);
+        if (rc) return rc;
         const size_t ljbytes = load_groups_bytes(groups);
         HIPCHK(c->loadjobs.ensure(ljbytes + 256));
         HIPCHK(c->h_loadjobs.ensure(ljbytes + 256));
@@ -4668,8 +4766,8 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
             uint64_t *hs = c->h_symoff.as<uint64_t>();
             for (uint32_t i : order) {
                 const EncHost &h = H[i];
-                if (h.nblk) memcpy(hb + mb0[i], h.eb.data(), (size_t)h.nblk * sizeof(EncBlock));
-                if (h.nblk) memcpy(hs + mb0[i], h.symoff.data(), (size_t)h.nblk * 8);
+                if (h.nblk) memcpy(hb + h.mb0, h.eb.data(), (size_t)h.nblk * sizeof(EncBlock));
+                if (h.nblk) memcpy(hs + h.mb0, h.symoff.data(), (size_t)h.nblk * 8);
             }
             hs[nblk] = sym_total;
         }
@@ -4694,84 +4792,11 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
                                 h.cp.irrev, false);
                 }
         }
-        HIPCHK(dwt_upload(dplan[1], c->dwtjobs, c->h_dwtjobs, 1, s));
-        HIPCHK(dwt_upload(dplan[0], c->dwtjobs53, c->h_dwtjobs53, 0, s));
-        c->ltimes.clear();
-        c->lidx.clear();
-        LaunchLog llog{&c->lev, &c->ltimes, &c->lidx};
-        HIPCHK(dwt_launch(dplan[1], c->dwtjobs, 1, false, s, c->launch_timing ? &llog : nullptr));
-        HIPCHK(dwt_launch(dplan[0], c->dwtjobs53, 0, false, s, c->launch_timing ? &llog : nullptr));
-        nl += dwt_launch_count(dplan[1], false) + dwt_launch_count(dplan[0], false);
+        HIPCHK(dwt_upload_plans(c, dplan));
+        HIPCHK(dwt_launch_plans(c, dplan, false, &nl));
         HIPCHK(hipEventRecord(c->ev[3], s));
-        HIPCHK(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, (size_t)nblk * sizeof(EncBlock), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->symoff.p, c->h_symoff.p, ((size_t)nblk + 1) * 8, hipMemcpyHostToDevice, s));
-        for (const StyGroup &g : sg) {
-            HIPCHK(launch_t1_encode(c->blocks.as<EncBlock>() + g.b0, g.n, c->coef.as<int32_t>(),
-                                    c->scratch.as<uint8_t>() + g.scr0, c->sym.as<uint8_t>(),
-                                    c->symoff.as<uint64_t>() + g.b0, g.maxdepth, c->mqout.as<uint8_t>(),
-                                    c->results.as<EncResult>() + g.b0, s, g.sty, lone ? lone_bpw(g.n) : 0,
-                                    c->t1order.as<uint32_t>() + g.ord0));
-            nl += t1_encode_launch_count(g.n);
-        }
-        // the rate-controlled blocks' distortion factors and record slots: per
-        // group its factors, then (all groups) the slots, nrc + one end per group
-        const size_t p0_words = (size_t)nrc + sg.size();
-        if (nrc) {
-            HIPCHK(c->h_pinfo.ensure(((size_t)nrc + p0_words) * 8 + 256));
-            HIPCHK(c->pinfo.ensure(((size_t)nrc + p0_words) * 8 + 256));
-            double *wf = c->h_pinfo.as<double>();
-            uint64_t *p0 = (uint64_t *)(wf + nrc);
-            for (size_t gi = 0; gi < sg.size(); ++gi) {
-                const StyGroup &g = sg[gi];
-                uint64_t sl = 0;
-                for (uint32_t i : g.items) {
-                    const EncHost &h = H[i];
-                    if (!h.need_rc) continue;
-                    sl = slot0[i];
-                    for (uint32_t q = 0; q < h.nblk; ++q) {
-                        wf[rcb0[i] + q] = h.wfac(q);
-                        p0[rcb0[i] + gi + q] = sl;
-                        sl += h.pcap[q];
-                    }
-                }
-                if (g.nrc) p0[(size_t)g.rc0 + gi + g.nrc] = sl;
-                else p0[(size_t)g.rc0 + gi] = 0;
-            }
-            HIPCHK(hipMemcpyAsync(c->pinfo.p, c->h_pinfo.p, ((size_t)nrc + p0_words) * 8, hipMemcpyHostToDevice, s));
-        }
-        for (const StyGroup &g : sg) {
-            if (!g.nrc) continue;
-            HIPCHK(launch_t1_dist(c->blocks.as<EncBlock>() + g.b0, g.n, g.maxdepth, c->coef.as<int32_t>(),
-                                  c->scratch.as<uint8_t>() + g.scr0, c->results.as<EncResult>() + g.b0, s));
-            ++nl;
-        }
-        HIPCHK(hipEventRecord(c->ev[4], s));
-        const size_t sum_bytes = ((size_t)nrc * sizeof(PassSum) + 255) & ~(size_t)255;
-        if (nrc) {
-            HIPCHK(c->precs.ensure(sum_bytes + slots * sizeof(DevPass) + 256));
-            HIPCHK(c->h_psum.ensure(sum_bytes + 256));
-            HIPCHK(c->h_precs.ensure(slots * sizeof(DevPass) + 256));
-            PassSum *dsum = c->precs.as<PassSum>();
-            DevPass *dpass = (DevPass *)(c->precs.as<uint8_t>() + sum_bytes);
-            const double *dwf = c->pinfo.as<double>();
-            const uint64_t *dp0 = (const uint64_t *)(dwf + nrc);
-            for (size_t gi = 0; gi < sg.size(); ++gi) {
-                const StyGroup &g = sg[gi];
-                if (!g.nrc) continue;
-                HIPCHK(launch_pass_records(c->blocks.as<EncBlock>() + g.b0, c->results.as<EncResult>() + g.b0,
-                                           dwf + g.rc0, dp0 + g.rc0 + gi, g.nrc, g.sty, dpass, dsum + g.rc0, s));
-                ++nl;
-            }
-            HIPCHK(hipMemcpyAsync(c->h_psum.p, dsum, (size_t)nrc * sizeof(PassSum), hipMemcpyDeviceToHost, s));
-            if (slots) HIPCHK(hipMemcpyAsync(c->h_precs.p, dpass, slots * sizeof(DevPass), hipMemcpyDeviceToHost, s));
-        }
-        for (const StyGroup &g : sg) {  // the other blocks' results, rates only
-            if (g.n == g.nrc) continue;
-            const size_t o = ((size_t)g.b0 + g.nrc) * sizeof(EncResult);
-            HIPCHK(hipMemcpy2DAsync(c->h_results.as<uint8_t>() + o, sizeof(EncResult), c->results.as<uint8_t>() + o,
-                                    sizeof(EncResult), ENC_RESULT_RATE_BYTES, g.n - g.nrc, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
+        rc = enc_t1_stage(c, sg, H.data(), nblk, nrc, slots, &nl);
+        if (rc) return rc;
 
         // pass records per item, then rate allocation and packets over
         // (item, tile) pairs, all on the host pool
@@ -4787,9 +4812,9 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
             for (size_t q = a; q < b; ++q) {
                 const uint32_t i = order[q];
                 EncHost &h = H[i];
-                const int rc = h.need_rc ? h.records_dev(sm + rcb0[i], hp0 + rcb0[i] + gidx[i],
-                                                         c->h_precs.as<EncPass>() + slot0[i])
-                                         : h.records_host_count(res + mb0[i]);
+                const int rc = h.need_rc ? h.records_dev(sm + h.rcb0, hp0 + h.rcb0 + gidx[i],
+                                                         c->h_precs.as<EncPass>() + h.slot0)
+                                         : h.records_host_count(res + h.mb0);
                 if (rc) fail(i, rc);
             }
         });
@@ -4805,7 +4830,7 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
                 const uint32_t i = order[q];
                 if (items[i].status) continue;
                 EncHost &h = H[i];
-                if (!h.need_rc) h.records_host_fill(res + mb0[i], c->enc_passes.data() + hpass0[i]);
+                if (!h.need_rc) h.records_host_fill(res + h.mb0, c->enc_passes.data() + hpass0[i]);
                 const int rc = h.finish_begin();
                 if (rc) fail(i, rc);
             }
@@ -4835,10 +4860,7 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
             hdr.putn(h.hdr.v.data(), h.hdr.size());
             total = (total + 15) & ~(uint64_t)15;
             cs_off[i] = total;
-            for (const PlanItem &pi : h.plan) {
-                if (pi.len) gi.push_back({pi.kind == 0 ? pi.src + base : pi.src, total, pi.len, pi.kind});
-                total += pi.len;
-            }
+            gather_append(gi, h.plan, base, total);
             cs_len[i] = total - cs_off[i];
             cs_sum += cs_len[i];
             nsym += h.nsym;
@@ -4854,34 +4876,9 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
         }
         if (gi.size() > 0x7fffffffull) return set_err(GRKGPU_EUNSUPPORTED, "batch too large for one call");
         const double t_t2_end = now_ms();
-        HIPCHK(c->gather.ensure(gi.size() * sizeof(GatherItem) + hdr.size() + 512));
-        HIPCHK(c->h_gather.ensure(gi.size() * sizeof(GatherItem) + hdr.size() + 512));
-        HIPCHK(c->packed.ensure(total + 256));
-        std::unique_lock<std::mutex> out_lk(c->out_mu);
-        if (!c->h_out.p && !c->out_spare.empty()) {  // taken by a view: reuse a given-back buffer
-            auto big = std::max_element(c->out_spare.begin(), c->out_spare.end(),
-                                        [](const auto &a, const auto &b) { return a.second < b.second; });
-            c->h_out.p = big->first;
-            c->h_out.cap = big->second;
-            c->out_spare.erase(big);
-        }
-        HIPCHK(c->h_out.ensure(total + 256));
-        const size_t gbytes = gi.size() * sizeof(GatherItem);
-        const size_t hoff = (gbytes + 255) & ~(size_t)255;
-        memcpy(c->h_gather.p, gi.data(), gbytes);
-        memcpy(c->h_gather.as<uint8_t>() + hoff, hdr.v.data(), hdr.size());
-        HIPCHK(hipEventRecord(c->ev[5], s));
-        HIPCHK(hipMemcpyAsync(c->gather.p, c->h_gather.p, hoff + hdr.size(), hipMemcpyHostToDevice, s));
-        if (!gi.empty()) {
-            HIPCHK(launch_gather(c->gather.as<uint8_t>() + hoff, c->mqout.as<uint8_t>(), c->gather.as<GatherItem>(),
-                                 (uint32_t)gi.size(), c->packed.as<uint8_t>(), s));
-            ++nl;
-        }
-        HIPCHK(hipEventRecord(c->ev[6], s));
-        // (the pad bytes before a stream's 16-byte boundary are copied as they are: no item's cs / len covers them)
-        if (total) HIPCHK(hipMemcpyAsync(c->h_out.p, c->packed.p, total, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(c->ev[7], s));
-        HIPCHK(hipStreamSynchronize(s));
+        std::unique_lock<std::mutex> out_lk(c->out_mu, std::defer_lock);
+        rc = enc_output_stage(c, gi, hdr, total, out_lk, &nl);
+        if (rc) return rc;
         const double t_end = now_ms();
         for (uint32_t i = 0; i < n; ++i) {
             if (items[i].status) continue;
@@ -4890,29 +4887,8 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
         }
         if (info) info->n_ok = n_done;
 
-        grkgpu_stats &st = c->stats;
-        memset(&st, 0, sizeof(st));
-        hipEventElapsedTime(&st.h2d_ms, c->ev[0], c->ev[1]);
-        hipEventElapsedTime(&st.dcshift_mct_ms, c->ev[1], c->ev[2]);
-        hipEventElapsedTime(&st.dwt_ms, c->ev[2], c->ev[3]);
-        hipEventElapsedTime(&st.t1_ms, c->ev[3], c->ev[4]);
-        hipEventElapsedTime(&st.gather_ms, c->ev[5], c->ev[6]);
-        hipEventElapsedTime(&st.d2h_ms, c->ev[6], c->ev[7]);
-        log_collect(c);
-        st.host_t2_ms = (float)(t_t2_end - t_t2);
-        st.total_ms = (float)(t_end - t_start);
-        st.num_cblks = nblk;
-        st.cs_bytes = cs_sum;
-        st.mq_symbols = nsym;
-        st.rate_ms = (float)t_rate;
-        st.packet_ms = (float)t_packets;
-        st.rate_probes = rsum.probes;
-        st.rate_probes_skipped = rsum.skipped;
-        st.rate_block_evals = rsum.evals;
-        st.rate_precinct_sims = rsum.sims;
-        st.rate_form_ms = (float)rsum.form_ms;
-        st.rate_sim_ms = (float)rsum.sim_ms;
-        st.passrec_ms = (float)t_passrec;
+        const EncStatsTail tail{t_t2, t_t2_end, t_passrec, t_rate, t_packets, cs_sum, rsum};
+        fill_enc_stats(c, t_start, t_end, nblk, nsym, &tail);
         return GRKGPU_OK;
     }();
     if (drc) {  // a device error leaves no item encoded

@@ -30,8 +30,10 @@ struct ShiftArr { int32_t v[GRK_MAX_COMPS]; };
 // t1/Tier1.cpp:24-96 encodeBlockInfo).
 struct EncBlock {
     uint64_t coef_off;  // element offset of the block's top-left in the coefficient arena
-    uint64_t out_off;   // byte offset of the block's output in the MQ slab (out[-1] == 0); the block may write
-                        // t1_enc_slab_bytes(w, h, sty, numbps) bytes, rounded up to 4, from there on
+    uint64_t out_off;   // byte offset of the block's output in the MQ slab, a multiple of 4 and >= 4: the coder
+                        // zeroes out[out_off - 4 .. out_off - 1] (its pad byte, committed with its dword), so no
+                        // other block's bytes may lie there; the block may write t1_enc_slab_bytes(w, h, sty,
+                        // numbps) bytes, rounded up to 4, from out_off on
     uint32_t stride, w, h, orient;
     int32_t qmfbid, inv_step;
 };
@@ -376,9 +378,6 @@ hipError_t launch_t1_encode(const EncBlock *blocks, uint32_t n, const int32_t *c
                             hipStream_t s, uint32_t cblksty = 0, uint32_t bpw = 0, uint32_t *order = nullptr);
 // device words the MQ coder's work order needs (launch_t1_encode `order`)
 uint32_t t1_order_words(uint32_t nblocks);
-// Per-pass distortion sums of the blocks k_t1_model coded (same scratch and
-// maxdepth): nmsedec[pass] of every block, in the pass order of
-// t1_encode_cblk (t1.cpp:1222-1260).
 // Pass records formed on the device when a layer is rate-controlled: the
 // host's per-pass loop of the encoder (codec.cpp: rate, length, termination
 // t1.cpp:1131-1151, cumulative distortion t1.cpp:1249-1254 with
@@ -402,6 +401,9 @@ struct PassSum {
 };
 hipError_t launch_pass_records(const EncBlock *blocks, const EncResult *res, const double *wfac, const uint64_t *pass0,
                                uint32_t n, uint32_t cblksty, DevPass *out, PassSum *sum, hipStream_t s);
+// Per-pass distortion sums of the blocks k_t1_model coded (same scratch and
+// maxdepth): nmsedec[pass] of every block, in the pass order of
+// t1_encode_cblk (t1.cpp:1222-1260).
 hipError_t launch_t1_dist(const EncBlock *blocks, uint32_t n, uint32_t maxdepth, const int32_t *coef,
                           const void *scratch, EncResult *res, hipStream_t s);
 // ubuf: unstuffed-stream arena; block i's region at ubuf + i * fixed_words
