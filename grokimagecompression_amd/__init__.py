@@ -300,6 +300,25 @@ def _out_ops(colour, out_prec, prec_mode, force_rgb=False):
                   prec_mode=_PREC_MODES[prec_mode])
 
 
+SRC_RAW, SRC_SAMPLES = 1, 2  # GRKGPU_SRC_*: grkgpu_convert_comp.kind (SRC_SAMPLES + GRKGPU_SAMPLE_*)
+
+
+class ConvertComp(ctypes.Structure):
+    """grkgpu_convert_comp: one component of a grkgpu_convert_job."""
+    _fields_ = [("src", ctypes.c_void_p), ("stride", ctypes.c_uint32), ("gx0", ctypes.c_int32),
+                ("gy0", ctypes.c_int32), ("zx0", ctypes.c_int32), ("zy0", ctypes.c_int32), ("dx", ctypes.c_uint8),
+                ("dy", ctypes.c_uint8), ("kind", ctypes.c_uint8), ("wavelet", ctypes.c_uint8),
+                ("shift", ctypes.c_int32), ("min", ctypes.c_int32), ("max", ctypes.c_int32)]
+
+
+class ConvertJob(ctypes.Structure):
+    """grkgpu_convert_job: one rectangle of grkgpu_convert_jobs_to."""
+    _fields_ = [("comp", ConvertComp * 4), ("dst", ctypes.c_void_p * 4), ("x0", ctypes.c_uint32),
+                ("y0", ctypes.c_uint32), ("x1", ctypes.c_uint32), ("y1", ctypes.c_uint32),
+                ("dst_stride", ctypes.c_uint32), ("numcomps", ctypes.c_uint32), ("mct", ctypes.c_int32),
+                ("pad_", ctypes.c_uint32), ("ops", OutOps)]
+
+
 COLOUR_AUTO = 2  # grkgpu_jp2_decompress only: sYCC -> RGB when the file's colr box says sYCC
 COLOUR_AUTO_RGB = 5  # grkgpu_jp2_decompress only: sYCC / eYCC / CMYK -> RGB by the file's colr box
 JP2_MAX_CDEF = 64
@@ -448,6 +467,10 @@ def lib():
             L.grkgpu_decompress_batch.argtypes = [VP, P(BatchItem), U32, P(DParams), P(BatchInfo)]
             L.grkgpu_batch_plan.argtypes = [P(BatchItem), U32, P(DParams), P(BatchInfo)]
             L.grkgpu_mct_inv_dcshift_jobs_to.argtypes = [P(StoreJob), U32, U32, U32, VP]
+        if hasattr(L, "grkgpu_decompress_batch_convert"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_decompress_batch_convert.argtypes = [VP, P(BatchItem), P(OutOps), U32, P(DParams), P(BatchInfo)]
+            L.grkgpu_batch_convert_plan.argtypes = [P(BatchItem), P(OutOps), U32, P(DParams), P(BatchInfo)]
+            L.grkgpu_convert_jobs_to.argtypes = [P(ConvertJob), U32, U32, U32, VP]
         if hasattr(L, "grkgpu_compress_batch"):  # not in an older library given by GRKGPU_LIB (A/B runs)
             L.grkgpu_compress_batch.argtypes = [VP, P(CBatchItem), U32, P(CBatchInfo)]
             L.grkgpu_compress_batch_plan.argtypes = [P(CBatchItem), U32, P(CBatchInfo)]
@@ -687,6 +710,140 @@ def plan_batch(bufs, reduce=0, layers=0):
                status=[items[i].status for i in range(len(bufs))],
                img=[ImageDesc.from_buffer_copy(items[i].img) for i in range(len(bufs))])
     return res
+
+
+def _per_stream(v, n, name):
+    """One value for all n streams of a batch decode, or a list / tuple with one entry per stream."""
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise GrkGpuError("%s: one entry per stream (got %d for %d)" % (name, len(v), n))
+        return list(v)
+    return [v] * n
+
+
+def _batch_ops(n, colour, out_prec, prec_mode):
+    """The grkgpu_out_ops array of a batch (None: no item converts) and the
+    per-item colour / out_prec lists; each argument one value or a list."""
+    colours, precs = _per_stream(colour, n, "colour"), _per_stream(out_prec, n, "out_prec")
+    modes = _per_stream(prec_mode, n, "prec_mode")
+    # (an OutOps in a colour slot goes to the library as it is: what the keywords cannot say, for its refusals)
+    each = [colours[i] if isinstance(colours[i], OutOps) else _out_ops(colours[i], precs[i], modes[i])
+            for i in range(n)]
+    colours = [None if isinstance(v, OutOps) else v for v in colours]
+    if all(o is None for o in each):
+        return None, colours, precs
+    arr = (OutOps * max(n, 1))()
+    for i, o in enumerate(each):
+        if o is not None:
+            arr[i] = o
+    return arr, colours, precs
+
+
+def plan_batch_convert(bufs, dtype=None, layout="chw", reduce=0, layers=0, upsample=False, colour=None,
+                       out_prec=None, prec_mode="clip", ops=None):
+    """grkgpu_batch_convert_plan: the host half of Codec.decompress_batch_convert
+    -- no device call.  dtype / layout / upsample / colour / out_prec / prec_mode
+    are one value or a list with one entry per stream; ops (a list of OutOps or
+    None entries) stands in for the last three where a test needs values the
+    keywords refuse.  Returns plan_batch's dict."""
+    bufs = list(bufs)
+    n = len(bufs)
+    items, keep = _batch_items(bufs)
+    if ops is not None:
+        arr = (OutOps * max(n, 1))()
+        for i, o in enumerate(ops):
+            if o is not None:
+                arr[i] = o
+    else:
+        arr, _, _ = _batch_ops(n, colour, out_prec, prec_mode)
+    dtypes, layouts = _per_stream(dtype, n, "dtype"), _per_stream(layout, n, "layout")
+    ups = _per_stream(upsample, n, "upsample")
+    for i in range(n):
+        _layout_shape((1, 1, 1), layouts[i])
+        items[i].out.sample_fmt = _out_format(dtypes[i])[1]
+        items[i].out.layout = _LAYOUTS[layouts[i]] | (LAYOUT_UPSAMPLE if ups[i] else 0)
+    info = BatchInfo()
+    dp = DParams(cp_reduce=reduce, cp_layer=layers)
+    rc = lib().grkgpu_batch_convert_plan(items, arr, n, ctypes.byref(dp), ctypes.byref(info))
+    res = info.as_dict()
+    res.update(rc=rc, error=lib().grkgpu_last_error().decode() if rc else "",
+               status=[items[i].status for i in range(n)],
+               img=[ImageDesc.from_buffer_copy(items[i].img) for i in range(n)])
+    return res
+
+
+def convert_jobs_to(jobs, layout="chw"):
+    """grkgpu_convert_jobs_to: the converting / upsampling stores of
+    Codec.decompress_batch_convert for a list of rectangles in one launch set.
+    jobs: dicts with
+      rect   (x0, y0, x1, y1) on the reference grid
+      comps  1 .. 4 dicts: src (2-D cuda tensor (rows, stride) holding the
+             component's grid from `origin` on -- int32 with raw=True, a tile
+             buffer, else finished samples of its dtype -- or None: zeros),
+             prec, sgnd, dx, dy, origin (gx0, gy0), lead (zx0, zy0; default
+             the origin), irreversible (raw: 9/7 float bit patterns)
+      dst    flat cuda tensor, every job's of one dtype; planar: channel k's
+             plane at k * (y1 - y0) * dst_stride
+      dst_stride (default: a row), mct, colour, out_prec, prec_mode
+    Returns the dsts."""
+    _layout_shape((1, 1, 1), layout)
+    il = layout == "hwc"
+    if not jobs:
+        return []
+    dt, fmt = _out_format(_out_dtype(jobs[0]["dst"]))
+    arr = (ConvertJob * len(jobs))()
+    for i, q in enumerate(jobs):
+        x0, y0, x1, y1 = [int(v) for v in q["rect"]]
+        comps, dst = q["comps"], q["dst"]
+        w, h = max(x1 - x0, 0), max(y1 - y0, 0)
+        j = arr[i]
+        if not 1 <= len(comps) <= 4:
+            raise GrkGpuError("convert_jobs_to: job %d: 1 .. 4 components" % i)
+        chans = _out_channels(q.get("colour"), False, [u["prec"] for u in comps], [u["sgnd"] for u in comps],
+                              q.get("out_prec"))
+        no = len(chans)
+        row = w * no if il else w
+        stride = row if q.get("dst_stride") is None else int(q["dst_stride"])
+        need = ((h - 1) * stride + row if il else (no * h - 1) * stride + row) if w and h else 0
+        if dst.dim() != 1 or not dst.is_contiguous() or not dst.is_cuda or _out_dtype(dst) != dt or dst.numel() < need \
+                or stride < row:
+            raise GrkGpuError("convert_jobs_to: job %d: dst flat %s on the GPU, %d samples" % (i, dt.name, need))
+        for k, u in enumerate(comps):
+            cc = j.comp[k]
+            src, prec, sgnd = u["src"], int(u["prec"]), bool(u["sgnd"])
+            cc.dx, cc.dy = int(u["dx"]), int(u["dy"])
+            cc.gx0, cc.gy0 = [int(v) for v in u["origin"]]
+            cc.zx0, cc.zy0 = [int(v) for v in u.get("lead", u["origin"])]
+            raw = bool(u.get("raw"))
+            cc.kind = SRC_RAW
+            cc.wavelet = 1 if raw and u.get("irreversible") else 0
+            cc.shift = 0 if sgnd or not raw else 1 << (prec - 1)
+            cc.min = -(1 << (prec - 1)) if sgnd else 0
+            cc.max = (1 << (prec - 1)) - 1 if sgnd else (1 << prec) - 1
+            if src is None:
+                if not raw:
+                    cc.kind = SRC_SAMPLES + _out_format(u.get("dtype", np.int32))[1]
+                continue
+            sdt = _out_dtype(src)
+            if src.dim() != 2 or not src.is_contiguous() or not src.is_cuda or src.device != dst.device or sdt is None \
+                    or (raw and sdt != np.dtype(np.int32)):
+                raise GrkGpuError("convert_jobs_to: job %d: component %d: a 2-D cuda tensor of samples" % (i, k))
+            rows, sstride = src.shape
+            if w and h and cc.dx and cc.dy and ((x1 - 1) // cc.dx - cc.gx0 >= sstride
+                                                 or (y1 - 1) // cc.dy - cc.gy0 >= rows):
+                raise GrkGpuError("convert_jobs_to: job %d: component %d does not hold the rectangle" % (i, k))
+            if not raw:
+                cc.kind = SRC_SAMPLES + _NP_FMT[sdt]
+            cc.src, cc.stride = src.data_ptr(), sstride
+        for k in range(1 if il else no):
+            j.dst[k] = dst.data_ptr() + k * h * stride * dt.itemsize
+        j.x0, j.y0, j.x1, j.y1 = x0, y0, x1, y1
+        j.dst_stride, j.numcomps, j.mct = stride, len(comps), int(q.get("mct", 0))
+        o = _out_ops(q.get("colour"), q.get("out_prec"), q.get("prec_mode", "clip"))
+        if o is not None:
+            j.ops = o
+    _check(lib().grkgpu_convert_jobs_to(arr, len(jobs), fmt, _LAYOUTS[layout], _stream_handle(jobs[0]["dst"].device)))
+    return [q["dst"] for q in jobs]
 
 
 def _per_item(v, n, name):
@@ -1448,6 +1605,123 @@ class Codec:
         info = BatchInfo()
         dp = DParams(cp_reduce=reduce, cp_layer=layers)
         rc = lib().grkgpu_decompress_batch(self._ctx, items, n, ctypes.byref(dp), ctypes.byref(info))
+        self.batch_info = info.as_dict()
+        msg = lib().grkgpu_last_error().decode() if rc else ""
+        failed = [i for i in range(n) if items[i].status]
+        if rc and (errors == "raise" or not failed):
+            raise GrkGpuError("grkgpu error %d: %s" % (rc, msg))
+        if stacked is not None:
+            return stacked
+        for i in failed:
+            outs[i] = GrkGpuError("grkgpu error %d: item %d failed%s" % (items[i].status, i,
+                                                                         msg[msg.index(":"):] if failed[0] == i else ""))
+        return outs
+
+    def decompress_batch_convert(self, bufs, dtype=None, layout="chw", device_out=False, out=None, reduce=0, layers=0,
+                                 upsample=False, colour=None, out_prec=None, prec_mode="clip", stack=False,
+                                 errors="raise"):
+        """decompress_batch with decompress's output steps
+        (grkgpu_decompress_batch_convert): item i is what decompress(buf,
+        dtype=, layout=, device_out=, out=, reduce=, layers=, upsample=,
+        colour=, out_prec=, prec_mode=) returns, bit for bit -- a list of host
+        planes for a stream with subsampled components that is not upsampled,
+        an array or cuda tensor otherwise -- so a list of 4:2:0 or 12-bit
+        streams decodes straight to (h,w,3) uint8 RGB in one launch set.
+        upsample, colour, out_prec and prec_mode are one value for all streams
+        or a list with one entry per stream, like dtype / layout / device_out.
+        force-RGB and custom-MCT streams are refused item by item.  stack,
+        errors and self.batch_info as decompress_batch: with upsample / colour,
+        stack=True gives the (n, h, w, 3) tensor a loader wants."""
+        if errors not in ("raise", "return"):
+            raise GrkGpuError("errors must be 'raise' or 'return'")
+        bufs = list(bufs)
+        n = len(bufs)
+
+        dtypes, layouts = _per_stream(dtype, n, "dtype"), _per_stream(layout, n, "layout")
+        devs, ups = _per_stream(device_out, n, "device_out"), _per_stream(upsample, n, "upsample")
+        ops, colours, precs = _batch_ops(n, colour, out_prec, prec_mode)
+        outs = [None] * n if out is None else _per_stream(list(out), n, "out")
+        if layers < 0 or reduce < 0:
+            raise GrkGpuError("reduce and layers must be >= 0")
+        if stack and out is not None:
+            raise GrkGpuError("stack=True allocates the output itself")
+        items, keep = _batch_items(bufs)
+        cd = lambda v, s: -(-v // s)  # noqa: E731
+        R = 1 << reduce
+        shapes, any_dev = [None] * n, False
+        for i, buf in enumerate(bufs):
+            # geometry from the main header alone, by decompress's rules (the
+            # library checks everything else); a stream whose header does not
+            # read gets no destination and fails inside the call with its own code
+            d = ImageDesc()
+            hdr_ok = lib().grkgpu_read_header(ctypes.c_void_p(items[i].cs), items[i].len, ctypes.byref(d)) == 0
+            dt, fmt = _out_format(dtypes[i])
+            o = outs[i]
+            if o is not None and _out_dtype(o) is not None:
+                if dtypes[i] is not None and _out_dtype(o) != dt:
+                    raise GrkGpuError("item %d: out holds %s samples, dtype asks for %s"
+                                      % (i, _out_dtype(o).name, dt.name))
+                dt, fmt = _out_format(_out_dtype(o))
+            _layout_shape((1, 1, 1), layouts[i])
+            items[i].out.sample_fmt, items[i].out.layout = fmt, _LAYOUTS[layouts[i]]
+            if not hdr_ok:
+                continue
+            c = d.numcomps
+            grid = [(d.dx[k], d.dy[k]) for k in range(c)]
+            subsampled = any(g != (1, 1) for g in grid)
+            chans = _out_channels(colours[i], False, [d.prec[k] for k in range(c)], [d.sgnd[k] for k in range(c)],
+                                  precs[i])
+            if len(chans) != c:  # (CMYK: the black ink's plane goes; one grid either way)
+                grid = [grid[0]] * len(chans)
+            c = len(chans)
+            up = (bool(ups[i]) or colours[i] == "sycc") and subsampled
+            extent = lambda a0, a1, s: cd(cd(a1, s) - cd(a0, s), R)  # noqa: E731
+            if subsampled and not up:  # a list of host planes, each on its grid
+                if o is not None or devs[i] or stack or (layouts[i] != "chw" and all(g == grid[0] for g in grid)):
+                    raise GrkGpuError("item %d: subsampled components decode to host planes only" % i)
+                o = [np.empty((extent(d.y0, d.y1, g[1]), extent(d.x0, d.x1, g[0])), dtype=dt) for g in grid]
+                outs[i] = o
+                items[i].out = self._out_planes(o, c, fmt, "chw", False)
+                items[i].out.layout = _LAYOUTS[layouts[i]]
+                continue
+            shp = (c, extent(d.y0, d.y1, 1), extent(d.x0, d.x1, 1))
+            shapes[i] = (_layout_shape(shp, layouts[i]), dt, up)
+            if stack:
+                continue
+            if o is not None:
+                on_dev = _check_out(o, shp, self.device, dt, layouts[i])
+            else:
+                on_dev = bool(devs[i])
+                if on_dev:
+                    o = _torch().empty(shapes[i][0], dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
+                else:
+                    o = np.empty(shapes[i][0], dtype=dt)
+                outs[i] = o
+            any_dev = any_dev or on_dev
+            items[i].out = self._out_planes(o, c, fmt, layouts[i], on_dev)
+            if up:
+                items[i].out.layout |= LAYOUT_UPSAMPLE
+        stacked = None
+        if stack and n:
+            if any(sh is None for sh in shapes) or any(sh[:2] != shapes[0][:2] for sh in shapes) or len(set(devs)) != 1:
+                raise GrkGpuError("stack=True needs streams of one shape, dtype, layout and destination")
+            shp, dt, _ = shapes[0]
+            any_dev = bool(devs[0])
+            if any_dev:
+                stacked = _torch().empty((n,) + tuple(shp), dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
+            else:
+                stacked = np.empty((n,) + tuple(shp), dtype=dt)
+            c = shp[0] if layouts[0] == "chw" else shp[2]
+            for i in range(n):
+                outs[i] = stacked[i]
+                items[i].out = self._out_planes(stacked[i], c, _out_format(dt)[1], layouts[i], any_dev)
+                if shapes[i][2]:
+                    items[i].out.layout |= LAYOUT_UPSAMPLE
+        if any_dev:
+            lib().grkgpu_set_stream(self._ctx, _stream_handle(self.device))
+        info = BatchInfo()
+        dp = DParams(cp_reduce=reduce, cp_layer=layers)
+        rc = lib().grkgpu_decompress_batch_convert(self._ctx, items, ops, n, ctypes.byref(dp), ctypes.byref(info))
         self.batch_info = info.as_dict()
         msg = lib().grkgpu_last_error().decode() if rc else ""
         failed = [i for i in range(n) if items[i].status]

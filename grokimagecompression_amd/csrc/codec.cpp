@@ -20,6 +20,7 @@
 #include <atomic>
 #include <array>
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -2951,7 +2952,9 @@ struct DecHost {
     uint32_t tb = 0, te = 0xffffffffu, reduce = 0, max_layers = 0;
     const Rect *win = nullptr;
     bool host_only = false;
-    bool batch = false;  // an item of a batch decode: a stream with a subsampled component is refused
+    // an item of grkgpu_decompress_batch / grkgpu_batch_plan, the batch without the converting store: a stream
+    // with a subsampled component is refused (grkgpu_decompress_batch_convert takes it)
+    bool batch = false;
     // begin()
     void *const *planes = nullptr;
     int planes_on_device = 0;
@@ -3011,6 +3014,68 @@ struct DecHost {
     }
     void parse_tiles(size_t l0, size_t l1);
     int finish();
+
+    // The last store's decisions as the batch decode's records need them
+    // (decompress_impl states the same rules inline, for its per-tile launches).
+    // Upsampled: which components go through a staging plane -- all when they
+    // share one subsampled grid (their MCT runs first); otherwise those with a
+    // tile boundary that is no multiple of dx / dy, where the tile's first
+    // pixels map to a sample of the neighbouring tile-component (it starts at
+    // ceil(tx0 / dx)).  The others are read from the tile buffers, like the
+    // full-resolution components.
+    bool staged(uint32_t k) const {
+        if (!up || (cp.dx[k] == 1 && cp.dy[k] == 1)) return false;
+        const bool xseam = cp.tw > 1 && (cp.tx0 % cp.dx[k] || cp.tdx % cp.dx[k]);
+        const bool yseam = cp.th > 1 && (cp.ty0 % cp.dy[k] || cp.tdy % cp.dy[k]);
+        return !mixed || xseam || yseam;
+    }
+    // bytes of component k's staging plane (format sfmt), rounded so that the next one starts on a 16-byte boundary
+    size_t stage_bytes(uint32_t k) const {
+        return staged(k) ? ((size_t)(ooff[k + 1] - ooff[k]) * ssb + 15) & ~(size_t)15 : 0;
+    }
+    // the output regions: the planes, or the one interleaved image
+    uint32_t nout() const { return il ? 1 : no; }
+    // the store on the components' own grids converts (precision or colour on one grid, or precision on each
+    // plane's own grid); else the ops, if any, run in the upsampling store
+    bool grid_ops() const { return conv && !up; }
+    // samples nothing decoded leave as the colour conversion of zeros, by a converting store over null sources
+    bool converted_zeros() const { return colconv && !up && !cm && (opad || missing); }
+    // the clamped, shifted tile at the decoded resolution: where component k's samples of tile lt lie in
+    // its tile buffer (tr) and the part of them inside the output (out)
+    Rect tile_res(uint32_t lt, uint32_t k) const {
+        const TileComp &tc = tiles[lt].comps[k];
+        return tc.res[tc.numres - 1 - reduce].r;
+    }
+    // component k of an upsampled decode's tile as the upsampling store reads it: its staging plane `stg`
+    // (staged(k)) or the tile buffer `buf` (null: a tile never reached)
+    UpComp up_comp(uint32_t lt, uint32_t k, const void *stg, const int32_t *buf) const {
+        UpComp u{};
+        u.dx = (uint8_t)cp.dx[k];
+        u.dy = (uint8_t)cp.dy[k];
+        if (staged(k)) {
+            u.src = stg;
+            u.stride = orect[k].w();
+            u.gx0 = (int32_t)orect[k].x0;
+            u.gy0 = (int32_t)orect[k].y0;
+        } else {
+            const Rect tr = comp_rect(tiles[lt].r, cp.dx[k], cp.dy[k]);
+            u.raw = 1;
+            u.gx0 = (int32_t)tr.x0;
+            u.gy0 = (int32_t)tr.y0;
+            u.stride = tr.w();
+            if (!tiles[lt].comps.empty()) {
+                u.src = buf;
+                u.irrev = (uint8_t)tiles[lt].comps[k].irrev;
+            }
+            u.shift = cp.shift[k];
+            u.mn = cp.sgnd[k] ? -(1 << (cp.prec[k] - 1)) : 0;
+            u.mx = cp.sgnd[k] ? (1 << (cp.prec[k] - 1)) - 1 : (1 << cp.prec[k]) - 1;
+        }
+        // the zero lead-in: left of / above the output rectangle's origin on the component's grid
+        u.zx0 = std::max((int32_t)orect[k].x0, u.gx0);
+        u.zy0 = std::max((int32_t)orect[k].y0, u.gy0);
+        return u;
+    }
 };
 
 int DecHost::begin() {
@@ -4187,8 +4252,115 @@ static hipError_t store_groups_launch(const StoreGroup (&groups)[10], const void
     return hipSuccess;
 }
 
+// The tables of the converting stores (grkgpu_decompress_batch_convert,
+// grkgpu_convert_jobs_to): StoreJobs with ops, one group per (sample format,
+// layout, op class); ConvJobs, one group per (sample format, layout, thread
+// shape, sYCC or not); and the OutOps the jobs index.  In the device buffer:
+// the StoreJob groups, the ConvJob groups, the OutOps, then every group's
+// first-workgroup array -- from a 16-byte boundary on, records of 8-byte
+// multiples.
+static_assert(sizeof(StoreJob) % 8 == 0 && sizeof(ConvJob) % 8 == 0 && sizeof(OutOps) % 8 == 0, "table records stay aligned");
+template <typename J>
+struct JobGroup {
+    int32_t fmt = 0;
+    bool il = false;
+    int cls = 0;  // StoreJob: OP_* (1 precision, 2 sYCC, 3 eYCC, 4 CMYK); ConvJob: bit 0 run shape, bit 1 sYCC
+    std::vector<J> jobs;
+    std::vector<uint32_t> first;
+};
+struct ConvTables {
+    std::vector<JobGroup<StoreJob>> sg;
+    std::vector<JobGroup<ConvJob>> cg;
+    std::vector<OutOps> ops;
+    uint32_t njobs = 0;
+};
+template <typename J>
+static bool job_group_add(std::vector<JobGroup<J>> &groups, int32_t fmt, bool il, int cls, const J &j, uint64_t wgs) {
+    JobGroup<J> *g = nullptr;
+    for (auto &q : groups)
+        if (q.fmt == fmt && q.il == il && q.cls == cls) g = &q;
+    if (wgs > STORE_JOB_MAX_WGS || (g ? g->first.back() : 0) + wgs > 0x7fffffffull) return false;
+    if (!g) {
+        groups.emplace_back();
+        g = &groups.back();
+        g->fmt = fmt; g->il = il; g->cls = cls;
+        g->first.push_back(0);
+    }
+    g->jobs.push_back(j);
+    g->first.push_back(g->first.back() + (uint32_t)wgs);
+    return true;
+}
+// the op class of a store on one grid (launch_inv_ops' choice)
+static int store_op_class(const OutOps &o) {
+    return o.col == COL_EYCC ? 3 : (o.col == COL_CMYK ? 4 : (o.sycc ? 2 : 1));
+}
+// false: the job takes a launch of its own (too many workgroups)
+static bool conv_add_store(ConvTables &T, int32_t fmt, bool il, const OutOps &o, StoreJob j, uint32_t ops_index) {
+    j.ops = ops_index;
+    if (!job_group_add(T.sg, fmt, il, store_op_class(o), j, store_job_wgs(j, sample_bytes(fmt), il))) return false;
+    ++T.njobs;
+    return true;
+}
+static bool conv_add_up(ConvTables &T, int32_t fmt, bool il, const OutOps &o, ConvJob j, uint32_t ops_index) {
+    j.ops = ops_index;
+    const bool fast = conv_job_fast(j.c, j.ncomp, fmt, o.col);
+    if (!job_group_add(T.cg, fmt, il, (fast ? 1 : 0) | (fast && o.sycc ? 2 : 0), j,
+                       conv_job_wgs(j, sample_bytes(fmt), fast)))
+        return false;
+    ++T.njobs;
+    return true;
+}
+static size_t conv_tables_bytes(const ConvTables &T) {
+    size_t b = T.ops.size() * sizeof(OutOps);
+    for (const auto &g : T.sg) b += g.jobs.size() * sizeof(StoreJob) + g.first.size() * 4;
+    for (const auto &g : T.cg) b += g.jobs.size() * sizeof(ConvJob) + g.first.size() * 4;
+    return b;
+}
+static hipError_t conv_tables_upload(const ConvTables &T, uint8_t *stage, void *dev, hipStream_t s) {
+    size_t o = 0;
+    auto put = [&](const void *p, size_t bytes) { memcpy(stage + o, p, bytes); o += bytes; };
+    for (const auto &g : T.sg) put(g.jobs.data(), g.jobs.size() * sizeof(StoreJob));
+    for (const auto &g : T.cg) put(g.jobs.data(), g.jobs.size() * sizeof(ConvJob));
+    put(T.ops.data(), T.ops.size() * sizeof(OutOps));
+    for (const auto &g : T.sg) put(g.first.data(), g.first.size() * 4);
+    for (const auto &g : T.cg) put(g.first.data(), g.first.size() * 4);
+    return o ? hipMemcpyAsync(dev, stage, o, hipMemcpyHostToDevice, s) : hipSuccess;
+}
+// phase 1 (the StoreJobs with ops) or phase 2 (the ConvJobs): same-stream order carries the dependency
+static hipError_t conv_tables_launch(const ConvTables &T, const void *dev, int phase, hipStream_t s, uint32_t *nl) {
+    const uint8_t *const d = (const uint8_t *)dev;
+    size_t jo = 0, fo = T.ops.size() * sizeof(OutOps);
+    for (const auto &g : T.sg) fo += g.jobs.size() * sizeof(StoreJob);
+    for (const auto &g : T.cg) fo += g.jobs.size() * sizeof(ConvJob);
+    const OutOps *const ops = (const OutOps *)(d + fo - T.ops.size() * sizeof(OutOps));
+    for (const auto &g : T.sg) {
+        if (phase == 1 && g.first.back()) {
+            const hipError_t e = launch_store_jobs_ops((const StoreJob *)(d + jo), (const uint32_t *)(d + fo),
+                                                       (uint32_t)g.jobs.size(), g.first.back(), ops, g.fmt, g.il, g.cls, s);
+            if (e != hipSuccess) return e;
+            if (nl) ++*nl;
+        }
+        jo += g.jobs.size() * sizeof(StoreJob);
+        fo += g.first.size() * 4;
+    }
+    for (const auto &g : T.cg) {
+        if (phase == 2 && g.first.back()) {
+            const hipError_t e = launch_conv_jobs((const ConvJob *)(d + jo), (const uint32_t *)(d + fo),
+                                                  (uint32_t)g.jobs.size(), g.first.back(), ops, g.fmt, g.il,
+                                                  (g.cls & 1) != 0, (g.cls & 2) != 0, s);
+            if (e != hipSuccess) return e;
+            if (nl) ++*nl;
+        }
+        jo += g.jobs.size() * sizeof(ConvJob);
+        fo += g.first.size() * 4;
+    }
+    return hipSuccess;
+}
+
+// ops / convert: grkgpu_decompress_batch_convert (ops null: no item converts)
 static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
-                      grkgpu_batch_info *info, bool host_only) {
+                      grkgpu_batch_info *info, bool host_only, bool convert = false,
+                      const grkgpu_out_ops *ops = nullptr) {
     if (info) *info = grkgpu_batch_info{};
     if ((!c && !host_only) || (n && !items)) return set_err(GRKGPU_EINVAL, "null argument");
     if (p && (p->DA_x0 || p->DA_y0 || p->DA_x1 || p->DA_y1))
@@ -4208,13 +4380,18 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
             it.img = grkgpu_image_desc{};
             DecHost &h = H[i];
             int rc = it.cs ? check_out_planes(&it.out) : set_err(GRKGPU_EINVAL, "null argument");
-            if (!rc && (it.out.layout & GRKGPU_LAYOUT_UPSAMPLE))
+            if (!rc && !convert && (it.out.layout & GRKGPU_LAYOUT_UPSAMPLE))
                 rc = set_err(GRKGPU_EUNSUPPORTED, "upsampled output is not supported in a batch");
+            const grkgpu_out_ops *const o = convert && ops && out_ops_active(&ops[i]) ? &ops[i] : nullptr;
+            if (!rc && convert && ops) rc = check_out_ops(&ops[i], it.out.sample_fmt);
+            if (!rc && o && (o->colour & GRKGPU_COLOUR_FORCE_RGB))
+                rc = set_err(GRKGPU_EUNSUPPORTED, "force-RGB is not supported in a batch");
             if (!rc) {
                 h.csb = it.cs; h.len = it.len; h.img = &it.img;
-                h.od = DecodeOut{it.out.planes, (int32_t)it.out.sample_fmt, it.out.layout == GRKGPU_LAYOUT_INTERLEAVED,
-                                 it.out.on_device, 0, nullptr, 0, nullptr, 0};
-                h.reduce = reduce; h.max_layers = layers; h.host_only = host_only; h.batch = true;
+                h.od = DecodeOut{it.out.planes, (int32_t)it.out.sample_fmt,
+                                 (it.out.layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED,
+                                 it.out.on_device, (it.out.layout & GRKGPU_LAYOUT_UPSAMPLE) != 0, o, 0, nullptr, 0};
+                h.reduce = reduce; h.max_layers = layers; h.host_only = host_only; h.batch = !convert;
                 rc = h.begin();
             }
             if (rc) fail(i, rc);
@@ -4311,7 +4488,7 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
     for (uint32_t i = 0; i < n; ++i) {
         const DecHost &h = H[i];
         if (items[i].status || h.planes_on_device || host_only) continue;
-        for (uint32_t k = 0; k < (h.il ? 1u : h.nc); ++k) {
+        for (uint32_t k = 0; k < h.nout(); ++k) {
             Region r{(uint8_t *)h.planes[k], 0, h.region_bytes(k)};
             const bool adj = !regions.empty() && regions.back().host + regions.back().bytes == r.host &&
                              (regions.back().off + regions.back().bytes) % h.sb == 0;
@@ -4321,61 +4498,234 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
             regions.push_back(r);
         }
     }
+    // the staging planes of the upsampled items' staged components, behind the
+    // output staging, each on a 16-byte boundary
+    std::vector<std::array<size_t, GRKGPU_MAX_COMPS>> stoff(n);
+    // [zero0, zero1): the span from the first to the last staging plane of a
+    // stream with tiles it never reached -- zeroed by one fill, the planes of
+    // complete streams that lie between included (phase 1 writes every sample
+    // of theirs afterwards), so that N copies take the fills of one
+    size_t zero0 = 0, zero1 = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const DecHost &h = H[i];
+        if (items[i].status || !h.up) continue;
+        for (uint32_t k = 0; k < h.nc; ++k) {
+            if (!h.staged(k)) continue;
+            img_bytes = (img_bytes + 15) & ~(size_t)15;
+            stoff[i][k] = img_bytes;
+            img_bytes += h.stage_bytes(k);
+            if (h.missing) {
+                if (zero1 == 0) zero0 = stoff[i][k];
+                zero1 = img_bytes;
+            }
+        }
+    }
     if (!host_only) {
         HIPCHK(hipSetDevice(c->device));
         if (img_bytes) HIPCHK(c->img.ensure(img_bytes + 256));
         HIPCHK(c->work.ensure(arena * 4 + 256));
     }
-    // the last store: a StoreJob per tile of every item of up to four
-    // components, per-tile launches for the others
+    // The last store, decompress_impl's launches as records: a StoreJob per
+    // tile (per tile-component of a mixed-grid item) for the stores on the
+    // components' own grids -- with an ops index where that store converts
+    // (DecHost::grid_ops) --, a ConvJob per tile of an upsampled item and per
+    // rectangle of converted zeros, and per-tile launches for what no table
+    // takes (more than four components, too many workgroups for one job).
     StoreGroup groups[10];
     std::vector<TileStore> singles;
+    ConvTables ctab;
+    std::vector<std::function<hipError_t(hipStream_t)>> conv_singles, up_singles;  // (phase 1 with ops, phase 2)
     uint32_t n_store_jobs = 0;
     const uintptr_t work0 = host_only ? 0 : (uintptr_t)c->work.p, img0 = host_only ? 0 : (uintptr_t)c->img.p;
     auto dst_of = [&](uint32_t i, uint32_t k) {
+        if (host_only) return (uintptr_t)0;
         return H[i].planes_on_device ? (uintptr_t)H[i].planes[k] : img0 + roff[i][k];
+    };
+    auto tile_store_of = [](const StoreJob &j, int32_t fmt, bool il) {
+        TileStore ts{};
+        for (uint32_t k = 0; k < 4; ++k) {
+            ts.src.p[k] = const_cast<int32_t *>(j.src[k]);
+            ts.dst.p[k] = j.dst[k];
+            ts.sh.v[k] = j.shift[k]; ts.mn.v[k] = j.mn[k]; ts.mx.v[k] = j.mx[k];
+        }
+        ts.sstride = j.sstride; ts.w = j.w; ts.h = j.h; ts.dstride = j.dstride; ts.nc = j.ncomp;
+        ts.fmt = fmt; ts.il = il; ts.mct = j.mct; ts.wmask = (int32_t)j.irrev;
+        return ts;
+    };
+    auto ops_single = [&](const TileStore &ts, const OutOps &o) {
+        conv_singles.push_back([ts, o](hipStream_t s) {
+            return launch_mct_inv_dcshift_ops(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc,
+                                              ts.sh, ts.mn, ts.mx, ts.mct, ts.wmask, o, s);
+        });
     };
     for (uint32_t i = 0; i < n; ++i) {
         if (items[i].status) continue;
         const DecHost &h = H[i];
-        const uint32_t nc = h.nc, nout = h.il ? 1 : nc, ow = h.orect[0].w();
-        const size_t eb = h.il ? (size_t)nc * h.sb : h.sb;
+        const uint32_t nc = h.nc, no = h.no, nout = h.nout(), ow = h.orect[0].w();
+        const size_t eb = h.il ? (size_t)no * h.sb : h.sb;
+        const bool gops = h.grid_ops();
+        // the item's entry of the OutOps table (all zero where it converts nothing), made when first needed
+        uint32_t ops_at = 0xffffffffu, kops_at[GRKGPU_MAX_COMPS];
+        for (uint32_t k = 0; k < GRKGPU_MAX_COMPS; ++k) kops_at[k] = 0xffffffffu;
+        auto item_ops = [&]() {
+            if (ops_at == 0xffffffffu) { ops_at = (uint32_t)ctab.ops.size(); ctab.ops.push_back(h.dops); }
+            return ops_at;
+        };
+        // where the stores on the components' own grids put component k: the
+        // output, or (upsampled) its staging plane, in format gfmt
+        const int32_t gfmt = h.up ? h.sfmt : h.od.fmt;
+        auto cat = [&](uint32_t k, uint64_t elem) {
+            return h.up ? (void *)(img0 + stoff[i][k] + elem * h.ssb) : (void *)(dst_of(i, k) + elem * eb);
+        };
         for (uint32_t lt = 0; lt < h.nsh; ++lt) {
             const Tile &tile = h.tiles[lt];
-            if (tile.comps.empty()) continue;
-            const Rect tr = tile.comps[0].res[tile.comps[0].numres - 1 - reduce].r;  // the tile at the decoded resolution
-            const Rect out = intersect(tr, h.orect[0]);                            // its part of the output
-            if (out.empty()) continue;
-            const uint64_t soff = (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0);
-            const uint64_t doff = ((uint64_t)(out.y0 - h.orect[0].y0) * ow + (out.x0 - h.orect[0].x0)) * eb;
-            int32_t wmask = 0;  // components holding 9/7 (float) samples
-            for (uint32_t k = 0; k < nc; ++k) wmask |= tile.comps[k].irrev << k;
-            TileStore ts{};
-            for (uint32_t k = 0; k < nc; ++k) {
-                ts.src.p[k] = (int32_t *)(work0 + (tile.comps[k].arena_off + soff) * 4);
-                ts.sh.v[k] = h.cp.shift[k];
-                clamp_bounds(h.cp, k, ts.mn.v[k], ts.mx.v[k]);
+            if (!tile.comps.empty() && h.mixed) {  // each tile-component on its own grid, no MCT
+                for (uint32_t k = 0; k < nc; ++k) {
+                    const TileComp &tc = tile.comps[k];
+                    const Rect tr = h.tile_res(lt, k), out = intersect(tr, h.orect[k]);
+                    if (out.empty() || (h.up && !h.staged(k))) continue;
+                    StoreJob j{};
+                    j.src[0] = (const int32_t *)(work0 + (tc.arena_off + (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0)) * 4);
+                    j.dst[0] = cat(k, (uint64_t)(out.y0 - h.orect[k].y0) * h.orect[k].w() + (out.x0 - h.orect[k].x0));
+                    j.shift[0] = h.cp.shift[k];
+                    clamp_bounds(h.cp, k, j.mn[0], j.mx[0]);
+                    j.sstride = tr.w(); j.dstride = h.orect[k].w(); j.w = out.w(); j.h = out.h();
+                    j.ncomp = 1; j.irrev = (uint32_t)tc.irrev;
+                    if (gops) {  // each plane on its own grid, converted
+                        OutOps ok{};
+                        ok.pc[0] = h.dops.pc[k];
+                        if (kops_at[k] == 0xffffffffu) { kops_at[k] = (uint32_t)ctab.ops.size(); ctab.ops.push_back(ok); }
+                        if (!conv_add_store(ctab, h.od.fmt, false, ok, j, kops_at[k]))
+                            ops_single(tile_store_of(j, h.od.fmt, false), ok);
+                    } else if (store_group_add(groups, gfmt, false, j)) {
+                        ++n_store_jobs;
+                    } else {
+                        singles.push_back(tile_store_of(j, gfmt, false));
+                    }
+                }
+            } else if (!tile.comps.empty()) {
+                // every component on one grid: one job, MCT included (orect[k] is the
+                // output on that grid -- the image itself without subsampling)
+                const Rect tr = h.tile_res(lt, 0);            // the tile at the decoded resolution
+                const Rect out = intersect(tr, h.orect[0]);  // its part of the output
+                if (!out.empty()) {
+                    const uint64_t soff = (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0);
+                    const uint64_t delem = (uint64_t)(out.y0 - h.orect[0].y0) * ow + (out.x0 - h.orect[0].x0);
+                    const bool pil = h.il && !h.up;  // (staging planes are planes)
+                    int32_t wmask = 0;  // components holding 9/7 (float) samples
+                    for (uint32_t k = 0; k < nc; ++k) wmask |= tile.comps[k].irrev << k;
+                    TileStore ts{};
+                    for (uint32_t k = 0; k < nc; ++k) {
+                        ts.src.p[k] = (int32_t *)(work0 + (tile.comps[k].arena_off + soff) * 4);
+                        ts.sh.v[k] = h.cp.shift[k];
+                        clamp_bounds(h.cp, k, ts.mn.v[k], ts.mx.v[k]);
+                    }
+                    for (uint32_t k = 0; k < (h.up ? nc : nout); ++k) ts.dst.p[k] = cat(k, delem);
+                    ts.sstride = tr.w(); ts.w = out.w(); ts.h = out.h();
+                    ts.dstride = pil ? ow * no : ow;  // (h.il: ow * no fits 32 bits, checked by begin())
+                    ts.nc = nc; ts.fmt = gops ? h.od.fmt : gfmt; ts.il = pil; ts.mct = h.tmct[lt]; ts.wmask = wmask;
+                    bool tabled = false;
+                    if (nc <= 4) {
+                        StoreJob j{};
+                        for (uint32_t k = 0; k < nc; ++k) {
+                            j.src[k] = ts.src.p[k];
+                            j.dst[k] = ts.dst.p[k];
+                            j.shift[k] = ts.sh.v[k]; j.mn[k] = ts.mn.v[k]; j.mx[k] = ts.mx.v[k];
+                        }
+                        j.sstride = ts.sstride; j.dstride = ts.dstride; j.w = ts.w; j.h = ts.h;
+                        j.ncomp = nc; j.mct = ts.mct; j.irrev = (uint32_t)wmask;
+                        if (gops) {
+                            tabled = conv_add_store(ctab, ts.fmt, ts.il, h.dops, j, item_ops());
+                        } else {
+                            tabled = store_group_add(groups, ts.fmt, ts.il, j);
+                            if (tabled) ++n_store_jobs;
+                        }
+                    }
+                    if (!tabled && gops) ops_single(ts, h.dops);
+                    else if (!tabled) singles.push_back(ts);
+                }
             }
-            for (uint32_t k = 0; k < nout; ++k) ts.dst.p[k] = (void *)(dst_of(i, k) + doff);
-            ts.sstride = tr.w(); ts.w = out.w(); ts.h = out.h();
-            ts.dstride = h.il ? ow * nc : ow;  // (h.il: ow * nc fits 32 bits, checked by begin())
-            ts.nc = nc; ts.fmt = h.od.fmt; ts.il = h.il; ts.mct = h.tmct[lt]; ts.wmask = wmask;
+            // upsampled: the output, tile by tile (the tiles never reached included)
+            const Rect uout = intersect(tile.r, {h.ix0, h.iy0, h.ix1, h.iy1});  // the tile's pixels of the output
+            if (!h.up || uout.empty()) continue;
+            UpPlan pl{};
+            for (uint32_t k = 0; k < nc; ++k) {
+                pl.c[k] = h.up_comp(lt, k, (const void *)(img0 + stoff[i][k]),
+                                    tile.comps.empty() ? nullptr : (const int32_t *)(work0 + tile.comps[k].arena_off * 4));
+                if (h.staged(k) && h.conv) pl.c[k].raw = (uint8_t)(UPCOMP_FIN + h.sfmt);
+            }
+            const uint64_t delem = (uint64_t)(uout.y0 - h.iy0) * h.iw + (uout.x0 - h.ix0);
+            DstPlanes tdst{};
+            for (uint32_t k = 0; k < nout; ++k) tdst.p[k] = (void *)(dst_of(i, k) + delem * eb);
+            const uint32_t dstride = h.il ? h.iw * no : h.iw;
             bool tabled = false;
             if (nc <= 4) {
-                StoreJob j{};
+                ConvJob j{};
                 for (uint32_t k = 0; k < nc; ++k) {
-                    j.src[k] = ts.src.p[k];
-                    j.dst[k] = ts.dst.p[k];
-                    j.shift[k] = ts.sh.v[k]; j.mn[k] = ts.mn.v[k]; j.mx[k] = ts.mx.v[k];
+                    j.c[k] = pl.c[k];
+                    if (h.staged(k)) j.c[k].raw = (uint8_t)(UPCOMP_FIN + h.sfmt);  // (a table's finished source names its format)
                 }
-                j.sstride = ts.sstride; j.dstride = ts.dstride; j.w = ts.w; j.h = ts.h;
-                j.ncomp = nc; j.mct = ts.mct; j.irrev = (uint32_t)wmask;
-                tabled = store_group_add(groups, ts.fmt, ts.il, j);
+                for (uint32_t k = 0; k < nout; ++k) j.dst[k] = tdst.p[k];
+                j.X0 = uout.x0; j.Y0 = uout.y0; j.x1 = uout.x1; j.y1 = uout.y1;
+                j.dstride = dstride; j.ncomp = nc;
+                tabled = conv_add_up(ctab, h.od.fmt, h.il, h.dops, j, item_ops());
             }
-            if (tabled) ++n_store_jobs;
-            else singles.push_back(ts);
+            if (!tabled) {
+                const OutOps o = h.dops;
+                const int32_t fmt = h.od.fmt;
+                const bool il = h.il, conv = h.conv;
+                up_singles.push_back([pl, nc, uout, tdst, fmt, il, dstride, o, conv](hipStream_t s) {
+                    return conv ? launch_upsample_ops(pl, nc, uout.x0, uout.y0, uout.w(), uout.h(), tdst, fmt, il, dstride, o, s)
+                                : launch_upsample_to(pl, nc, uout.x0, uout.y0, uout.w(), uout.h(), tdst, fmt, il, dstride, s);
+                });
+            }
+        }
+        // Samples nothing decoded, where the colour step converts them
+        // (decompress_impl's fill_converted): the converting store over null
+        // sources -- on the margin of a reduced decode (the output beyond the
+        // decoded rectangle cwin[0]) and on the tiles the stream never reached,
+        // which no other job writes, so the order among the jobs is free.
+        if (!h.converted_zeros()) continue;
+        std::vector<Rect> zr;
+        const Rect &o0 = h.orect[0], &cw = h.cwin[0];
+        if (h.opad) {
+            zr.push_back({std::max(cw.x1, o0.x0), o0.y0, o0.x1, o0.y1});
+            zr.push_back({o0.x0, std::max(cw.y1, o0.y0), std::min(cw.x1, o0.x1), o0.y1});
+        }
+        for (uint32_t t = h.tb; h.missing && t < h.te; ++t) {
+            if (h.walk.decoded[t] || h.wskip[t]) continue;
+            const Rect cr = comp_rect(tile_rect(h.cp, t), h.cp.dx[0], h.cp.dy[0]);  // (one grid; sYCC: the image's)
+            zr.push_back(intersect({ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
+                                    ceil_pow2(cr.y1, reduce)}, o0));
+        }
+        for (const Rect &o : zr) {
+            if (o.empty()) continue;
+            UpPlan zero{};
+            for (uint32_t k = 0; k < nc; ++k) zero.c[k].dx = zero.c[k].dy = 1;
+            DstPlanes fdst{};
+            for (uint32_t k = 0; k < nout; ++k)
+                fdst.p[k] = (void *)(dst_of(i, k) + ((uint64_t)(o.y0 - o0.y0) * ow + (o.x0 - o0.x0)) * eb);
+            const uint32_t dstride = h.il ? ow * no : ow;
+            bool tabled = false;
+            if (nc <= 4) {
+                ConvJob j{};
+                for (uint32_t k = 0; k < nc; ++k) j.c[k] = zero.c[k];
+                for (uint32_t k = 0; k < nout; ++k) j.dst[k] = fdst.p[k];
+                j.X0 = o.x0; j.Y0 = o.y0; j.x1 = o.x1; j.y1 = o.y1;
+                j.dstride = dstride; j.ncomp = nc;
+                tabled = conv_add_up(ctab, h.od.fmt, h.il, h.dops, j, item_ops());
+            }
+            if (!tabled) {
+                const OutOps od = h.dops;
+                const int32_t fmt = h.od.fmt;
+                const bool il = h.il;
+                up_singles.push_back([zero, nc, o, fdst, fmt, il, dstride, od](hipStream_t s) {
+                    return launch_upsample_ops(zero, nc, o.x0, o.y0, o.w(), o.h(), fdst, fmt, il, dstride, od, s);
+                });
+            }
         }
     }
+    n_store_jobs += ctab.njobs;
     if (info) {
         info->n_ok = n_ok;
         info->n_blocks = nblk;
@@ -4393,9 +4743,11 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
         HIPCHK(c->h_cs.ensure(cs_total + 256));
         HIPCHK(c->coef.ensure(arena * 4 + 256));
         HIPCHK(c->ll.ensure(llarena * 4 + 256));
-        const size_t sjbytes = store_groups_bytes(groups);
-        HIPCHK(c->storejobs.ensure(sjbytes + 256));
-        HIPCHK(c->h_storejobs.ensure(sjbytes + 256));
+        // the converting stores' tables ride behind the StoreJob table, from a 16-byte boundary on
+        const size_t sjbytes = store_groups_bytes(groups), cjoff = (sjbytes + 15) & ~(size_t)15;
+        const size_t cjbytes = conv_tables_bytes(ctab);
+        HIPCHK(c->storejobs.ensure(cjoff + cjbytes + 256));
+        HIPCHK(c->h_storejobs.ensure(cjoff + cjbytes + 256));
         // the streams packed into the pinned buffer, on the host pool: the
         // bytes between them are never addressed by a segment
         host_parallel_for(n, 1, [&](size_t a, size_t b) {
@@ -4412,6 +4764,7 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
         rc = t1.upload(c);
         if (rc) return rc;
         HIPCHK(store_groups_upload(groups, c->h_storejobs.as<uint8_t>(), c->storejobs.p, s));
+        HIPCHK(conv_tables_upload(ctab, c->h_storejobs.as<uint8_t>() + cjoff, c->storejobs.as<uint8_t>() + cjoff, s));
         DwtPlan dplan[2];  // one plan per wavelet over every item's tile-components
         for (uint32_t i = 0; i < n; ++i) {
             if (items[i].status) continue;
@@ -4431,16 +4784,36 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
         HIPCHK(hipEventRecord(c->ev[2], s));
         HIPCHK(dwt_launch_plans(c, dplan, true, &nl));
         HIPCHK(hipEventRecord(c->ev[3], s));
+        // tiles a stream never reached are zero in its staging planes; in the
+        // output the upsampling store writes their pixels
+        if (zero1 > zero0) {
+            HIPCHK(hipMemsetAsync(c->img.as<uint8_t>() + zero0, 0, zero1 - zero0, s));
+            ++nl;
+        }
         for (uint32_t i = 0; i < n; ++i) {
             if (items[i].status) continue;
+            const DecHost &h = H[i];
+            if (h.converted_zeros()) continue;  // (ConvJobs over null sources)
             void *dst[GRKGPU_MAX_COMPS];
-            for (uint32_t k = 0; k < (H[i].il ? 1u : H[i].nc); ++k) dst[k] = (void *)dst_of(i, k);
-            HIPCHK(dec_zero_fills(H[i], dst, s, &nl));
+            for (uint32_t k = 0; k < h.nout(); ++k) dst[k] = (void *)dst_of(i, k);
+            HIPCHK(dec_zero_fills(h, dst, s, &nl));
         }
+        // phase 1: the stores on the components' own grids
         HIPCHK(store_groups_launch(groups, c->storejobs.p, s, &nl));
+        HIPCHK(conv_tables_launch(ctab, c->storejobs.as<uint8_t>() + cjoff, 1, s, &nl));
         for (const TileStore &ts : singles) {
             HIPCHK(launch_mct_inv_dcshift_to(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc,
                                              ts.sh, ts.mn, ts.mx, ts.mct, ts.wmask, s));
+            ++nl;
+        }
+        for (const auto &f : conv_singles) {
+            HIPCHK(f(s));
+            ++nl;
+        }
+        // phase 2: the upsampling / converting store
+        HIPCHK(conv_tables_launch(ctab, c->storejobs.as<uint8_t>() + cjoff, 2, s, &nl));
+        for (const auto &f : up_singles) {
+            HIPCHK(f(s));
             ++nl;
         }
         HIPCHK(hipEventRecord(c->ev[4], s));
@@ -4478,6 +4851,16 @@ extern "C" int grkgpu_decompress_batch(grkgpu_ctx *c, grkgpu_batch_item *items, 
 extern "C" int grkgpu_batch_plan(grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
                                  grkgpu_batch_info *info) {
     return batch_impl(nullptr, items, n, p, info, true);
+}
+
+extern "C" int grkgpu_decompress_batch_convert(grkgpu_ctx *c, grkgpu_batch_item *items, const grkgpu_out_ops *ops,
+                                               uint32_t n, const grkgpu_dparams *p, grkgpu_batch_info *info) {
+    return batch_impl(c, items, n, p, info, false, true, ops);
+}
+
+extern "C" int grkgpu_batch_convert_plan(grkgpu_batch_item *items, const grkgpu_out_ops *ops, uint32_t n,
+                                         const grkgpu_dparams *p, grkgpu_batch_info *info) {
+    return batch_impl(nullptr, items, n, p, info, true, true, ops);
 }
 
 // ---------------------------------------------------------------------------
@@ -5594,6 +5977,160 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
     }
     HIPCHK(launch_upsample_ops(pl, numcomps, x0, y0, x1 - x0, y1 - y0, d, fmt, il, dst_stride, dops,
                                (hipStream_t)stream));
+    return GRKGPU_OK;
+}
+
+static_assert(sizeof(grkgpu_convert_comp) == sizeof(UpComp) && offsetof(grkgpu_convert_comp, stride) == offsetof(UpComp, stride) &&
+                  offsetof(grkgpu_convert_comp, gx0) == offsetof(UpComp, gx0) &&
+                  offsetof(grkgpu_convert_comp, zy0) == offsetof(UpComp, zy0) &&
+                  offsetof(grkgpu_convert_comp, dx) == offsetof(UpComp, dx) &&
+                  offsetof(grkgpu_convert_comp, kind) == offsetof(UpComp, raw) &&
+                  offsetof(grkgpu_convert_comp, wavelet) == offsetof(UpComp, irrev) &&
+                  offsetof(grkgpu_convert_comp, shift) == offsetof(UpComp, shift) &&
+                  offsetof(grkgpu_convert_comp, max) == offsetof(UpComp, mx),
+              "grkgpu_convert_comp is UpComp");
+static_assert(sizeof(grkgpu_convert_job) == sizeof(ConvJob) + sizeof(grkgpu_out_ops) &&
+                  offsetof(grkgpu_convert_job, ops) == sizeof(ConvJob) &&
+                  offsetof(grkgpu_convert_job, dst) == offsetof(ConvJob, dst) &&
+                  offsetof(grkgpu_convert_job, x0) == offsetof(ConvJob, X0) &&
+                  offsetof(grkgpu_convert_job, y1) == offsetof(ConvJob, y1) &&
+                  offsetof(grkgpu_convert_job, dst_stride) == offsetof(ConvJob, dstride) &&
+                  offsetof(grkgpu_convert_job, numcomps) == offsetof(ConvJob, ncomp) &&
+                  offsetof(grkgpu_convert_job, mct) == offsetof(ConvJob, mct_) &&
+                  offsetof(grkgpu_convert_job, pad_) == offsetof(ConvJob, ops),
+              "grkgpu_convert_job is ConvJob with its ops behind it");
+static_assert(GRKGPU_SRC_RAW == 1 && GRKGPU_SRC_SAMPLES == UPCOMP_FIN, "grkgpu_convert_comp.kind is UpComp::raw");
+
+// the precision and sign whose range [mn, mx] is
+static bool range_prec(int32_t mn, int32_t mx, uint32_t &prec, int32_t &sgnd) {
+    if (mx < 0 || ((uint32_t)mx & ((uint32_t)mx + 1))) return false;  // 2^q - 1
+    const uint32_t q = (uint32_t)__builtin_popcount((uint32_t)mx);
+    if (mn == 0 && q >= 1) { prec = q; sgnd = 0; return true; }
+    if (mn == -mx - 1 && q <= 30) { prec = q + 1; sgnd = 1; return true; }
+    return false;
+}
+
+extern "C" int grkgpu_convert_jobs_to(const grkgpu_convert_job *jobs, uint32_t n, uint32_t sample_fmt, uint32_t layout,
+                                      void *stream) {
+    if (sample_fmt > GRKGPU_SAMPLE_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if (layout > GRKGPU_LAYOUT_INTERLEAVED) return set_err(GRKGPU_EINVAL, "unknown layout");
+    if (!n) return GRKGPU_OK;
+    if (!jobs) return set_err(GRKGPU_EINVAL, "null argument");
+    const int32_t fmt = (int32_t)sample_fmt;
+    const bool il = layout == GRKGPU_LAYOUT_INTERLEAVED;
+    const uint32_t sb = sample_bytes(fmt);
+    ConvTables T;
+    std::vector<std::function<hipError_t(hipStream_t)>> singles[2];  // (phase 1, phase 2)
+    for (uint32_t i = 0; i < n; ++i) {
+        const grkgpu_convert_job &q = jobs[i];
+        const uint32_t nc = q.numcomps;
+        int rc = check_out_ops(&q.ops, sample_fmt);
+        if (rc) return rc;
+        if (q.ops.colour & GRKGPU_COLOUR_FORCE_RGB)
+            return set_err(GRKGPU_EUNSUPPORTED, "force-RGB is not supported in a job table");
+        if (nc < 1 || nc > 4 || q.x1 > 0x7fffffffu || q.y1 > 0x7fffffffu)
+            return set_err(GRKGPU_EINVAL, "bad arguments (1 .. 4 components)");
+        const bool empty = q.x1 <= q.x0 || q.y1 <= q.y0;
+        uint32_t prec[4], dx[4], dy[4];
+        int32_t sgnd[4];
+        bool grid1 = true;  // raw sources on one grid, no lead-in inside the rectangle: a StoreJob
+        for (uint32_t k = 0; k < nc; ++k) {
+            const grkgpu_convert_comp &u = q.comp[k];
+            if (!u.dx || !u.dy) return set_err(GRKGPU_EINVAL, "bad arguments (dx / dy must be 1 .. 255)");
+            const bool raw = u.kind == GRKGPU_SRC_RAW;
+            if (!raw && (u.kind < GRKGPU_SRC_SAMPLES || u.kind > GRKGPU_SRC_SAMPLES + GRKGPU_SAMPLE_I16))
+                return set_err(GRKGPU_EINVAL, "unknown source kind");
+            if (!range_prec(u.min, u.max, prec[k], sgnd[k]))
+                return set_err(GRKGPU_EINVAL, "min / max must be the range of a precision and sign");
+            const int32_t sf = raw ? (int32_t)SMP_I32 : (int32_t)(u.kind - GRKGPU_SRC_SAMPLES);
+            const bool ssg = sf == SMP_I8 || sf == SMP_I16;
+            if (sf != SMP_I32 && ((sgnd[k] != 0) != ssg || prec[k] > 8 * sample_bytes(sf)))
+                return set_err(GRKGPU_EINVAL, "source format does not hold the component's precision / signedness");
+            if ((uintptr_t)u.src % sample_bytes(sf)) return set_err(GRKGPU_EINVAL, "misaligned source");
+            if (u.zx0 < u.gx0 || u.zy0 < u.gy0 || u.gx0 < 0 || u.gy0 < 0)
+                return set_err(GRKGPU_EINVAL, "bad arguments (0 <= gx0 <= zx0, 0 <= gy0 <= zy0)");
+            if (u.src && !empty && (int64_t)((q.x1 - 1) / u.dx) - u.gx0 >= (int64_t)u.stride)
+                return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
+            if (u.dx == 1 && u.dy == 1 && !empty && ((int64_t)u.zx0 > (int64_t)q.x0 || (int64_t)u.zy0 > (int64_t)q.y0))
+                return set_err(GRKGPU_EINVAL, "bad arguments (a component at (1,1) has no lead-in)");
+            dx[k] = u.dx; dy[k] = u.dy;
+            grid1 = grid1 && raw && u.src && u.dx == 1 && u.dy == 1 && u.stride == q.comp[0].stride &&
+                    u.gx0 == q.comp[0].gx0 && u.gy0 == q.comp[0].gy0 && (int64_t)u.zx0 <= (int64_t)q.x0 &&
+                    (int64_t)u.zy0 <= (int64_t)q.y0;
+        }
+        if (q.mct && (!grid1 || nc < 3)) return set_err(GRKGPU_EINVAL, "an MCT needs three raw sources on one grid");
+        OutOps dops{};
+        uint32_t no = nc, oprec[GRKGPU_MAX_COMPS];
+        int32_t osgnd[GRKGPU_MAX_COMPS];
+        rc = resolve_out_ops(&q.ops, nc, prec, sgnd, dx, dy, dops, no, oprec, osgnd);
+        if (rc) return rc;
+        for (uint32_t k = 0; k < no; ++k) {
+            const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
+            if (fmt != SMP_I32 && ((osgnd[k] != 0) != sg || oprec[k] > 8 * sb))
+                return set_err(GRKGPU_EINVAL, "sample format does not hold the output precision / signedness");
+        }
+        if (empty) continue;
+        const uint32_t w = q.x1 - q.x0;
+        if ((uint64_t)q.dst_stride < (uint64_t)w * (il ? no : 1))
+            return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
+        for (uint32_t k = 0; k < (il ? 1u : no); ++k)
+            if (!q.dst[k] || (uintptr_t)q.dst[k] % sb) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+        const uint32_t ops_at = (uint32_t)T.ops.size();
+        T.ops.push_back(dops);
+        if (grid1) {
+            StoreJob j{};
+            for (uint32_t k = 0; k < nc; ++k) {
+                const grkgpu_convert_comp &u = q.comp[k];
+                j.src[k] = (const int32_t *)u.src + ((uint64_t)(q.y0 - (uint32_t)u.gy0) * u.stride + (q.x0 - (uint32_t)u.gx0));
+                j.shift[k] = u.shift; j.mn[k] = u.min; j.mx[k] = u.max;
+                j.irrev |= (u.wavelet ? 1u : 0u) << k;
+            }
+            for (uint32_t k = 0; k < (il ? 1u : no); ++k) j.dst[k] = q.dst[k];
+            j.sstride = q.comp[0].stride; j.dstride = q.dst_stride; j.w = w; j.h = q.y1 - q.y0;
+            j.ncomp = nc; j.mct = q.mct;
+            if (conv_add_store(T, fmt, il, dops, j, ops_at)) continue;
+            PlanePtrs sp{};
+            DstPlanes dp{};
+            ShiftArr sh{}, mn{}, mx{};
+            for (uint32_t k = 0; k < 4; ++k) {
+                sp.p[k] = const_cast<int32_t *>(j.src[k]); dp.p[k] = j.dst[k];
+                sh.v[k] = j.shift[k]; mn.v[k] = j.mn[k]; mx.v[k] = j.mx[k];
+            }
+            singles[0].push_back([=](hipStream_t s) {
+                return launch_mct_inv_dcshift_ops(sp, j.sstride, j.w, j.h, dp, fmt, il, j.dstride, nc, sh, mn, mx, j.mct,
+                                                  (int32_t)j.irrev, dops, s);
+            });
+            continue;
+        }
+        ConvJob j{};
+        memcpy((void *)&j, &q, sizeof(j));  // (grkgpu_convert_job is ConvJob with its ops behind it)
+        for (uint32_t k = nc; k < 4; ++k) j.c[k] = UpComp{};
+        for (uint32_t k = il ? 1 : no; k < 4; ++k) j.dst[k] = nullptr;
+        j.mct_ = 0;
+        if (conv_add_up(T, fmt, il, dops, j, ops_at)) continue;
+        UpPlan pl{};
+        DstPlanes dp{};
+        for (uint32_t k = 0; k < 4; ++k) { pl.c[k] = j.c[k]; dp.p[k] = j.dst[k]; }
+        singles[1].push_back([=](hipStream_t s) {
+            return launch_upsample_ops(pl, nc, j.X0, j.Y0, j.x1 - j.X0, j.y1 - j.Y0, dp, fmt, il, j.dstride, dops, s);
+        });
+    }
+    int rc = check_device(-1);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = conv_tables_bytes(T);
+    std::vector<uint8_t> stage(bytes);
+    void *dev = nullptr;
+    if (bytes) HIPCHK(hipMalloc(&dev, bytes));
+    hipError_t e = bytes ? conv_tables_upload(T, stage.data(), dev, s) : hipSuccess;
+    for (int phase = 1; phase <= 2; ++phase) {
+        if (e == hipSuccess) e = conv_tables_launch(T, dev, phase, s, nullptr);
+        for (size_t i = 0; e == hipSuccess && i < singles[phase - 1].size(); ++i) e = singles[phase - 1][i](s);
+    }
+    const hipError_t es = hipStreamSynchronize(s);  // the tables and their staging are freed below
+    if (dev) hipFree(dev);
+    HIPCHK(e);
+    HIPCHK(es);
     return GRKGPU_OK;
 }
 

@@ -110,7 +110,8 @@ struct StoreJob {
     uint32_t sstride, dstride, w, h;
     uint32_t ncomp;
     int32_t mct;
-    uint32_t irrev, pad_;
+    uint32_t irrev;
+    uint32_t ops;  // launch_store_jobs_ops: the job's entry of the OutOps table (launch_store_jobs does not read it)
     int32_t shift[4], mn[4], mx[4];
 };
 // threads along a row of a job: the lead run and the runs of 16 bytes
@@ -238,6 +239,50 @@ hipError_t launch_mct_inv_dcshift_ops(const PlanePtrs &src, uint32_t sstride, ui
 hipError_t launch_upsample_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
                                const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
                                const OutOps &ops, hipStream_t s);
+// The converting stores for a table of jobs in one launch (the batch decode
+// with output ops, grkgpu_convert_jobs_to).  The ops of every job are an entry
+// of a device table of OutOps uploaded with the jobs (one per item; a job that
+// converts nothing points at an all-zero entry), uniform over its workgroups.
+//
+// launch_store_jobs_ops is launch_mct_inv_dcshift_ops for a table: StoreJob
+// with its `ops` index, all jobs of a launch in one sample format, layout and
+// op class (OP_* of kernels.hip: 1 precision only, 2 sYCC, 3 eYCC, 4 CMYK).
+// sYCC / eYCC jobs have three components, CMYK jobs four (three channels
+// stored); the row threads are store_job_row_threads' either way.
+hipError_t launch_store_jobs_ops(const StoreJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg,
+                                 const OutOps *ops, int32_t fmt, bool interleaved, int op, hipStream_t s);
+// launch_upsample_ops for a table: the rectangle [X0, x1) x [Y0, y1) of the
+// reference grid from up to four UpComps (a finished one always carries its
+// format, raw = UPCOMP_FIN + f), dst at the rectangle's first pixel.
+// grkgpu_convert_job's layout up to its ops (static_assert in codec.cpp).
+struct ConvJob {
+    UpComp c[4];
+    void *dst[4];  // planar: plane k of the output channels; interleaved: dst[0]
+    uint32_t X0, Y0, x1, y1;
+    uint32_t dstride, ncomp;
+    int32_t mct_;  // (grkgpu_convert_job.mct: such a job runs as a StoreJob)
+    uint32_t ops;
+};
+// the two thread shapes, by launch_up_ops' rule: the 16-byte runs of
+// k_upsample_420 (fast) or k_upsample_any's thread per pixel
+__host__ __device__ inline bool conv_job_fast(const UpComp *c, uint32_t ncomp, int32_t fmt, int32_t col) {
+    return (fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16) && !col && ncomp == 3 && c[0].dx == 1 &&
+           c[0].dy == 1 && c[1].dx == 2 && c[2].dx == 2 && c[1].dy == c[2].dy && (c[1].dy == 1 || c[1].dy == 2);
+}
+// threads along a row of a job (sb = bytes of a destination sample) and its workgroups of 256 threads
+__host__ __device__ inline uint32_t conv_job_row_threads(uint32_t w, uint32_t sb, bool fast) {
+    if (!fast) return w;
+    const uint32_t n = 16 / sb;
+    return (uint32_t)(((uint64_t)w + n - 1) / n + 1);
+}
+inline uint64_t conv_job_wgs(const ConvJob &j, uint32_t sb, bool fast) {
+    if (j.x1 <= j.X0 || j.y1 <= j.Y0) return 0;
+    return ((uint64_t)conv_job_row_threads(j.x1 - j.X0, sb, fast) * (j.y1 - j.Y0) + 255) / 256;
+}
+// fast: every job has conv_job_fast's shape, sycc = the op class (all jobs with the sYCC conversion or all
+// without); else any shape, the colour step read from each job's OutOps
+hipError_t launch_conv_jobs(const ConvJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg,
+                            const OutOps *ops, int32_t fmt, bool interleaved, bool fast, bool sycc, hipStream_t s);
 // Inverse custom MCT (Part 2 array-based; COD MCT = 2) + offsets + clamp of one
 // tile, where launch_mct_inv_dcshift_to / _ops run for the other streams: src =
 // the components' 9/7 samples (float bit patterns), out_j = clamp(lrintf(sum

@@ -1123,23 +1123,24 @@ __device__ __forceinline__ int32_t up_sample(const UpComp &c, int32_t col, int32
 //
 // OP != 0 (OutOps): the sYCC chroma terms are computed once per source sample
 // (NS pairs), not per pixel, and replicated like the samples themselves.
-template <typename T, bool IL, int OP = 0, typename... O>
-__global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h, DstPlanes dst,
-                               uint32_t dstride, O... o) {
-    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
-    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
+//
+// upsample_420_run is thread t of row y (pc = the three components, dstp = the
+// destination planes, both uniform): the body of k_upsample_420, and of the
+// job-table kernel k_conv_jobs_420.
+template <typename T, bool IL, int OP>
+__device__ __forceinline__ void upsample_420_run(const UpComp *pc, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t t,
+                                                 uint32_t y, void *const *dstp, uint32_t dstride,
+                                                 [[maybe_unused]] const OutOps *ops) {
     typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
     constexpr int N = NarrowRun<T>::N, H = N / 2, NS = H + 1;
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (y >= h) return;
     const size_t drow = (size_t)y * dstride;
     uint32_t x0;
-    const int n = run_of<N>((uintptr_t)((T *)dst.p[0] + drow), (IL ? 3 : 1) * sizeof(T), t, w, x0);
+    const int n = run_of<N>((uintptr_t)((T *)dstp[0] + drow), (IL ? 3 : 1) * sizeof(T), t, w, x0);
     if (n <= 0) return;
     const uint32_t X = X0 + x0, Y = Y0 + y;
     int32_t v[3][N];
     {
-        const UpComp &c = p.c[0];  // (1,1): every pixel has its sample
+        const UpComp &c = pc[0];  // (1,1): every pixel has its sample
         const size_t si = (size_t)(Y - (uint32_t)c.gy0) * c.stride + (X - (uint32_t)c.gx0);
         if (!c.src) {
 #pragma unroll
@@ -1161,7 +1162,7 @@ __global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, u
     const bool odd = X & 1;
 #pragma unroll
     for (int k = 1; k < 3; ++k) {
-        const UpComp &c = p.c[k];
+        const UpComp &c = pc[k];
         const int32_t row = (int32_t)(Y >> (c.dy - 1));
         int32_t s[NS];
         if (row < c.zy0 || !c.src) {
@@ -1221,11 +1222,20 @@ __global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, u
         for (int i = 0; i < N; ++i)
 #pragma unroll
             for (int k = 0; k < 3; ++k) px[i * 3 + k] = v[k][i];
-        store_samples<T, N * 3>((T *)dst.p[0] + drow + (size_t)x0 * 3, px, n * 3);
+        store_samples<T, N * 3>((T *)dstp[0] + drow + (size_t)x0 * 3, px, n * 3);
     } else {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) store_samples<T, N>((T *)dst.p[k] + drow + x0, v[k], n);
+        for (int k = 0; k < 3; ++k) store_samples<T, N>((T *)dstp[k] + drow + x0, v[k], n);
     }
+}
+
+template <typename T, bool IL, int OP = 0, typename... O>
+__global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h, DstPlanes dst,
+                               uint32_t dstride, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (y >= h) return;
+    upsample_420_run<T, IL, OP>(p.c, X0, Y0, w, t, y, dst.p, dstride, ops_ptr(o...));
 }
 
 // any component count and any dx / dy in 1 .. 255: one thread per pixel, one store per sample.
@@ -1233,13 +1243,14 @@ __global__ void k_upsample_420(UpPlan p, uint32_t X0, uint32_t Y0, uint32_t w, u
 // sYCC (ops.sycc, three components -- the shapes k_upsample_420 does not take:
 // chroma at (1,1) fed finished samples, and the converted value of samples
 // nothing decoded) at run time.
-template <typename T, int OP = 0, typename... O>
-__global__ void k_upsample_any(UpPlan p, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
-                               DstPlanes dst, int32_t il, uint32_t dstride, O... o) {
-    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
-    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
-    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= w || y >= h) return;
+//
+// upsample_any_pixel is pixel (x, y) of the rectangle (pc = the components,
+// dstp = the destination planes, both uniform): the body of k_upsample_any,
+// and of the job-table kernel k_conv_jobs_any.
+template <typename T, int OP>
+__device__ __forceinline__ void upsample_any_pixel(const UpComp *pc, uint32_t ncomp, uint32_t X0, uint32_t Y0,
+                                                   uint32_t x, uint32_t y, void *const *dstp, int32_t il,
+                                                   uint32_t dstride, [[maybe_unused]] const OutOps *ops) {
     const uint32_t X = X0 + x, Y = Y0 + y;
     const size_t drow = (size_t)y * dstride;
     if constexpr (OP != 0) {
@@ -1247,12 +1258,12 @@ __global__ void k_upsample_any(UpPlan p, uint32_t ncomp, uint32_t X0, uint32_t Y
             int32_t v[3][1];
 #pragma unroll
             for (int k = 0; k < 3; ++k)
-                v[k][0] = up_sample<T, OP>(p.c[k], (int32_t)(X / p.c[k].dx), (int32_t)(Y / p.c[k].dy));
+                v[k][0] = up_sample<T, OP>(pc[k], (int32_t)(X / pc[k].dx), (int32_t)(Y / pc[k].dy));
             sycc_run<1>(v[0], v[1], v[2], *ops);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 prec_run<1>(v[k], ops->pc[k]);
-                T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * 3 + k : (T *)dst.p[k] + drow + x;
+                T *const d = il ? (T *)dstp[0] + drow + (size_t)x * 3 + k : (T *)dstp[k] + drow + x;
                 __builtin_nontemporal_store((T)v[k][0], d);
             }
             return;
@@ -1261,12 +1272,12 @@ __global__ void k_upsample_any(UpPlan p, uint32_t ncomp, uint32_t X0, uint32_t Y
             int32_t v[3][1];
 #pragma unroll
             for (int k = 0; k < 3; ++k)
-                v[k][0] = up_sample<T, OP>(p.c[k], (int32_t)(X / p.c[k].dx), (int32_t)(Y / p.c[k].dy));
+                v[k][0] = up_sample<T, OP>(pc[k], (int32_t)(X / pc[k].dx), (int32_t)(Y / pc[k].dy));
             eycc_run<1>(v[0], v[1], v[2], *ops);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 prec_run<1>(v[k], ops->pc[k]);
-                T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * 3 + k : (T *)dst.p[k] + drow + x;
+                T *const d = il ? (T *)dstp[0] + drow + (size_t)x * 3 + k : (T *)dstp[k] + drow + x;
                 __builtin_nontemporal_store((T)v[k][0], d);
             }
             return;
@@ -1275,36 +1286,44 @@ __global__ void k_upsample_any(UpPlan p, uint32_t ncomp, uint32_t X0, uint32_t Y
             int32_t v[4][1];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                v[k][0] = up_sample<T, OP>(p.c[k], (int32_t)(X / p.c[k].dx), (int32_t)(Y / p.c[k].dy));
+                v[k][0] = up_sample<T, OP>(pc[k], (int32_t)(X / pc[k].dx), (int32_t)(Y / pc[k].dy));
             cmyk_run<1>(v[0], v[1], v[2], v[3], *ops);
             for (uint32_t ch = 0; ch + 1 < ncomp; ++ch) {
                 int32_t a[1];
                 if (ch < 3) {
                     a[0] = ch == 0 ? v[0][0] : (ch == 1 ? v[1][0] : v[2][0]);
                 } else {
-                    const UpComp &c = p.c[ch + 1];
+                    const UpComp &c = pc[ch + 1];
                     a[0] = up_sample<T, OP>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy));
                 }
                 prec_run<1>(a, ops->pc[ch]);
-                T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * (ncomp - 1) + ch : (T *)dst.p[ch] + drow + x;
+                T *const d = il ? (T *)dstp[0] + drow + (size_t)x * (ncomp - 1) + ch : (T *)dstp[ch] + drow + x;
                 __builtin_nontemporal_store((T)a[0], d);
             }
             return;
         }
     }
     for (uint32_t k = 0; k < ncomp; ++k) {
-        const UpComp &c = p.c[k];
+        const UpComp &c = pc[k];
         if constexpr (OP == 0) {
             const int32_t v = up_sample<T>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy));
-            T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * ncomp + k : (T *)dst.p[k] + drow + x;
+            T *const d = il ? (T *)dstp[0] + drow + (size_t)x * ncomp + k : (T *)dstp[k] + drow + x;
             __builtin_nontemporal_store((T)v, d);
         } else {
             int32_t v[1] = {up_sample<T, OP>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy))};
             prec_run<1>(v, ops->pc[k]);
-            T *const d = il ? (T *)dst.p[0] + drow + (size_t)x * ncomp + k : (T *)dst.p[k] + drow + x;
+            T *const d = il ? (T *)dstp[0] + drow + (size_t)x * ncomp + k : (T *)dstp[k] + drow + x;
             __builtin_nontemporal_store((T)v[0], d);
         }
     }
+}
+template <typename T, int OP = 0, typename... O>
+__global__ void k_upsample_any(UpPlan p, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                               DstPlanes dst, int32_t il, uint32_t dstride, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w || y >= h) return;
+    upsample_any_pixel<T, OP>(p.c, ncomp, X0, Y0, x, y, dst.p, il, dstride, ops_ptr(o...));
 }
 
 // ---------------------------------------------------------------------------
@@ -2882,6 +2901,228 @@ hipError_t launch_upsample_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, u
         default: return hipErrorInvalidValue;
     }
 #undef GRK_UP
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The converting stores for a table of jobs (the batch decode with output
+// ops): k_store_jobs' workgroup-to-job search in front of the per-tile
+// kernels' bodies.  The search, the job record and the job's OutOps depend on
+// blockIdx alone, so they are uniform over the workgroup.  No LDS, no atomics,
+// nothing shared between workgroups.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t job_of_wg(const uint32_t *__restrict__ first, uint32_t njobs, uint32_t wg) {
+    uint32_t lo = 0, hi = njobs;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first[mid] <= wg) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// k_mct_inv_dcshift_pixels' body on a job: NC components read, NCH channels stored
+template <typename T, int NC, int OP>
+__device__ __forceinline__ void store_job_pixels_ops(const StoreJob &J, uint32_t y, uint32_t t, const ShiftArr &shift,
+                                                     const ShiftArr &minv, const ShiftArr &maxv, int32_t mct,
+                                                     int32_t irrev, const OutOps &ops) {
+    constexpr int N = NarrowRun<T>::N;
+    constexpr int NCH = OP == OP_CMYK ? NC - 1 : NC;
+    T *const drow = (T *)J.dst[0] + (size_t)y * J.dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)drow, NCH * sizeof(T), t, J.w, x0);
+    if (n <= 0) return;
+    const size_t si = (size_t)y * J.sstride + x0;
+    int32_t v[NC][N];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) load_run<N>(J.src[k] + si, n, v[k]);
+    if (mct) inv_mct_run<N>(v[0], v[1], v[2], irrev, shift, minv, maxv);
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+        if (!mct || k >= 3) inv_plain_run<N>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+    if constexpr (op_ycc(OP)) ycc_run<OP, N>(v[0], v[1], v[2], ops);
+    if constexpr (OP == OP_CMYK) cmyk_run<N>(v[0], v[1], v[2], v[3], ops);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) prec_run<N>(v[chan_comp(OP, c)], ops.pc[c]);
+    int32_t px[N * NCH];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) px[i * NCH + c] = v[chan_comp(OP, c)][i];
+    store_samples<T, N * NCH>(drow + (size_t)x0 * NCH, px, n * NCH);
+}
+
+// launch_mct_inv_dcshift_ops for a table: OP_SYCC / OP_EYCC jobs have three
+// components, OP_CMYK jobs four
+template <typename T, bool IL, int OP>
+__global__ void __launch_bounds__(256) k_store_jobs_ops(const StoreJob *__restrict__ jobs,
+                                                        const uint32_t *__restrict__ first, uint32_t njobs,
+                                                        const OutOps *__restrict__ opstab) {
+    constexpr int N = NarrowRun<T>::N;
+    const uint32_t wg = blockIdx.x;
+    const uint32_t lo = job_of_wg(first, njobs, wg);
+    const StoreJob J = jobs[lo];
+    const OutOps &ops = opstab[J.ops];
+    const uint32_t ncomp = op_ycc(OP) ? 3u : (OP == OP_CMYK ? 4u : J.ncomp), tw = J.w, th = J.h;
+    const int32_t mct = J.mct && ncomp >= 3, irrev = (int32_t)J.irrev;
+    ShiftArr shift{}, minv{}, maxv{};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { shift.v[k] = J.shift[k]; minv.v[k] = J.mn[k]; maxv.v[k] = J.mx[k]; }
+    const uint32_t rpr = store_job_row_threads(tw, ncomp, (uint32_t)sizeof(T), IL);
+    const uint32_t g = (wg - first[lo]) * 256u + threadIdx.x;
+    const uint32_t y = g / rpr, t = g - y * rpr;
+    if (y >= th) return;
+    if constexpr (IL) {
+        if constexpr (op_ycc(OP)) { store_job_pixels_ops<T, 3, OP>(J, y, t, shift, minv, maxv, mct, irrev, ops); return; }
+        if constexpr (OP == OP_CMYK) { store_job_pixels_ops<T, 4, OP>(J, y, t, shift, minv, maxv, mct, irrev, ops); return; }
+        if constexpr (OP == OP_PREC) {
+            if (ncomp == 3) { store_job_pixels_ops<T, 3, OP>(J, y, t, shift, minv, maxv, mct, irrev, ops); return; }
+            if (ncomp == 4) { store_job_pixels_ops<T, 4, OP>(J, y, t, shift, minv, maxv, mct, irrev, ops); return; }
+            if (ncomp == 2) {  // a thread per pixel, a store per sample
+                const size_t si = (size_t)y * J.sstride + t;
+                T *const d = (T *)J.dst[0] + (size_t)y * J.dstride + (size_t)t * 2;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    int32_t a[1] = {J.src[k][si]};
+                    inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+                    prec_run<1>(a, ops.pc[k]);
+                    __builtin_nontemporal_store((T)a[0], d + k);
+                }
+                return;
+            }
+        }
+    }
+    // planar (one interleaved component is a plane): k_mct_inv_dcshift_planar's body
+    const size_t drow = (size_t)y * J.dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)((T *)J.dst[0] + drow), sizeof(T), t, tw, x0);
+    if (n <= 0) return;
+    const size_t si = (size_t)y * J.sstride + x0, di = drow + x0;
+    if constexpr (OP == OP_CMYK) {
+        PlanePtrs sp{};
+        DstPlanes dp{};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { sp.p[k] = const_cast<int32_t *>(J.src[k]); dp.p[k] = J.dst[k]; }
+        cmyk_planar_run<T>(sp, si, dp, di, n, shift, minv, maxv, mct, irrev, ops);
+        return;
+    }
+    if (op_ycc(OP) || mct) {
+        int32_t a[N], b[N], c[N];
+        load_run<N>(J.src[0] + si, n, a);
+        load_run<N>(J.src[1] + si, n, b);
+        load_run<N>(J.src[2] + si, n, c);
+        if (!op_ycc(OP) || mct) {
+            inv_mct_run<N>(a, b, c, irrev, shift, minv, maxv);
+        } else {
+            inv_plain_run<N>(a, irrev & 1, shift.v[0], minv.v[0], maxv.v[0]);
+            inv_plain_run<N>(b, (irrev >> 1) & 1, shift.v[1], minv.v[1], maxv.v[1]);
+            inv_plain_run<N>(c, (irrev >> 2) & 1, shift.v[2], minv.v[2], maxv.v[2]);
+        }
+        if constexpr (op_ycc(OP)) ycc_run<OP, N>(a, b, c, ops);
+        prec_run<N>(a, ops.pc[0]);
+        prec_run<N>(b, ops.pc[1]);
+        prec_run<N>(c, ops.pc[2]);
+        store_samples<T, N>((T *)J.dst[0] + di, a, n);
+        store_samples<T, N>((T *)J.dst[1] + di, b, n);
+        store_samples<T, N>((T *)J.dst[2] + di, c, n);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if ((uint32_t)k >= ncomp || ((op_ycc(OP) || mct) && k < 3)) continue;
+        int32_t a[N];
+        load_run<N>(J.src[k] + si, n, a);
+        inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        prec_run<N>(a, ops.pc[k]);
+        store_samples<T, N>((T *)J.dst[k] + di, a, n);
+    }
+}
+
+hipError_t launch_store_jobs_ops(const StoreJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg,
+                                 const OutOps *ops, int32_t fmt, bool interleaved, int op, hipStream_t s) {
+    if (!njobs || !nwg) return hipSuccess;
+    if (op < OP_PREC || op > OP_CMYK) return hipErrorInvalidValue;
+    if (op != OP_PREC && fmt != SMP_I32 && fmt != SMP_U8 && fmt != SMP_U16) return hipErrorInvalidValue;
+#define GRK_JO(T, IL, OP) \
+    hipLaunchKernelGGL((k_store_jobs_ops<T, IL, OP>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs, ops)
+#define GRK_JP(T)                                                          \
+    do {                                                                   \
+        if (interleaved) GRK_JO(T, true, OP_PREC); else GRK_JO(T, false, OP_PREC); \
+    } while (0)
+#define GRK_JC(T)                                                                          \
+    do {                                                                                   \
+        if (op == OP_PREC) GRK_JP(T);                                                      \
+        else if (op == OP_SYCC) { if (interleaved) GRK_JO(T, true, OP_SYCC); else GRK_JO(T, false, OP_SYCC); } \
+        else if (op == OP_EYCC) { if (interleaved) GRK_JO(T, true, OP_EYCC); else GRK_JO(T, false, OP_EYCC); } \
+        else { if (interleaved) GRK_JO(T, true, OP_CMYK); else GRK_JO(T, false, OP_CMYK); }  \
+    } while (0)
+    switch (fmt) {
+        case SMP_I32: GRK_JC(int32_t); break;
+        case SMP_U8: GRK_JC(uint8_t); break;
+        case SMP_I8: GRK_JP(int8_t); break;
+        case SMP_U16: GRK_JC(uint16_t); break;
+        case SMP_I16: GRK_JP(int16_t); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_JC
+#undef GRK_JP
+#undef GRK_JO
+    return hipGetLastError();
+}
+
+// launch_upsample_ops for a table, in its two thread shapes.  The job stays
+// in memory: its components and destinations are indexed at run time.
+template <typename T, bool IL, int OP>
+__global__ void __launch_bounds__(256) k_conv_jobs_420(const ConvJob *__restrict__ jobs,
+                                                       const uint32_t *__restrict__ first, uint32_t njobs,
+                                                       const OutOps *__restrict__ opstab) {
+    const uint32_t wg = blockIdx.x;
+    const uint32_t lo = job_of_wg(first, njobs, wg);
+    const ConvJob &J = jobs[lo];
+    const uint32_t w = J.x1 - J.X0, h = J.y1 - J.Y0;
+    const uint32_t rpr = conv_job_row_threads(w, (uint32_t)sizeof(T), true);
+    const uint32_t g = (wg - first[lo]) * 256u + threadIdx.x;
+    const uint32_t y = g / rpr, t = g - y * rpr;
+    if (y >= h) return;
+    upsample_420_run<T, IL, OP>(J.c, J.X0, J.Y0, w, t, y, J.dst, J.dstride, opstab + J.ops);
+}
+template <typename T>
+__global__ void __launch_bounds__(256) k_conv_jobs_any(const ConvJob *__restrict__ jobs,
+                                                       const uint32_t *__restrict__ first, uint32_t njobs,
+                                                       const OutOps *__restrict__ opstab, int32_t il) {
+    const uint32_t wg = blockIdx.x;
+    const uint32_t lo = job_of_wg(first, njobs, wg);
+    const ConvJob &J = jobs[lo];
+    const uint32_t w = J.x1 - J.X0, h = J.y1 - J.Y0;
+    const uint32_t g = (wg - first[lo]) * 256u + threadIdx.x;
+    const uint32_t y = g / w, x = g - y * w;
+    if (y >= h) return;
+    upsample_any_pixel<T, OP_PREC>(J.c, J.ncomp, J.X0, J.Y0, x, y, J.dst, il, J.dstride, opstab + J.ops);
+}
+
+hipError_t launch_conv_jobs(const ConvJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg,
+                            const OutOps *ops, int32_t fmt, bool interleaved, bool fast, bool sycc, hipStream_t s) {
+    if (!njobs || !nwg) return hipSuccess;
+    if (fast && fmt != SMP_I32 && fmt != SMP_U8 && fmt != SMP_U16) return hipErrorInvalidValue;
+#define GRK_C420(T, IL, OP) \
+    hipLaunchKernelGGL((k_conv_jobs_420<T, IL, OP>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs, ops)
+#define GRK_CANY(T) \
+    hipLaunchKernelGGL(k_conv_jobs_any<T>, dim3(nwg), dim3(256), 0, s, jobs, first, njobs, ops, interleaved ? 1 : 0)
+#define GRK_CJ(T)                                                                                        \
+    do {                                                                                                 \
+        if (!fast) GRK_CANY(T);                                                                          \
+        else if (interleaved) { if (sycc) GRK_C420(T, true, OP_SYCC); else GRK_C420(T, true, OP_PREC); } \
+        else { if (sycc) GRK_C420(T, false, OP_SYCC); else GRK_C420(T, false, OP_PREC); }                \
+    } while (0)
+    switch (fmt) {
+        case SMP_I32: GRK_CJ(int32_t); break;
+        case SMP_U8: GRK_CJ(uint8_t); break;
+        case SMP_I8: GRK_CANY(int8_t); break;
+        case SMP_U16: GRK_CJ(uint16_t); break;
+        case SMP_I16: GRK_CANY(int16_t); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef GRK_CJ
+#undef GRK_CANY
+#undef GRK_C420
     return hipGetLastError();
 }
 

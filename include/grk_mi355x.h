@@ -780,6 +780,39 @@ typedef struct { uint32_t n_ok, n_blocks, n_store_jobs, n_launches; } grkgpu_bat
 int grkgpu_decompress_batch(grkgpu_ctx *ctx, grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
                             grkgpu_batch_info *info);
 int grkgpu_batch_plan(grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p, grkgpu_batch_info *info);
+/* grkgpu_decompress_batch with the converting and upsampling last store: item i
+ * is grkgpu_decompress_convert(ctx, cs, len, p, 0, 0xffffffff, &img, &out,
+ * &ops[i]) and receives that call's samples and img descriptor bit for bit
+ * (output channels, precision and sign, dx = dy = 1 where that call reports
+ * them).  ops is NULL (no item converts) or has n entries.  Beyond what
+ * grkgpu_decompress_batch takes, an item may be a stream with subsampled
+ * components -- on their own grids (one plane per component), or with
+ * GRKGPU_LAYOUT_UPSAMPLE in out.layout on the image grid -- and may ask for
+ * GRKGPU_COLOUR_SYCC (which implies the upsampled output), _EYCC, _CMYK and an
+ * output precision of 1 .. 16 bits, clipped or scaled; cp_reduce and cp_layer
+ * follow the single call's rules per item (cp_reduce with SYCC or the
+ * upsample flag on a subsampled stream is that item's GRKGPU_EINVAL).  The
+ * last store is then two table phases in stream order behind the zero fills:
+ * the stores on the components' own grids (to the output, or to staging
+ * planes behind the output staging), then the upsampling / converting store
+ * (grkgpu_convert_jobs_to's kernels), one launch per (phase, thread shape,
+ * sample format, layout, op class) present, so 64 copies of a 4:2:0 stream
+ * take the launches of one.  Samples nothing decoded (a reduced decode's zero
+ * margin, tiles a cut stream never reached) are converted like any other, by
+ * jobs with null sources.  Items of more than four components go through the
+ * single call's per-tile launches.
+ * Refused per item with GRKGPU_EUNSUPPORTED: GRKGPU_COLOUR_FORCE_RGB and a
+ * custom-MCT stream; GRKGPU_COLOUR_AUTO / _AUTO_RGB and bad ops are
+ * GRKGPU_EINVAL as in the single call; all on the host before the first
+ * device call.  The call-level rules, the failing items' untouched
+ * destinations and info are grkgpu_decompress_batch's (n_store_jobs counts
+ * the records of every table).  With ops == NULL, no subsampled item and no
+ * upsample flag the call is grkgpu_decompress_batch, launch for launch.
+ * grkgpu_batch_convert_plan is the host half alone. */
+int grkgpu_decompress_batch_convert(grkgpu_ctx *ctx, grkgpu_batch_item *items, const grkgpu_out_ops *ops,
+                                    uint32_t n, const grkgpu_dparams *p, grkgpu_batch_info *info);
+int grkgpu_batch_convert_plan(grkgpu_batch_item *items, const grkgpu_out_ops *ops, uint32_t n,
+                              const grkgpu_dparams *p, grkgpu_batch_info *info);
 /* Encode a batch of images in one launch set: item i is the whole-image encode
  * grkgpu_compress_ex(ctx, &img, p, &in, 0, 0xffffffff, GRKGPU_PART_ALL, ...)
  * and receives that call's codestream byte for byte, but the n items share
@@ -1074,6 +1107,56 @@ int grkgpu_convert_to(const void *const *src, const uint32_t *src_stride, uint32
                       const uint32_t *dx, const uint32_t *dy, const uint32_t *prec, const int32_t *sgnd,
                       uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
                       const grkgpu_out_planes *dst, uint32_t dst_stride, const grkgpu_out_ops *ops, void *stream);
+/* grkgpu_convert_to / grkgpu_upsample_to for a table of n jobs (the last two
+ * kernels of grkgpu_decompress_batch_convert on their own; the counterpart of
+ * grkgpu_mct_inv_dcshift_jobs_to): jobs is a host array, every job storing
+ * the rectangle [x0, x1) x [y0, y1) of the reference grid (x1 <= x0 or
+ * y1 <= y0: nothing) in the sample format and layout given, dst[] (device) at
+ * the rectangle's first pixel -- one plane per output channel, or dst[0]
+ * interleaved -- rows dst_stride samples apart.  numcomps 1 .. 4 components,
+ * pixel (X, Y) taking component k's sample at column floor(X / dx), row
+ * floor(Y / dy) of its grid:
+ *   src     device memory holding the grid from column gx0, row gy0 on, rows
+ *           `stride` elements apart; NULL: zeros
+ *   kind    GRKGPU_SRC_RAW: an int32 tile buffer (wavelet = 1: 9/7 float bit
+ *           patterns), finished on the way by shift and the clamp to
+ *           [min, max] as in grkgpu_store_job; GRKGPU_SRC_SAMPLES +
+ *           GRKGPU_SAMPLE_*: finished samples of that format
+ *   zx0/zy0 columns left of zx0 and rows above zy0 read as zero (the
+ *           reference's lead-in: ceil(origin / dx) of the image the rectangle
+ *           is cut from); zx0 >= gx0, zy0 >= gy0
+ *   min/max the component's range, that of a precision and sign (ops and the
+ *           destination format are checked against it)
+ * mct != 0 (inverse RCT / ICT by component 0's wavelet, on components 0 .. 2)
+ * needs raw sources on one grid: every component at dx = dy = 1 with one
+ * stride and origin and no lead-in inside the rectangle; such jobs, with or
+ * without an MCT, run the store of grkgpu_mct_inv_dcshift_jobs_to with the
+ * ops in it, every other job the upsampling store, as 16-byte runs for three
+ * components at (1,1), (2,dy), (2,dy) (dy 1 or 2; U8 / U16 / I32, no eYCC /
+ * CMYK) and a thread per pixel otherwise.  ops as in grkgpu_convert_to
+ * (GRKGPU_COLOUR_FORCE_RGB: GRKGPU_EUNSUPPORTED); CMYK stores numcomps - 1
+ * channels.  One launch per (store, thread shape, op class) present.  The
+ * tables are copied to the device and freed after the launches, so the call
+ * synchronises `stream`. */
+enum { GRKGPU_SRC_RAW = 1, GRKGPU_SRC_SAMPLES = 2 };
+typedef struct {
+    const void *src;
+    uint32_t stride;
+    int32_t gx0, gy0, zx0, zy0;
+    uint8_t dx, dy, kind, wavelet;
+    int32_t shift, min, max;
+} grkgpu_convert_comp;
+typedef struct {
+    grkgpu_convert_comp comp[4];
+    void *dst[4];
+    uint32_t x0, y0, x1, y1;
+    uint32_t dst_stride, numcomps;
+    int32_t mct;
+    uint32_t pad_;
+    grkgpu_out_ops ops;
+} grkgpu_convert_job;
+int grkgpu_convert_jobs_to(const grkgpu_convert_job *jobs, uint32_t n, uint32_t sample_fmt, uint32_t layout,
+                           void *stream);
 /* grkgpu_dcshift_mct_fwd out of place, from the sample format and layout of
  * src (the first kernel of grkgpu_compress_ex on its own; the counterpart of
  * grkgpu_mct_inv_dcshift_to): src->planes are device pointers (on_device, row0
