@@ -694,6 +694,24 @@ def _batch_items(bufs):
     return items, keep
 
 
+def _per_item(v, n, name, noun="stream", seq=(list, tuple)):
+    """One value for all n items of a batch, or a list (`seq`: the types that count as one) with one entry per item."""
+    if isinstance(v, seq):
+        if len(v) != n:
+            raise GrkGpuError("%s: one entry per %s (got %d for %d)" % (name, noun, len(v), n))
+        return list(v)
+    return [v] * n
+
+
+def _plan_result(rc, info, items, n, img=True):
+    """The dict the plan_* calls return: the info's fields, rc / error, the items' statuses (and geometry)."""
+    res = info.as_dict()
+    res.update(rc=rc, error=lib().grkgpu_last_error().decode() if rc else "", status=[items[i].status for i in range(n)])
+    if img:
+        res["img"] = [ImageDesc.from_buffer_copy(items[i].img) for i in range(n)]
+    return res
+
+
 def plan_batch(bufs, reduce=0, layers=0):
     """grkgpu_batch_plan: the host half of Codec.decompress_batch -- no device
     call.  Returns a dict: "status" (one grkgpu code per stream, 0 = it would
@@ -705,27 +723,14 @@ def plan_batch(bufs, reduce=0, layers=0):
     info = BatchInfo()
     dp = DParams(cp_reduce=reduce, cp_layer=layers)
     rc = lib().grkgpu_batch_plan(items, len(bufs), ctypes.byref(dp), ctypes.byref(info))
-    res = info.as_dict()
-    res.update(rc=rc, error=lib().grkgpu_last_error().decode() if rc else "",
-               status=[items[i].status for i in range(len(bufs))],
-               img=[ImageDesc.from_buffer_copy(items[i].img) for i in range(len(bufs))])
-    return res
-
-
-def _per_stream(v, n, name):
-    """One value for all n streams of a batch decode, or a list / tuple with one entry per stream."""
-    if isinstance(v, (list, tuple)):
-        if len(v) != n:
-            raise GrkGpuError("%s: one entry per stream (got %d for %d)" % (name, len(v), n))
-        return list(v)
-    return [v] * n
+    return _plan_result(rc, info, items, len(bufs))
 
 
 def _batch_ops(n, colour, out_prec, prec_mode):
     """The grkgpu_out_ops array of a batch (None: no item converts) and the
     per-item colour / out_prec lists; each argument one value or a list."""
-    colours, precs = _per_stream(colour, n, "colour"), _per_stream(out_prec, n, "out_prec")
-    modes = _per_stream(prec_mode, n, "prec_mode")
+    colours, precs = _per_item(colour, n, "colour"), _per_item(out_prec, n, "out_prec")
+    modes = _per_item(prec_mode, n, "prec_mode")
     # (an OutOps in a colour slot goes to the library as it is: what the keywords cannot say, for its refusals)
     each = [colours[i] if isinstance(colours[i], OutOps) else _out_ops(colours[i], precs[i], modes[i])
             for i in range(n)]
@@ -756,8 +761,8 @@ def plan_batch_convert(bufs, dtype=None, layout="chw", reduce=0, layers=0, upsam
                 arr[i] = o
     else:
         arr, _, _ = _batch_ops(n, colour, out_prec, prec_mode)
-    dtypes, layouts = _per_stream(dtype, n, "dtype"), _per_stream(layout, n, "layout")
-    ups = _per_stream(upsample, n, "upsample")
+    dtypes, layouts = _per_item(dtype, n, "dtype"), _per_item(layout, n, "layout")
+    ups = _per_item(upsample, n, "upsample")
     for i in range(n):
         _layout_shape((1, 1, 1), layouts[i])
         items[i].out.sample_fmt = _out_format(dtypes[i])[1]
@@ -765,11 +770,7 @@ def plan_batch_convert(bufs, dtype=None, layout="chw", reduce=0, layers=0, upsam
     info = BatchInfo()
     dp = DParams(cp_reduce=reduce, cp_layer=layers)
     rc = lib().grkgpu_batch_convert_plan(items, arr, n, ctypes.byref(dp), ctypes.byref(info))
-    res = info.as_dict()
-    res.update(rc=rc, error=lib().grkgpu_last_error().decode() if rc else "",
-               status=[items[i].status for i in range(n)],
-               img=[ImageDesc.from_buffer_copy(items[i].img) for i in range(n)])
-    return res
+    return _plan_result(rc, info, items, n)
 
 
 def convert_jobs_to(jobs, layout="chw"):
@@ -846,15 +847,6 @@ def convert_jobs_to(jobs, layout="chw"):
     return [q["dst"] for q in jobs]
 
 
-def _per_item(v, n, name):
-    """One value for all n items of a batch, or a list with one entry per item."""
-    if isinstance(v, list):
-        if len(v) != n:
-            raise GrkGpuError("%s: one entry per image (got %d for %d)" % (name, len(v), n))
-        return list(v)
-    return [v] * n
-
-
 def plan_compress_batch(descs):
     """grkgpu_compress_batch_plan: the host half of Codec.compress_batch -- no
     device call, no samples.  descs: one dict per image with "shape" (c, h, w)
@@ -886,10 +878,7 @@ def plan_compress_batch(descs):
         items[i].in_.sample_fmt = q.get("fmt", SAMPLE_I32)
     info = CBatchInfo()
     rc = lib().grkgpu_compress_batch_plan(items, n, ctypes.byref(info))
-    res = info.as_dict()
-    res.update(rc=rc, error=lib().grkgpu_last_error().decode() if rc else "",
-               status=[items[i].status for i in range(n)])
-    return res
+    return _plan_result(rc, info, items, n, img=False)
 
 
 def _read_mct(buf):
@@ -1172,8 +1161,9 @@ class Codec:
             raise GrkGpuError("errors must be 'raise' or 'return'")
         imgs = list(imgs)
         n = len(imgs)
-        precs, pars, offs = _per_item(prec, n, "prec"), _per_item(params, n, "params"), _per_item(offset, n, "offset")
-        sgnds, layouts = _per_item(sgnd, n, "sgnd"), _per_item(layout, n, "layout")
+        each = lambda v, name: _per_item(v, n, name, "image", list)  # noqa: E731  (a tuple is one value: offset)
+        precs, pars, offs = each(prec, "prec"), each(params, "params"), each(offset, "offset")
+        sgnds, layouts = each(sgnd, "sgnd"), each(layout, "layout")
         items = (CBatchItem * max(n, 1))()
         keep = []
         default = CParams.make()
@@ -1513,134 +1503,22 @@ class Codec:
             _check(lib().grkgpu_decompress(self._ctx, bp, bn, None, ptrs, 1 if on_dev else 0))
         return out
 
-    def decompress_batch(self, bufs, dtype=None, layout="chw", device_out=False, out=None, reduce=0, layers=0,
-                         stack=False, errors="raise"):
-        """Decode a list of .j2k codestreams in one launch set
-        (grkgpu_decompress_batch) -> a list with one array / cuda tensor per
-        stream, each what decompress(buf, dtype=, layout=, device_out=, out=,
-        reduce=, layers=) returns, bit for bit.  dtype, layout and device_out
-        apply to every stream, or are lists with one entry per stream; out is
-        None or a list of outputs (entries may be None).  Streams with
-        subsampled components or a custom MCT are refused item by item, as is
-        anything decompress refuses; the other streams are still decoded and a
-        failing stream's `out` is left untouched.  errors="raise": raise
-        GrkGpuError naming the first failing item after the call;
-        errors="return": the GrkGpuError in that item's slot.  stack=True: the
-        streams must decode to one shape; the result is one (n, ...) array or
-        tensor whose slices are the items' destinations, so a host result
-        leaves the device in one copy.  self.batch_info holds the call's
-        grkgpu_batch_info afterwards."""
+    def _decompress_batch(self, convert, bufs, dtype, layout, device_out, out, reduce, layers, stack, errors,
+                          upsample=False, colour=None, out_prec=None, prec_mode="clip"):
+        """decompress_batch (convert=False: grkgpu_decompress_batch, a
+        subsampled stream gets no destination and the call refuses it) and
+        decompress_batch_convert (grkgpu_decompress_batch_convert with its
+        ops, LAYOUT_UPSAMPLE and the shapes colour / out_prec leave; a
+        subsampled stream that is not upsampled gets host planes), from the
+        argument checks to the list or stacked tensor they return."""
         if errors not in ("raise", "return"):
             raise GrkGpuError("errors must be 'raise' or 'return'")
         bufs = list(bufs)
         n = len(bufs)
-
-        def per_item(v, name):
-            if isinstance(v, (list, tuple)):
-                if len(v) != n:
-                    raise GrkGpuError("%s: one entry per stream (got %d for %d)" % (name, len(v), n))
-                return list(v)
-            return [v] * n
-        dtypes, layouts, devs = per_item(dtype, "dtype"), per_item(layout, "layout"), per_item(device_out, "device_out")
-        outs = per_item(None, "out") if out is None else per_item(list(out), "out")
-        if layers < 0 or reduce < 0:
-            raise GrkGpuError("reduce and layers must be >= 0")
-        if stack and out is not None:
-            raise GrkGpuError("stack=True allocates the output itself")
-        items, keep = _batch_items(bufs)
-        cd = lambda v, s: -(-v // s)  # noqa: E731
-        R = 1 << reduce
-        shapes, any_dev = [None] * n, False
-        for i, buf in enumerate(bufs):
-            # geometry from the main header alone (the library checks everything
-            # else); a stream whose header does not read gets no destination and
-            # fails inside the call with its own code
-            d = ImageDesc()
-            hdr_ok = lib().grkgpu_read_header(ctypes.c_void_p(items[i].cs), items[i].len, ctypes.byref(d)) == 0
-            dt, fmt = _out_format(dtypes[i])
-            o = outs[i]
-            if o is not None and _out_dtype(o) is not None:
-                if dtypes[i] is not None and _out_dtype(o) != dt:
-                    raise GrkGpuError("item %d: out holds %s samples, dtype asks for %s"
-                                      % (i, _out_dtype(o).name, dt.name))
-                dt, fmt = _out_format(_out_dtype(o))
-            _layout_shape((1, 1, 1), layouts[i])
-            items[i].out.sample_fmt, items[i].out.layout = fmt, _LAYOUTS[layouts[i]]
-            if not hdr_ok:
-                continue
-            c = d.numcomps
-            if any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)):
-                continue  # refused by the call
-            shp = (c, cd(d.y1 - d.y0, R), cd(d.x1 - d.x0, R))
-            shapes[i] = (_layout_shape(shp, layouts[i]), dt)
-            if stack:
-                continue
-            if o is not None:
-                on_dev = _check_out(o, shp, self.device, dt, layouts[i])
-            else:
-                on_dev = bool(devs[i])
-                if on_dev:
-                    o = _torch().empty(shapes[i][0], dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
-                else:
-                    o = np.empty(shapes[i][0], dtype=dt)
-                outs[i] = o
-            any_dev = any_dev or on_dev
-            items[i].out = self._out_planes(o, c, fmt, layouts[i], on_dev)
-        stacked = None
-        if stack and n:
-            if any(sh is None for sh in shapes) or any(sh != shapes[0] for sh in shapes) or len(set(devs)) != 1:
-                raise GrkGpuError("stack=True needs streams of one shape, dtype, layout and destination")
-            shp, dt = shapes[0]
-            any_dev = bool(devs[0])
-            if any_dev:
-                stacked = _torch().empty((n,) + tuple(shp), dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
-            else:
-                stacked = np.empty((n,) + tuple(shp), dtype=dt)
-            c = shp[0] if layouts[0] == "chw" else shp[2]
-            for i in range(n):
-                outs[i] = stacked[i]
-                items[i].out = self._out_planes(stacked[i], c, _out_format(dt)[1], layouts[i], any_dev)
-        if any_dev:
-            lib().grkgpu_set_stream(self._ctx, _stream_handle(self.device))
-        info = BatchInfo()
-        dp = DParams(cp_reduce=reduce, cp_layer=layers)
-        rc = lib().grkgpu_decompress_batch(self._ctx, items, n, ctypes.byref(dp), ctypes.byref(info))
-        self.batch_info = info.as_dict()
-        msg = lib().grkgpu_last_error().decode() if rc else ""
-        failed = [i for i in range(n) if items[i].status]
-        if rc and (errors == "raise" or not failed):
-            raise GrkGpuError("grkgpu error %d: %s" % (rc, msg))
-        if stacked is not None:
-            return stacked
-        for i in failed:
-            outs[i] = GrkGpuError("grkgpu error %d: item %d failed%s" % (items[i].status, i,
-                                                                         msg[msg.index(":"):] if failed[0] == i else ""))
-        return outs
-
-    def decompress_batch_convert(self, bufs, dtype=None, layout="chw", device_out=False, out=None, reduce=0, layers=0,
-                                 upsample=False, colour=None, out_prec=None, prec_mode="clip", stack=False,
-                                 errors="raise"):
-        """decompress_batch with decompress's output steps
-        (grkgpu_decompress_batch_convert): item i is what decompress(buf,
-        dtype=, layout=, device_out=, out=, reduce=, layers=, upsample=,
-        colour=, out_prec=, prec_mode=) returns, bit for bit -- a list of host
-        planes for a stream with subsampled components that is not upsampled,
-        an array or cuda tensor otherwise -- so a list of 4:2:0 or 12-bit
-        streams decodes straight to (h,w,3) uint8 RGB in one launch set.
-        upsample, colour, out_prec and prec_mode are one value for all streams
-        or a list with one entry per stream, like dtype / layout / device_out.
-        force-RGB and custom-MCT streams are refused item by item.  stack,
-        errors and self.batch_info as decompress_batch: with upsample / colour,
-        stack=True gives the (n, h, w, 3) tensor a loader wants."""
-        if errors not in ("raise", "return"):
-            raise GrkGpuError("errors must be 'raise' or 'return'")
-        bufs = list(bufs)
-        n = len(bufs)
-
-        dtypes, layouts = _per_stream(dtype, n, "dtype"), _per_stream(layout, n, "layout")
-        devs, ups = _per_stream(device_out, n, "device_out"), _per_stream(upsample, n, "upsample")
-        ops, colours, precs = _batch_ops(n, colour, out_prec, prec_mode)
-        outs = [None] * n if out is None else _per_stream(list(out), n, "out")
+        dtypes, layouts = _per_item(dtype, n, "dtype"), _per_item(layout, n, "layout")
+        devs, ups = _per_item(device_out, n, "device_out"), _per_item(upsample, n, "upsample")
+        ops, colours, precs = _batch_ops(n, colour, out_prec, prec_mode) if convert else (None, [None] * n, [None] * n)
+        outs = [None] * n if out is None else _per_item(list(out), n, "out")
         if layers < 0 or reduce < 0:
             raise GrkGpuError("reduce and layers must be >= 0")
         if stack and out is not None:
@@ -1669,6 +1547,8 @@ class Codec:
             c = d.numcomps
             grid = [(d.dx[k], d.dy[k]) for k in range(c)]
             subsampled = any(g != (1, 1) for g in grid)
+            if subsampled and not convert:
+                continue  # refused by the call
             chans = _out_channels(colours[i], False, [d.prec[k] for k in range(c)], [d.sgnd[k] for k in range(c)],
                                   precs[i])
             if len(chans) != c:  # (CMYK: the black ink's plane goes; one grid either way)
@@ -1721,7 +1601,10 @@ class Codec:
             lib().grkgpu_set_stream(self._ctx, _stream_handle(self.device))
         info = BatchInfo()
         dp = DParams(cp_reduce=reduce, cp_layer=layers)
-        rc = lib().grkgpu_decompress_batch_convert(self._ctx, items, ops, n, ctypes.byref(dp), ctypes.byref(info))
+        if convert:
+            rc = lib().grkgpu_decompress_batch_convert(self._ctx, items, ops, n, ctypes.byref(dp), ctypes.byref(info))
+        else:
+            rc = lib().grkgpu_decompress_batch(self._ctx, items, n, ctypes.byref(dp), ctypes.byref(info))
         self.batch_info = info.as_dict()
         msg = lib().grkgpu_last_error().decode() if rc else ""
         failed = [i for i in range(n) if items[i].status]
@@ -1733,6 +1616,43 @@ class Codec:
             outs[i] = GrkGpuError("grkgpu error %d: item %d failed%s" % (items[i].status, i,
                                                                          msg[msg.index(":"):] if failed[0] == i else ""))
         return outs
+
+    def decompress_batch(self, bufs, dtype=None, layout="chw", device_out=False, out=None, reduce=0, layers=0,
+                         stack=False, errors="raise"):
+        """Decode a list of .j2k codestreams in one launch set
+        (grkgpu_decompress_batch) -> a list with one array / cuda tensor per
+        stream, each what decompress(buf, dtype=, layout=, device_out=, out=,
+        reduce=, layers=) returns, bit for bit.  dtype, layout and device_out
+        apply to every stream, or are lists with one entry per stream; out is
+        None or a list of outputs (entries may be None).  Streams with
+        subsampled components or a custom MCT are refused item by item, as is
+        anything decompress refuses; the other streams are still decoded and a
+        failing stream's `out` is left untouched.  errors="raise": raise
+        GrkGpuError naming the first failing item after the call;
+        errors="return": the GrkGpuError in that item's slot.  stack=True: the
+        streams must decode to one shape; the result is one (n, ...) array or
+        tensor whose slices are the items' destinations, so a host result
+        leaves the device in one copy.  self.batch_info holds the call's
+        grkgpu_batch_info afterwards."""
+        return self._decompress_batch(False, bufs, dtype, layout, device_out, out, reduce, layers, stack, errors)
+
+    def decompress_batch_convert(self, bufs, dtype=None, layout="chw", device_out=False, out=None, reduce=0, layers=0,
+                                 upsample=False, colour=None, out_prec=None, prec_mode="clip", stack=False,
+                                 errors="raise"):
+        """decompress_batch with decompress's output steps
+        (grkgpu_decompress_batch_convert): item i is what decompress(buf,
+        dtype=, layout=, device_out=, out=, reduce=, layers=, upsample=,
+        colour=, out_prec=, prec_mode=) returns, bit for bit -- a list of host
+        planes for a stream with subsampled components that is not upsampled,
+        an array or cuda tensor otherwise -- so a list of 4:2:0 or 12-bit
+        streams decodes straight to (h,w,3) uint8 RGB in one launch set.
+        upsample, colour, out_prec and prec_mode are one value for all streams
+        or a list with one entry per stream, like dtype / layout / device_out.
+        force-RGB and custom-MCT streams are refused item by item.  stack,
+        errors and self.batch_info as decompress_batch: with upsample / colour,
+        stack=True gives the (n, h, w, 3) tensor a loader wants."""
+        return self._decompress_batch(True, bufs, dtype, layout, device_out, out, reduce, layers, stack, errors,
+                                      upsample, colour, out_prec, prec_mode)
 
     def decompress_jp2(self, buf, dtype=None, layout="chw", colour="auto", out_prec=None, prec_mode="clip",
                        window=None, reduce=0, layers=0, device_out=False, force_rgb=False):

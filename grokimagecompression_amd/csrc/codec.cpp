@@ -9,6 +9,7 @@
 // Decode (TileProcessor::decode_tile, TileProcessor.cpp:1069-1179):
 //   host header + Tier-2 parse -> H2D codestream -> ONE T1 decode launch ->
 //   per tile/component inverse DWT levels -> inverse MCT + DC shift.
+#include <assert.h>
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -20,7 +21,6 @@
 #include <atomic>
 #include <array>
 #include <chrono>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -4183,16 +4183,91 @@ static_assert(sizeof(grkgpu_store_job) == sizeof(StoreJob) && offsetof(grkgpu_st
                   offsetof(grkgpu_store_job, max) == offsetof(StoreJob, mx),
               "grkgpu_store_job is StoreJob");
 
-// The StoreJob tables of a launch set, one group per (sample format, layout):
-// jobs in table order, `first` their first-workgroup numbers.
-struct StoreGroup {
-    int32_t fmt = 0;
-    bool il = false;
-    std::vector<StoreJob> jobs;
-    std::vector<uint32_t> first;
+// A job table: the records of a launch set's jobs of one type, in groups.  A
+// group's key selects its launch: the sample format, the layout (stores: 1
+// interleaved) or load mode, and -- StoreJobs with ops -- the op class (OP_*:
+// 1 precision, 2 sYCC, 3 eYCC, 4 CMYK) or -- ConvJobs -- the thread shape (bit
+// 0 run shape, bit 1 sYCC).  Groups in order of first use; a group's records
+// in table order, `first` their first-workgroup numbers.
+struct JobKey {
+    int32_t fmt;
+    int mode, cls;
+    bool operator==(const JobKey &o) const { return fmt == o.fmt && mode == o.mode && cls == o.cls; }
 };
-// a tile the job table does not take (more than four components, or too many
-// workgroups for one job): launch_mct_inv_dcshift_to's arguments
+template <typename J>
+struct JobTable {
+    struct Group {
+        JobKey key;
+        std::vector<J> jobs;
+        std::vector<uint32_t> first;
+    };
+    std::vector<Group> groups;
+    uint32_t njobs = 0;
+    // false: not tabled, the job takes a launch of its own -- more workgroups
+    // than the kernels' 32-bit thread index holds, or than a grid takes
+    bool add(const JobKey &key, const J &j, uint64_t wgs) {
+        Group *g = nullptr;
+        for (Group &q : groups)
+            if (q.key == key) g = &q;
+        if (wgs > STORE_JOB_MAX_WGS || (g ? g->first.back() : 0) + wgs > 0x7fffffffull) return false;
+        if (!g) {
+            groups.push_back(Group{key, {}, {0}});
+            g = &groups.back();
+        }
+        g->jobs.push_back(j);
+        g->first.push_back(g->first.back() + (uint32_t)wgs);
+        ++njobs;
+        return true;
+    }
+    // In a buffer the records of every group lie back to back from `rec` on and
+    // the first arrays from `fst` on (alone in its buffer: fst = rec_bytes()).
+    size_t rec_bytes() const { return (size_t)njobs * sizeof(J); }
+    size_t first_bytes() const { return ((size_t)njobs + groups.size()) * 4; }
+    size_t bytes() const { return rec_bytes() + first_bytes(); }
+    // the one walk over that layout: f(group, offset of its records, offset of its first array)
+    template <typename F>
+    hipError_t walk(size_t rec, size_t fst, F &&f) const {
+        for (const Group &g : groups) {
+            const hipError_t e = f(g, rec, fst);
+            if (e != hipSuccess) return e;
+            rec += g.jobs.size() * sizeof(J);
+            fst += g.first.size() * 4;
+        }
+        return hipSuccess;
+    }
+    // the table into a staging buffer -> the bytes written
+    size_t fill(uint8_t *stage, size_t rec, size_t fst) const {
+        size_t b = 0;
+        walk(rec, fst, [&](const Group &g, size_t r, size_t f) {
+            memcpy(stage + r, g.jobs.data(), g.jobs.size() * sizeof(J));
+            memcpy(stage + f, g.first.data(), g.first.size() * 4);
+            b += g.jobs.size() * sizeof(J) + g.first.size() * 4;
+            return hipSuccess;
+        });
+        return b;
+    }
+    // launch(records, first, njobs, nwgs, key) for every group with workgroups, the table at `dev` as filled
+    template <typename L>
+    hipError_t launch(const void *dev, size_t rec, size_t fst, uint32_t *nl, L &&launch) const {
+        return walk(rec, fst, [&](const Group &g, size_t r, size_t f) {
+            if (!g.first.back()) return hipSuccess;
+            const hipError_t e = launch((const J *)((const uint8_t *)dev + r), (const uint32_t *)((const uint8_t *)dev + f),
+                                        (uint32_t)g.jobs.size(), g.first.back(), g.key);
+            if (e == hipSuccess && nl) ++*nl;
+            return e;
+        });
+    }
+};
+// `filled` bytes of tables, staged at `stage`, to the device (the fills' sum against the layout's size)
+static hipError_t upload_tables(const uint8_t *stage, void *dev, size_t filled, size_t bytes, hipStream_t s) {
+    assert(filled == bytes);
+    return bytes ? hipMemcpyAsync(dev, stage, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+}
+
+// What the job tables do not take (more than four components, or too many
+// workgroups for one job), launched tile by tile: the arguments of
+// launch_mct_inv_dcshift_to, of launch_mct_inv_dcshift_ops and of
+// launch_upsample_to / _ops (conv).
 struct TileStore {
     PlanePtrs src;
     DstPlanes dst;
@@ -4201,160 +4276,303 @@ struct TileStore {
     bool il;
     ShiftArr sh, mn, mx;
 };
-static bool store_group_add(StoreGroup (&groups)[10], int32_t fmt, bool il, const StoreJob &j) {
-    const uint64_t wgs = store_job_wgs(j, sample_bytes(fmt), il);
-    StoreGroup &g = groups[fmt * 2 + (il ? 1 : 0)];
-    if (wgs > STORE_JOB_MAX_WGS || (g.first.empty() ? 0 : g.first.back()) + wgs > 0x7fffffffull) return false;
-    g.fmt = fmt;
-    g.il = il;
-    if (g.first.empty()) g.first.push_back(0);
-    g.jobs.push_back(j);
-    g.first.push_back(g.first.back() + (uint32_t)wgs);
-    return true;
-}
-// The groups' tables in one device buffer (jobs of every group, then their
-// first arrays), uploaded through `stage`, and their launches.
-static size_t store_groups_bytes(const StoreGroup (&groups)[10]) {
-    size_t b = 0;
-    for (const StoreGroup &g : groups) b += g.jobs.size() * sizeof(StoreJob) + g.first.size() * 4;
-    return b;
-}
-static hipError_t store_groups_upload(const StoreGroup (&groups)[10], uint8_t *stage, void *dev, hipStream_t s) {
-    size_t o = 0;
-    for (const StoreGroup &g : groups) {
-        if (g.jobs.empty()) continue;
-        memcpy(stage + o, g.jobs.data(), g.jobs.size() * sizeof(StoreJob));
-        o += g.jobs.size() * sizeof(StoreJob);
+struct TileOpsStore {
+    TileStore ts;
+    OutOps o;
+};
+struct TileConv {
+    UpPlan pl;
+    uint32_t nc;
+    Rect r;
+    DstPlanes dst;
+    int32_t fmt;
+    bool il;
+    uint32_t dstride;
+    OutOps o;
+    bool conv;
+};
+// a tile as a record (nc <= 4) and back
+static StoreJob store_job_of(const TileStore &ts) {
+    StoreJob j{};
+    for (uint32_t k = 0; k < 4; ++k) {
+        j.src[k] = ts.src.p[k];
+        j.dst[k] = ts.dst.p[k];
+        j.shift[k] = ts.sh.v[k]; j.mn[k] = ts.mn.v[k]; j.mx[k] = ts.mx.v[k];
     }
-    for (const StoreGroup &g : groups) {
-        if (g.jobs.empty()) continue;
-        memcpy(stage + o, g.first.data(), g.first.size() * 4);
-        o += g.first.size() * 4;
-    }
-    return o ? hipMemcpyAsync(dev, stage, o, hipMemcpyHostToDevice, s) : hipSuccess;
+    j.sstride = ts.sstride; j.dstride = ts.dstride; j.w = ts.w; j.h = ts.h;
+    j.ncomp = ts.nc; j.mct = ts.mct; j.irrev = (uint32_t)ts.wmask;
+    return j;
 }
-static hipError_t store_groups_launch(const StoreGroup (&groups)[10], const void *dev, hipStream_t s, uint32_t *nl) {
-    size_t njobs = 0;
-    for (const StoreGroup &g : groups) njobs += g.jobs.size();
-    size_t jo = 0, fo = njobs * sizeof(StoreJob);
-    for (const StoreGroup &g : groups) {
-        if (g.jobs.empty()) continue;
-        if (g.first.back()) {
-            hipError_t e = launch_store_jobs((const StoreJob *)((const uint8_t *)dev + jo),
-                                             (const uint32_t *)((const uint8_t *)dev + fo), (uint32_t)g.jobs.size(),
-                                             g.first.back(), g.fmt, g.il, s);
-            if (e != hipSuccess) return e;
-            if (nl) ++*nl;
-        }
-        jo += g.jobs.size() * sizeof(StoreJob);
-        fo += g.first.size() * 4;
+static TileStore tile_store_of(const StoreJob &j, int32_t fmt, bool il) {
+    TileStore ts{};
+    for (uint32_t k = 0; k < j.ncomp; ++k) {
+        ts.src.p[k] = const_cast<int32_t *>(j.src[k]);
+        ts.sh.v[k] = j.shift[k]; ts.mn.v[k] = j.mn[k]; ts.mx.v[k] = j.mx[k];
     }
-    return hipSuccess;
+    for (uint32_t k = 0; k < (il ? 1u : j.ncomp); ++k) ts.dst.p[k] = j.dst[k];
+    ts.sstride = j.sstride; ts.w = j.w; ts.h = j.h; ts.dstride = j.dstride; ts.nc = j.ncomp;
+    ts.fmt = fmt; ts.il = il; ts.mct = j.mct; ts.wmask = (int32_t)j.irrev;
+    return ts;
 }
 
-// The tables of the converting stores (grkgpu_decompress_batch_convert,
-// grkgpu_convert_jobs_to): StoreJobs with ops, one group per (sample format,
-// layout, op class); ConvJobs, one group per (sample format, layout, thread
-// shape, sYCC or not); and the OutOps the jobs index.  In the device buffer:
-// the StoreJob groups, the ConvJob groups, the OutOps, then every group's
-// first-workgroup array -- from a 16-byte boundary on, records of 8-byte
-// multiples.
+// The last store of a launch set (grkgpu_decompress_batch / _convert and the
+// two stage calls): plain StoreJobs, StoreJobs with ops, ConvJobs, the OutOps
+// the jobs index, and the per-tile launches.  One device buffer holds the
+// tables: the records of the three (sizes multiples of 8, from a 16-byte
+// boundary), the OutOps, then every first array.
 static_assert(sizeof(StoreJob) % 8 == 0 && sizeof(ConvJob) % 8 == 0 && sizeof(OutOps) % 8 == 0, "table records stay aligned");
-template <typename J>
-struct JobGroup {
-    int32_t fmt = 0;
-    bool il = false;
-    int cls = 0;  // StoreJob: OP_* (1 precision, 2 sYCC, 3 eYCC, 4 CMYK); ConvJob: bit 0 run shape, bit 1 sYCC
-    std::vector<J> jobs;
-    std::vector<uint32_t> first;
-};
-struct ConvTables {
-    std::vector<JobGroup<StoreJob>> sg;
-    std::vector<JobGroup<ConvJob>> cg;
+struct StorePlan {
+    JobTable<StoreJob> plain, conv;
+    JobTable<ConvJob> up;
     std::vector<OutOps> ops;
-    uint32_t njobs = 0;
+    std::vector<TileStore> singles;
+    std::vector<TileOpsStore> conv_singles;
+    std::vector<TileConv> up_singles;
+
+    uint32_t njobs() const { return plain.njobs + conv.njobs + up.njobs; }
+    bool add_store(int32_t fmt, bool il, const StoreJob &j) {
+        return plain.add({fmt, il, 0}, j, store_job_wgs(j, sample_bytes(fmt), il));
+    }
+    // the op class of a store on one grid is launch_inv_ops' choice
+    bool add_conv_store(int32_t fmt, bool il, const OutOps &o, StoreJob j, uint32_t ops_index) {
+        j.ops = ops_index;
+        const int cls = o.col == COL_EYCC ? 3 : (o.col == COL_CMYK ? 4 : (o.sycc ? 2 : 1));
+        return conv.add({fmt, il, cls}, j, store_job_wgs(j, sample_bytes(fmt), il));
+    }
+    bool add_up(int32_t fmt, bool il, const OutOps &o, ConvJob j, uint32_t ops_index) {
+        j.ops = ops_index;
+        const bool fast = conv_job_fast(j.c, j.ncomp, fmt, o.col);
+        return up.add({fmt, il, (fast ? 1 : 0) | (fast && o.sycc ? 2 : 0)}, j, conv_job_wgs(j, sample_bytes(fmt), fast));
+    }
+
+    // the buffer: the three tables' records at rec[], the OutOps, the first arrays at fst[]
+    struct Places { size_t rec[3], ops, fst[3], end; };
+    Places places() const {
+        Places p{};
+        p.rec[1] = plain.rec_bytes();
+        p.rec[2] = p.rec[1] + conv.rec_bytes();
+        p.ops = p.rec[2] + up.rec_bytes();
+        p.fst[0] = p.ops + ops.size() * sizeof(OutOps);
+        p.fst[1] = p.fst[0] + plain.first_bytes();
+        p.fst[2] = p.fst[1] + conv.first_bytes();
+        p.end = p.fst[2] + up.first_bytes();
+        return p;
+    }
+    size_t bytes() const { return places().end; }
+    hipError_t upload(uint8_t *stage, void *dev, hipStream_t s) const {
+        const Places p = places();
+        if (!ops.empty()) memcpy(stage + p.ops, ops.data(), ops.size() * sizeof(OutOps));
+        const size_t filled = plain.fill(stage, p.rec[0], p.fst[0]) + conv.fill(stage, p.rec[1], p.fst[1]) +
+                              up.fill(stage, p.rec[2], p.fst[2]) + ops.size() * sizeof(OutOps);
+        return upload_tables(stage, dev, filled, p.end, s);
+    }
+    // Phase 1, the stores on the components' own grids, then phase 2, the
+    // upsampling / converting stores (same-stream order carries the
+    // dependency); in each the tables, then the per-tile launches.
+    hipError_t launch(const void *dev, hipStream_t s, uint32_t *nl) const {
+        const Places p = places();
+        const OutOps *const dops = (const OutOps *)((const uint8_t *)dev + p.ops);
+        hipError_t e = plain.launch(dev, p.rec[0], p.fst[0], nl,
+                                    [&](const StoreJob *j, const uint32_t *first, uint32_t n, uint32_t nwg, const JobKey &k) {
+                                        return launch_store_jobs(j, first, n, nwg, k.fmt, k.mode != 0, s);
+                                    });
+        if (e == hipSuccess)
+            e = conv.launch(dev, p.rec[1], p.fst[1], nl,
+                            [&](const StoreJob *j, const uint32_t *first, uint32_t n, uint32_t nwg, const JobKey &k) {
+                                return launch_store_jobs_ops(j, first, n, nwg, dops, k.fmt, k.mode != 0, k.cls, s);
+                            });
+        for (size_t i = 0; e == hipSuccess && i < singles.size(); ++i) {
+            const TileStore &ts = singles[i];
+            e = launch_mct_inv_dcshift_to(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc, ts.sh,
+                                          ts.mn, ts.mx, ts.mct, ts.wmask, s);
+            if (e == hipSuccess && nl) ++*nl;
+        }
+        for (size_t i = 0; e == hipSuccess && i < conv_singles.size(); ++i) {
+            const TileStore &ts = conv_singles[i].ts;
+            e = launch_mct_inv_dcshift_ops(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc, ts.sh,
+                                           ts.mn, ts.mx, ts.mct, ts.wmask, conv_singles[i].o, s);
+            if (e == hipSuccess && nl) ++*nl;
+        }
+        if (e == hipSuccess)
+            e = up.launch(dev, p.rec[2], p.fst[2], nl,
+                          [&](const ConvJob *j, const uint32_t *first, uint32_t n, uint32_t nwg, const JobKey &k) {
+                              return launch_conv_jobs(j, first, n, nwg, dops, k.fmt, k.mode != 0, (k.cls & 1) != 0,
+                                                      (k.cls & 2) != 0, s);
+                          });
+        for (size_t i = 0; e == hipSuccess && i < up_singles.size(); ++i) {
+            const TileConv &t = up_singles[i];
+            e = t.conv ? launch_upsample_ops(t.pl, t.nc, t.r.x0, t.r.y0, t.r.w(), t.r.h(), t.dst, t.fmt, t.il, t.dstride, t.o, s)
+                       : launch_upsample_to(t.pl, t.nc, t.r.x0, t.r.y0, t.r.w(), t.r.h(), t.dst, t.fmt, t.il, t.dstride, s);
+            if (e == hipSuccess && nl) ++*nl;
+        }
+        return e;
+    }
+
+    // a stage call's run: the tables in a buffer of the call's own, freed once the stream has drained
+    int run_alone(hipStream_t s) const {
+        std::vector<uint8_t> stage(bytes());
+        void *dev = nullptr;
+        if (bytes()) HIPCHK(hipMalloc(&dev, bytes()));
+        hipError_t e = upload(stage.data(), dev, s);
+        if (e == hipSuccess) e = launch(dev, s, nullptr);
+        const hipError_t es = hipStreamSynchronize(s);
+        if (dev) hipFree(dev);
+        HIPCHK(e);
+        HIPCHK(es);
+        return GRKGPU_OK;
+    }
 };
-template <typename J>
-static bool job_group_add(std::vector<JobGroup<J>> &groups, int32_t fmt, bool il, int cls, const J &j, uint64_t wgs) {
-    JobGroup<J> *g = nullptr;
-    for (auto &q : groups)
-        if (q.fmt == fmt && q.il == il && q.cls == cls) g = &q;
-    if (wgs > STORE_JOB_MAX_WGS || (g ? g->first.back() : 0) + wgs > 0x7fffffffull) return false;
-    if (!g) {
-        groups.emplace_back();
-        g = &groups.back();
-        g->fmt = fmt; g->il = il; g->cls = cls;
-        g->first.push_back(0);
+
+
+// Where an item of a batch lies on the device: its tile buffers from work0,
+// its host-bound output regions at img0 + roff[k], its staging planes at
+// img0 + stoff[k] (host half only: all null).
+struct ItemBases {
+    uintptr_t work0, img0;
+    const size_t *roff, *stoff;
+    bool host_only;
+    uintptr_t dst(const DecHost &h, uint32_t k) const {
+        if (host_only) return 0;
+        return h.planes_on_device ? (uintptr_t)h.planes[k] : img0 + roff[k];
     }
-    g->jobs.push_back(j);
-    g->first.push_back(g->first.back() + (uint32_t)wgs);
-    return true;
-}
-// the op class of a store on one grid (launch_inv_ops' choice)
-static int store_op_class(const OutOps &o) {
-    return o.col == COL_EYCC ? 3 : (o.col == COL_CMYK ? 4 : (o.sycc ? 2 : 1));
-}
-// false: the job takes a launch of its own (too many workgroups)
-static bool conv_add_store(ConvTables &T, int32_t fmt, bool il, const OutOps &o, StoreJob j, uint32_t ops_index) {
-    j.ops = ops_index;
-    if (!job_group_add(T.sg, fmt, il, store_op_class(o), j, store_job_wgs(j, sample_bytes(fmt), il))) return false;
-    ++T.njobs;
-    return true;
-}
-static bool conv_add_up(ConvTables &T, int32_t fmt, bool il, const OutOps &o, ConvJob j, uint32_t ops_index) {
-    j.ops = ops_index;
-    const bool fast = conv_job_fast(j.c, j.ncomp, fmt, o.col);
-    if (!job_group_add(T.cg, fmt, il, (fast ? 1 : 0) | (fast && o.sycc ? 2 : 0), j,
-                       conv_job_wgs(j, sample_bytes(fmt), fast)))
-        return false;
-    ++T.njobs;
-    return true;
-}
-static size_t conv_tables_bytes(const ConvTables &T) {
-    size_t b = T.ops.size() * sizeof(OutOps);
-    for (const auto &g : T.sg) b += g.jobs.size() * sizeof(StoreJob) + g.first.size() * 4;
-    for (const auto &g : T.cg) b += g.jobs.size() * sizeof(ConvJob) + g.first.size() * 4;
-    return b;
-}
-static hipError_t conv_tables_upload(const ConvTables &T, uint8_t *stage, void *dev, hipStream_t s) {
-    size_t o = 0;
-    auto put = [&](const void *p, size_t bytes) { memcpy(stage + o, p, bytes); o += bytes; };
-    for (const auto &g : T.sg) put(g.jobs.data(), g.jobs.size() * sizeof(StoreJob));
-    for (const auto &g : T.cg) put(g.jobs.data(), g.jobs.size() * sizeof(ConvJob));
-    put(T.ops.data(), T.ops.size() * sizeof(OutOps));
-    for (const auto &g : T.sg) put(g.first.data(), g.first.size() * 4);
-    for (const auto &g : T.cg) put(g.first.data(), g.first.size() * 4);
-    return o ? hipMemcpyAsync(dev, stage, o, hipMemcpyHostToDevice, s) : hipSuccess;
-}
-// phase 1 (the StoreJobs with ops) or phase 2 (the ConvJobs): same-stream order carries the dependency
-static hipError_t conv_tables_launch(const ConvTables &T, const void *dev, int phase, hipStream_t s, uint32_t *nl) {
-    const uint8_t *const d = (const uint8_t *)dev;
-    size_t jo = 0, fo = T.ops.size() * sizeof(OutOps);
-    for (const auto &g : T.sg) fo += g.jobs.size() * sizeof(StoreJob);
-    for (const auto &g : T.cg) fo += g.jobs.size() * sizeof(ConvJob);
-    const OutOps *const ops = (const OutOps *)(d + fo - T.ops.size() * sizeof(OutOps));
-    for (const auto &g : T.sg) {
-        if (phase == 1 && g.first.back()) {
-            const hipError_t e = launch_store_jobs_ops((const StoreJob *)(d + jo), (const uint32_t *)(d + fo),
-                                                       (uint32_t)g.jobs.size(), g.first.back(), ops, g.fmt, g.il, g.cls, s);
-            if (e != hipSuccess) return e;
-            if (nl) ++*nl;
+};
+// The upsampling / converting store of rectangle r of the reference grid from
+// pl to dst: a ConvJob where the table takes it -- indexing the item's entry
+// of the OutOps table (all zero where it converts nothing), made when first
+// needed --, else a per-tile launch.
+static void plan_conv(StorePlan &P, const DecHost &h, uint32_t &ops_at, const UpPlan &pl, const Rect &r,
+                      const DstPlanes &dst, uint32_t dstride) {
+    if (h.nc <= 4) {
+        ConvJob j{};
+        for (uint32_t k = 0; k < h.nc; ++k) {
+            j.c[k] = pl.c[k];
+            if (h.staged(k)) j.c[k].raw = (uint8_t)(UPCOMP_FIN + h.sfmt);  // (a table's finished source names its format)
         }
-        jo += g.jobs.size() * sizeof(StoreJob);
-        fo += g.first.size() * 4;
+        for (uint32_t k = 0; k < h.nout(); ++k) j.dst[k] = dst.p[k];
+        j.X0 = r.x0; j.Y0 = r.y0; j.x1 = r.x1; j.y1 = r.y1;
+        j.dstride = dstride; j.ncomp = h.nc;
+        if (ops_at == 0xffffffffu) { ops_at = (uint32_t)P.ops.size(); P.ops.push_back(h.dops); }
+        if (P.add_up(h.od.fmt, h.il, h.dops, j, ops_at)) return;
     }
-    for (const auto &g : T.cg) {
-        if (phase == 2 && g.first.back()) {
-            const hipError_t e = launch_conv_jobs((const ConvJob *)(d + jo), (const uint32_t *)(d + fo),
-                                                  (uint32_t)g.jobs.size(), g.first.back(), ops, g.fmt, g.il,
-                                                  (g.cls & 1) != 0, (g.cls & 2) != 0, s);
-            if (e != hipSuccess) return e;
-            if (nl) ++*nl;
+    P.up_singles.push_back(TileConv{pl, h.nc, r, dst, h.od.fmt, h.il, dstride, h.dops, h.conv});
+}
+// The last store of one item, decompress_impl's launches as records: a
+// StoreJob per tile (per tile-component of a mixed-grid item) for the stores on
+// the components' own grids -- with an ops index where that store converts
+// (DecHost::grid_ops) --, a ConvJob per tile of an upsampled item and per
+// rectangle of converted zeros, and per-tile launches for what no table takes.
+static void plan_item_stores(StorePlan &P, const DecHost &h, const ItemBases &B) {
+    const uint32_t nc = h.nc, no = h.no, nout = h.nout(), ow = h.orect[0].w();
+    const size_t eb = h.il ? (size_t)no * h.sb : h.sb;
+    const bool gops = h.grid_ops();
+    uint32_t ops_at = 0xffffffffu, kops_at[GRKGPU_MAX_COMPS];  // the item's entries of the OutOps table, made when first needed
+    for (uint32_t k = 0; k < GRKGPU_MAX_COMPS; ++k) kops_at[k] = 0xffffffffu;
+    // where the stores on the components' own grids put component k: the
+    // output, or (upsampled) its staging plane, in format gfmt
+    const int32_t gfmt = h.up ? h.sfmt : h.od.fmt;
+    auto cat = [&](uint32_t k, uint64_t elem) {
+        return h.up ? (void *)(B.img0 + B.stoff[k] + elem * h.ssb) : (void *)(B.dst(h, k) + elem * eb);
+    };
+    // a store on the components' own grids: tabled, plain or with ops o (entry ops_index), or per tile
+    auto store = [&](const TileStore &ts, const OutOps *o, uint32_t ops_index) {
+        const bool tabled = ts.nc <= 4 && (o ? P.add_conv_store(ts.fmt, ts.il, *o, store_job_of(ts), ops_index)
+                                             : P.add_store(ts.fmt, ts.il, store_job_of(ts)));
+        if (!tabled && o) P.conv_singles.push_back(TileOpsStore{ts, *o});
+        else if (!tabled) P.singles.push_back(ts);
+    };
+    for (uint32_t lt = 0; lt < h.nsh; ++lt) {
+        const Tile &tile = h.tiles[lt];
+        if (!tile.comps.empty() && h.mixed) {  // each tile-component on its own grid, no MCT
+            for (uint32_t k = 0; k < nc; ++k) {
+                const TileComp &tc = tile.comps[k];
+                const Rect tr = h.tile_res(lt, k), out = intersect(tr, h.orect[k]);
+                if (out.empty() || (h.up && !h.staged(k))) continue;
+                TileStore ts{};
+                ts.src.p[0] = (int32_t *)(B.work0 + (tc.arena_off + (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0)) * 4);
+                ts.dst.p[0] = cat(k, (uint64_t)(out.y0 - h.orect[k].y0) * h.orect[k].w() + (out.x0 - h.orect[k].x0));
+                ts.sh.v[0] = h.cp.shift[k];
+                clamp_bounds(h.cp, k, ts.mn.v[0], ts.mx.v[0]);
+                ts.sstride = tr.w(); ts.dstride = h.orect[k].w(); ts.w = out.w(); ts.h = out.h();
+                ts.nc = 1; ts.wmask = tc.irrev; ts.fmt = gops ? h.od.fmt : gfmt;
+                if (gops) {  // each plane on its own grid, converted
+                    OutOps ok{};
+                    ok.pc[0] = h.dops.pc[k];
+                    if (kops_at[k] == 0xffffffffu) { kops_at[k] = (uint32_t)P.ops.size(); P.ops.push_back(ok); }
+                    store(ts, &ok, kops_at[k]);
+                } else {
+                    store(ts, nullptr, 0);
+                }
+            }
+        } else if (!tile.comps.empty()) {
+            // every component on one grid: one job, MCT included (orect[k] is the
+            // output on that grid -- the image itself without subsampling)
+            const Rect tr = h.tile_res(lt, 0);            // the tile at the decoded resolution
+            const Rect out = intersect(tr, h.orect[0]);  // its part of the output
+            if (!out.empty()) {
+                const uint64_t soff = (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0);
+                const uint64_t delem = (uint64_t)(out.y0 - h.orect[0].y0) * ow + (out.x0 - h.orect[0].x0);
+                const bool pil = h.il && !h.up;  // (staging planes are planes)
+                int32_t wmask = 0;  // components holding 9/7 (float) samples
+                for (uint32_t k = 0; k < nc; ++k) wmask |= tile.comps[k].irrev << k;
+                TileStore ts{};
+                for (uint32_t k = 0; k < nc; ++k) {
+                    ts.src.p[k] = (int32_t *)(B.work0 + (tile.comps[k].arena_off + soff) * 4);
+                    ts.sh.v[k] = h.cp.shift[k];
+                    clamp_bounds(h.cp, k, ts.mn.v[k], ts.mx.v[k]);
+                }
+                for (uint32_t k = 0; k < (h.up ? nc : nout); ++k) ts.dst.p[k] = cat(k, delem);
+                ts.sstride = tr.w(); ts.w = out.w(); ts.h = out.h();
+                ts.dstride = pil ? ow * no : ow;  // (h.il: ow * no fits 32 bits, checked by begin())
+                ts.nc = nc; ts.fmt = gops ? h.od.fmt : gfmt; ts.il = pil; ts.mct = h.tmct[lt]; ts.wmask = wmask;
+                if (gops) {
+                    if (nc <= 4 && ops_at == 0xffffffffu) { ops_at = (uint32_t)P.ops.size(); P.ops.push_back(h.dops); }
+                    store(ts, &h.dops, ops_at);
+                } else {
+                    store(ts, nullptr, 0);
+                }
+            }
         }
-        jo += g.jobs.size() * sizeof(ConvJob);
-        fo += g.first.size() * 4;
+        // upsampled: the output, tile by tile (the tiles never reached included)
+        const Rect uout = intersect(tile.r, {h.ix0, h.iy0, h.ix1, h.iy1});  // the tile's pixels of the output
+        if (!h.up || uout.empty()) continue;
+        UpPlan pl{};
+        for (uint32_t k = 0; k < nc; ++k) {
+            pl.c[k] = h.up_comp(lt, k, (const void *)(B.img0 + B.stoff[k]),
+                                tile.comps.empty() ? nullptr : (const int32_t *)(B.work0 + tile.comps[k].arena_off * 4));
+            if (h.staged(k) && h.conv) pl.c[k].raw = (uint8_t)(UPCOMP_FIN + h.sfmt);
+        }
+        const uint64_t delem = (uint64_t)(uout.y0 - h.iy0) * h.iw + (uout.x0 - h.ix0);
+        DstPlanes tdst{};
+        for (uint32_t k = 0; k < nout; ++k) tdst.p[k] = (void *)(B.dst(h, k) + delem * eb);
+        plan_conv(P, h, ops_at, pl, uout, tdst, h.il ? h.iw * no : h.iw);
     }
-    return hipSuccess;
+    // Samples nothing decoded, where the colour step converts them
+    // (decompress_impl's fill_converted): the converting store over null
+    // sources -- on the margin of a reduced decode (the output beyond the
+    // decoded rectangle cwin[0]) and on the tiles the stream never reached,
+    // which no other job writes, so the order among the jobs is free.
+    if (!h.converted_zeros()) return;
+    std::vector<Rect> zr;
+    const Rect &o0 = h.orect[0], &cw = h.cwin[0];
+    if (h.opad) {
+        zr.push_back({std::max(cw.x1, o0.x0), o0.y0, o0.x1, o0.y1});
+        zr.push_back({o0.x0, std::max(cw.y1, o0.y0), std::min(cw.x1, o0.x1), o0.y1});
+    }
+    for (uint32_t t = h.tb; h.missing && t < h.te; ++t) {
+        if (h.walk.decoded[t] || h.wskip[t]) continue;
+        const Rect cr = comp_rect(tile_rect(h.cp, t), h.cp.dx[0], h.cp.dy[0]);  // (one grid; sYCC: the image's)
+        zr.push_back(intersect({ceil_pow2(cr.x0, h.reduce), ceil_pow2(cr.y0, h.reduce), ceil_pow2(cr.x1, h.reduce),
+                                ceil_pow2(cr.y1, h.reduce)}, o0));
+    }
+    for (const Rect &o : zr) {
+        if (o.empty()) continue;
+        UpPlan zero{};
+        for (uint32_t k = 0; k < nc; ++k) zero.c[k].dx = zero.c[k].dy = 1;
+        DstPlanes fdst{};
+        for (uint32_t k = 0; k < nout; ++k)
+            fdst.p[k] = (void *)(B.dst(h, k) + ((uint64_t)(o.y0 - o0.y0) * ow + (o.x0 - o0.x0)) * eb);
+        plan_conv(P, h, ops_at, zero, o, fdst, h.il ? ow * no : ow);
+    }
 }
 
 // ops / convert: grkgpu_decompress_batch_convert (ops null: no item converts)
@@ -4525,211 +4743,18 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
         if (img_bytes) HIPCHK(c->img.ensure(img_bytes + 256));
         HIPCHK(c->work.ensure(arena * 4 + 256));
     }
-    // The last store, decompress_impl's launches as records: a StoreJob per
-    // tile (per tile-component of a mixed-grid item) for the stores on the
-    // components' own grids -- with an ops index where that store converts
-    // (DecHost::grid_ops) --, a ConvJob per tile of an upsampled item and per
-    // rectangle of converted zeros, and per-tile launches for what no table
-    // takes (more than four components, too many workgroups for one job).
-    StoreGroup groups[10];
-    std::vector<TileStore> singles;
-    ConvTables ctab;
-    std::vector<std::function<hipError_t(hipStream_t)>> conv_singles, up_singles;  // (phase 1 with ops, phase 2)
-    uint32_t n_store_jobs = 0;
-    const uintptr_t work0 = host_only ? 0 : (uintptr_t)c->work.p, img0 = host_only ? 0 : (uintptr_t)c->img.p;
-    auto dst_of = [&](uint32_t i, uint32_t k) {
-        if (host_only) return (uintptr_t)0;
-        return H[i].planes_on_device ? (uintptr_t)H[i].planes[k] : img0 + roff[i][k];
+    // the last store's records, item after item
+    StorePlan stores;
+    auto bases = [&](uint32_t i) {
+        return ItemBases{host_only ? 0 : (uintptr_t)c->work.p, host_only ? 0 : (uintptr_t)c->img.p, roff[i].data(),
+                         stoff[i].data(), host_only};
     };
-    auto tile_store_of = [](const StoreJob &j, int32_t fmt, bool il) {
-        TileStore ts{};
-        for (uint32_t k = 0; k < 4; ++k) {
-            ts.src.p[k] = const_cast<int32_t *>(j.src[k]);
-            ts.dst.p[k] = j.dst[k];
-            ts.sh.v[k] = j.shift[k]; ts.mn.v[k] = j.mn[k]; ts.mx.v[k] = j.mx[k];
-        }
-        ts.sstride = j.sstride; ts.w = j.w; ts.h = j.h; ts.dstride = j.dstride; ts.nc = j.ncomp;
-        ts.fmt = fmt; ts.il = il; ts.mct = j.mct; ts.wmask = (int32_t)j.irrev;
-        return ts;
-    };
-    auto ops_single = [&](const TileStore &ts, const OutOps &o) {
-        conv_singles.push_back([ts, o](hipStream_t s) {
-            return launch_mct_inv_dcshift_ops(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc,
-                                              ts.sh, ts.mn, ts.mx, ts.mct, ts.wmask, o, s);
-        });
-    };
-    for (uint32_t i = 0; i < n; ++i) {
-        if (items[i].status) continue;
-        const DecHost &h = H[i];
-        const uint32_t nc = h.nc, no = h.no, nout = h.nout(), ow = h.orect[0].w();
-        const size_t eb = h.il ? (size_t)no * h.sb : h.sb;
-        const bool gops = h.grid_ops();
-        // the item's entry of the OutOps table (all zero where it converts nothing), made when first needed
-        uint32_t ops_at = 0xffffffffu, kops_at[GRKGPU_MAX_COMPS];
-        for (uint32_t k = 0; k < GRKGPU_MAX_COMPS; ++k) kops_at[k] = 0xffffffffu;
-        auto item_ops = [&]() {
-            if (ops_at == 0xffffffffu) { ops_at = (uint32_t)ctab.ops.size(); ctab.ops.push_back(h.dops); }
-            return ops_at;
-        };
-        // where the stores on the components' own grids put component k: the
-        // output, or (upsampled) its staging plane, in format gfmt
-        const int32_t gfmt = h.up ? h.sfmt : h.od.fmt;
-        auto cat = [&](uint32_t k, uint64_t elem) {
-            return h.up ? (void *)(img0 + stoff[i][k] + elem * h.ssb) : (void *)(dst_of(i, k) + elem * eb);
-        };
-        for (uint32_t lt = 0; lt < h.nsh; ++lt) {
-            const Tile &tile = h.tiles[lt];
-            if (!tile.comps.empty() && h.mixed) {  // each tile-component on its own grid, no MCT
-                for (uint32_t k = 0; k < nc; ++k) {
-                    const TileComp &tc = tile.comps[k];
-                    const Rect tr = h.tile_res(lt, k), out = intersect(tr, h.orect[k]);
-                    if (out.empty() || (h.up && !h.staged(k))) continue;
-                    StoreJob j{};
-                    j.src[0] = (const int32_t *)(work0 + (tc.arena_off + (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0)) * 4);
-                    j.dst[0] = cat(k, (uint64_t)(out.y0 - h.orect[k].y0) * h.orect[k].w() + (out.x0 - h.orect[k].x0));
-                    j.shift[0] = h.cp.shift[k];
-                    clamp_bounds(h.cp, k, j.mn[0], j.mx[0]);
-                    j.sstride = tr.w(); j.dstride = h.orect[k].w(); j.w = out.w(); j.h = out.h();
-                    j.ncomp = 1; j.irrev = (uint32_t)tc.irrev;
-                    if (gops) {  // each plane on its own grid, converted
-                        OutOps ok{};
-                        ok.pc[0] = h.dops.pc[k];
-                        if (kops_at[k] == 0xffffffffu) { kops_at[k] = (uint32_t)ctab.ops.size(); ctab.ops.push_back(ok); }
-                        if (!conv_add_store(ctab, h.od.fmt, false, ok, j, kops_at[k]))
-                            ops_single(tile_store_of(j, h.od.fmt, false), ok);
-                    } else if (store_group_add(groups, gfmt, false, j)) {
-                        ++n_store_jobs;
-                    } else {
-                        singles.push_back(tile_store_of(j, gfmt, false));
-                    }
-                }
-            } else if (!tile.comps.empty()) {
-                // every component on one grid: one job, MCT included (orect[k] is the
-                // output on that grid -- the image itself without subsampling)
-                const Rect tr = h.tile_res(lt, 0);            // the tile at the decoded resolution
-                const Rect out = intersect(tr, h.orect[0]);  // its part of the output
-                if (!out.empty()) {
-                    const uint64_t soff = (uint64_t)(out.y0 - tr.y0) * tr.w() + (out.x0 - tr.x0);
-                    const uint64_t delem = (uint64_t)(out.y0 - h.orect[0].y0) * ow + (out.x0 - h.orect[0].x0);
-                    const bool pil = h.il && !h.up;  // (staging planes are planes)
-                    int32_t wmask = 0;  // components holding 9/7 (float) samples
-                    for (uint32_t k = 0; k < nc; ++k) wmask |= tile.comps[k].irrev << k;
-                    TileStore ts{};
-                    for (uint32_t k = 0; k < nc; ++k) {
-                        ts.src.p[k] = (int32_t *)(work0 + (tile.comps[k].arena_off + soff) * 4);
-                        ts.sh.v[k] = h.cp.shift[k];
-                        clamp_bounds(h.cp, k, ts.mn.v[k], ts.mx.v[k]);
-                    }
-                    for (uint32_t k = 0; k < (h.up ? nc : nout); ++k) ts.dst.p[k] = cat(k, delem);
-                    ts.sstride = tr.w(); ts.w = out.w(); ts.h = out.h();
-                    ts.dstride = pil ? ow * no : ow;  // (h.il: ow * no fits 32 bits, checked by begin())
-                    ts.nc = nc; ts.fmt = gops ? h.od.fmt : gfmt; ts.il = pil; ts.mct = h.tmct[lt]; ts.wmask = wmask;
-                    bool tabled = false;
-                    if (nc <= 4) {
-                        StoreJob j{};
-                        for (uint32_t k = 0; k < nc; ++k) {
-                            j.src[k] = ts.src.p[k];
-                            j.dst[k] = ts.dst.p[k];
-                            j.shift[k] = ts.sh.v[k]; j.mn[k] = ts.mn.v[k]; j.mx[k] = ts.mx.v[k];
-                        }
-                        j.sstride = ts.sstride; j.dstride = ts.dstride; j.w = ts.w; j.h = ts.h;
-                        j.ncomp = nc; j.mct = ts.mct; j.irrev = (uint32_t)wmask;
-                        if (gops) {
-                            tabled = conv_add_store(ctab, ts.fmt, ts.il, h.dops, j, item_ops());
-                        } else {
-                            tabled = store_group_add(groups, ts.fmt, ts.il, j);
-                            if (tabled) ++n_store_jobs;
-                        }
-                    }
-                    if (!tabled && gops) ops_single(ts, h.dops);
-                    else if (!tabled) singles.push_back(ts);
-                }
-            }
-            // upsampled: the output, tile by tile (the tiles never reached included)
-            const Rect uout = intersect(tile.r, {h.ix0, h.iy0, h.ix1, h.iy1});  // the tile's pixels of the output
-            if (!h.up || uout.empty()) continue;
-            UpPlan pl{};
-            for (uint32_t k = 0; k < nc; ++k) {
-                pl.c[k] = h.up_comp(lt, k, (const void *)(img0 + stoff[i][k]),
-                                    tile.comps.empty() ? nullptr : (const int32_t *)(work0 + tile.comps[k].arena_off * 4));
-                if (h.staged(k) && h.conv) pl.c[k].raw = (uint8_t)(UPCOMP_FIN + h.sfmt);
-            }
-            const uint64_t delem = (uint64_t)(uout.y0 - h.iy0) * h.iw + (uout.x0 - h.ix0);
-            DstPlanes tdst{};
-            for (uint32_t k = 0; k < nout; ++k) tdst.p[k] = (void *)(dst_of(i, k) + delem * eb);
-            const uint32_t dstride = h.il ? h.iw * no : h.iw;
-            bool tabled = false;
-            if (nc <= 4) {
-                ConvJob j{};
-                for (uint32_t k = 0; k < nc; ++k) {
-                    j.c[k] = pl.c[k];
-                    if (h.staged(k)) j.c[k].raw = (uint8_t)(UPCOMP_FIN + h.sfmt);  // (a table's finished source names its format)
-                }
-                for (uint32_t k = 0; k < nout; ++k) j.dst[k] = tdst.p[k];
-                j.X0 = uout.x0; j.Y0 = uout.y0; j.x1 = uout.x1; j.y1 = uout.y1;
-                j.dstride = dstride; j.ncomp = nc;
-                tabled = conv_add_up(ctab, h.od.fmt, h.il, h.dops, j, item_ops());
-            }
-            if (!tabled) {
-                const OutOps o = h.dops;
-                const int32_t fmt = h.od.fmt;
-                const bool il = h.il, conv = h.conv;
-                up_singles.push_back([pl, nc, uout, tdst, fmt, il, dstride, o, conv](hipStream_t s) {
-                    return conv ? launch_upsample_ops(pl, nc, uout.x0, uout.y0, uout.w(), uout.h(), tdst, fmt, il, dstride, o, s)
-                                : launch_upsample_to(pl, nc, uout.x0, uout.y0, uout.w(), uout.h(), tdst, fmt, il, dstride, s);
-                });
-            }
-        }
-        // Samples nothing decoded, where the colour step converts them
-        // (decompress_impl's fill_converted): the converting store over null
-        // sources -- on the margin of a reduced decode (the output beyond the
-        // decoded rectangle cwin[0]) and on the tiles the stream never reached,
-        // which no other job writes, so the order among the jobs is free.
-        if (!h.converted_zeros()) continue;
-        std::vector<Rect> zr;
-        const Rect &o0 = h.orect[0], &cw = h.cwin[0];
-        if (h.opad) {
-            zr.push_back({std::max(cw.x1, o0.x0), o0.y0, o0.x1, o0.y1});
-            zr.push_back({o0.x0, std::max(cw.y1, o0.y0), std::min(cw.x1, o0.x1), o0.y1});
-        }
-        for (uint32_t t = h.tb; h.missing && t < h.te; ++t) {
-            if (h.walk.decoded[t] || h.wskip[t]) continue;
-            const Rect cr = comp_rect(tile_rect(h.cp, t), h.cp.dx[0], h.cp.dy[0]);  // (one grid; sYCC: the image's)
-            zr.push_back(intersect({ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
-                                    ceil_pow2(cr.y1, reduce)}, o0));
-        }
-        for (const Rect &o : zr) {
-            if (o.empty()) continue;
-            UpPlan zero{};
-            for (uint32_t k = 0; k < nc; ++k) zero.c[k].dx = zero.c[k].dy = 1;
-            DstPlanes fdst{};
-            for (uint32_t k = 0; k < nout; ++k)
-                fdst.p[k] = (void *)(dst_of(i, k) + ((uint64_t)(o.y0 - o0.y0) * ow + (o.x0 - o0.x0)) * eb);
-            const uint32_t dstride = h.il ? ow * no : ow;
-            bool tabled = false;
-            if (nc <= 4) {
-                ConvJob j{};
-                for (uint32_t k = 0; k < nc; ++k) j.c[k] = zero.c[k];
-                for (uint32_t k = 0; k < nout; ++k) j.dst[k] = fdst.p[k];
-                j.X0 = o.x0; j.Y0 = o.y0; j.x1 = o.x1; j.y1 = o.y1;
-                j.dstride = dstride; j.ncomp = nc;
-                tabled = conv_add_up(ctab, h.od.fmt, h.il, h.dops, j, item_ops());
-            }
-            if (!tabled) {
-                const OutOps od = h.dops;
-                const int32_t fmt = h.od.fmt;
-                const bool il = h.il;
-                up_singles.push_back([zero, nc, o, fdst, fmt, il, dstride, od](hipStream_t s) {
-                    return launch_upsample_ops(zero, nc, o.x0, o.y0, o.w(), o.h(), fdst, fmt, il, dstride, od, s);
-                });
-            }
-        }
-    }
-    n_store_jobs += ctab.njobs;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!items[i].status) plan_item_stores(stores, H[i], bases(i));
     if (info) {
         info->n_ok = n_ok;
         info->n_blocks = nblk;
-        info->n_store_jobs = n_store_jobs;
+        info->n_store_jobs = stores.njobs();
     }
     if (host_only || !n_ok) return result();
 
@@ -4743,11 +4768,8 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
         HIPCHK(c->h_cs.ensure(cs_total + 256));
         HIPCHK(c->coef.ensure(arena * 4 + 256));
         HIPCHK(c->ll.ensure(llarena * 4 + 256));
-        // the converting stores' tables ride behind the StoreJob table, from a 16-byte boundary on
-        const size_t sjbytes = store_groups_bytes(groups), cjoff = (sjbytes + 15) & ~(size_t)15;
-        const size_t cjbytes = conv_tables_bytes(ctab);
-        HIPCHK(c->storejobs.ensure(cjoff + cjbytes + 256));
-        HIPCHK(c->h_storejobs.ensure(cjoff + cjbytes + 256));
+        HIPCHK(c->storejobs.ensure(stores.bytes() + 256));
+        HIPCHK(c->h_storejobs.ensure(stores.bytes() + 256));
         // the streams packed into the pinned buffer, on the host pool: the
         // bytes between them are never addressed by a segment
         host_parallel_for(n, 1, [&](size_t a, size_t b) {
@@ -4763,8 +4785,7 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
         HIPCHK(hipMemcpyAsync(c->cs.p, c->h_cs.p, cs_total, hipMemcpyHostToDevice, s));
         rc = t1.upload(c);
         if (rc) return rc;
-        HIPCHK(store_groups_upload(groups, c->h_storejobs.as<uint8_t>(), c->storejobs.p, s));
-        HIPCHK(conv_tables_upload(ctab, c->h_storejobs.as<uint8_t>() + cjoff, c->storejobs.as<uint8_t>() + cjoff, s));
+        HIPCHK(stores.upload(c->h_storejobs.as<uint8_t>(), c->storejobs.p, s));
         DwtPlan dplan[2];  // one plan per wavelet over every item's tile-components
         for (uint32_t i = 0; i < n; ++i) {
             if (items[i].status) continue;
@@ -4795,27 +4816,10 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
             const DecHost &h = H[i];
             if (h.converted_zeros()) continue;  // (ConvJobs over null sources)
             void *dst[GRKGPU_MAX_COMPS];
-            for (uint32_t k = 0; k < h.nout(); ++k) dst[k] = (void *)dst_of(i, k);
+            for (uint32_t k = 0; k < h.nout(); ++k) dst[k] = (void *)bases(i).dst(h, k);
             HIPCHK(dec_zero_fills(h, dst, s, &nl));
         }
-        // phase 1: the stores on the components' own grids
-        HIPCHK(store_groups_launch(groups, c->storejobs.p, s, &nl));
-        HIPCHK(conv_tables_launch(ctab, c->storejobs.as<uint8_t>() + cjoff, 1, s, &nl));
-        for (const TileStore &ts : singles) {
-            HIPCHK(launch_mct_inv_dcshift_to(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc,
-                                             ts.sh, ts.mn, ts.mx, ts.mct, ts.wmask, s));
-            ++nl;
-        }
-        for (const auto &f : conv_singles) {
-            HIPCHK(f(s));
-            ++nl;
-        }
-        // phase 2: the upsampling / converting store
-        HIPCHK(conv_tables_launch(ctab, c->storejobs.as<uint8_t>() + cjoff, 2, s, &nl));
-        for (const auto &f : up_singles) {
-            HIPCHK(f(s));
-            ++nl;
-        }
+        HIPCHK(stores.launch(c->storejobs.p, s, &nl));  // (phase 1, then phase 2)
         HIPCHK(hipEventRecord(c->ev[4], s));
         for (size_t r = 0; r < regions.size();) {  // one copy per run of adjacent regions
             size_t e = r + 1, bytes = regions[r].bytes;
@@ -4889,15 +4893,6 @@ static_assert(sizeof(grkgpu_load_job) == sizeof(LoadJob) && offsetof(grkgpu_load
               "grkgpu_load_job is LoadJob");
 static_assert(sizeof(DevPass) == sizeof(EncPass), "DevPass is EncPass");
 
-// The LoadJob tables of a launch set, one group per (sample format, mode):
-// jobs in table order, `first` their first-workgroup numbers.
-struct LoadGroup {
-    int32_t fmt = 0;
-    int mode = 0;
-    std::vector<LoadJob> jobs;
-    std::vector<uint32_t> first;
-};
-constexpr int LOAD_GROUPS = 20;  // 5 widths x 4 modes
 // a tile the job table does not take (more than four components, or too many
 // workgroups for one job): launch_dcshift_mct_fwd's arguments
 struct TileLoad {
@@ -4907,63 +4902,58 @@ struct TileLoad {
     int32_t lfmt, mct, irrev;
     ShiftArr sh;
 };
-static int load_mode(int32_t lfmt) { return ((lfmt & SMP_BIG_ENDIAN) ? 1 : 0) | ((lfmt & SMP_INTERLEAVED) ? 2 : 0); }
-static bool load_group_add(LoadGroup (&groups)[LOAD_GROUPS], int32_t lfmt, const LoadJob &j) {
-    const int mode = load_mode(lfmt);
-    const uint64_t wgs = load_job_wgs(j, (mode & 2) != 0);
-    LoadGroup &g = groups[(lfmt & 0xff) * 4 + mode];
-    if (wgs > STORE_JOB_MAX_WGS || (g.first.empty() ? 0 : g.first.back()) + wgs > 0x7fffffffull) return false;
-    g.fmt = lfmt & 0xff;
-    g.mode = mode;
-    if (g.first.empty()) g.first.push_back(0);
-    g.jobs.push_back(j);
-    g.first.push_back(g.first.back() + (uint32_t)wgs);
-    return true;
-}
-// The groups' tables in one device buffer (jobs of every group, then their
-// first arrays), uploaded through `stage`, and their launches.
-static size_t load_groups_bytes(const LoadGroup (&groups)[LOAD_GROUPS]) {
-    size_t b = 0;
-    for (const LoadGroup &g : groups) b += g.jobs.size() * sizeof(LoadJob) + g.first.size() * 4;
-    return b;
-}
-static hipError_t load_groups_upload(const LoadGroup (&groups)[LOAD_GROUPS], uint8_t *stage, void *dev, hipStream_t s) {
-    size_t o = 0;
-    for (const LoadGroup &g : groups) {
-        if (g.jobs.empty()) continue;
-        memcpy(stage + o, g.jobs.data(), g.jobs.size() * sizeof(LoadJob));
-        o += g.jobs.size() * sizeof(LoadJob);
+// a tile as a record (nc <= 4) and back
+static LoadJob load_job_of(const TileLoad &tl) {
+    LoadJob j{};
+    for (uint32_t k = 0; k < 4; ++k) {
+        j.src[k] = tl.src.p[k];
+        j.dst[k] = tl.dst.p[k];
+        j.shift[k] = tl.sh.v[k];
     }
-    for (const LoadGroup &g : groups) {
-        if (g.jobs.empty()) continue;
-        memcpy(stage + o, g.first.data(), g.first.size() * 4);
-        o += g.first.size() * 4;
-    }
-    return o ? hipMemcpyAsync(dev, stage, o, hipMemcpyHostToDevice, s) : hipSuccess;
+    j.sstride = tl.sstride; j.dstride = tl.dstride; j.w = tl.w; j.h = tl.h;
+    j.ncomp = tl.nc; j.mct = tl.mct; j.irrev = tl.irrev;
+    return j;
 }
-static hipError_t load_groups_launch(const LoadGroup (&groups)[LOAD_GROUPS], const void *dev, hipStream_t s, uint32_t *nl) {
-    size_t njobs = 0;
-    for (const LoadGroup &g : groups) njobs += g.jobs.size();
-    size_t jo = 0, fo = njobs * sizeof(LoadJob);
-    for (const LoadGroup &g : groups) {
-        if (g.jobs.empty()) continue;
-        if (g.first.back()) {
-            hipError_t e = launch_load_jobs((const LoadJob *)((const uint8_t *)dev + jo),
-                                            (const uint32_t *)((const uint8_t *)dev + fo), (uint32_t)g.jobs.size(),
-                                            g.first.back(), g.fmt, g.mode, s);
-            if (e != hipSuccess) return e;
-            if (nl) ++*nl;
+static TileLoad tile_load_of(const LoadJob &j, int32_t lfmt) {
+    TileLoad tl{};
+    for (uint32_t k = 0; k < ((lfmt & SMP_INTERLEAVED) ? 1u : j.ncomp); ++k) tl.src.p[k] = j.src[k];
+    for (uint32_t k = 0; k < j.ncomp; ++k) {
+        tl.dst.p[k] = j.dst[k];
+        tl.sh.v[k] = j.shift[k];
+    }
+    tl.sstride = j.sstride; tl.w = j.w; tl.h = j.h; tl.dstride = j.dstride; tl.nc = j.ncomp;
+    tl.lfmt = lfmt; tl.mct = j.mct; tl.irrev = j.irrev;
+    return tl;
+}
+// The DC shift + MCT of a launch set (grkgpu_compress_batch and its stage
+// call): the LoadJob table, one group per (sample format, mode: bit 0
+// big-endian, bit 1 interleaved), alone in its buffer, and the per-tile launches.
+struct LoadPlan {
+    JobTable<LoadJob> table;
+    std::vector<TileLoad> singles;
+    bool add(int32_t lfmt, const LoadJob &j) {
+        const int mode = ((lfmt & SMP_BIG_ENDIAN) ? 1 : 0) | ((lfmt & SMP_INTERLEAVED) ? 2 : 0);
+        return table.add({lfmt & 0xff, mode, 0}, j, load_job_wgs(j, (mode & 2) != 0));
+    }
+    hipError_t upload(uint8_t *stage, void *dev, hipStream_t s) const {
+        return upload_tables(stage, dev, table.fill(stage, 0, table.rec_bytes()), table.bytes(), s);
+    }
+    hipError_t launch(const void *dev, hipStream_t s, uint32_t *nl) const {
+        hipError_t e = table.launch(dev, 0, table.rec_bytes(), nl,
+                                    [&](const LoadJob *j, const uint32_t *first, uint32_t n, uint32_t nwg, const JobKey &k) {
+                                        return launch_load_jobs(j, first, n, nwg, k.fmt, k.mode, s);
+                                    });
+        for (size_t i = 0; e == hipSuccess && i < singles.size(); ++i) {
+            const TileLoad &t = singles[i];
+            e = t.dstride == t.w
+                    ? launch_dcshift_mct_fwd(t.src, t.lfmt, t.sstride, t.dst, t.w, t.h, t.nc, t.sh, t.mct, t.irrev, s)
+                    : launch_dcshift_mct_fwd_from(t.src, t.lfmt, t.sstride, t.dst, t.dstride, t.w, t.h, t.nc, t.sh, t.mct,
+                                                  t.irrev, s);
+            if (e == hipSuccess && nl) ++*nl;
         }
-        jo += g.jobs.size() * sizeof(LoadJob);
-        fo += g.first.size() * 4;
+        return e;
     }
-    return hipSuccess;
-}
-static hipError_t tile_load_launch(const TileLoad &t, hipStream_t s) {
-    if (t.dstride == t.w)
-        return launch_dcshift_mct_fwd(t.src, t.lfmt, t.sstride, t.dst, t.w, t.h, t.nc, t.sh, t.mct, t.irrev, s);
-    return launch_dcshift_mct_fwd_from(t.src, t.lfmt, t.sstride, t.dst, t.dstride, t.w, t.h, t.nc, t.sh, t.mct, t.irrev, s);
-}
+};
 
 static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grkgpu_cbatch_info *info, bool host_only) {
     if (info) *info = grkgpu_cbatch_info{};
@@ -5084,9 +5074,7 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
     }
     // the DC shift + MCT: a LoadJob per tile of every item of up to four
     // components, per-tile launches for the others
-    LoadGroup groups[LOAD_GROUPS];
-    std::vector<TileLoad> singles;
-    uint32_t n_load_jobs = 0;
+    LoadPlan loads;
     const uintptr_t work0 = host_only ? 0 : (uintptr_t)c->work.p, img0 = host_only ? 0 : (uintptr_t)c->img.p;
     for (uint32_t i : order) {
         const EncHost &h = H[i];
@@ -5107,26 +5095,13 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
             tl.sstride = h.prect[0].w() * (h.il ? nc : 1);  // interleaved: src.p[0] = the tile's first pixel
             tl.w = tcr.w(); tl.h = tcr.h(); tl.dstride = tcr.w(); tl.nc = nc;
             tl.lfmt = h.lfmt; tl.mct = h.cp.mct; tl.irrev = h.cp.irrev;
-            bool tabled = false;
-            if (nc <= 4) {
-                LoadJob j{};
-                for (uint32_t k = 0; k < nc; ++k) {
-                    j.src[k] = tl.src.p[k];
-                    j.dst[k] = tl.dst.p[k];
-                    j.shift[k] = tl.sh.v[k];
-                }
-                j.sstride = tl.sstride; j.dstride = tl.dstride; j.w = tl.w; j.h = tl.h;
-                j.ncomp = nc; j.mct = tl.mct; j.irrev = tl.irrev;
-                tabled = load_group_add(groups, h.lfmt, j);
-            }
-            if (tabled) ++n_load_jobs;
-            else singles.push_back(tl);
+            if (nc > 4 || !loads.add(h.lfmt, load_job_of(tl))) loads.singles.push_back(tl);
         }
     }
     if (info) {
         info->n_ok = n_ok;
         info->n_blocks = nblk;
-        info->n_load_jobs = n_load_jobs;
+        info->n_load_jobs = loads.table.njobs;
     }
     if (host_only || !n_ok) return result();
 
@@ -5135,9 +5110,8 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
     const int drc = [&]() -> int {
         int rc = enc_ensure(c, arena, llarena, scr_bytes, ord_words, out_total, sym_total, nblk);
         if (rc) return rc;
-        const size_t ljbytes = load_groups_bytes(groups);
-        HIPCHK(c->loadjobs.ensure(ljbytes + 256));
-        HIPCHK(c->h_loadjobs.ensure(ljbytes + 256));
+        HIPCHK(c->loadjobs.ensure(loads.table.bytes() + 256));
+        HIPCHK(c->h_loadjobs.ensure(loads.table.bytes() + 256));
         // the samples packed into the pinned buffer, on the host pool: the pad
         // bytes between planes are uploaded as they are and never addressed
         host_parallel_for(regions.size(), 1, [&](size_t a, size_t b) {
@@ -5156,13 +5130,9 @@ static int cbatch_impl(grkgpu_ctx *c, grkgpu_cbatch_item *items, uint32_t n, grk
         }
         HIPCHK(hipEventRecord(c->ev[0], s));
         if (img_bytes) HIPCHK(hipMemcpyAsync(c->img.p, c->h_img.p, img_bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(load_groups_upload(groups, c->h_loadjobs.as<uint8_t>(), c->loadjobs.p, s));
+        HIPCHK(loads.upload(c->h_loadjobs.as<uint8_t>(), c->loadjobs.p, s));
         HIPCHK(hipEventRecord(c->ev[1], s));
-        HIPCHK(load_groups_launch(groups, c->loadjobs.p, s, &nl));
-        for (const TileLoad &tl : singles) {
-            HIPCHK(tile_load_launch(tl, s));
-            ++nl;
-        }
+        HIPCHK(loads.launch(c->loadjobs.p, s, &nl));
         HIPCHK(hipEventRecord(c->ev[2], s));
         DwtPlan dplan[2];  // one plan per wavelet over every item's tile-components (never fused with the load)
         for (uint32_t i : order) {
@@ -5620,8 +5590,7 @@ extern "C" int grkgpu_mct_inv_dcshift_jobs_to(const grkgpu_store_job *jobs, uint
     const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
     const int64_t lo = fmt == SMP_I32 ? INT32_MIN : (sg ? -((int64_t)1 << (8 * sb - 1)) : 0);
     const int64_t hi = fmt == SMP_I32 ? INT32_MAX : (sg ? ((int64_t)1 << (8 * sb - 1)) - 1 : ((int64_t)1 << (8 * sb)) - 1);
-    StoreGroup groups[10];
-    std::vector<TileStore> singles;
+    StorePlan stores;
     for (uint32_t i = 0; i < n; ++i) {
         const grkgpu_store_job &q = jobs[i];
         const uint32_t nc = q.numcomps;
@@ -5632,42 +5601,18 @@ extern "C" int grkgpu_mct_inv_dcshift_jobs_to(const grkgpu_store_job *jobs, uint
         static_assert(sizeof(j) == sizeof(q), "grkgpu_store_job is StoreJob");
         memcpy(&j, &q, sizeof(j));
         for (uint32_t k = nc; k < 4; ++k) j.src[k] = nullptr;
-        TileStore ts{};
         for (uint32_t k = 0; k < nc; ++k) {
             if (!q.src[k] || (uintptr_t)q.src[k] % 4) return set_err(GRKGPU_EINVAL, "null or misaligned source plane");
             if (q.min[k] > q.max[k] || q.min[k] < lo || q.max[k] > hi)
                 return set_err(GRKGPU_EINVAL, "sample format does not hold the component's range");
-            ts.src.p[k] = const_cast<int32_t *>(q.src[k]);
-            ts.sh.v[k] = q.shift[k]; ts.mn.v[k] = q.min[k]; ts.mx.v[k] = q.max[k];
         }
-        for (uint32_t k = 0; k < (il ? 1u : nc); ++k) {
+        for (uint32_t k = 0; k < (il ? 1u : nc); ++k)
             if (!q.dst[k] || (uintptr_t)q.dst[k] % sb) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
-            ts.dst.p[k] = q.dst[k];
-        }
-        if (store_group_add(groups, fmt, il, j)) continue;
-        ts.sstride = q.src_stride; ts.w = q.w; ts.h = q.h; ts.dstride = q.dst_stride; ts.nc = nc;
-        ts.fmt = fmt; ts.il = il; ts.mct = q.mct; ts.wmask = (int32_t)q.wavelet_mask;
-        singles.push_back(ts);
+        if (!stores.add_store(fmt, il, j)) stores.singles.push_back(tile_store_of(j, fmt, il));
     }
     int rc = check_device(-1);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = store_groups_bytes(groups);
-    std::vector<uint8_t> stage(bytes);
-    void *dev = nullptr;
-    if (bytes) HIPCHK(hipMalloc(&dev, bytes));
-    hipError_t e = bytes ? store_groups_upload(groups, stage.data(), dev, s) : hipSuccess;
-    if (e == hipSuccess) e = store_groups_launch(groups, dev, s, nullptr);
-    for (size_t i = 0; e == hipSuccess && i < singles.size(); ++i) {
-        const TileStore &ts = singles[i];
-        e = launch_mct_inv_dcshift_to(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc, ts.sh,
-                                      ts.mn, ts.mx, ts.mct, ts.wmask, s);
-    }
-    const hipError_t es = hipStreamSynchronize(s);  // the table and its staging are freed below
-    if (dev) hipFree(dev);
-    HIPCHK(e);
-    HIPCHK(es);
-    return GRKGPU_OK;
+    return stores.run_alone((hipStream_t)stream);
 }
 
 extern "C" int grkgpu_dcshift_mct_fwd_jobs(grkgpu_ctx *c, const grkgpu_load_job *jobs, uint32_t n,
@@ -5683,8 +5628,7 @@ extern "C" int grkgpu_dcshift_mct_fwd_jobs(grkgpu_ctx *c, const grkgpu_load_job 
     const int32_t lfmt = fmt | fflags;
     const bool il = (fflags & SMP_INTERLEAVED) != 0;
     const uint32_t sb = sample_bytes(fmt);
-    LoadGroup groups[LOAD_GROUPS];
-    std::vector<TileLoad> singles;
+    LoadPlan loads;
     for (uint32_t i = 0; i < n; ++i) {
         const grkgpu_load_job &q = jobs[i];
         const uint32_t nc = q.numcomps;
@@ -5694,33 +5638,22 @@ extern "C" int grkgpu_dcshift_mct_fwd_jobs(grkgpu_ctx *c, const grkgpu_load_job 
         memcpy(&j, &q, sizeof(j));
         j.pad_ = 0;
         for (uint32_t k = nc; k < 4; ++k) { j.src[k] = nullptr; j.dst[k] = nullptr; }
-        TileLoad tl{};
-        for (uint32_t k = 0; k < (il ? 1u : nc); ++k) {
+        for (uint32_t k = 0; k < (il ? 1u : nc); ++k)
             // planar samples in host byte order are read with typed loads
             if (!q.src[k] || (!fflags && (uintptr_t)q.src[k] % sb))
                 return set_err(GRKGPU_EINVAL, "null or misaligned source plane");
-            tl.src.p[k] = q.src[k];
-        }
-        for (uint32_t k = 0; k < nc; ++k) {
+        for (uint32_t k = 0; k < nc; ++k)
             if (!q.dst[k] || (uintptr_t)q.dst[k] % 4) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
-            tl.dst.p[k] = q.dst[k];
-            tl.sh.v[k] = q.shift[k];
-        }
-        if (load_group_add(groups, lfmt, j)) continue;
-        tl.sstride = q.src_stride; tl.w = q.w; tl.h = q.h; tl.dstride = q.dst_stride; tl.nc = nc;
-        tl.lfmt = lfmt; tl.mct = q.mct; tl.irrev = q.irreversible;
-        singles.push_back(tl);
+        if (!loads.add(lfmt, j)) loads.singles.push_back(tile_load_of(j, lfmt));
     }
     int rc = check_device(c->device);
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const size_t bytes = load_groups_bytes(groups);
-    HIPCHK(c->loadjobs.ensure(bytes + 256));
-    HIPCHK(c->h_loadjobs.ensure(bytes + 256));
-    HIPCHK(load_groups_upload(groups, c->h_loadjobs.as<uint8_t>(), c->loadjobs.p, s));
-    HIPCHK(load_groups_launch(groups, c->loadjobs.p, s, nullptr));
-    for (const TileLoad &tl : singles) HIPCHK(tile_load_launch(tl, s));
+    HIPCHK(c->loadjobs.ensure(loads.table.bytes() + 256));
+    HIPCHK(c->h_loadjobs.ensure(loads.table.bytes() + 256));
+    HIPCHK(loads.upload(c->h_loadjobs.as<uint8_t>(), c->loadjobs.p, s));
+    HIPCHK(loads.launch(c->loadjobs.p, s, nullptr));
     HIPCHK(hipStreamSynchronize(s));  // the staging is the context's: free for the next call
     return GRKGPU_OK;
 }
@@ -6019,8 +5952,7 @@ extern "C" int grkgpu_convert_jobs_to(const grkgpu_convert_job *jobs, uint32_t n
     const int32_t fmt = (int32_t)sample_fmt;
     const bool il = layout == GRKGPU_LAYOUT_INTERLEAVED;
     const uint32_t sb = sample_bytes(fmt);
-    ConvTables T;
-    std::vector<std::function<hipError_t(hipStream_t)>> singles[2];  // (phase 1, phase 2)
+    StorePlan T;
     for (uint32_t i = 0; i < n; ++i) {
         const grkgpu_convert_job &q = jobs[i];
         const uint32_t nc = q.numcomps;
@@ -6088,18 +6020,7 @@ extern "C" int grkgpu_convert_jobs_to(const grkgpu_convert_job *jobs, uint32_t n
             for (uint32_t k = 0; k < (il ? 1u : no); ++k) j.dst[k] = q.dst[k];
             j.sstride = q.comp[0].stride; j.dstride = q.dst_stride; j.w = w; j.h = q.y1 - q.y0;
             j.ncomp = nc; j.mct = q.mct;
-            if (conv_add_store(T, fmt, il, dops, j, ops_at)) continue;
-            PlanePtrs sp{};
-            DstPlanes dp{};
-            ShiftArr sh{}, mn{}, mx{};
-            for (uint32_t k = 0; k < 4; ++k) {
-                sp.p[k] = const_cast<int32_t *>(j.src[k]); dp.p[k] = j.dst[k];
-                sh.v[k] = j.shift[k]; mn.v[k] = j.mn[k]; mx.v[k] = j.mx[k];
-            }
-            singles[0].push_back([=](hipStream_t s) {
-                return launch_mct_inv_dcshift_ops(sp, j.sstride, j.w, j.h, dp, fmt, il, j.dstride, nc, sh, mn, mx, j.mct,
-                                                  (int32_t)j.irrev, dops, s);
-            });
+            if (!T.add_conv_store(fmt, il, dops, j, ops_at)) T.conv_singles.push_back({tile_store_of(j, fmt, il), dops});
             continue;
         }
         ConvJob j{};
@@ -6107,31 +6028,14 @@ extern "C" int grkgpu_convert_jobs_to(const grkgpu_convert_job *jobs, uint32_t n
         for (uint32_t k = nc; k < 4; ++k) j.c[k] = UpComp{};
         for (uint32_t k = il ? 1 : no; k < 4; ++k) j.dst[k] = nullptr;
         j.mct_ = 0;
-        if (conv_add_up(T, fmt, il, dops, j, ops_at)) continue;
-        UpPlan pl{};
-        DstPlanes dp{};
-        for (uint32_t k = 0; k < 4; ++k) { pl.c[k] = j.c[k]; dp.p[k] = j.dst[k]; }
-        singles[1].push_back([=](hipStream_t s) {
-            return launch_upsample_ops(pl, nc, j.X0, j.Y0, j.x1 - j.X0, j.y1 - j.Y0, dp, fmt, il, j.dstride, dops, s);
-        });
+        if (T.add_up(fmt, il, dops, j, ops_at)) continue;
+        TileConv tc{UpPlan{}, nc, Rect{j.X0, j.Y0, j.x1, j.y1}, DstPlanes{}, fmt, il, j.dstride, dops, true};
+        for (uint32_t k = 0; k < 4; ++k) { tc.pl.c[k] = j.c[k]; tc.dst.p[k] = j.dst[k]; }
+        T.up_singles.push_back(tc);
     }
     int rc = check_device(-1);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = conv_tables_bytes(T);
-    std::vector<uint8_t> stage(bytes);
-    void *dev = nullptr;
-    if (bytes) HIPCHK(hipMalloc(&dev, bytes));
-    hipError_t e = bytes ? conv_tables_upload(T, stage.data(), dev, s) : hipSuccess;
-    for (int phase = 1; phase <= 2; ++phase) {
-        if (e == hipSuccess) e = conv_tables_launch(T, dev, phase, s, nullptr);
-        for (size_t i = 0; e == hipSuccess && i < singles[phase - 1].size(); ++i) e = singles[phase - 1][i](s);
-    }
-    const hipError_t es = hipStreamSynchronize(s);  // the tables and their staging are freed below
-    if (dev) hipFree(dev);
-    HIPCHK(e);
-    HIPCHK(es);
-    return GRKGPU_OK;
+    return T.run_alone((hipStream_t)stream);
 }
 
 static void dwt_stage_geom(uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t numres, int32_t irrev,
