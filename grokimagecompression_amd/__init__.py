@@ -222,6 +222,28 @@ class BatchInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class DecBlock(ctypes.Structure):
+    """grkgpu_dec_block: one code-block of grkgpu_dec_tables_of."""
+    _fields_ = [("data_off", ctypes.c_uint64), ("dst_off", ctypes.c_uint64), ("len", ctypes.c_uint32),
+                ("numpasses", ctypes.c_uint32), ("numbps", ctypes.c_uint32), ("w", ctypes.c_uint32),
+                ("h", ctypes.c_uint32), ("orient", ctypes.c_uint32), ("dstride", ctypes.c_uint32),
+                ("irreversible", ctypes.c_int32), ("stepsize", ctypes.c_float), ("pad", ctypes.c_uint32)]
+
+
+class DecSeg(ctypes.Structure):
+    """grkgpu_dec_seg: one codeword segment of grkgpu_dec_tables_of."""
+    _fields_ = [("data_off", ctypes.c_uint64), ("len", ctypes.c_uint32), ("npasses", ctypes.c_uint32),
+                ("pad_", ctypes.c_uint32 * 2)]
+
+
+class DecTables(ctypes.Structure):
+    """grkgpu_dec_tables: what the host half of a decode hands the device half."""
+    _fields_ = [("n_blocks", ctypes.c_uint32), ("n_segs", ctypes.c_uint32), ("data_bytes", ctypes.c_uint64),
+                ("coef_elems", ctypes.c_uint64), ("ll_elems", ctypes.c_uint64), ("blocks", ctypes.POINTER(DecBlock)),
+                ("segs", ctypes.POINTER(DecSeg)), ("seg_first", ctypes.POINTER(ctypes.c_uint32)),
+                ("style", ctypes.POINTER(ctypes.c_uint8)), ("roi", ctypes.POINTER(ctypes.c_uint8))]
+
+
 class StoreJob(ctypes.Structure):
     """grkgpu_store_job: one tile of grkgpu_mct_inv_dcshift_jobs_to."""
     _fields_ = [("src", ctypes.c_void_p * 4), ("dst", ctypes.c_void_p * 4), ("src_stride", ctypes.c_uint32),
@@ -458,6 +480,10 @@ def lib():
                                                 U32, P(P(ctypes.c_uint8)), P(ctypes.c_size_t)]
         L.grkgpu_decompress_tiles.argtypes = [VP, VP, ctypes.c_size_t, U32, U32, P(VP), ctypes.c_int]
         L.grkgpu_walk_tiles.argtypes = [VP, ctypes.c_size_t, P(ctypes.c_uint8), U32, P(U32)]
+        if hasattr(L, "grkgpu_dec_tables_of"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_dec_tables_of.argtypes = [VP, ctypes.c_size_t, P(DParams), P(DecTables)]
+            L.grkgpu_dec_tables_free.argtypes = [P(DecTables)]
+            L.grkgpu_dec_tables_free.restype = None
         L.grkgpu_decompress_reduced.argtypes = [VP, VP, ctypes.c_size_t, U32, P(ImageDesc), P(VP), ctypes.c_int]
         L.grkgpu_decompress_window.argtypes = [VP, VP, ctypes.c_size_t, U32, U32, U32, U32, P(ImageDesc), P(VP),
                                                ctypes.c_int]
@@ -1942,6 +1968,35 @@ def walk_tiles(cs):
     dec = (ctypes.c_uint8 * max(1, n.value))()
     _check(lib().grkgpu_walk_tiles(buf, len(cs), dec, n.value, ctypes.byref(n)))
     return [t for t in range(n.value) if dec[t]]
+
+
+def dec_tables(cs, reduce=0, layers=0):
+    """The tables the host half of a decode of codestream bytes `cs` hands the
+    device half, host only (grkgpu_dec_tables_of).  Returns a dict: "blocks" and
+    "segs" (numpy record arrays with the fields of grkgpu_dec_block /
+    grkgpu_dec_seg), "seg_first" (uint32, one more entry than blocks), "style",
+    "roi" (uint8 per block; roi None without an ROI shift) and the sizes
+    "data_bytes", "coef_elems", "ll_elems"; raises GrkGpuError where the decode
+    fails on the host."""
+    import numpy as np
+    buf = ctypes.create_string_buffer(bytes(cs), len(cs))
+    t = DecTables()
+    dp = DParams(cp_reduce=reduce, cp_layer=layers)
+    _check(lib().grkgpu_dec_tables_of(buf, len(cs), ctypes.byref(dp), ctypes.byref(t)))
+    try:
+        nb, ns = t.n_blocks, t.n_segs
+
+        def arr(p, n, dtype):
+            if not n:
+                return np.zeros(0, dtype)
+            return np.frombuffer(ctypes.string_at(p, n * np.dtype(dtype).itemsize), dtype=dtype).copy()
+
+        return dict(blocks=arr(t.blocks, nb, np.dtype(DecBlock)), segs=arr(t.segs, ns, np.dtype(DecSeg)),
+                    seg_first=arr(t.seg_first, nb + 1, np.uint32), style=arr(t.style, nb, np.uint8),
+                    roi=arr(t.roi, nb, np.uint8) if t.roi else None, data_bytes=t.data_bytes,
+                    coef_elems=t.coef_elems, ll_elems=t.ll_elems)
+    finally:
+        lib().grkgpu_dec_tables_free(ctypes.byref(t))
 
 
 # ---- stage entry points on torch device tensors (per-kernel parity tests) ----

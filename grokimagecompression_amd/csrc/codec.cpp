@@ -2581,6 +2581,7 @@ struct TileWalk {
     std::vector<std::vector<TpMarker>> marks;                  // per tile: its tile-part header markers
     std::vector<std::vector<uint32_t>> seq;                    // per tile: codestream index of each tile-part
     std::vector<uint8_t> decoded;                              // per tile: decoded by the walk
+    std::vector<uint32_t> order;                               // the decoded tiles, in the order the walk decodes them
     uint32_t ntp = 0;
 };
 
@@ -2623,6 +2624,7 @@ static bool walk_tile_parts(const uint8_t *cs, size_t len, size_t sot0, uint32_t
     w.marks.assign(ntiles, {});
     w.seq.assign(ntiles, {});
     w.decoded.assign(ntiles, 0);
+    w.order.clear();
     w.ntp = 0;
     std::vector<int32_t> cur_tp(ntiles, -1);
     std::vector<uint32_t> nb_tp(ntiles, 0);
@@ -2734,6 +2736,7 @@ static bool walk_tile_parts(const uint8_t *cs, size_t len, size_t sot0, uint32_t
         // j2k_decode_tile
         if (!has_data[tcur]) { err = "Failed to decode tile (no tile data)"; return false; }
         w.decoded[tcur] = 1;
+        w.order.push_back(tcur);
         has_data[tcur] = 0;
         ready = false;
         ++ndec;
@@ -2985,12 +2988,14 @@ struct DecHost {
     std::vector<std::pair<size_t, size_t>> ppm_chunk;  // (offset in ppm_buf, Nppm)
     uint32_t nsh = 0;
     std::vector<Tile> tiles;
-    std::vector<std::vector<uint8_t>> tbufs;    // tiles of several tile-parts: their data concatenated
     std::vector<std::vector<uint8_t>> tpacked;  // packed packet headers (PPM / PPT) of each tile
     std::vector<uint8_t> tpacked_on;
     std::vector<size_t> ppm_from;  // PPM: where each tile's packet headers start in ppm_buf
-    std::vector<uint8_t> contig;
-    std::vector<int> terr;
+    // PPM: the tiles are parsed one after the other in the walk's order (finish()), ppm_run the reference's
+    // one read pointer over the merged headers (cp->ppm_data, T2.cpp:375-378), valid after a parsed tile
+    bool ppm_serial = false, ppm_run_valid = false;
+    size_t ppm_run = 0;
+    std::vector<int> terr, twhy;  // twhy: decode_packet's code behind terr = 2
     std::vector<std::array<uint8_t, 16>> troi;  // per tile: ROI shift of each component
     std::vector<std::array<uint8_t, 16>> tsty;  // per tile: code-block style of each component
     std::vector<int32_t> tmct;                  // per tile: MCT (a tile COD may change it)
@@ -3294,17 +3299,16 @@ int DecHost::begin() {
     // host Tier-2 over every tile of the shard; code-block segments -> DecBlock table
     nsh = te - tb;
     tiles.assign(nsh, Tile());
-    tbufs.assign(nsh, {});
     tpacked.assign(nsh, {});
     tpacked_on.assign(nsh, 0);
     ppm_from.assign(nsh, 0);
-    contig.assign(nsh, 1);
     // 1: bad POC marker, 2: corrupt packet header, 3: bad tile-part COD / COC
     // / QCD / QCC / RGN / PPT, 4: tile-component parameters this decoder does
     // not take (code-block style, wavelet or MCT other than the main header's,
     // reduce >= its resolutions), 6: a custom MCT the tile-part headers touch
     // (MCT / MCC / MCO there, a tile COD with another MCT, a 5/3 component)
     terr.assign(nsh, 0);
+    twhy.assign(nsh, 0);
     troi.assign(nsh, {});
     tsty.assign(nsh, {});
     tmct.assign(nsh, cp.mct);
@@ -3329,6 +3333,12 @@ void DecHost::parse_tiles(size_t l0, size_t l1) {
             if (win && !overlap(comp_rect(tile.r, 1u << reduce, 1u << reduce), {ix0, iy0, ix1, iy1}))
                 continue;  // left without components: skipped below
             if (!walk.decoded[t]) continue;  // never reached: its samples stay zero
+            bool run_on = false;  // PPM: the headers go on where the tile decoded before this one left them
+            if (!ppm_chunk.empty()) {
+                if (!ppm_serial) continue;  // (finish() comes back for it)
+                run_on = ppm_run_valid && !win;
+                ppm_run_valid = false;
+            }
             // the tile's coding parameters: the main header's, then its
             // tile-part headers' markers (precedence tile COC > tile COD >
             // main COC > main COD; QCC / QCD alike); POC entries appended
@@ -3371,8 +3381,13 @@ void DecHost::parse_tiles(size_t l0, size_t l1) {
                 }
                 if (!check_qcd_steps(tcp, cp.qcc_set, tqcd, tqcc, e)) { terr[lt] = 5; continue; }
                 for (uint32_t k = 0; k < nc; ++k) {
+                    // a tile-part COD / COC's code-block style is read as a byte and never checked
+                    // (j2k_read_SPCod_SPCoc, j2k.cpp:7019); Tier-2 and Tier-1 look at its six Part-1 bits
+                    // only (T2::init_seg, T2.cpp:839-841; HT is the CAP marker's, j2k.cpp:6985), so the
+                    // reference decodes style 0x84 as 0x04
+                    tcp.comp[k].cblksty &= 0x3Fu;
                     const CompParams &cc = tcp.comp[k];
-                    if ((cc.cblksty & ~0x3Fu) || reduce >= cc.numres || cc.cblkw > 6 || cc.cblkh > 6) ok = false;
+                    if (reduce >= cc.numres || cc.cblkw > 6 || cc.cblkh > 6) ok = false;
                     troi[lt][k] = tcp.roishift[k];
                     tsty[lt][k] = (uint8_t)cc.cblksty;
                 }
@@ -3405,7 +3420,12 @@ void DecHost::parse_tiles(size_t l0, size_t l1) {
                     // tile-parts read, its later packets' headers still parsed)
                     for (uint32_t q : tpseq[t])
                         if (q >= ppm_chunk.size()) ok = false;
-                    if (ok && !tpseq[t].empty()) ppm_from[lt] = ppm_chunk[tpseq[t][0]].first;
+                    // the reference never moves its pointer to a tile's chunk (j2k_merge_ppm sets it once,
+                    // j2k.cpp:4883): a tile's headers start where the tile decoded before it stopped
+                    // reading, which in a well-formed stream is its first tile-part's chunk -- where a
+                    // tile starts when this decode did not parse the tile decoded before it (a shard, a
+                    // window)
+                    if (ok && !tpseq[t].empty()) ppm_from[lt] = run_on ? ppm_run : ppm_chunk[tpseq[t][0]].first;
                     tpacked_on[lt] = 1;
                 } else if (!ppt.empty()) {
                     for (auto &q : ppt) ph.insert(ph.end(), csb + q.off, csb + q.off + q.len);
@@ -3415,27 +3435,15 @@ void DecHost::parse_tiles(size_t l0, size_t l1) {
             }
             tile.comps.resize(nc);
             for (uint32_t k = 0; k < nc; ++k) build_tilecomp(tile.comps[k], tile.r, tcp, k, false);
-            // tile data: single tile-part -> decode in place; else concatenate
-            const uint8_t *td;
-            size_t tlen;
-            uint64_t base;
-            contig[lt] = tparts[t].size() <= 1;
-            if (contig[lt]) {
-                td = tparts[t].empty() ? csb : csb + tparts[t][0].first;
-                tlen = tparts[t].empty() ? 0 : tparts[t][0].second;
-                base = tparts[t].empty() ? 0 : tparts[t][0].first;
-            } else {
-                std::vector<uint8_t> &tbuf = tbufs[lt];
-                for (auto &pp : tparts[t]) tbuf.insert(tbuf.end(), csb + pp.first, csb + pp.first + pp.second);
-                td = tbuf.data();
-                tlen = tbuf.size();
-                base = 0;
-            }
+            // tile data: the tile-parts in place, walked as the reference's chunk buffer (TileData)
+            TileData td;
+            td.cs = csb;
+            td.cs_len = len;
+            for (auto &pp : tparts[t]) td.add(pp.first, pp.second);
             // packets in the tile's progression (T2::decode_packets, T2.cpp:194-258),
             // POC entries of the main header followed by the tile's own
             std::vector<PacketId> order;
             decode_packet_order(tcp, tile, order);
-            size_t off = 0;
             uint32_t packno = 0;
             PackedHdr packed = ppm_chunk.empty() ? PackedHdr{tpacked[lt].data(), tpacked[lt].size(), 0}
                                                  : PackedHdr{ppm_buf.data() + ppm_from[lt], ppm_buf.size() - ppm_from[lt], 0};
@@ -3444,13 +3452,15 @@ void DecHost::parse_tiles(size_t l0, size_t l1) {
                 // the remaining packets are empty (a zero-length header reads
                 // as "no data", T2.cpp:393-400) -- unless the headers are packed
                 // (PPM / PPT), which keep coming; their bodies are then empty
-                if (off >= tlen && !tpacked_on[lt]) break;
+                if (!td.left() && !tpacked_on[lt]) break;
                 const bool skip = max_layers && pk.layno >= max_layers;
-                int64_t used = decode_packet(tile.comps[pk.compno], pk.resno, pk.precno, pk.layno, td + off, tlen - off,
-                                             base + off, tcp.csty, &packno, skip, tcp.comp[pk.compno].cblksty,
-                                             tpacked_on[lt] ? &packed : nullptr);
-                if (used < 0) { terr[lt] = 2; break; }
-                off += (size_t)used;
+                const int prc = decode_packet(tile.comps[pk.compno], pk.resno, pk.precno, pk.layno, td, tcp.csty, &packno,
+                                              skip, tcp.comp[pk.compno].cblksty, tpacked_on[lt] ? &packed : nullptr);
+                if (prc < 0) { terr[lt] = 2; twhy[lt] = prc; break; }
+            }
+            if (!ppm_chunk.empty() && !tpseq[t].empty()) {
+                ppm_run = ppm_from[lt] + packed.off;
+                ppm_run_valid = true;
             }
         }
     }
@@ -3458,11 +3468,24 @@ void DecHost::parse_tiles(size_t l0, size_t l1) {
 
 // The tiles' errors in tile order, then the arenas and the block table.
 int DecHost::finish() {
+    if (!ppm_chunk.empty()) {
+        ppm_serial = true;
+        ppm_run_valid = false;
+        for (uint32_t t : walk.order)
+            if (t >= tb && t < te) parse_tiles(t - tb, t - tb + 1);
+            else ppm_run_valid = false;
+    }
     arena = llarena = 0;
     lloff.assign((size_t)nsh * nc, 0);
     for (uint32_t lt = 0; lt < nsh; ++lt) {
         if (terr[lt] == 1) return set_err(GRKGPU_ECORRUPT, "Error reading POC marker");
-        if (terr[lt] == 2) return set_err(GRKGPU_ECORRUPT, "corrupt packet header");
+        if (terr[lt] == 2) {
+            static const char *const why[] = {"", "SOP marker packet counter does not match", "inclusion bit",
+                                              "zero bit-plane tag tree", "impossibly many bit-planes", "number of passes",
+                                              "length indicator increment", "too many bits in segment length",
+                                              "unable to read packet header"};
+            return set_err(GRKGPU_ECORRUPT, std::string("corrupt packet header (") + why[-twhy[lt]] + ")");
+        }
         if (terr[lt] == 3) return set_err(GRKGPU_ECORRUPT, "corrupt tile-part header marker (COD/COC/QCD/QCC/RGN/PPT/PPM)");
         if (terr[lt] == 5)
             return set_err(GRKGPU_ECORRUPT, "QCD marker: number of step sizes is less than 3 * (tile decompositions) + 1");
@@ -3470,7 +3493,7 @@ int DecHost::finish() {
             return set_err(GRKGPU_EUNSUPPORTED, "custom MCT: MCT / MCC / MCO in a tile-part header, a tile COD with "
                                                 "another MCT or a 5/3 tile-component are not supported");
         if (terr[lt] == 4)
-            return set_err(GRKGPU_EUNSUPPORTED, "tile-component coding style not supported (HT code-block style, "
+            return set_err(GRKGPU_EUNSUPPORTED, "tile-component coding style not supported ("
                                                 "code-blocks above 64 x 64, MCT over components of different "
                                                 "wavelets or sizes, or reduce too large)");
     }
@@ -3487,8 +3510,6 @@ int DecHost::finish() {
             lloff[lt * nc + k] = llarena;
             llarena += ll_geom(tile.comps[k]).elems;
         }
-        const bool contiguous = contig[lt] != 0;
-        const std::vector<uint8_t> &tilebuf = tbufs[lt];
         for (uint32_t k = 0; k < nc; ++k) {
             TileComp &tc = tile.comps[k];
             const BandNeed need = win ? window_need(tc, cwin[k], nullptr, reduce) : BandNeed();
@@ -3515,12 +3536,12 @@ int DecHost::finish() {
                     DecSeg ds{};
                     ds.len = sg.len;
                     ds.npasses = sg.numpasses;
-                    if (sg.chunks.size() == 1 && contiguous) {
+                    if (sg.chunks.size() == 1) {
                         ds.data_off = sg.chunks[0].first;
                     } else if (!sg.chunks.empty()) {
                         ds.data_off = (uint64_t)len + extra.size();  // placed after the codestream
                         for (auto &ch : sg.chunks) {
-                            const uint8_t *srcp = contiguous ? csb + ch.first : tilebuf.data() + ch.first;
+                            const uint8_t *srcp = csb + ch.first;
                             extra.insert(extra.end(), srcp, srcp + ch.second);
                         }
                     } else {
@@ -4109,6 +4130,62 @@ extern "C" int grkgpu_walk_tiles(const uint8_t *csb, size_t len, uint8_t *decode
     *ntiles = (uint32_t)dec.size();
     if (decoded)
         for (uint32_t t = 0; t < dec.size() && t < cap; ++t) decoded[t] = dec[t];
+    return GRKGPU_OK;
+}
+
+static_assert(sizeof(grkgpu_dec_block) == sizeof(DecBlock) && offsetof(grkgpu_dec_block, dst_off) == offsetof(DecBlock, dst_off) &&
+                  offsetof(grkgpu_dec_block, numbps) == offsetof(DecBlock, numbps) &&
+                  offsetof(grkgpu_dec_block, dstride) == offsetof(DecBlock, dstride) &&
+                  offsetof(grkgpu_dec_block, stepsize) == offsetof(DecBlock, step),
+              "grkgpu_dec_block is DecBlock");
+static_assert(sizeof(grkgpu_dec_seg) == sizeof(DecSeg) && offsetof(grkgpu_dec_seg, npasses) == offsetof(DecSeg, npasses),
+              "grkgpu_dec_seg is DecSeg");
+
+extern "C" void grkgpu_dec_tables_free(grkgpu_dec_tables *t) {
+    if (!t) return;
+    free(t->blocks); free(t->segs); free(t->seg_first); free(t->style); free(t->roi);
+    *t = grkgpu_dec_tables{};
+}
+
+extern "C" int grkgpu_dec_tables_of(const uint8_t *csb, size_t len, const grkgpu_dparams *dp, grkgpu_dec_tables *t) {
+    if (!csb || !t) return set_err(GRKGPU_EINVAL, "null argument");
+    *t = grkgpu_dec_tables{};
+    const bool win = dp && (dp->DA_x0 || dp->DA_y0 || dp->DA_x1 || dp->DA_y1);
+    const Rect w = win ? Rect{dp->DA_x0, dp->DA_y0, dp->DA_x1, dp->DA_y1} : Rect{};
+    if (win && (dp->DA_x1 <= dp->DA_x0 || dp->DA_y1 <= dp->DA_y0)) return set_err(GRKGPU_EINVAL, "empty decode area");
+    ActiveCall active;
+    DecHost H;
+    H.csb = csb; H.len = len; H.host_only = true;
+    H.reduce = dp ? dp->cp_reduce : 0; H.max_layers = dp ? dp->cp_layer : 0; H.win = win ? &w : nullptr;
+    int rc = H.begin();
+    if (rc) return rc;
+    host_parallel_for(H.nsh, 1, [&](size_t l0, size_t l1) { H.parse_tiles(l0, l1); });
+    rc = H.finish();
+    if (rc) return rc;
+    const size_t nb = H.db.size(), ns = H.dsegs.size();
+    if (nb > 0xfffffffeull || ns > 0xffffffffull) return set_err(GRKGPU_EUNSUPPORTED, "codestream too large for one call");
+    t->n_blocks = (uint32_t)nb;
+    t->n_segs = (uint32_t)ns;
+    t->data_bytes = (uint64_t)len + H.extra.size();
+    t->coef_elems = H.arena;
+    t->ll_elems = H.llarena;
+    t->blocks = (grkgpu_dec_block *)malloc(std::max<size_t>(nb, 1) * sizeof(DecBlock));
+    t->segs = (grkgpu_dec_seg *)malloc(std::max<size_t>(ns, 1) * sizeof(DecSeg));
+    t->seg_first = (uint32_t *)malloc((nb + 1) * sizeof(uint32_t));
+    t->style = (uint8_t *)malloc(std::max<size_t>(nb, 1));
+    if (!H.droi.empty()) t->roi = (uint8_t *)malloc(nb);
+    if (!t->blocks || !t->segs || !t->seg_first || !t->style || (!H.droi.empty() && !t->roi)) {
+        grkgpu_dec_tables_free(t);
+        return set_err(GRKGPU_EUNSUPPORTED, "out of host memory for the decode tables");
+    }
+    if (nb) {
+        memcpy(t->blocks, H.db.data(), nb * sizeof(DecBlock));
+        memcpy(t->seg_first, H.seg_first.data(), nb * sizeof(uint32_t));
+        memcpy(t->style, H.dsty.data(), nb);
+        if (t->roi) memcpy(t->roi, H.droi.data(), nb);
+    }
+    if (ns) memcpy(t->segs, H.dsegs.data(), ns * sizeof(DecSeg));
+    t->seg_first[nb] = (uint32_t)ns;
     return GRKGPU_OK;
 }
 

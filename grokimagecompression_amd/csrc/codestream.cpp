@@ -191,7 +191,9 @@ void build_tilecomp(TileComp &tc, const Rect &tile_r, const CodingParams &cp, ui
             b.stepsize = (float)((1.0 + st.mant / 2048.0) * std::pow(2.0, (int32_t)(numbps - st.expn))) *
                          (encoder ? 1.0f : 0.5f);
             b.numbps = cp.roishift[compno] + st.expn + cc.numgbits - 1;  // + ROI (Quantizer.cpp:90-93)
-            b.inv_step = (uint32_t)((8192.0 / b.stepsize) + 0.5f);
+            // the encoder's 13-bit inverse (its own step sizes); a decoded QCD may carry a step so small
+            // that the quotient leaves uint32's range, which the conversion must not see
+            b.inv_step = encoder ? (uint32_t)((8192.0 / b.stepsize) + 0.5f) : 0;
             uint32_t np = res.pw * res.ph;
             b.precs.assign(np, Precinct());
             for (uint32_t precno = 0; precno < np; ++precno) {
@@ -442,12 +444,15 @@ struct BitReader {
 };
 }  // namespace
 
-int64_t decode_packet(TileComp &tc, uint32_t resno, uint32_t precno, uint32_t layno, const uint8_t *p, size_t n,
-                      uint64_t base_off, uint32_t csty, uint32_t *packno, bool skip_data, uint32_t cblksty,
-                      PackedHdr *hdr) {
+int decode_packet(TileComp &tc, uint32_t resno, uint32_t precno, uint32_t layno, TileData &td, uint32_t csty,
+                  uint32_t *packno, bool skip_data, uint32_t cblksty, PackedHdr *hdr) {
+    // the packet's SOP and -- unless they are packed -- header bits: at the
+    // cursor, as far as the tile's remaining bytes go (T2.cpp:319-322, :385-389)
+    const uint8_t *const p = td.cs + td.pos();
+    const size_t n = td.left();
     // passes per codeword segment (T2::init_seg, T2.cpp:821-850): 1 when every
     // pass is terminated; BYPASS: 10 for the first, then 2 (raw) and 1 (MQ)
-    // alternately; else 109 (a longer block is cut there, T2.cpp:566-577)
+    // alternately; else 109
     auto seg_max = [cblksty](const Cblk &c) -> uint32_t {
         if (cblksty & 0x04) return 1;
         if (cblksty & 0x01) {
@@ -457,7 +462,6 @@ int64_t decode_packet(TileComp &tc, uint32_t resno, uint32_t precno, uint32_t la
         }
         return 109;
     };
-    const bool single = !(cblksty & 0x05);
     Resolution &res = tc.res[resno];
     if (layno == 0) {
         for (uint32_t bandno = 0; bandno < res.numbands; ++bandno) {
@@ -503,23 +507,22 @@ int64_t decode_packet(TileComp &tc, uint32_t resno, uint32_t precno, uint32_t la
                 // (the bits read so far, zeros below, are its value)
                 const uint32_t f0 = r.fails;
                 uint32_t inc = c.included ? r.read(1) : (r.tagtree(pr.incl, cb, layno + 1) <= (int64_t)layno);
-                if (r.fails != f0) return -1;
+                if (r.fails != f0) return -2;
                 if (!inc) continue;
                 if (!c.included) {
                     int64_t k = r.tagtree(pr.imsb, cb, INT64_MAX);
-                    if (r.fails != f0 || k < 0) return -1;
+                    if (r.fails != f0 || k < 0) return -3;
                     // more missing bit-planes than the band has: the reference
                     // warns and takes the band's count (T2.cpp:516-521)
                     c.numbps = k > (int64_t)b.numbps ? b.numbps : (uint32_t)((int64_t)b.numbps - k);
-                    if (c.numbps > 16 + 33 * 5) return -1;  // T2.cpp:523-529
+                    if (c.numbps > 16 + 33 * 5) return -4;  // T2.cpp:523-529
                     c.numlenbits = 3;
                     c.included = true;
                 }
                 uint32_t np = r.numpasses();
-                if (r.fails != f0) return -1;
+                if (r.fails != f0) return -5;
                 c.numlenbits += r.comma();
-                if (r.fails != f0) return -1;
-                if (single && np > 109) np = 109;  // single segment: truncated (T2.cpp:566-577)
+                if (r.fails != f0) return -6;
                 // the packet's passes fill the open segment, then new ones
                 // (T2::read_packet_header, T2.cpp:560-605)
                 auto open_seg = [&]() {
@@ -531,9 +534,14 @@ int64_t decode_packet(TileComp &tc, uint32_t resno, uint32_t precno, uint32_t la
                 uint32_t left = np;
                 while (left) {
                     const uint32_t si = (uint32_t)c.segs.size() - 1;
-                    const uint32_t take = std::min(left, c.segs[si].maxpasses - c.segs[si].numpasses);
+                    // without a mode switch a segment takes up to 109 of the packet's passes whatever
+                    // it holds already, and the rest -- np reaches 164 -- open the next one (T2.cpp:570-581,
+                    // :609-616: "truncating" there only ends the segment)
+                    const uint32_t take = c.segs[si].maxpasses == 109
+                                              ? std::min(left, 109u)
+                                              : std::min(left, c.segs[si].maxpasses - c.segs[si].numpasses);
                     const uint32_t bits = c.numlenbits + (uint32_t)floorlog2((int32_t)take);
-                    if (bits > 32) return -1;  // "too many bits in segment length", T2.cpp:590-593
+                    if (bits > 32) return -7;  // "too many bits in segment length", T2.cpp:590-593
                     const uint32_t L = r.read(bits);
                     parts.push_back({&c, si, take, L});
                     c.segs[si].numpasses += take;
@@ -544,30 +552,30 @@ int64_t decode_packet(TileComp &tc, uint32_t resno, uint32_t precno, uint32_t la
             }
         }
     }
-    if (!r.align()) return -1;
+    if (!r.align()) return -8;
     // EPH (T2.cpp:405-418 / 640-652): skipped when present -- it ends the
     // header, wherever the header is
     size_t hoff = r.off;
     if ((csty & CSTY_EPH) && hoff + 2 <= hn && hp[hoff] == 0xFF && hp[hoff + 1] == 0x92) hoff += 2;
-    size_t off = hstart;
+    // one step over the SOP and the header read here (T2.cpp:427-428, :648-649), then one per segment
     if (hdr) hdr->off += hoff;
-    else off += hoff;
+    td.advance(hdr ? hstart : hstart + hoff);
     for (auto &pt : parts) {
         // T2::read_packet_data (T2.cpp:686-698): a segment running past the
         // tile data is truncated to what is there (the decoder reads the
         // missing tail as the 0xFF fill), not an error
-        if (off + pt.len > n) pt.len = (uint32_t)(n - off);
+        if (pt.len > td.left()) pt.len = (uint32_t)td.left();
         // a layer beyond the decoded ones (T2::skip_packet_data, T2.cpp:
         // 758-819): its passes still count, its bytes are stepped over
         if (!skip_data) {
             Cblk::Seg &sg = pt.c->segs[pt.seg];
-            if (pt.len) sg.chunks.push_back({base_off + off, pt.len});
+            if (pt.len) sg.chunks.push_back({td.pos(), pt.len});
             sg.len += pt.len;
             pt.c->seglen += pt.len;
         }
-        off += pt.len;
+        td.advance(pt.len);
     }
-    return (int64_t)off;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -649,7 +657,8 @@ int32_t parse_coc(const uint8_t *p, uint32_t size, CodingParams &cp, std::string
     if (size < room + 1) { err = "Error reading COC marker"; return -1; }
     const uint32_t k = room == 2 ? rd16(p) : p[0];
     if (k >= cp.numcomps) { err = "Error reading COC marker (bad number of components)"; return -1; }
-    if (p[room] & ~1u) { err = "unknown Scoc bits"; return -1; }
+    // Scoc: only the precinct flag is looked at -- unlike Scod (j2k.cpp:3836-3841), the other bits are
+    // read and never checked (j2k_read_coc, j2k.cpp:4018; J2K_CCP_CSTY_PRT, :7034)
     CompParams c = cp.comp[k];
     if (!parse_spcod(p + room + 1, size - room - 1, (p[room] & 1) != 0, c, err)) return -1;
     CompParams &d = cp.comp[k];

@@ -300,8 +300,39 @@ bool parse_main_header(const uint8_t *cs, size_t len, CodingParams &cp, size_t &
                        bool accept_custom_mct = false, bool *corrupt = nullptr);
 // POC marker segment body of `size` bytes (main or tile-part header)
 bool parse_poc(const uint8_t *p, uint32_t size, CodingParams &cp);
-// returns bytes consumed or -1 (T2::read_packet_header / read_packet_data,
-// T2.cpp:314-725); csty: SOP / EPH markers; packno: SOP packet counter;
+// A tile's data as the reference's T2 walks it: one chunk per tile-part read
+// (ChunkBuffer, zero-copy over the caller's stream: j2k_read_sod, j2k.cpp:
+// 5453-5472), a cursor (chunk, offset) that every advance clamps to the end
+// of its chunk and then moves to the next one (ChunkBuffer::
+// incr_cur_chunk_offset, ChunkBuffer.cpp:174-180; grk_buf::incr_offset,
+// util.cpp:143-157), lengths checked against the bytes of all chunks left
+// (T2.cpp:320, :686-698), and reads that start at the cursor and run on in the
+// stream's memory.  Packets of a well-formed stream end where their tile-part
+// ends, so none of this shows; in a damaged one a packet running over the end
+// of a tile-part takes the next SOT's bytes with it and the cursor comes back
+// into step at the next tile-part's first packet.
+struct TileData {
+    const uint8_t *cs = nullptr;  // the codestream
+    size_t cs_len = 0;
+    std::vector<std::pair<size_t, size_t>> parts;  // (offset in cs, bytes) of the tile-parts' data, empty ones left out
+    size_t cur = 0, off = 0, before = 0, total = 0;
+    void add(size_t at, size_t n) { if (n) { parts.push_back({at, n}); total += n; } }
+    size_t pos() const { return parts.empty() ? 0 : parts[cur].first + off; }  // in cs
+    size_t left() const {  // bytes of all chunks behind the cursor, never past the stream
+        const size_t g = total - (before + off), p = pos();
+        return std::min(g, p <= cs_len ? cs_len - p : 0);
+    }
+    void advance(size_t k) {
+        if (parts.empty()) return;
+        off = k < parts[cur].second - off ? off + k : parts[cur].second;
+        if (off == parts[cur].second && cur + 1 < parts.size()) { before += off; ++cur; off = 0; }
+    }
+};
+// returns 0, or a negative code for a packet header the reference refuses
+// (T2::read_packet_header / read_packet_data, T2.cpp:314-725: -1 SOP counter,
+// -2 inclusion, -3 zero bit-planes, -4 bit-plane count, -5 passes, -6 length
+// increment, -7 length bits, -8 alignment); td: the tile's data, advanced past
+// the packet; csty: SOP / EPH markers; packno: SOP packet counter;
 // skip_data: a layer beyond the decoded ones (T2::skip_packet); cblksty: the
 // code-block style (segment boundaries)
 // hdr: packed packet headers (PPM / PPT, j2k.cpp:4693-4990): the packet's
@@ -311,8 +342,7 @@ struct PackedHdr {
     const uint8_t *p = nullptr;
     size_t n = 0, off = 0;
 };
-int64_t decode_packet(TileComp &tc, uint32_t resno, uint32_t precno, uint32_t layno, const uint8_t *p, size_t n,
-                      uint64_t base_off, uint32_t csty = 0, uint32_t *packno = nullptr, bool skip_data = false,
-                      uint32_t cblksty = 0, PackedHdr *hdr = nullptr);
+int decode_packet(TileComp &tc, uint32_t resno, uint32_t precno, uint32_t layno, TileData &td, uint32_t csty = 0,
+                  uint32_t *packno = nullptr, bool skip_data = false, uint32_t cblksty = 0, PackedHdr *hdr = nullptr);
 
 }  // namespace grkgpu

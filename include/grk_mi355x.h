@@ -1017,6 +1017,49 @@ int grkgpu_decompress_multi(const grkgpu_device_set *devs, const uint8_t *cs, si
  * tile count; decoded holds cap entries (may be NULL). */
 int grkgpu_walk_tiles(const uint8_t *cs, size_t len, uint8_t *decoded, uint32_t cap, uint32_t *ntiles);
 
+/* The tables the host half of a decode hands the device half, host only (no
+ * device needed): main header, tile-part walk, packet headers and the table
+ * layout of grkgpu_decompress_ex(cs, len, p), then copies of
+ *   blocks[n_blocks]        one code-block each: where its bytes lie in the
+ *                           data buffer (the codestream followed by the
+ *                           segments gathered from several chunks), where its
+ *                           samples go in the coefficient arena (element offset
+ *                           of the top-left sample, rows dstride apart), its
+ *                           size, band orientation, bit-planes and coding passes
+ *   segs[n_segs], seg_first[n_blocks + 1]
+ *                           the codeword segments: block i's are
+ *                           segs[seg_first[i] .. seg_first[i + 1])
+ *   style[n_blocks]         code-block style of each block's tile-component
+ *   roi[n_blocks]           its ROI shift; NULL when no component has one
+ * and the sizes those offsets must stay inside: data_bytes, coef_elems (int32
+ * / float elements of the coefficient arena) and ll_elems (of the LL arena).
+ * The tables are in stream order, before the Tier-1 launch plan reorders
+ * them.  Fails as the decode would, before anything is allocated; the arrays
+ * are the library's, released by grkgpu_dec_tables_free (which zeroes *t). */
+typedef struct {
+    uint64_t data_off;    /* byte offset of the block's (first) segment in the data buffer */
+    uint64_t dst_off;     /* element offset of the block's top-left in the destination arena */
+    uint32_t len, numpasses, numbps, w, h, orient, dstride;
+    int32_t irreversible;
+    float stepsize;       /* decode step size (Quantizer.cpp:65-104, fraction 0.5) */
+    uint32_t pad;
+} grkgpu_dec_block;       /* (also the record of the stage call grkgpu_t1_decode_blocks) */
+typedef struct {
+    uint64_t data_off;
+    uint32_t len, npasses, pad_[2];
+} grkgpu_dec_seg;
+typedef struct {
+    uint32_t n_blocks, n_segs;
+    uint64_t data_bytes, coef_elems, ll_elems;
+    grkgpu_dec_block *blocks;
+    grkgpu_dec_seg *segs;
+    uint32_t *seg_first;
+    uint8_t *style;
+    uint8_t *roi;
+} grkgpu_dec_tables;
+int grkgpu_dec_tables_of(const uint8_t *cs, size_t len, const grkgpu_dparams *p, grkgpu_dec_tables *t);
+void grkgpu_dec_tables_free(grkgpu_dec_tables *t);
+
 void grkgpu_free(void *p);
 
 /* ---- stage entry points (device pointers, asynchronous on `stream`) ---- */
@@ -1228,14 +1271,7 @@ typedef struct {
                              t1.cpp:912-930); filled when with_distortion */
 } grkgpu_enc_result;
 
-typedef struct {
-    uint64_t data_off;    /* byte offset of the block's single segment in `data` */
-    uint64_t dst_off;     /* element offset of the block's top-left in `dst` */
-    uint32_t len, numpasses, numbps, w, h, orient, dstride;
-    int32_t irreversible;
-    float stepsize;       /* decode step size (Quantizer.cpp:65-104, fraction 0.5) */
-    uint32_t pad;
-} grkgpu_dec_block;
+/* (grkgpu_dec_block: above, with grkgpu_dec_tables_of) */
 
 /* scratch: >= grkgpu_t1_scratch_bytes_n(nblocks) device bytes, encode and
  * decode -- that is (nblocks rounded up to a multiple of 64) *

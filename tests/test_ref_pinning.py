@@ -116,6 +116,25 @@ def test_foreign_fixtures_regenerate():
     assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
 
 
+def test_cut_fixtures_regenerate():
+    """tests/golden/manifest_cut.json: goldens cut at ~1,400 positions, decoded
+    again by the reference (oracle/make_golden_cut.py)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "make_golden_cut.py"), "--check"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
+
+
+def test_damage_fixtures_regenerate():
+    """tests/golden/manifest_damage.json: goldens with 1 to 3 bytes replaced
+    inside their tile-parts, the same seeded draws decoded again by the
+    reference (oracle/make_golden_damage.py): every stratum a stream has the
+    structure for holds a case, at most 1 % of a stream's draws left out, at
+    least 15 % refusals and 30 % decodes -- asserted by the generator."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "make_golden_damage.py"), "--check"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
+
+
 def test_cstr_info_matches_reference():
     """grk_get_cstr_info of our libgrok.so (ref_driver_mi355x: the same driver
     relinked against it; header parsing needs no GPU) prints exactly what the
