@@ -1868,6 +1868,31 @@ class dwt_options:
         return False
 
 
+def _flat_dst(name, tail, dst, dfmt, nch, h, w, layout, dst_stride, bad, upsample=False):
+    """The flat destination of a stage call: nch channels of h x w samples of
+    dfmt = (dtype, sample format) in `layout`, rows dst_stride samples apart
+    (None: tight).  Returns (OutPlanes, stride).  `bad` (the caller's own
+    argument checks), a dst that is not flat and contiguous, a stride below a
+    row or fewer samples than needed raise "<name>: <tail>", tail taking the
+    sample count."""
+    il = layout == "hwc"
+    row = w * nch if il else w
+    stride = row if dst_stride is None else dst_stride
+    need = (h - 1) * stride + row if il else (nch * h - 1) * stride + row
+    if bad or dst.dim() != 1 or not dst.is_contiguous() or stride < row or dst.numel() < need:
+        raise GrkGpuError("%s: %s" % (name, tail % need))
+    op = OutPlanes(sample_fmt=dfmt[1], layout=_LAYOUTS[layout] | (LAYOUT_UPSAMPLE if upsample else 0), on_device=1)
+    for k in range(1 if il else nch):
+        op.planes[k] = dst.data_ptr() + k * h * stride * dfmt[0].itemsize
+    return op, stride
+
+
+def _prec_arrays(prec, sgnd, c):
+    """prec / sgnd (one value, or one per component) as the uint32 / int32 arrays of a stage call."""
+    return ((ctypes.c_uint32 * c)(*_per_comp(prec, c)),
+            (ctypes.c_int32 * c)(*[1 if v else 0 for v in _per_comp(sgnd, c)]))
+
+
 def upsample_to(src, dst, rect, subsampling, layout="chw", dst_stride=None):
     """grkgpu_upsample_to.  src: one 2-D cuda tensor per component, of dst's
     dtype, on the component's grid of rect = (x0, y0, x1, y1) -- component k
@@ -1879,17 +1904,13 @@ def upsample_to(src, dst, rect, subsampling, layout="chw", dst_stride=None):
     dst_stride, "hwc" pixels of c samples.  Returns dst."""
     x0, y0, x1, y1 = rect
     c, w, h = len(src), x1 - x0, y1 - y0
-    dt, fmt = _out_format(_out_dtype(dst))
+    dfmt = _out_format(_out_dtype(dst))
     _layout_shape((c, h, w), layout)  # refuses an unknown layout
     cd = lambda v, s: -(-v // s)  # noqa: E731
     if len(subsampling) != c or not 1 <= c <= MAXC or w <= 0 or h <= 0:
         raise GrkGpuError("upsample_to: one (dx, dy) per component, 1 .. %d components, a non-empty rect" % MAXC)
-    il = layout == "hwc"
-    row = w * c if il else w
-    stride = row if dst_stride is None else dst_stride
-    need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
-    if dst.dim() != 1 or not dst.is_contiguous() or not dst.is_cuda or stride < row or dst.numel() < need:
-        raise GrkGpuError("upsample_to: dst flat, %d samples, on a cuda device" % need)
+    op, stride = _flat_dst("upsample_to", "dst flat, %d samples, on a cuda device", dst, dfmt, c, h, w, layout,
+                           dst_stride, not dst.is_cuda, upsample=True)
     for a, (dx, dy) in zip(src, subsampling):
         if dx < 1 or dy < 1:
             break  # the library's refusal
@@ -1898,9 +1919,6 @@ def upsample_to(src, dst, rect, subsampling, layout="chw", dst_stride=None):
                 or (a.numel() and shape[1] > 1 and a.stride(1) != 1)):
             raise GrkGpuError("upsample_to: component plane %s %s, its grid needs %s %s on dst's device"
                               % (tuple(a.shape), a.dtype, shape, dst.dtype))
-    op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout] | LAYOUT_UPSAMPLE, on_device=1)
-    for k in range(1 if il else c):
-        op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
     ptrs = (ctypes.c_void_p * c)(*[a.data_ptr() for a in src])
     ss = (ctypes.c_uint32 * c)(*[a.stride(0) if a.shape[0] > 1 and a.numel() else max(1, a.shape[1]) for a in src])
     dxs = (ctypes.c_uint32 * c)(*[s[0] for s in subsampling])
@@ -1923,20 +1941,16 @@ def convert_to(src, dst, rect, subsampling, prec, sgnd=False, layout="chw", dst_
     x0, y0, x1, y1 = rect
     c, w, h = len(src), x1 - x0, y1 - y0
     ops = _out_ops(colour, out_prec, prec_mode, force_rgb)
-    dt, fmt = _out_format(_out_dtype(dst))
+    dfmt = _out_format(_out_dtype(dst))
     _layout_shape((c, h, w), layout)  # refuses an unknown layout
     cd = lambda v, s: -(-v // s)  # noqa: E731
     if len(subsampling) != c or not 1 <= c <= MAXC or w <= 0 or h <= 0:
         raise GrkGpuError("convert_to: one (dx, dy) per component, 1 .. %d components, a non-empty rect" % MAXC)
     precs, sgnds = _per_comp(prec, c), _per_comp(sgnd, c)
     sdt, sfmt = _out_format(_out_dtype(src[0]))
-    il = layout == "hwc"
     co = len(_out_channels(colour, force_rgb, precs, sgnds, out_prec))  # the channels dst holds
-    row = w * co if il else w
-    stride = row if dst_stride is None else dst_stride
-    need = (h - 1) * stride + row if il else (co * h - 1) * stride + row
-    if dst.dim() != 1 or not dst.is_contiguous() or not dst.is_cuda or stride < row or dst.numel() < need:
-        raise GrkGpuError("convert_to: dst flat, %d samples, on a cuda device" % need)
+    op, stride = _flat_dst("convert_to", "dst flat, %d samples, on a cuda device", dst, dfmt, co, h, w, layout,
+                           dst_stride, not dst.is_cuda, upsample=True)
     for a, (dx, dy) in zip(src, subsampling):
         if dx < 1 or dy < 1:
             break  # the library's refusal
@@ -1945,15 +1959,12 @@ def convert_to(src, dst, rect, subsampling, prec, sgnd=False, layout="chw", dst_
                 or (a.numel() and shape[1] > 1 and a.stride(1) != 1)):
             raise GrkGpuError("convert_to: component plane %s %s, its grid needs %s %s on dst's device"
                               % (tuple(a.shape), a.dtype, shape, src[0].dtype))
-    op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout] | LAYOUT_UPSAMPLE, on_device=1)
-    for k in range(1 if il else co):
-        op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
     ptrs = (ctypes.c_void_p * c)(*[a.data_ptr() for a in src])
     ss = (ctypes.c_uint32 * c)(*[a.stride(0) if a.shape[0] > 1 and a.numel() else max(1, a.shape[1]) for a in src])
     dxs = (ctypes.c_uint32 * c)(*[s[0] for s in subsampling])
     dys = (ctypes.c_uint32 * c)(*[s[1] for s in subsampling])
-    _check(lib().grkgpu_convert_to(ptrs, ss, sfmt, c, dxs, dys, (ctypes.c_uint32 * c)(*precs),
-                                   (ctypes.c_int32 * c)(*sgnds), x0, y0, x1, y1, ctypes.byref(op), stride,
+    pr, sg = _prec_arrays(precs, sgnds, c)
+    _check(lib().grkgpu_convert_to(ptrs, ss, sfmt, c, dxs, dys, pr, sg, x0, y0, x1, y1, ctypes.byref(op), stride,
                                    ctypes.byref(ops) if ops is not None else None, _stream_handle(dst.device)))
     return dst
 
@@ -2078,8 +2089,7 @@ def dcshift_mct_fwd_from(src, fmt, byte_offset, dst, w, h, shifts, mct, irrevers
 def mct_inv_dcshift(planes, prec, sgnd, mct, irreversible):
     c, h, w = planes.shape
     ptrs = (ctypes.c_void_p * c)(*[planes[k].data_ptr() for k in range(c)])
-    pr = (ctypes.c_uint32 * c)(*([prec] * c))
-    sg = (ctypes.c_int32 * c)(*([1 if sgnd else 0] * c))
+    pr, sg = _prec_arrays(prec, sgnd, c)
     _check(lib().grkgpu_mct_inv_dcshift(ptrs, c, w, h, w, pr, sg, mct, 1 if irreversible else 0,
                                         _stream_handle(planes.device)))
     return planes
@@ -2093,23 +2103,14 @@ def mct_inv_dcshift_to(src, dst, w, prec, sgnd, mct, irreversible, layout="chw",
     (default: tight): "chw" plane k from k * h * dst_stride, "hwc" pixels of c
     samples.  Returns dst."""
     c, h, sstride = src.shape
-    dt, fmt = _out_format(_out_dtype(dst))
+    dfmt = _out_format(_out_dtype(dst))
     _layout_shape((c, h, w), layout)  # refuses an unknown layout
-    il = layout == "hwc"
-    row = w * c if il else w
-    stride = row if dst_stride is None else dst_stride
-    need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
-    if (src.dtype != _torch_dtype(np.int32) or not src.is_contiguous() or not src.is_cuda or dst.dim() != 1
-            or not dst.is_contiguous() or dst.device != src.device or w > sstride or stride < row
-            or dst.numel() < need):
-        raise GrkGpuError("mct_inv_dcshift_to: src (c,h,stride >= w) int32, dst flat, %d samples, on src's device"
-                          % need)
-    op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout], on_device=1)
-    for k in range(1 if il else c):
-        op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
+    bad = (src.dtype != _torch_dtype(np.int32) or not src.is_contiguous() or not src.is_cuda
+           or dst.device != src.device or w > sstride)
+    op, stride = _flat_dst("mct_inv_dcshift_to", "src (c,h,stride >= w) int32, dst flat, %d samples, on src's device",
+                           dst, dfmt, c, h, w, layout, dst_stride, bad)
     ptrs = (ctypes.c_void_p * c)(*[src[k].data_ptr() for k in range(c)])
-    pr = (ctypes.c_uint32 * c)(*([prec] * c))
-    sg = (ctypes.c_int32 * c)(*([1 if sgnd else 0] * c))
+    pr, sg = _prec_arrays(prec, sgnd, c)
     _check(lib().grkgpu_mct_inv_dcshift_to(ptrs, c, w, h, sstride, pr, sg, mct, 1 if irreversible else 0,
                                            ctypes.byref(op), stride, _stream_handle(src.device)))
     return dst
@@ -2163,25 +2164,16 @@ def mct_inv_custom_to(src, dst, w, matrix, offsets, prec, sgnd, layout="chw", ds
     offsets (c,) (None: zeros) as read_mct returns them; dst, layout and
     dst_stride as mct_inv_dcshift_to.  Returns dst."""
     c, h, sstride = src.shape
-    dt, fmt = _out_format(_out_dtype(dst))
+    dfmt = _out_format(_out_dtype(dst))
     _layout_shape((c, h, w), layout)  # refuses an unknown layout
-    il = layout == "hwc"
-    row = w * c if il else w
-    stride = row if dst_stride is None else dst_stride
-    need = (h - 1) * stride + row if il else (c * h - 1) * stride + row
     m = np.ascontiguousarray(matrix, dtype=np.float32)
     o = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int32)
-    if (src.dtype != _torch().float32 or not src.is_contiguous() or not src.is_cuda or dst.dim() != 1
-            or not dst.is_contiguous() or dst.device != src.device or w > sstride or stride < row
-            or dst.numel() < need or m.shape != (c, c) or (o is not None and o.shape != (c,))):
-        raise GrkGpuError("mct_inv_custom_to: src (c,h,stride >= w) float32, matrix (c,c), offsets (c,), dst flat, "
-                          "%d samples, on src's device" % need)
-    op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout], on_device=1)
-    for k in range(1 if il else c):
-        op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
+    bad = (src.dtype != _torch().float32 or not src.is_contiguous() or not src.is_cuda or dst.device != src.device
+           or w > sstride or m.shape != (c, c) or (o is not None and o.shape != (c,)))
+    op, stride = _flat_dst("mct_inv_custom_to", "src (c,h,stride >= w) float32, matrix (c,c), offsets (c,), dst flat, "
+                           "%d samples, on src's device", dst, dfmt, c, h, w, layout, dst_stride, bad)
     ptrs = (ctypes.c_void_p * c)(*[src[k].data_ptr() for k in range(c)])
-    pr = (ctypes.c_uint32 * c)(*_per_comp(prec, c))
-    sg = (ctypes.c_int32 * c)(*[1 if v else 0 for v in _per_comp(sgnd, c)])
+    pr, sg = _prec_arrays(prec, sgnd, c)
     _check(lib().grkgpu_mct_inv_custom_to(ptrs, c, w, h, sstride, m.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                           None if o is None else o.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                           pr, sg, ctypes.byref(op), stride, _stream_handle(src.device)))
@@ -2199,18 +2191,12 @@ def palette_to(src, dst, w, prec, sgnd, chan_comp, chan_pcol, chan_prec, table=N
     as mct_inv_dcshift_to, over the channels.  Returns dst."""
     c, h, sstride = src.shape
     nch = len(chan_comp)
-    dt, fmt = _out_format(_out_dtype(dst))
+    dfmt = _out_format(_out_dtype(dst))
     _layout_shape((nch, h, w), layout)  # refuses an unknown layout
-    il = layout == "hwc"
-    row = w * nch if il else w
-    stride = row if dst_stride is None else dst_stride
-    need = (h - 1) * stride + row if il else (nch * h - 1) * stride + row
-    torch = _torch()
-    if (src.dtype != torch.int32 or not src.is_contiguous() or not src.is_cuda or dst.dim() != 1
-            or not dst.is_contiguous() or dst.device != src.device or w > sstride or stride < row
-            or dst.numel() < need or len(chan_pcol) != nch or len(chan_prec) != nch):
-        raise GrkGpuError("palette_to: src (c,h,stride >= w) int32, one comp / pcol / prec per channel, dst flat, "
-                          "%d samples, on src's device" % need)
+    bad = (src.dtype != _torch().int32 or not src.is_contiguous() or not src.is_cuda or dst.device != src.device
+           or w > sstride or len(chan_pcol) != nch or len(chan_prec) != nch)
+    op, stride = _flat_dst("palette_to", "src (c,h,stride >= w) int32, one comp / pcol / prec per channel, dst flat, "
+                           "%d samples, on src's device", dst, dfmt, nch, h, w, layout, dst_stride, bad)
     ne = npc = 0
     tp = None
     if table is not None:
@@ -2218,12 +2204,8 @@ def palette_to(src, dst, w, prec, sgnd, chan_comp, chan_pcol, chan_prec, table=N
             raise GrkGpuError("palette_to: table (NE, NPC) of 16-bit entries on src's device")
         ne, npc = table.shape
         tp = table.data_ptr()
-    op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout], on_device=1)
-    for k in range(1 if il else nch):
-        op.planes[k] = dst.data_ptr() + k * h * stride * dt.itemsize
     ptrs = (ctypes.c_void_p * c)(*[src[k].data_ptr() for k in range(c)])
-    pr = (ctypes.c_uint32 * c)(*_per_comp(prec, c))
-    sg = (ctypes.c_int32 * c)(*[1 if v else 0 for v in _per_comp(sgnd, c)])
+    pr, sg = _prec_arrays(prec, sgnd, c)
     cc = (ctypes.c_uint32 * nch)(*[int(v) for v in chan_comp])
     cpc = (ctypes.c_int32 * nch)(*[-1 if v is None else int(v) for v in chan_pcol])
     cpr = (ctypes.c_uint32 * nch)(*[int(v) for v in chan_prec])

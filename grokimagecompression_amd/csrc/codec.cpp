@@ -3700,10 +3700,38 @@ struct DecT1Stage {
     }
 };
 
+// the sample range of a precision (1 .. 31) and sign, and the DC shift into it
+struct SampleRange { int32_t shift, mn, mx; };
+static SampleRange sample_range(uint32_t prec, int32_t sgnd) {
+    const int32_t half = (int32_t)(1u << (prec - 1));
+    if (sgnd) return {0, -half, half - 1};
+    return {half, 0, (int32_t)((1u << prec) - 1)};
+}
+// ... as component k of a launch's clamp bounds (and shifts)
+static void set_range(uint32_t k, uint32_t prec, int32_t sgnd, ShiftArr &mn, ShiftArr &mx, ShiftArr *sh = nullptr) {
+    const SampleRange r = sample_range(prec, sgnd);
+    mn.v[k] = r.mn; mx.v[k] = r.mx;
+    if (sh) sh->v[k] = r.shift;
+}
 // the sample range a component's decoded values are clamped to
 static void clamp_bounds(const CodingParams &cp, uint32_t k, int32_t &mn, int32_t &mx) {
-    mn = cp.sgnd[k] ? -(1 << (cp.prec[k] - 1)) : 0;
-    mx = cp.sgnd[k] ? (1 << (cp.prec[k] - 1)) - 1 : (1 << cp.prec[k]) - 1;
+    const SampleRange r = sample_range(cp.prec[k], cp.sgnd[k]);
+    mn = r.mn; mx = r.mx;
+}
+// a sample format holds every value of a precision and sign
+static bool fmt_holds(int32_t fmt, uint32_t prec, int32_t sgnd) {
+    if (fmt == SMP_I32) return true;
+    return (sgnd != 0) == (fmt == SMP_I8 || fmt == SMP_I16) && prec <= 8 * sample_bytes(fmt);
+}
+// The n destination planes of a store in format fmt (interleaved: the one
+// plane of pixels), bound to d where given; a null or misaligned one refuses.
+static int bind_dst(void *const *planes, uint32_t n, int32_t fmt, DstPlanes *d = nullptr) {
+    for (uint32_t k = 0; k < n; ++k) {
+        if (!planes[k] || (uintptr_t)planes[k] % sample_bytes(fmt))
+            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+        if (d) d->p[k] = planes[k];
+    }
+    return GRKGPU_OK;
 }
 
 // Samples nothing decodes are zero (the plain case: no channel map, no colour
@@ -4410,7 +4438,7 @@ struct StorePlan {
     bool add_store(int32_t fmt, bool il, const StoreJob &j) {
         return plain.add({fmt, il, 0}, j, store_job_wgs(j, sample_bytes(fmt), il));
     }
-    // the op class of a store on one grid is launch_inv_ops' choice
+    // the op class of a store on one grid is launch_mct_inv_dcshift_ops' choice
     bool add_conv_store(int32_t fmt, bool il, const OutOps &o, StoreJob j, uint32_t ops_index) {
         j.ops = ops_index;
         const int cls = o.col == COL_EYCC ? 3 : (o.col == COL_CMYK ? 4 : (o.sycc ? 2 : 1));
@@ -4456,7 +4484,7 @@ struct StorePlan {
         if (e == hipSuccess)
             e = conv.launch(dev, p.rec[1], p.fst[1], nl,
                             [&](const StoreJob *j, const uint32_t *first, uint32_t n, uint32_t nwg, const JobKey &k) {
-                                return launch_store_jobs_ops(j, first, n, nwg, dops, k.fmt, k.mode != 0, k.cls, s);
+                                return launch_store_jobs(j, first, n, nwg, k.fmt, k.mode != 0, s, k.cls, dops);
                             });
         for (size_t i = 0; e == hipSuccess && i < singles.size(); ++i) {
             const TileStore &ts = singles[i];
@@ -5608,9 +5636,7 @@ extern "C" int grkgpu_mct_inv_dcshift(int32_t *const *planes, uint32_t numcomps,
     ShiftArr sh{}, mn{}, mx{};
     for (uint32_t k = 0; k < numcomps; ++k) {
         p.p[k] = planes[k];
-        sh.v[k] = sgnd[k] ? 0 : (1 << (prec[k] - 1));
-        if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
-        else { mn.v[k] = 0; mx.v[k] = (1 << prec[k]) - 1; }
+        set_range(k, prec[k], sgnd[k], mn, mx, &sh);
     }
     HIPCHK(launch_mct_inv_dcshift(p, stride, w, h, p, stride, numcomps, sh, mn, mx, mct, irreversible ? 0xFFFF : 0,
                                   (hipStream_t)stream));
@@ -5626,7 +5652,6 @@ extern "C" int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t num
     if (dst->layout & GRKGPU_LAYOUT_UPSAMPLE) return set_err(GRKGPU_EINVAL, "unknown layout");
     const bool il = dst->layout == GRKGPU_LAYOUT_INTERLEAVED;
     const int32_t fmt = (int32_t)dst->sample_fmt;
-    const uint32_t sb = sample_bytes(fmt);
     if (!src || !prec || !sgnd || numcomps < 1 || numcomps > 16 || src_stride < w ||
         (uint64_t)dst_stride < (uint64_t)w * (il ? numcomps : 1))
         return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
@@ -5635,19 +5660,13 @@ extern "C" int grkgpu_mct_inv_dcshift_to(const int32_t *const *src, uint32_t num
     ShiftArr sh{}, mn{}, mx{};
     for (uint32_t k = 0; k < numcomps; ++k) {
         if (prec[k] < 1 || prec[k] > 31 || !src[k]) return set_err(GRKGPU_EINVAL, "bad arguments");
-        const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
-        if (fmt != SMP_I32 && ((sgnd[k] != 0) != sg || prec[k] > 8 * sb))
+        if (!fmt_holds(fmt, prec[k], sgnd[k]))
             return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
         p.p[k] = const_cast<int32_t *>(src[k]);
-        sh.v[k] = sgnd[k] ? 0 : (1 << (prec[k] - 1));
-        if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
-        else { mn.v[k] = 0; mx.v[k] = (int32_t)((1u << prec[k]) - 1); }
+        set_range(k, prec[k], sgnd[k], mn, mx, &sh);
     }
-    for (uint32_t k = 0; k < (il ? 1u : numcomps); ++k) {
-        if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
-            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
-        d.p[k] = dst->planes[k];
-    }
+    rc = bind_dst(dst->planes, il ? 1u : numcomps, fmt, &d);
+    if (rc) return rc;
     rc = check_device(-1);
     if (rc) return rc;
     HIPCHK(launch_mct_inv_dcshift_to(p, src_stride, w, h, d, fmt, il, dst_stride, numcomps, sh, mn, mx, mct,
@@ -5683,8 +5702,7 @@ extern "C" int grkgpu_mct_inv_dcshift_jobs_to(const grkgpu_store_job *jobs, uint
             if (q.min[k] > q.max[k] || q.min[k] < lo || q.max[k] > hi)
                 return set_err(GRKGPU_EINVAL, "sample format does not hold the component's range");
         }
-        for (uint32_t k = 0; k < (il ? 1u : nc); ++k)
-            if (!q.dst[k] || (uintptr_t)q.dst[k] % sb) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+        if (int rc = bind_dst(q.dst, il ? 1u : nc, fmt)) return rc;
         if (!stores.add_store(fmt, il, j)) stores.singles.push_back(tile_store_of(j, fmt, il));
     }
     int rc = check_device(-1);
@@ -5744,7 +5762,6 @@ extern "C" int grkgpu_mct_inv_custom_to(const float *const *src, uint32_t numcom
     if (dst->layout & GRKGPU_LAYOUT_UPSAMPLE) return set_err(GRKGPU_EINVAL, "unknown layout");
     const bool il = dst->layout == GRKGPU_LAYOUT_INTERLEAVED;
     const int32_t fmt = (int32_t)dst->sample_fmt;
-    const uint32_t sb = sample_bytes(fmt);
     if (!src || !matrix || !prec || !sgnd || numcomps < 1 || numcomps > 16 || src_stride < w ||
         (uint64_t)dst_stride < (uint64_t)w * (il ? numcomps : 1))
         return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
@@ -5758,19 +5775,14 @@ extern "C" int grkgpu_mct_inv_custom_to(const float *const *src, uint32_t numcom
     for (uint32_t k = 0; k < numcomps; ++k) {
         if (prec[k] < 1 || prec[k] > 31 || !src[k] || (uintptr_t)src[k] % 4)
             return set_err(GRKGPU_EINVAL, "bad arguments");
-        const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
-        if (fmt != SMP_I32 && ((sgnd[k] != 0) != sg || prec[k] > 8 * sb))
+        if (!fmt_holds(fmt, prec[k], sgnd[k]))
             return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
         p.p[k] = reinterpret_cast<int32_t *>(const_cast<float *>(src[k]));
         off.v[k] = offsets ? offsets[k] : 0;
-        if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
-        else { mn.v[k] = 0; mx.v[k] = (int32_t)((1u << prec[k]) - 1); }
+        set_range(k, prec[k], sgnd[k], mn, mx);
     }
-    for (uint32_t k = 0; k < (il ? 1u : numcomps); ++k) {
-        if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
-            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
-        d.p[k] = dst->planes[k];
-    }
+    rc = bind_dst(dst->planes, il ? 1u : numcomps, fmt, &d);
+    if (rc) return rc;
     rc = check_device(-1);
     if (rc) return rc;
     HIPCHK(launch_mct_inv_custom(p, src_stride, w, h, d, fmt, il, dst_stride, numcomps, m, off, mn, mx, nullptr,
@@ -5788,7 +5800,6 @@ extern "C" int grkgpu_palette_to(const int32_t *const *src, uint32_t numcomps, u
     if (dst->layout & GRKGPU_LAYOUT_UPSAMPLE) return set_err(GRKGPU_EINVAL, "unknown layout");
     const bool il = dst->layout == GRKGPU_LAYOUT_INTERLEAVED;
     const int32_t fmt = (int32_t)dst->sample_fmt;
-    const uint32_t sb = sample_bytes(fmt);
     if (!src || !prec || !sgnd || !chan_comp || !chan_pcol || !chan_prec || numcomps < 1 || numcomps > 16 ||
         numchannels < 1 || numchannels > 16 || src_stride < w ||
         (uint64_t)dst_stride < (uint64_t)w * (il ? numchannels : 1))
@@ -5800,30 +5811,25 @@ extern "C" int grkgpu_palette_to(const int32_t *const *src, uint32_t numcomps, u
     for (uint32_t k = 0; k < numcomps; ++k) {
         if (prec[k] < 1 || prec[k] > 31 || !src[k] || (uintptr_t)src[k] % 4) return set_err(GRKGPU_EINVAL, "bad arguments");
         p.p[k] = const_cast<int32_t *>(src[k]);
-        if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
-        else { sh.v[k] = 1 << (prec[k] - 1); mn.v[k] = 0; mx.v[k] = (int32_t)((1u << prec[k]) - 1); }
+        set_range(k, prec[k], sgnd[k], mn, mx, &sh);
     }
     PalMap map{};
     map.nch = numchannels;
     map.ne = table ? ne : 0;
     map.npc = table ? npc : 0;
-    const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
     for (uint32_t ch = 0; ch < numchannels; ++ch) {
         if (chan_comp[ch] >= numcomps || chan_pcol[ch] >= (int32_t)map.npc || chan_prec[ch] < 1 || chan_prec[ch] > 31)
             return set_err(GRKGPU_EINVAL, "channel map outside the components / the palette");
         const bool chs = chan_pcol[ch] < 0 && sgnd[chan_comp[ch]];
         const uint32_t chp = chan_pcol[ch] < 0 ? std::max(chan_prec[ch], prec[chan_comp[ch]]) : chan_prec[ch];
-        if (fmt != SMP_I32 && (chs != sg || chp > 8 * sb))
+        if (!fmt_holds(fmt, chp, chs))
             return set_err(GRKGPU_EINVAL, "sample format does not hold the channel's precision / signedness");
         map.comp[ch] = (uint8_t)chan_comp[ch];
         map.pcol[ch] = (int8_t)(chan_pcol[ch] < 0 ? -1 : chan_pcol[ch]);
     }
     set_pal_used(map);
-    for (uint32_t k = 0; k < (il ? 1u : numchannels); ++k) {
-        if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
-            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
-        d.p[k] = dst->planes[k];
-    }
+    rc = bind_dst(dst->planes, il ? 1u : numchannels, fmt, &d);
+    if (rc) return rc;
     rc = check_device(-1);
     if (rc) return rc;
     HIPCHK(launch_palette(p, src_stride, w, h, d, fmt, il, dst_stride, numcomps, sh, mn, mx, 0, 0, map, table, nullptr,
@@ -5857,11 +5863,8 @@ extern "C" int grkgpu_upsample_to(const void *const *src, const uint32_t *src_st
         pl.c[k] = UpComp{src[k], src_stride[k], (int32_t)cr.x0, (int32_t)cr.y0, (int32_t)cr.x0, (int32_t)cr.y0,
                          (uint8_t)dx[k], (uint8_t)dy[k], 0, 0, 0, 0, 0};
     }
-    for (uint32_t k = 0; k < (il ? 1u : numcomps); ++k) {
-        if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
-            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
-        d.p[k] = dst->planes[k];
-    }
+    rc = bind_dst(dst->planes, il ? 1u : numcomps, fmt, &d);
+    if (rc) return rc;
     rc = check_device(-1);
     if (rc) return rc;
     HIPCHK(launch_upsample_to(pl, numcomps, x0, y0, x1 - x0, y1 - y0, d, fmt, il, dst_stride, (hipStream_t)stream));
@@ -5880,7 +5883,7 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
     if (src_fmt > GRKGPU_SAMPLE_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
     const bool il = (dst->layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED;
     const int32_t fmt = (int32_t)dst->sample_fmt, sfmt = (int32_t)src_fmt;
-    const uint32_t sb = sample_bytes(fmt), ssb = sample_bytes(sfmt);
+    const uint32_t ssb = sample_bytes(sfmt);
     if (!src || !src_stride || !dx || !dy || !prec || !sgnd || numcomps < 1 || numcomps > 16 || x1 <= x0 ||
         y1 <= y0 || x1 > 0x7fffffffu || y1 > 0x7fffffffu)
         return set_err(GRKGPU_EINVAL, "bad arguments");
@@ -5900,8 +5903,7 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
         if (dx[k] < 1 || dx[k] > 255 || dy[k] < 1 || dy[k] > 255)
             return set_err(GRKGPU_EINVAL, "bad arguments (dx / dy must be 1 .. 255)");
         if (prec[k] < 1 || prec[k] > 31) return set_err(GRKGPU_EINVAL, "bad arguments (prec must be 1 .. 31)");
-        const bool sg = sfmt == SMP_I8 || sfmt == SMP_I16;
-        if (sfmt != SMP_I32 && ((sgnd[k] != 0) != sg || prec[k] > 8 * ssb))
+        if (!fmt_holds(sfmt, prec[k], sgnd[k]))
             return set_err(GRKGPU_EINVAL, "source format does not hold the component's precision / signedness");
         full = full && dx[k] == 1 && dy[k] == 1;
     }
@@ -5924,11 +5926,9 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
     if (rc) return rc;
     UpPlan pl{};
     DstPlanes d{};
-    for (uint32_t k = 0; k < no; ++k) {
-        const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
-        if (fmt != SMP_I32 && ((osgnd[k] != 0) != sg || oprec[k] > 8 * sb))
+    for (uint32_t k = 0; k < no; ++k)
+        if (!fmt_holds(fmt, oprec[k], osgnd[k]))
             return set_err(GRKGPU_EINVAL, "sample format does not hold the output precision / signedness");
-    }
     for (uint32_t k = 0; k < numcomps; ++k) {
         const Rect cr = comp_rect({x0, y0, x1, y1}, dx[k], dy[k]);
         if (src_stride[k] < cr.w()) return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
@@ -5938,11 +5938,8 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
         pl.c[k] = UpComp{src[k], src_stride[k], (int32_t)cr.x0, (int32_t)cr.y0, (int32_t)cr.x0, (int32_t)cr.y0,
                          (uint8_t)dx[k], (uint8_t)dy[k], (uint8_t)(UPCOMP_FIN + sfmt), 0, 0, 0, 0};
     }
-    for (uint32_t k = 0; k < (il ? 1u : no); ++k) {
-        if (!dst->planes[k] || (uintptr_t)dst->planes[k] % sb)
-            return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
-        d.p[k] = dst->planes[k];
-    }
+    rc = bind_dst(dst->planes, il ? 1u : no, fmt, &d);
+    if (rc) return rc;
     if (forced) {
         // channel 0 three times, a second one behind it: the palette kernels' direct map on finished int32 planes
         for (uint32_t k = 0; k < numcomps; ++k) full = full && src_stride[k] == src_stride[0];
@@ -5958,8 +5955,7 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
         set_pal_used(map);
         for (uint32_t k = 0; k < numcomps; ++k) {
             p.p[k] = (int32_t *)const_cast<void *>(src[k]);
-            if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
-            else { mn.v[k] = 0; mx.v[k] = (int32_t)((1u << prec[k]) - 1); }
+            set_range(k, prec[k], sgnd[k], mn, mx);
         }
         HIPCHK(launch_palette(p, src_stride[0], x1 - x0, y1 - y0, d, fmt, il, dst_stride, numcomps, sh, mn, mx, 0, 0, map,
                               nullptr, &dops, (hipStream_t)stream));
@@ -5975,8 +5971,7 @@ extern "C" int grkgpu_convert_to(const void *const *src, const uint32_t *src_str
         uint32_t ss = src_stride[0];
         for (uint32_t k = 0; k < numcomps; ++k) {
             p.p[k] = (int32_t *)const_cast<void *>(src[k]);
-            if (sgnd[k]) { mn.v[k] = -(1 << (prec[k] - 1)); mx.v[k] = (1 << (prec[k] - 1)) - 1; }
-            else { mn.v[k] = 0; mx.v[k] = (int32_t)((1u << prec[k]) - 1); }
+            set_range(k, prec[k], sgnd[k], mn, mx);
             full = full && src_stride[k] == ss;
         }
         if (full) {
@@ -6028,7 +6023,6 @@ extern "C" int grkgpu_convert_jobs_to(const grkgpu_convert_job *jobs, uint32_t n
     if (!jobs) return set_err(GRKGPU_EINVAL, "null argument");
     const int32_t fmt = (int32_t)sample_fmt;
     const bool il = layout == GRKGPU_LAYOUT_INTERLEAVED;
-    const uint32_t sb = sample_bytes(fmt);
     StorePlan T;
     for (uint32_t i = 0; i < n; ++i) {
         const grkgpu_convert_job &q = jobs[i];
@@ -6052,8 +6046,7 @@ extern "C" int grkgpu_convert_jobs_to(const grkgpu_convert_job *jobs, uint32_t n
             if (!range_prec(u.min, u.max, prec[k], sgnd[k]))
                 return set_err(GRKGPU_EINVAL, "min / max must be the range of a precision and sign");
             const int32_t sf = raw ? (int32_t)SMP_I32 : (int32_t)(u.kind - GRKGPU_SRC_SAMPLES);
-            const bool ssg = sf == SMP_I8 || sf == SMP_I16;
-            if (sf != SMP_I32 && ((sgnd[k] != 0) != ssg || prec[k] > 8 * sample_bytes(sf)))
+            if (!fmt_holds(sf, prec[k], sgnd[k]))
                 return set_err(GRKGPU_EINVAL, "source format does not hold the component's precision / signedness");
             if ((uintptr_t)u.src % sample_bytes(sf)) return set_err(GRKGPU_EINVAL, "misaligned source");
             if (u.zx0 < u.gx0 || u.zy0 < u.gy0 || u.gx0 < 0 || u.gy0 < 0)
@@ -6073,17 +6066,15 @@ extern "C" int grkgpu_convert_jobs_to(const grkgpu_convert_job *jobs, uint32_t n
         int32_t osgnd[GRKGPU_MAX_COMPS];
         rc = resolve_out_ops(&q.ops, nc, prec, sgnd, dx, dy, dops, no, oprec, osgnd);
         if (rc) return rc;
-        for (uint32_t k = 0; k < no; ++k) {
-            const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
-            if (fmt != SMP_I32 && ((osgnd[k] != 0) != sg || oprec[k] > 8 * sb))
+        for (uint32_t k = 0; k < no; ++k)
+            if (!fmt_holds(fmt, oprec[k], osgnd[k]))
                 return set_err(GRKGPU_EINVAL, "sample format does not hold the output precision / signedness");
-        }
         if (empty) continue;
         const uint32_t w = q.x1 - q.x0;
         if ((uint64_t)q.dst_stride < (uint64_t)w * (il ? no : 1))
             return set_err(GRKGPU_EINVAL, "bad arguments (strides must hold a row)");
-        for (uint32_t k = 0; k < (il ? 1u : no); ++k)
-            if (!q.dst[k] || (uintptr_t)q.dst[k] % sb) return set_err(GRKGPU_EINVAL, "null or misaligned output plane");
+        rc = bind_dst(q.dst, il ? 1u : no, fmt);
+        if (rc) return rc;
         const uint32_t ops_at = (uint32_t)T.ops.size();
         T.ops.push_back(dops);
         if (grid1) {

@@ -99,11 +99,13 @@ hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uin
                                      const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
                                      uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn, const ShiftArr &mx,
                                      int32_t mct, int32_t irrev, hipStream_t s);
-// launch_mct_inv_dcshift_to for a table of tiles in one launch (the batch
-// decode, grkgpu_mct_inv_dcshift_jobs_to): each tile's arguments as a record
-// in device memory (grkgpu_store_job's layout; static_assert in codec.cpp),
-// 1 .. 4 components, all jobs of a launch in one sample format and layout.
-// irrev: bit k set = component k holds 9/7 samples.
+// launch_mct_inv_dcshift_to / _ops (below) for a table of tiles in one launch
+// (the batch decode, grkgpu_mct_inv_dcshift_jobs_to / grkgpu_convert_jobs_to):
+// each tile's arguments as a record in device memory (grkgpu_store_job's
+// layout; static_assert in codec.cpp), 1 .. 4 components, all jobs of a launch
+// in one sample format, layout and op class.  irrev: bit k set = component k
+// holds 9/7 samples.  One kernel template, k_store_jobs, runs every class: the
+// per-tile kernels' store bodies behind a workgroup-to-job search.
 struct StoreJob {
     const int32_t *src[4];  // component k's coefficients at the tile's first stored sample
     void *dst[4];           // planar: plane k there; interleaved: dst[0]
@@ -111,11 +113,11 @@ struct StoreJob {
     uint32_t ncomp;
     int32_t mct;
     uint32_t irrev;
-    uint32_t ops;  // launch_store_jobs_ops: the job's entry of the OutOps table (launch_store_jobs does not read it)
+    uint32_t ops;  // op != 0: the job's entry of the OutOps table (not read otherwise)
     int32_t shift[4], mn[4], mx[4];
 };
 // threads along a row of a job: the lead run and the runs of 16 bytes
-// (launch_inv_to's), or the pixels of a two-component interleaved tile
+// (launch_inv's), or the pixels of a two-component interleaved tile
 __host__ __device__ inline uint32_t store_job_row_threads(uint32_t w, uint32_t ncomp, uint32_t sb, bool interleaved) {
     if (interleaved && ncomp == 2) return w;
     const uint32_t n = 16 / sb;
@@ -128,9 +130,14 @@ inline uint64_t store_job_wgs(const StoreJob &j, uint32_t sb, bool interleaved) 
     return ((uint64_t)store_job_row_threads(j.w, j.ncomp, sb, interleaved) * j.h + 255) / 256;
 }
 constexpr uint64_t STORE_JOB_MAX_WGS = (uint64_t)1 << 24;
-// first: njobs + 1 first-workgroup numbers (prefix sums of store_job_wgs), nwg = first[njobs]
+// first: njobs + 1 first-workgroup numbers (prefix sums of store_job_wgs), nwg = first[njobs].
+// op: the jobs' op class (OP_* of kernels.hip: 0 none, 1 precision only, 2 sYCC, 3 eYCC, 4 CMYK); op != 0 takes
+// ops, the device table of OutOps (below) uploaded with the jobs -- one per item, a job that converts nothing
+// pointing at an all-zero entry.  sYCC / eYCC jobs have three components, CMYK jobs four (three channels
+// stored); the row threads are store_job_row_threads' either way.
+struct OutOps;
 hipError_t launch_store_jobs(const StoreJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg, int32_t fmt,
-                             bool interleaved, hipStream_t s);
+                             bool interleaved, hipStream_t s, int op = 0, const OutOps *ops = nullptr);
 // launch_dcshift_mct_fwd / _from for a table of tiles in one launch (the batch
 // encode, grkgpu_dcshift_mct_fwd_jobs): each tile's arguments as a record in
 // device memory (grkgpu_load_job's layout; static_assert in codec.cpp), 1 .. 4
@@ -239,19 +246,9 @@ hipError_t launch_mct_inv_dcshift_ops(const PlanePtrs &src, uint32_t sstride, ui
 hipError_t launch_upsample_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
                                const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
                                const OutOps &ops, hipStream_t s);
-// The converting stores for a table of jobs in one launch (the batch decode
-// with output ops, grkgpu_convert_jobs_to).  The ops of every job are an entry
-// of a device table of OutOps uploaded with the jobs (one per item; a job that
-// converts nothing points at an all-zero entry), uniform over its workgroups.
-//
-// launch_store_jobs_ops is launch_mct_inv_dcshift_ops for a table: StoreJob
-// with its `ops` index, all jobs of a launch in one sample format, layout and
-// op class (OP_* of kernels.hip: 1 precision only, 2 sYCC, 3 eYCC, 4 CMYK).
-// sYCC / eYCC jobs have three components, CMYK jobs four (three channels
-// stored); the row threads are store_job_row_threads' either way.
-hipError_t launch_store_jobs_ops(const StoreJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg,
-                                 const OutOps *ops, int32_t fmt, bool interleaved, int op, hipStream_t s);
-// launch_upsample_ops for a table: the rectangle [X0, x1) x [Y0, y1) of the
+// launch_upsample_ops for a table of jobs in one launch (the batch decode with
+// output ops, grkgpu_convert_jobs_to; the ops of every job an entry of
+// launch_store_jobs' table, uniform over its workgroups): the rectangle [X0, x1) x [Y0, y1) of the
 // reference grid from up to four UpComps (a finished one always carries its
 // format, raw = UPCOMP_FIN + f), dst at the rectangle's first pixel.
 // grkgpu_convert_job's layout up to its ops (static_assert in codec.cpp).
@@ -263,7 +260,7 @@ struct ConvJob {
     int32_t mct_;  // (grkgpu_convert_job.mct: such a job runs as a StoreJob)
     uint32_t ops;
 };
-// the two thread shapes, by launch_up_ops' rule: the 16-byte runs of
+// the two thread shapes, by launch_upsample_ops' rule: the 16-byte runs of
 // k_upsample_420 (fast) or k_upsample_any's thread per pixel
 __host__ __device__ inline bool conv_job_fast(const UpComp *c, uint32_t ncomp, int32_t fmt, int32_t col) {
     return (fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16) && !col && ncomp == 3 && c[0].dx == 1 &&

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace grkgpu {
 
@@ -460,34 +461,53 @@ __device__ __forceinline__ void cmyk_planar_run(const PlanePtrs &src, size_t si,
     for (int j = 0; j < 3; ++j) store_packed<T>((T *)dst.p[j] + di, pk[j], n);
 }
 
-// planar: dst.p[c] = plane c (samples T), rows dstride samples apart
-template <typename T, int OP = 0, typename... O>
-__global__ void k_mct_inv_dcshift_planar(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
-                                         uint32_t dstride, uint32_t ncomp, ShiftArr shift, ShiftArr minv,
-                                         ShiftArr maxv, int32_t mct, int32_t irrev, O... o) {
-    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
-    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
+// The three bodies of that store, shared by the per-tile kernels below (the
+// pixel run excepted) and the job-table kernel k_store_jobs: thread t of row y finishes its run and
+// stores it.  Every argument is uniform over the workgroup.  KMAX is the
+// component count the caller's src / dst hold: GRK_MAX_COMPS for kernel
+// arguments, which the loops index at run time, or 4 for a StoreJob's, which
+// sit in scalar registers and so take static indices only (the loops unrolled
+// behind uniform guards).  ops: null exactly when OP = 0.
+//
+// component k outside the MCT and the colour conversion: its n samples at si,
+// finished, through the precision op of channel ch, to that channel's plane
+// at di (each address is formed where it is used, not before)
+template <typename T, int OP>
+__device__ __forceinline__ void store_plain_run(const PlanePtrs &src, size_t si, const DstPlanes &dst, size_t di, int n,
+                                                uint32_t k, uint32_t ch, int32_t irrev, const ShiftArr &shift,
+                                                const ShiftArr &minv, const ShiftArr &maxv,
+                                                [[maybe_unused]] const OutOps *ops) {
     constexpr int N = NarrowRun<T>::N;
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (y >= th) return;
+    int32_t a[N];
+    load_run<N>(src.p[k] + si, n, a);
+    inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+    if constexpr (OP != 0) prec_run<N>(a, ops->pc[ch]);
+    store_samples<T, N>((T *)dst.p[ch] + di, a, n);
+}
+
+// planar: dst.p[c] = plane c (samples T), rows dstride samples apart
+template <typename T, int OP, int KMAX = GRK_MAX_COMPS>
+__device__ __forceinline__ void store_planar_run(const PlanePtrs &src, uint32_t sstride, uint32_t tw,
+                                                 const DstPlanes &dst, uint32_t dstride, uint32_t ncomp, uint32_t y, uint32_t t,
+                                                 const ShiftArr &shift, const ShiftArr &minv, const ShiftArr &maxv,
+                                                 int32_t mct, int32_t irrev, [[maybe_unused]] const OutOps *ops) {
+    constexpr int N = NarrowRun<T>::N;
     const size_t drow = (size_t)y * dstride;
     uint32_t x0;
     const int n = run_of<N>((uintptr_t)((T *)dst.p[0] + drow), sizeof(T), t, tw, x0);
     if (n <= 0) return;
     const size_t si = (size_t)y * sstride + x0, di = drow + x0;
-    uint32_t c0 = 0;
     if constexpr (OP == OP_CMYK) {  // four or more components: channels R, G, B, then components 4 ..
         cmyk_planar_run<T>(src, si, dst, di, n, shift, minv, maxv, mct, irrev, *ops);
-        for (uint32_t k = 4; k < ncomp; ++k) {
-            int32_t a[N];
-            load_run<N>(src.p[k] + si, n, a);
-            inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-            prec_run<N>(a, ops->pc[k - 1]);
-            store_samples<T, N>((T *)dst.p[k - 1] + di, a, n);
-        }
+        if constexpr (KMAX > 4)
+            for (uint32_t k = 4; k < ncomp; ++k)
+                store_plain_run<T, OP>(src, si, dst, di, n, k, k - 1, irrev, shift, minv, maxv, ops);
         return;
     }
-    if (op_ycc(OP) || (mct && ncomp >= 3)) {  // (sYCC / eYCC: exactly three components, with or without an MCT)
+    // (sYCC / eYCC: exactly three components, with or without an MCT)
+    const bool three = op_ycc(OP) || (mct && ncomp >= 3);
+    uint32_t c0 = 0;
+    if (three) {
         int32_t a[N], b[N], c[N];
         load_run<N>(src.p[0] + si, n, a);
         load_run<N>(src.p[1] + si, n, b);
@@ -510,29 +530,153 @@ __global__ void k_mct_inv_dcshift_planar(PlanePtrs src, uint32_t sstride, uint32
         store_samples<T, N>((T *)dst.p[2] + di, c, n);
         c0 = 3;
     }
-    for (uint32_t k = c0; k < ncomp; ++k) {
-        int32_t a[N];
-        load_run<N>(src.p[k] + si, n, a);
-        inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-        if constexpr (OP != 0) prec_run<N>(a, ops->pc[k]);
-        store_samples<T, N>((T *)dst.p[k] + di, a, n);
+    if constexpr (KMAX > 4) {
+        // store_plain_run's statements, in place: a call from this loop costs the 8-bit
+        // precision-op kernels a wave per SIMD (74 VGPRs for 71 in the compiler's report)
+        for (uint32_t k = c0; k < ncomp; ++k) {
+            int32_t a[N];
+            load_run<N>(src.p[k] + si, n, a);
+            inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+            if constexpr (OP != 0) prec_run<N>(a, ops->pc[k]);
+            store_samples<T, N>((T *)dst.p[k] + di, a, n);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if ((uint32_t)k < ncomp && !(three && k < 3))
+                store_plain_run<T, OP>(src, si, dst, di, n, k, k, irrev, shift, minv, maxv, ops);
     }
 }
 
-// interleaved, NC = 3 or 4 components: sample (y, x, c) at dst.p[0][y * dstride + x * NC + c]
-template <typename T, int NC, int OP = 0, typename... O>
-__global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
-                                         uint32_t dstride, ShiftArr shift, ShiftArr minv, ShiftArr maxv, int32_t mct,
-                                         int32_t irrev, O... o) {
-    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
-    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
+// interleaved, NC = 3 or 4 components (OP_CMYK: 4 or 5, one channel fewer):
+// sample (y, x, c) at dst0[y * dstride + x * NCH + c].  The job-table kernel's
+// form of k_mct_inv_dcshift_pixels' body below, which has to keep the
+// statements in the kernel (see there).
+template <typename T, int NC, int OP>
+__device__ __forceinline__ void store_pixels_run(const PlanePtrs &src, uint32_t sstride, uint32_t tw, void *dst0,
+                                                 uint32_t dstride, uint32_t y, uint32_t t, const ShiftArr &shift,
+                                                 const ShiftArr &minv, const ShiftArr &maxv, int32_t mct, int32_t irrev,
+                                                 [[maybe_unused]] const OutOps *ops) {
     static_assert(!op_ycc(OP) || NC == 3, "sYCC / eYCC: three components");
     static_assert(OP != OP_CMYK || NC >= 4, "CMYK: four inks");
     constexpr int N = NarrowRun<T>::N;
     // the pixels stored: NCH channels each (OP_CMYK: one fewer than the components read)
     constexpr int NCH = OP == OP_CMYK ? NC - 1 : NC;
+    T *const drow = (T *)dst0 + (size_t)y * dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)drow, NCH * sizeof(T), t, tw, x0);
+    if (n <= 0) return;
+    const size_t si = (size_t)y * sstride + x0;
+    int32_t v[NC][N];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) load_run<N>(src.p[k] + si, n, v[k]);
+    if (mct) inv_mct_run<N>(v[0], v[1], v[2], irrev, shift, minv, maxv);
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+        if (!mct || k >= 3) inv_plain_run<N>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+    if constexpr (op_ycc(OP)) ycc_run<OP, N>(v[0], v[1], v[2], *ops);
+    if constexpr (OP == OP_CMYK) cmyk_run<N>(v[0], v[1], v[2], v[3], *ops);
+    if constexpr (OP != 0) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) prec_run<N>(v[chan_comp(OP, c)], ops->pc[c]);
+    }
+    int32_t px[N * NCH];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) px[i * NCH + c] = v[chan_comp(OP, c)][i];
+    store_samples<T, N * NCH>(drow + (size_t)x0 * NCH, px, n * NCH);
+}
+
+// ... and one sample of such a component to its channel of the pixel at d (the thread-per-pixel form)
+template <typename T, int OP>
+__device__ __forceinline__ void store_plain_sample(const PlanePtrs &src, size_t si, T *d, uint32_t k, uint32_t ch,
+                                                   int32_t irrev, const ShiftArr &shift, const ShiftArr &minv,
+                                                   const ShiftArr &maxv, [[maybe_unused]] const OutOps *ops) {
+    int32_t a[1] = {src.p[k][si]};
+    inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+    if constexpr (OP != 0) prec_run<1>(a, ops->pc[ch]);
+    __builtin_nontemporal_store((T)a[0], d + ch);
+}
+
+// interleaved, any other component count: pixel x of row y, one store per
+// sample
+template <typename T, int OP, int KMAX = GRK_MAX_COMPS>
+__device__ __forceinline__ void store_pixel_any(const PlanePtrs &src, uint32_t sstride, void *dst0, uint32_t dstride,
+                                                uint32_t ncomp, uint32_t y, uint32_t x, const ShiftArr &shift,
+                                                const ShiftArr &minv, const ShiftArr &maxv, int32_t mct, int32_t irrev,
+                                                [[maybe_unused]] const OutOps *ops) {
+    const size_t si = (size_t)y * sstride + x;
+    if constexpr (OP == OP_CMYK) {  // ncomp >= 4 components, pixels of ncomp - 1 channels
+        T *const d = (T *)dst0 + (size_t)y * dstride + (size_t)x * (ncomp - 1);
+        int32_t v[4][1];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k][0] = src.p[k][si];
+        if (mct) inv_mct_run<1>(v[0], v[1], v[2], irrev, shift, minv, maxv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (!mct || k == 3) inv_plain_run<1>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
+        cmyk_run<1>(v[0], v[1], v[2], v[3], *ops);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            prec_run<1>(v[j], ops->pc[j]);
+            __builtin_nontemporal_store((T)v[j][0], d + j);
+        }
+        if constexpr (KMAX > 4)
+            for (uint32_t k = 4; k < ncomp; ++k)
+                store_plain_sample<T, OP>(src, si, d, k, k - 1, irrev, shift, minv, maxv, ops);
+        return;
+    }
+    T *const d = (T *)dst0 + (size_t)y * dstride + (size_t)x * ncomp;
+    uint32_t c0 = 0;
+    if (mct && ncomp >= 3) {
+        int32_t a[1] = {src.p[0][si]}, b[1] = {src.p[1][si]}, c[1] = {src.p[2][si]};
+        inv_mct_run<1>(a, b, c, irrev, shift, minv, maxv);
+        if constexpr (OP != 0) {
+            prec_run<1>(a, ops->pc[0]);
+            prec_run<1>(b, ops->pc[1]);
+            prec_run<1>(c, ops->pc[2]);
+        }
+        __builtin_nontemporal_store((T)a[0], d);
+        __builtin_nontemporal_store((T)b[0], d + 1);
+        __builtin_nontemporal_store((T)c[0], d + 2);
+        c0 = 3;
+    }
+    if constexpr (KMAX > 4) {
+        for (uint32_t k = c0; k < ncomp; ++k)
+            store_plain_sample<T, OP>(src, si, d, k, k, irrev, shift, minv, maxv, ops);
+    } else {
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if ((uint32_t)k >= c0 && (uint32_t)k < ncomp)
+                store_plain_sample<T, OP>(src, si, d, k, k, irrev, shift, minv, maxv, ops);
+    }
+}
+
+// The per-tile kernels: a (row threads, rows) grid in front of those bodies.
+template <typename T, int OP = 0, typename... O>
+__global__ void k_mct_inv_dcshift_planar(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
+                                         uint32_t dstride, uint32_t ncomp, ShiftArr shift, ShiftArr minv,
+                                         ShiftArr maxv, int32_t mct, int32_t irrev, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (y >= th) return;
+    store_planar_run<T, OP>(src, sstride, tw, dst, dstride, ncomp, y, t, shift, minv, maxv, mct, irrev, ops_ptr(o...));
+}
+
+template <typename T, int NC, int OP = 0, typename... O>
+__global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
+                                         uint32_t dstride, ShiftArr shift, ShiftArr minv, ShiftArr maxv, int32_t mct,
+                                         int32_t irrev, O... o) {
+    static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (y >= th) return;
+    // store_pixels_run's statements, in place: behind a call the compiler fetches the plane pointers and
+    // clamp arrays ahead of the branches that use them, and the 8-bit RGB store then takes 0.032 ms for
+    // 0.028 on a 4K frame (MI355X, profiles/last_store_ab.json)
+    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
+    constexpr int N = NarrowRun<T>::N;
+    constexpr int NCH = OP == OP_CMYK ? NC - 1 : NC;
     T *const drow = (T *)dst.p[0] + (size_t)y * dstride;
     uint32_t x0;
     const int n = run_of<N>((uintptr_t)drow, NCH * sizeof(T), t, tw, x0);
@@ -559,60 +703,14 @@ __global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32
     store_samples<T, N * NCH>(drow + (size_t)x0 * NCH, px, n * NCH);
 }
 
-// interleaved, any other component count: one thread per pixel, one store per sample
 template <typename T, int OP = 0, typename... O>
 __global__ void k_mct_inv_dcshift_pixels_any(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th, DstPlanes dst,
                                              uint32_t dstride, uint32_t ncomp, ShiftArr shift, ShiftArr minv,
                                              ShiftArr maxv, int32_t mct, int32_t irrev, O... o) {
     static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
-    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= tw || y >= th) return;
-    const size_t si = (size_t)y * sstride + x;
-    if constexpr (OP == OP_CMYK) {  // ncomp >= 4 components, pixels of ncomp - 1 channels
-        T *const d = (T *)dst.p[0] + (size_t)y * dstride + (size_t)x * (ncomp - 1);
-        int32_t v[4][1];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k][0] = src.p[k][si];
-        if (mct) inv_mct_run<1>(v[0], v[1], v[2], irrev, shift, minv, maxv);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (!mct || k == 3) inv_plain_run<1>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-        cmyk_run<1>(v[0], v[1], v[2], v[3], *ops);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            prec_run<1>(v[j], ops->pc[j]);
-            __builtin_nontemporal_store((T)v[j][0], d + j);
-        }
-        for (uint32_t k = 4; k < ncomp; ++k) {
-            int32_t a[1] = {src.p[k][si]};
-            inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-            prec_run<1>(a, ops->pc[k - 1]);
-            __builtin_nontemporal_store((T)a[0], d + (k - 1));
-        }
-        return;
-    }
-    T *const d = (T *)dst.p[0] + (size_t)y * dstride + (size_t)x * ncomp;
-    uint32_t c0 = 0;
-    if (mct && ncomp >= 3) {
-        int32_t a[1] = {src.p[0][si]}, b[1] = {src.p[1][si]}, c[1] = {src.p[2][si]};
-        inv_mct_run<1>(a, b, c, irrev, shift, minv, maxv);
-        if constexpr (OP != 0) {
-            prec_run<1>(a, ops->pc[0]);
-            prec_run<1>(b, ops->pc[1]);
-            prec_run<1>(c, ops->pc[2]);
-        }
-        __builtin_nontemporal_store((T)a[0], d);
-        __builtin_nontemporal_store((T)b[0], d + 1);
-        __builtin_nontemporal_store((T)c[0], d + 2);
-        c0 = 3;
-    }
-    for (uint32_t k = c0; k < ncomp; ++k) {
-        int32_t a[1] = {src.p[k][si]};
-        inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-        if constexpr (OP != 0) prec_run<1>(a, ops->pc[k]);
-        __builtin_nontemporal_store((T)a[0], d + k);
-    }
+    store_pixel_any<T, OP>(src, sstride, dst.p[0], dstride, ncomp, y, x, shift, minv, maxv, mct, irrev, ops_ptr(o...));
 }
 
 // ---------------------------------------------------------------------------
@@ -2180,6 +2278,50 @@ static int src_mode(int32_t fmt, uint32_t ncomp) {
     return ((fmt & SMP_BIG_ENDIAN) ? 1 : 0) | ((fmt & SMP_INTERLEAVED) && ncomp > 1 ? 2 : 0);
 }
 
+// f(T{}) with the sample type T of fmt (a SampleFmt without flags), then the
+// error of what f launched; hipErrorInvalidValue for any other fmt
+template <typename F>
+static hipError_t with_sample_type(int32_t fmt, F &&f) {
+    switch (fmt) {
+        case SMP_I32: f(int32_t{}); break;
+        case SMP_U8: f(uint8_t{}); break;
+        case SMP_I8: f(int8_t{}); break;
+        case SMP_U16: f(uint16_t{}); break;
+        case SMP_I16: f(int16_t{}); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+// The formats with a colour conversion (sYCC / eYCC / CMYK output is unsigned)
+// and with the 4:2:0 run kernel: U8 / U16 / I32.  The signed narrow formats
+// have the OP = 0 and OP_PREC instantiations only.
+template <typename T>
+constexpr bool colour_fmt = std::is_unsigned<T>::value || sizeof(T) == 4;
+constexpr bool colour_fmt_of(int32_t fmt) { return fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16; }
+// a compile-time OP / flag handed to a generic lambda
+template <int V>
+using Const = std::integral_constant<int, V>;
+// f(Const<OP>{}) with the OP the ops select (sycc_launchable holds): the
+// colour conversion in the formats that have one, else the precision ops alone
+template <typename T, typename F>
+static void with_op(const OutOps &ops, F &&f) {
+    if constexpr (colour_fmt<T>) {
+        if (ops.sycc) return f(Const<OP_SYCC>{});
+        if (ops.col == COL_EYCC) return f(Const<OP_EYCC>{});
+        if (ops.col == COL_CMYK) return f(Const<OP_CMYK>{});
+    }
+    f(Const<OP_PREC>{});
+}
+// the (row threads, rows) grid of the kernels that own runs of 16 bytes: the
+// lead run + the runs of NarrowRun<T>::N pixels along a row of tw
+template <typename T>
+static dim3 run_grid(uint32_t tw, uint32_t rows) {
+    const uint32_t runs = (uint32_t)(((uint64_t)tw + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
+    return dim3((runs + 255) / 256, rows);
+}
+// ... and of the kernels with a thread per pixel
+static dim3 pixel_grid(uint32_t tw, uint32_t rows) { return dim3((tw + 255) / 256, rows); }
+
 hipError_t launch_dcshift_mct_fwd(const SrcPlanes &src, int32_t fmt, uint32_t sstride, const PlanePtrs &dst,
                                   uint32_t tw, uint32_t th, uint32_t ncomp, const ShiftArr &shift, int32_t mct,
                                   int32_t irrev, hipStream_t s) {
@@ -2292,26 +2434,34 @@ hipError_t launch_mct_inv_dcshift(const PlanePtrs &src, uint32_t sstride, uint32
     return hipGetLastError();
 }
 
-template <typename T>
-static void launch_inv_to(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
-                          bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift,
-                          const ShiftArr &mn, const ShiftArr &mx, int32_t mct, int32_t irrev, hipStream_t s) {
-    // threads of a row: the lead run + the runs of RUN pixels
-    const uint32_t runs = (uint32_t)(((uint64_t)tw + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
-    const dim3 grid((runs + 255) / 256, th);
+// The narrowing store of one tile with the ops of class OP (none, or one
+// OutOps) as the kernels' trailing pack.  sYCC / eYCC have three components
+// and CMYK four or more (checked by the callers).
+template <typename T, int OP = 0, typename... O>
+static void launch_inv(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
+                       bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn,
+                       const ShiftArr &mx, int32_t mct, int32_t irrev, hipStream_t s, const O &...ops) {
+    const dim3 grid = run_grid<T>(tw, th);
     mct = mct && ncomp >= 3;
-    if (!interleaved || ncomp == 1)
-        hipLaunchKernelGGL(k_mct_inv_dcshift_planar<T>, grid, dim3(256), 0, s, src, sstride, tw, th, dst, dstride,
-                           ncomp, shift, mn, mx, mct, irrev);
-    else if (ncomp == 3)
-        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 3>), grid, dim3(256), 0, s, src, sstride, tw, th, dst, dstride,
-                           shift, mn, mx, mct, irrev);
-    else if (ncomp == 4)
-        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 4>), grid, dim3(256), 0, s, src, sstride, tw, th, dst, dstride,
-                           shift, mn, mx, mct, irrev);
-    else
-        hipLaunchKernelGGL(k_mct_inv_dcshift_pixels_any<T>, dim3((tw + 255) / 256, th), dim3(256), 0, s, src, sstride,
-                           tw, th, dst, dstride, ncomp, shift, mn, mx, mct, irrev);
+    // nc...: the planar and any-count kernels' ncomp argument
+    const auto run = [&](auto kernel, dim3 g, auto... nc) {
+        hipLaunchKernelGGL(kernel, g, dim3(256), 0, s, src, sstride, tw, th, dst, dstride, nc..., shift, mn, mx, mct,
+                           irrev, ops...);
+    };
+    if constexpr (op_ycc(OP)) {
+        if (!interleaved) run(k_mct_inv_dcshift_planar<T, OP, O...>, grid, ncomp);
+        else run(k_mct_inv_dcshift_pixels<T, 3, OP, O...>, grid);
+    } else if constexpr (OP == OP_CMYK) {  // one channel fewer than components
+        if (!interleaved) run(k_mct_inv_dcshift_planar<T, OP, O...>, grid, ncomp);
+        else if (ncomp == 4) run(k_mct_inv_dcshift_pixels<T, 4, OP, O...>, grid);
+        else if (ncomp == 5) run(k_mct_inv_dcshift_pixels<T, 5, OP, O...>, grid);
+        else run(k_mct_inv_dcshift_pixels_any<T, OP, O...>, pixel_grid(tw, th), ncomp);
+    } else {
+        if (!interleaved || ncomp == 1) run(k_mct_inv_dcshift_planar<T, OP, O...>, grid, ncomp);
+        else if (ncomp == 3) run(k_mct_inv_dcshift_pixels<T, 3, OP, O...>, grid);
+        else if (ncomp == 4) run(k_mct_inv_dcshift_pixels<T, 4, OP, O...>, grid);
+        else run(k_mct_inv_dcshift_pixels_any<T, OP, O...>, pixel_grid(tw, th), ncomp);
+    }
 }
 
 hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th,
@@ -2325,17 +2475,9 @@ hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uin
         for (uint32_t k = 0; k < ncomp; ++k) d.p[k] = (int32_t *)dst.p[k];
         return launch_mct_inv_dcshift(src, sstride, tw, th, d, dstride, ncomp, shift, mn, mx, mct, irrev, s);
     }
-#define GRK_INV(T) launch_inv_to<T>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev, s)
-    switch (fmt) {
-        case SMP_I32: GRK_INV(int32_t); break;
-        case SMP_U8: GRK_INV(uint8_t); break;
-        case SMP_I8: GRK_INV(int8_t); break;
-        case SMP_U16: GRK_INV(uint16_t); break;
-        case SMP_I16: GRK_INV(int16_t); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_INV
-    return hipGetLastError();
+    return with_sample_type(fmt, [&](auto t) {
+        launch_inv<decltype(t)>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev, s);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2344,128 +2486,115 @@ hipError_t launch_mct_inv_dcshift_to(const PlanePtrs &src, uint32_t sstride, uin
 // than the tiles' samples.  Workgroup wg belongs to the last job j with
 // first[j] <= wg (first: the jobs' first workgroup numbers, njobs + 1 entries,
 // an empty job's equal to its successor's, so it is never found).  The search
-// depends on blockIdx alone: it and the record's fields are uniform over the
-// workgroup, read with scalar loads before the first store and kept in scalar
-// registers.  Thread g of a job -- g counted over its workgroups -- owns run
-// (g % rpr) of row (g / rpr), rpr = store_job_row_threads: the runs
-// k_mct_inv_dcshift_planar / _pixels lay on the destination's 16-byte grid
-// (IL with two components: k_mct_inv_dcshift_pixels_any's thread per pixel),
-// finished and stored by the same helpers, statement for statement.  No LDS,
-// no atomics, nothing shared between workgroups.
+// depends on blockIdx alone: it, the record's fields and the job's OutOps are
+// uniform over the workgroup, read with scalar loads before the first store
+// and kept in scalar registers.  Thread g of a job -- g counted over its
+// workgroups -- owns run (g % rpr) of row (g / rpr), rpr =
+// store_job_row_threads: store_planar_run / store_pixels_run's run on the
+// destination's 16-byte grid, or (IL with two components) store_pixel_any's
+// pixel -- the bodies the per-tile kernels call.  No LDS, no atomics, nothing
+// shared between workgroups.
+//
+// OP and the trailing pack are the per-tile kernels': OP = 0 takes no further
+// argument, any other OP the device table of OutOps that StoreJob::ops
+// indexes.  OP_SYCC / OP_EYCC jobs have three components, OP_CMYK jobs four.
 // ---------------------------------------------------------------------------
-template <typename T, int NC>
-__device__ __forceinline__ void store_job_pixels(const StoreJob &J, uint32_t y, uint32_t t, const ShiftArr &shift,
-                                                 const ShiftArr &minv, const ShiftArr &maxv, int32_t mct,
-                                                 int32_t irrev) {
-    constexpr int N = NarrowRun<T>::N;
-    T *const drow = (T *)J.dst[0] + (size_t)y * J.dstride;
-    uint32_t x0;
-    const int n = run_of<N>((uintptr_t)drow, NC * sizeof(T), t, J.w, x0);
-    if (n <= 0) return;
-    const size_t si = (size_t)y * J.sstride + x0;
-    int32_t v[NC][N];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) load_run<N>(J.src[k] + si, n, v[k]);
-    if (mct) inv_mct_run<N>(v[0], v[1], v[2], irrev, shift, minv, maxv);
-#pragma unroll
-    for (int k = 0; k < NC; ++k)
-        if (!mct || k >= 3) inv_plain_run<N>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-    int32_t px[N * NC];
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) px[i * NC + c] = v[c][i];
-    store_samples<T, N * NC>(drow + (size_t)x0 * NC, px, n * NC);
-}
-
-template <typename T, bool IL>
-__global__ void __launch_bounds__(256) k_store_jobs(const StoreJob *__restrict__ jobs,
-                                                    const uint32_t *__restrict__ first, uint32_t njobs) {
-    constexpr int N = NarrowRun<T>::N;
-    const uint32_t wg = blockIdx.x;
+__device__ __forceinline__ uint32_t job_of_wg(const uint32_t *__restrict__ first, uint32_t njobs, uint32_t wg) {
     uint32_t lo = 0, hi = njobs;
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
         if (first[mid] <= wg) lo = mid; else hi = mid;
     }
+    return lo;
+}
+
+using OpsTable = const OutOps *__restrict__;
+__device__ __forceinline__ const OutOps *job_ops(uint32_t) { return nullptr; }
+__device__ __forceinline__ const OutOps *job_ops(uint32_t i, OpsTable tab) { return tab + i; }
+
+template <typename T, bool IL, int OP = 0, typename... O>
+__global__ void __launch_bounds__(256) k_store_jobs(const StoreJob *__restrict__ jobs,
+                                                    const uint32_t *__restrict__ first, uint32_t njobs, O... opstab) {
+    static_assert(sizeof...(O) == (OP != 0), "the OutOps table exactly when OP != 0");
+    const uint32_t wg = blockIdx.x;
+    const uint32_t lo = job_of_wg(first, njobs, wg);
     const StoreJob J = jobs[lo];
-    const uint32_t ncomp = J.ncomp, tw = J.w, th = J.h;
+    const OutOps *const ops = job_ops(J.ops, opstab...);
+    const uint32_t ncomp = op_ycc(OP) ? 3u : (OP == OP_CMYK ? 4u : J.ncomp), tw = J.w, th = J.h;
     const int32_t mct = J.mct && ncomp >= 3, irrev = (int32_t)J.irrev;
+    PlanePtrs src{};
+    DstPlanes dst{};
     ShiftArr shift{}, minv{}, maxv{};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { shift.v[k] = J.shift[k]; minv.v[k] = J.mn[k]; maxv.v[k] = J.mx[k]; }
+    for (int k = 0; k < 4; ++k) {
+        src.p[k] = const_cast<int32_t *>(J.src[k]); dst.p[k] = J.dst[k];
+        shift.v[k] = J.shift[k]; minv.v[k] = J.mn[k]; maxv.v[k] = J.mx[k];
+    }
     const uint32_t rpr = store_job_row_threads(tw, ncomp, (uint32_t)sizeof(T), IL);
     const uint32_t g = (wg - first[lo]) * 256u + threadIdx.x;
     const uint32_t y = g / rpr, t = g - y * rpr;
     if (y >= th) return;
     if constexpr (IL) {
-        if (ncomp == 3) { store_job_pixels<T, 3>(J, y, t, shift, minv, maxv, mct, irrev); return; }
-        if (ncomp == 4) { store_job_pixels<T, 4>(J, y, t, shift, minv, maxv, mct, irrev); return; }
-        if (ncomp == 2) {  // a thread per pixel, a store per sample
-            const size_t si = (size_t)y * J.sstride + t;
-            T *const d = (T *)J.dst[0] + (size_t)y * J.dstride + (size_t)t * 2;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                int32_t a[1] = {J.src[k][si]};
-                inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-                __builtin_nontemporal_store((T)a[0], d + k);
-            }
+        if constexpr (op_ycc(OP) || OP == OP_CMYK) {
+            store_pixels_run<T, OP == OP_CMYK ? 4 : 3, OP>(src, J.sstride, tw, J.dst[0], J.dstride, y, t, shift, minv, maxv,
+                                                           mct, irrev, ops);
             return;
+        } else {
+            if (ncomp == 3) {
+                store_pixels_run<T, 3, OP>(src, J.sstride, tw, J.dst[0], J.dstride, y, t, shift, minv, maxv, mct, irrev, ops);
+                return;
+            }
+            if (ncomp == 4) {
+                store_pixels_run<T, 4, OP>(src, J.sstride, tw, J.dst[0], J.dstride, y, t, shift, minv, maxv, mct, irrev, ops);
+                return;
+            }
+            if (ncomp == 2) {  // a thread per pixel, a store per sample
+                store_pixel_any<T, OP, 4>(src, J.sstride, J.dst[0], J.dstride, 2u, y, t, shift, minv, maxv, 0, irrev, ops);
+                return;
+            }
         }
     }
     // planar (one interleaved component is a plane)
-    const size_t drow = (size_t)y * J.dstride;
-    uint32_t x0;
-    const int n = run_of<N>((uintptr_t)((T *)J.dst[0] + drow), sizeof(T), t, tw, x0);
-    if (n <= 0) return;
-    const size_t si = (size_t)y * J.sstride + x0, di = drow + x0;
-    if (mct) {
-        int32_t a[N], b[N], c[N];
-        load_run<N>(J.src[0] + si, n, a);
-        load_run<N>(J.src[1] + si, n, b);
-        load_run<N>(J.src[2] + si, n, c);
-        inv_mct_run<N>(a, b, c, irrev, shift, minv, maxv);
-        store_samples<T, N>((T *)J.dst[0] + di, a, n);
-        store_samples<T, N>((T *)J.dst[1] + di, b, n);
-        store_samples<T, N>((T *)J.dst[2] + di, c, n);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if ((uint32_t)k >= ncomp || (mct && k < 3)) continue;
-        int32_t a[N];
-        load_run<N>(J.src[k] + si, n, a);
-        inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-        store_samples<T, N>((T *)J.dst[k] + di, a, n);
-    }
+    store_planar_run<T, OP, 4>(src, J.sstride, tw, dst, J.dstride, ncomp, y, t, shift, minv, maxv, mct, irrev, ops);
 }
 
 hipError_t launch_store_jobs(const StoreJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg, int32_t fmt,
-                             bool interleaved, hipStream_t s) {
+                             bool interleaved, hipStream_t s, int op, const OutOps *ops) {
     if (!njobs || !nwg) return hipSuccess;
-#define GRK_JOBS(T)                                                                                                   \
-    do {                                                                                                              \
-        if (interleaved) hipLaunchKernelGGL((k_store_jobs<T, true>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs); \
-        else hipLaunchKernelGGL((k_store_jobs<T, false>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs);            \
-    } while (0)
-    switch (fmt) {
-        case SMP_I32: GRK_JOBS(int32_t); break;
-        case SMP_U8: GRK_JOBS(uint8_t); break;
-        case SMP_I8: GRK_JOBS(int8_t); break;
-        case SMP_U16: GRK_JOBS(uint16_t); break;
-        case SMP_I16: GRK_JOBS(int16_t); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_JOBS
-    return hipGetLastError();
+    if (op < 0 || op > OP_CMYK || (op != 0) != (ops != nullptr)) return hipErrorInvalidValue;
+    if (op > OP_PREC && !colour_fmt_of(fmt)) return hipErrorInvalidValue;
+    return with_sample_type(fmt, [&](auto t) {
+        using T = decltype(t);
+        // (the table's type is spelled out: deduced from `ops` it would lose its __restrict__)
+        const auto launch = [&](auto c, auto il) {
+            constexpr int OP = decltype(c)::value;
+            constexpr bool IL = decltype(il)::value != 0;
+            if constexpr (OP == 0)
+                hipLaunchKernelGGL((k_store_jobs<T, IL>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs);
+            else
+                hipLaunchKernelGGL((k_store_jobs<T, IL, OP, OpsTable>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs,
+                                   ops);
+        };
+        const auto layouts = [&](auto c) {
+            if (interleaved) launch(c, Const<1>{});
+            else launch(c, Const<0>{});
+        };
+        if (op == 0) return layouts(Const<0>{});
+        if constexpr (colour_fmt<T>) {
+            if (op == OP_SYCC) return layouts(Const<OP_SYCC>{});
+            if (op == OP_EYCC) return layouts(Const<OP_EYCC>{});
+            if (op == OP_CMYK) return layouts(Const<OP_CMYK>{});
+        }
+        layouts(Const<OP_PREC>{});
+    });
 }
 
 // ---------------------------------------------------------------------------
 // The DC shift + forward MCT of a table of tiles in one launch (the batch
 // encode: a few workgroups per tile, hundreds of tiles) -- the forward mirror
-// of k_store_jobs.  Workgroup wg finds its job by binary search over the
-// jobs' first-workgroup numbers; the search depends on blockIdx alone, so it
-// and the job record are wave-uniform: scalar loads, the record in scalar
-// registers.  Thread g of a job -- g counted over its workgroups -- owns
+// of k_store_jobs.  Workgroup wg finds its job with job_of_wg; the search
+// depends on blockIdx alone, so it and the job record are wave-uniform: scalar
+// loads, the record in scalar registers.  Thread g of a job -- g counted over its workgroups -- owns
 // position (g % rpr) of row (g / rpr), rpr = load_job_row_threads: a run of
 // PIX_RUN pixels of an interleaved 3 / 4-component source
 // (k_dcshift_mct_fwd_pixels' runs on the source row's best aligned grid, read
@@ -2529,11 +2658,7 @@ __global__ void __launch_bounds__(256) k_load_jobs(const LoadJob *__restrict__ j
                                                    const uint32_t *__restrict__ first, uint32_t njobs) {
     constexpr bool BE = (M & 1) != 0, IL = (M & 2) != 0;
     const uint32_t wg = blockIdx.x;
-    uint32_t lo = 0, hi = njobs;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (first[mid] <= wg) lo = mid; else hi = mid;
-    }
+    const uint32_t lo = job_of_wg(first, njobs, wg);
     const LoadJob J = jobs[lo];
     const uint32_t ncomp = J.ncomp, tw = J.w, th = J.h;
     const int32_t mct = J.mct && ncomp >= 3, irrev = J.irrev;
@@ -2588,52 +2713,42 @@ hipError_t launch_load_jobs(const LoadJob *jobs, const uint32_t *first, uint32_t
                             int mode, hipStream_t s) {
     if (!njobs || !nwg) return hipSuccess;
     if (mode < 0 || mode > 3) return hipErrorInvalidValue;
-#define GRK_LJ(S, MM) hipLaunchKernelGGL((k_load_jobs<S, MM>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs)
-#define GRK_LJ8(S)                         \
-    do {                                   \
-        if (mode & 1) return hipErrorInvalidValue; \
-        if (mode & 2) GRK_LJ(S, 2);        \
-        else GRK_LJ(S, 0);                 \
-    } while (0)
-#define GRK_LJ16(S)                  \
-    do {                             \
-        if (mode == 0) GRK_LJ(S, 0); \
-        else if (mode == 1) GRK_LJ(S, 1); \
-        else if (mode == 2) GRK_LJ(S, 2); \
-        else GRK_LJ(S, 3);           \
-    } while (0)
-    switch (fmt) {
-        case SMP_I32: GRK_LJ8(int32_t); break;
-        case SMP_U8: GRK_LJ8(uint8_t); break;
-        case SMP_I8: GRK_LJ8(int8_t); break;
-        case SMP_U16: GRK_LJ16(uint16_t); break;
-        case SMP_I16: GRK_LJ16(int16_t); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_LJ16
-#undef GRK_LJ8
-#undef GRK_LJ
-    return hipGetLastError();
+    if ((mode & 1) && fmt != SMP_U16 && fmt != SMP_I16) return hipErrorInvalidValue;  // big-endian: 16-bit samples only
+    return with_sample_type(fmt, [&](auto t) {
+        using S = decltype(t);
+        const auto run = [&](auto m) {
+            hipLaunchKernelGGL((k_load_jobs<S, decltype(m)::value>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs);
+        };
+        if constexpr (sizeof(S) == 2) {
+            if (mode == 1) return run(Const<1>{});
+            if (mode == 3) return run(Const<3>{});
+        }
+        if (mode & 2) run(Const<2>{});
+        else run(Const<0>{});
+    });
 }
 
-template <typename T, bool FAST>
+// The upsampling store of one rectangle with the ops of class OP (none, or one
+// OutOps) as the kernels' trailing pack.  fast: conv_job_fast's shape, which
+// runs k_upsample_420 (OP_SYCC only there); everything else runs
+// k_upsample_any, which reads its colour step from the ops at run time.
+template <typename T, int OP = 0, typename... O>
 static void launch_up(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
-                      const DstPlanes &dst, bool interleaved, uint32_t dstride, hipStream_t s) {
-    const UpComp *c = src.c;
-    if constexpr (FAST) {
-        if (ncomp == 3 && c[0].dx == 1 && c[0].dy == 1 && c[1].dx == 2 && c[2].dx == 2 && c[1].dy == c[2].dy &&
-            (c[1].dy == 1 || c[1].dy == 2)) {
-            const uint32_t runs = (uint32_t)(((uint64_t)w + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
-            const dim3 grid((runs + 255) / 256, h);
+                      const DstPlanes &dst, bool interleaved, uint32_t dstride, bool fast, hipStream_t s,
+                      const O &...ops) {
+    if constexpr (colour_fmt<T>) {
+        if (fast) {
             if (interleaved)
-                hipLaunchKernelGGL((k_upsample_420<T, true>), grid, dim3(256), 0, s, src, X0, Y0, w, h, dst, dstride);
+                hipLaunchKernelGGL((k_upsample_420<T, true, OP, O...>), run_grid<T>(w, h), dim3(256), 0, s, src, X0, Y0,
+                                   w, h, dst, dstride, ops...);
             else
-                hipLaunchKernelGGL((k_upsample_420<T, false>), grid, dim3(256), 0, s, src, X0, Y0, w, h, dst, dstride);
+                hipLaunchKernelGGL((k_upsample_420<T, false, OP, O...>), run_grid<T>(w, h), dim3(256), 0, s, src, X0, Y0,
+                                   w, h, dst, dstride, ops...);
             return;
         }
     }
-    hipLaunchKernelGGL(k_upsample_any<T>, dim3((w + 255) / 256, h), dim3(256), 0, s, src, ncomp, X0, Y0, w, h, dst,
-                       interleaved ? 1 : 0, dstride);
+    hipLaunchKernelGGL((k_upsample_any<T, OP ? OP_PREC : 0, O...>), pixel_grid(w, h), dim3(256), 0, s, src, ncomp, X0,
+                       Y0, w, h, dst, interleaved ? 1 : 0, dstride, ops...);
 }
 
 hipError_t launch_upsample_to(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
@@ -2642,84 +2757,20 @@ hipError_t launch_upsample_to(const UpPlan &src, uint32_t ncomp, uint32_t X0, ui
     for (uint32_t k = 0; k < ncomp; ++k)
         if (!src.c[k].dx || !src.c[k].dy) return hipErrorInvalidValue;
     if (!w || !h) return hipSuccess;
-#define GRK_UP(T, FAST) launch_up<T, FAST>(src, ncomp, X0, Y0, w, h, dst, interleaved, dstride, s)
-    switch (fmt) {
-        case SMP_I32: GRK_UP(int32_t, true); break;
-        case SMP_U8: GRK_UP(uint8_t, true); break;
-        case SMP_I8: GRK_UP(int8_t, false); break;
-        case SMP_U16: GRK_UP(uint16_t, true); break;
-        case SMP_I16: GRK_UP(int16_t, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_UP
-    return hipGetLastError();
-}
-
-// the same launches with the OutOps in their stores (the grids are those above)
-template <typename T, bool SY>
-static void launch_inv_ops(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
-                           bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift,
-                           const ShiftArr &mn, const ShiftArr &mx, int32_t mct, int32_t irrev, const OutOps &ops,
-                           hipStream_t s) {
-    const uint32_t runs = (uint32_t)(((uint64_t)tw + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
-    const dim3 grid((runs + 255) / 256, th);
-    mct = mct && ncomp >= 3;
-    if constexpr (SY) {
-        if (ops.col == COL_EYCC) {  // three components (checked by the caller)
-            if (!interleaved)
-                hipLaunchKernelGGL((k_mct_inv_dcshift_planar<T, OP_EYCC>), grid, dim3(256), 0, s, src, sstride, tw,
-                                   th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
-            else
-                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 3, OP_EYCC>), grid, dim3(256), 0, s, src, sstride,
-                                   tw, th, dst, dstride, shift, mn, mx, mct, irrev, ops);
-            return;
-        }
-        if (ops.col == COL_CMYK) {  // four or more components (checked by the caller), one channel fewer
-            if (!interleaved)
-                hipLaunchKernelGGL((k_mct_inv_dcshift_planar<T, OP_CMYK>), grid, dim3(256), 0, s, src, sstride, tw,
-                                   th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
-            else if (ncomp == 4)
-                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 4, OP_CMYK>), grid, dim3(256), 0, s, src, sstride,
-                                   tw, th, dst, dstride, shift, mn, mx, mct, irrev, ops);
-            else if (ncomp == 5)
-                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 5, OP_CMYK>), grid, dim3(256), 0, s, src, sstride,
-                                   tw, th, dst, dstride, shift, mn, mx, mct, irrev, ops);
-            else
-                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels_any<T, OP_CMYK>), dim3((tw + 255) / 256, th), dim3(256),
-                                   0, s, src, sstride, tw, th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
-            return;
-        }
-        if (ops.sycc) {  // three components (checked by the caller)
-            if (!interleaved)
-                hipLaunchKernelGGL((k_mct_inv_dcshift_planar<T, OP_SYCC>), grid, dim3(256), 0, s, src, sstride, tw,
-                                   th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
-            else
-                hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 3, OP_SYCC>), grid, dim3(256), 0, s, src, sstride,
-                                   tw, th, dst, dstride, shift, mn, mx, mct, irrev, ops);
-            return;
-        }
-    }
-    if (!interleaved || ncomp == 1)
-        hipLaunchKernelGGL((k_mct_inv_dcshift_planar<T, OP_PREC>), grid, dim3(256), 0, s, src, sstride, tw, th, dst,
-                           dstride, ncomp, shift, mn, mx, mct, irrev, ops);
-    else if (ncomp == 3)
-        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 3, OP_PREC>), grid, dim3(256), 0, s, src, sstride, tw, th,
-                           dst, dstride, shift, mn, mx, mct, irrev, ops);
-    else if (ncomp == 4)
-        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels<T, 4, OP_PREC>), grid, dim3(256), 0, s, src, sstride, tw, th,
-                           dst, dstride, shift, mn, mx, mct, irrev, ops);
-    else
-        hipLaunchKernelGGL((k_mct_inv_dcshift_pixels_any<T, OP_PREC>), dim3((tw + 255) / 256, th), dim3(256), 0, s, src,
-                           sstride, tw, th, dst, dstride, ncomp, shift, mn, mx, mct, irrev, ops);
+    const bool fast = conv_job_fast(src.c, ncomp, fmt, COL_NONE);
+    return with_sample_type(fmt, [&](auto t) {
+        launch_up<decltype(t)>(src, ncomp, X0, Y0, w, h, dst, interleaved, dstride, fast, s);
+    });
 }
 
 // sYCC / eYCC / CMYK output is unsigned: its formats are U8 / U16 / I32
 static bool sycc_launchable(const OutOps &ops, uint32_t ncomp, int32_t fmt) {
     if (ops.col != COL_NONE && (ops.sycc || (ops.col != COL_EYCC && ops.col != COL_CMYK))) return false;
     if (!ops.sycc && ops.col == COL_NONE) return true;
-    return (ops.col == COL_CMYK ? ncomp >= 4 : ncomp == 3) && (fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16);
+    return (ops.col == COL_CMYK ? ncomp >= 4 : ncomp == 3) && colour_fmt_of(fmt);
 }
 
+// the same launches with the OutOps in their stores
 hipError_t launch_mct_inv_dcshift_ops(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th,
                                       const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
                                       uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn, const ShiftArr &mx,
@@ -2727,28 +2778,42 @@ hipError_t launch_mct_inv_dcshift_ops(const PlanePtrs &src, uint32_t sstride, ui
     if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS || !sycc_launchable(ops, ncomp, fmt))
         return hipErrorInvalidValue;
     if (!tw || !th) return hipSuccess;
-#define GRK_INV(T, SY) \
-    launch_inv_ops<T, SY>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev, ops, s)
-    switch (fmt) {
-        case SMP_I32: GRK_INV(int32_t, true); break;
-        case SMP_U8: GRK_INV(uint8_t, true); break;
-        case SMP_I8: GRK_INV(int8_t, false); break;
-        case SMP_U16: GRK_INV(uint16_t, true); break;
-        case SMP_I16: GRK_INV(int16_t, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_INV
-    return hipGetLastError();
+    return with_sample_type(fmt, [&](auto t) {
+        using T = decltype(t);
+        with_op<T>(ops, [&](auto op) {
+            launch_inv<T, decltype(op)::value, OutOps>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift,
+                                                       mn, mx, mct, irrev, s, ops);
+        });
+    });
 }
 
-// the custom-MCT stores: the grids of launch_inv_to, the ops (none, or one
+hipError_t launch_upsample_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
+                               const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
+                               const OutOps &ops, hipStream_t s) {
+    if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS || !sycc_launchable(ops, ncomp, fmt))
+        return hipErrorInvalidValue;
+    for (uint32_t k = 0; k < ncomp; ++k)
+        if (!src.c[k].dx || !src.c[k].dy) return hipErrorInvalidValue;
+    if (!w || !h) return hipSuccess;
+    // (eYCC / CMYK need one grid, which the fast shape is not: k_upsample_any's)
+    const bool fast = conv_job_fast(src.c, ncomp, fmt, ops.col);
+    return with_sample_type(fmt, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (colour_fmt<T>) {
+            if (fast && ops.sycc)
+                return launch_up<T, OP_SYCC, OutOps>(src, ncomp, X0, Y0, w, h, dst, interleaved, dstride, fast, s, ops);
+        }
+        launch_up<T, OP_PREC, OutOps>(src, ncomp, X0, Y0, w, h, dst, interleaved, dstride, fast, s, ops);
+    });
+}
+
+// the custom-MCT stores: the grids of launch_inv, the ops (none, or one
 // OutOps) as the kernels' trailing pack
 template <typename T, int OP, typename... O>
 static void launch_custom(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
                           bool interleaved, uint32_t dstride, uint32_t ncomp, const MctInv &m, const ShiftArr &off,
                           const ShiftArr &mn, const ShiftArr &mx, hipStream_t s, const O &...ops) {
-    const uint32_t runs = (uint32_t)(((uint64_t)tw + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
-    const dim3 grid((runs + 255) / 256, th);
+    const dim3 grid = run_grid<T>(tw, th);
 #define GRK_CUSTOM(KERNEL, NC, GRID) \
     hipLaunchKernelGGL((KERNEL<T, OP, NC>), GRID, dim3(256), 0, s, src, sstride, tw, th, dst, dstride, ncomp, m, off, \
                        mn, mx, ops...)
@@ -2757,7 +2822,7 @@ static void launch_custom(const PlanePtrs &src, uint32_t sstride, uint32_t tw, u
         else GRK_CUSTOM(k_mct_inv_custom_pixels, 3, grid);
     } else if constexpr (OP == OP_CMYK) {  // four or more components: the any-count forms
         if (!interleaved) GRK_CUSTOM(k_mct_inv_custom_planar, 0, grid);
-        else GRK_CUSTOM(k_mct_inv_custom_pixels, 0, dim3((tw + 255) / 256, th));
+        else GRK_CUSTOM(k_mct_inv_custom_pixels, 0, pixel_grid(tw, th));
     } else if (!interleaved || ncomp == 1) {
         if (ncomp == 3) GRK_CUSTOM(k_mct_inv_custom_planar, 3, grid);
         else if (ncomp == 4) GRK_CUSTOM(k_mct_inv_custom_planar, 4, grid);
@@ -2767,7 +2832,7 @@ static void launch_custom(const PlanePtrs &src, uint32_t sstride, uint32_t tw, u
     } else if (ncomp == 4) {
         GRK_CUSTOM(k_mct_inv_custom_pixels, 4, grid);
     } else {
-        GRK_CUSTOM(k_mct_inv_custom_pixels, 0, dim3((tw + 255) / 256, th));
+        GRK_CUSTOM(k_mct_inv_custom_pixels, 0, pixel_grid(tw, th));
     }
 #undef GRK_CUSTOM
 }
@@ -2779,42 +2844,25 @@ hipError_t launch_mct_inv_custom(const PlanePtrs &src, uint32_t sstride, uint32_
     if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS || (ops && !sycc_launchable(*ops, ncomp, fmt)))
         return hipErrorInvalidValue;
     if (!tw || !th) return hipSuccess;
-#define GRK_INV(T, SY) \
-    do { \
-        if (!ops) launch_custom<T, 0>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, mn, mx, s); \
-        else if (SY && ops->sycc) \
-            launch_custom<T, SY ? OP_SYCC : OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, \
-                                                     mn, mx, s, *ops); \
-        else if (SY && ops->col == COL_EYCC) \
-            launch_custom<T, SY ? OP_EYCC : OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, \
-                                                     mn, mx, s, *ops); \
-        else if (SY && ops->col == COL_CMYK) \
-            launch_custom<T, SY ? OP_CMYK : OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, \
-                                                     mn, mx, s, *ops); \
-        else launch_custom<T, OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, mn, mx, s, *ops); \
-    } while (0)
-    switch (fmt) {
-        case SMP_I32: GRK_INV(int32_t, true); break;
-        case SMP_U8: GRK_INV(uint8_t, true); break;
-        case SMP_I8: GRK_INV(int8_t, false); break;
-        case SMP_U16: GRK_INV(uint16_t, true); break;
-        case SMP_I16: GRK_INV(int16_t, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_INV
-    return hipGetLastError();
+    return with_sample_type(fmt, [&](auto t) {
+        using T = decltype(t);
+        if (!ops) return launch_custom<T, 0>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, mn, mx, s);
+        with_op<T>(*ops, [&](auto op) {
+            launch_custom<T, decltype(op)::value>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, m, off, mn,
+                                                  mx, s, *ops);
+        });
+    });
 }
 
-// the palette stores: launch_inv_to's run grid over PAL_ROWS rows per
+// the palette stores: launch_inv's run grid over PAL_ROWS rows per
 // workgroup, the table's bytes as dynamic LDS
 template <typename T, int OP, typename... O>
 static void launch_pal(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint32_t th, const DstPlanes &dst,
                        bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift, const ShiftArr &mn,
                        const ShiftArr &mx, int32_t mct, int32_t irrev, const PalMap &map, const uint16_t *table,
                        hipStream_t s, const O &...ops) {
-    const uint32_t runs = (uint32_t)(((uint64_t)tw + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
     const uint32_t rows = (th + PAL_ROWS - 1) / PAL_ROWS;
-    const dim3 grid((runs + 255) / 256, rows);
+    const dim3 grid = run_grid<T>(tw, rows);
     const size_t lds = ((size_t)map.ne * map.npc * 2 + 3) & ~(size_t)3;
 #define GRK_PAL(KERNEL, GRID) \
     hipLaunchKernelGGL(KERNEL, GRID, dim3(256), lds, s, src, sstride, tw, th, dst, dstride, ncomp, shift, mn, mx, mct, \
@@ -2822,7 +2870,7 @@ static void launch_pal(const PlanePtrs &src, uint32_t sstride, uint32_t tw, uint
     if (!interleaved || map.nch == 1) GRK_PAL((k_palette_planar<T, OP>), grid);
     else if (map.nch == 3) GRK_PAL((k_palette_pixels<T, 3, OP>), grid);
     else if (map.nch == 4) GRK_PAL((k_palette_pixels<T, 4, OP>), grid);
-    else GRK_PAL((k_palette_pixels<T, 0, OP>), dim3((tw + 255) / 256, rows));
+    else GRK_PAL((k_palette_pixels<T, 0, OP>), pixel_grid(tw, rows));
 #undef GRK_PAL
 }
 
@@ -2838,238 +2886,22 @@ hipError_t launch_palette(const PlanePtrs &src, uint32_t sstride, uint32_t tw, u
         if (map.pcol[c] >= 0 && (!table || !map.ne || (uint32_t)map.pcol[c] >= map.npc)) return hipErrorInvalidValue;
     }
     if (!tw || !th) return hipSuccess;
-#define GRK_PALF(T) \
-    do { \
-        if (!ops) launch_pal<T, 0>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev, \
-                                   map, table, s); \
-        else launch_pal<T, OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev, \
-                                    map, table, s, *ops); \
-    } while (0)
-    switch (fmt) {
-        case SMP_I32: GRK_PALF(int32_t); break;
-        case SMP_U8: GRK_PALF(uint8_t); break;
-        case SMP_I8: GRK_PALF(int8_t); break;
-        case SMP_U16: GRK_PALF(uint16_t); break;
-        case SMP_I16: GRK_PALF(int16_t); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_PALF
-    return hipGetLastError();
-}
-
-template <typename T, bool FAST>
-static void launch_up_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
-                          const DstPlanes &dst, bool interleaved, uint32_t dstride, const OutOps &ops,
-                          hipStream_t s) {
-    const UpComp *c = src.c;
-    if constexpr (FAST) {
-        // (eYCC / CMYK need one grid, which this shape is not: k_upsample_any's)
-        if (!ops.col && ncomp == 3 && c[0].dx == 1 && c[0].dy == 1 && c[1].dx == 2 && c[2].dx == 2 &&
-            c[1].dy == c[2].dy && (c[1].dy == 1 || c[1].dy == 2)) {
-            const uint32_t runs = (uint32_t)(((uint64_t)w + NarrowRun<T>::N - 1) / NarrowRun<T>::N + 1);
-            const dim3 grid((runs + 255) / 256, h);
-#define GRK_420(IL, OP) \
-    hipLaunchKernelGGL((k_upsample_420<T, IL, OP>), grid, dim3(256), 0, s, src, X0, Y0, w, h, dst, dstride, ops)
-            if (interleaved) {
-                if (ops.sycc) GRK_420(true, OP_SYCC); else GRK_420(true, OP_PREC);
-            } else {
-                if (ops.sycc) GRK_420(false, OP_SYCC); else GRK_420(false, OP_PREC);
-            }
-#undef GRK_420
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_upsample_any<T, OP_PREC>), dim3((w + 255) / 256, h), dim3(256), 0, s, src, ncomp, X0, Y0, w, h,
-                       dst, interleaved ? 1 : 0, dstride, ops);
-}
-
-hipError_t launch_upsample_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, uint32_t Y0, uint32_t w, uint32_t h,
-                               const DstPlanes &dst, int32_t fmt, bool interleaved, uint32_t dstride,
-                               const OutOps &ops, hipStream_t s) {
-    if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS || !sycc_launchable(ops, ncomp, fmt))
-        return hipErrorInvalidValue;
-    for (uint32_t k = 0; k < ncomp; ++k)
-        if (!src.c[k].dx || !src.c[k].dy) return hipErrorInvalidValue;
-    if (!w || !h) return hipSuccess;
-#define GRK_UP(T, FAST) launch_up_ops<T, FAST>(src, ncomp, X0, Y0, w, h, dst, interleaved, dstride, ops, s)
-    switch (fmt) {
-        case SMP_I32: GRK_UP(int32_t, true); break;
-        case SMP_U8: GRK_UP(uint8_t, true); break;
-        case SMP_I8: GRK_UP(int8_t, false); break;
-        case SMP_U16: GRK_UP(uint16_t, true); break;
-        case SMP_I16: GRK_UP(int16_t, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_UP
-    return hipGetLastError();
+    return with_sample_type(fmt, [&](auto t) {
+        using T = decltype(t);
+        if (!ops) launch_pal<T, 0>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev,
+                                   map, table, s);
+        else launch_pal<T, OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev,
+                                    map, table, s, *ops);
+    });
 }
 
 // ---------------------------------------------------------------------------
-// The converting stores for a table of jobs (the batch decode with output
-// ops): k_store_jobs' workgroup-to-job search in front of the per-tile
-// kernels' bodies.  The search, the job record and the job's OutOps depend on
-// blockIdx alone, so they are uniform over the workgroup.  No LDS, no atomics,
+// launch_upsample_ops for a table of jobs (ConvJob; the batch decode with
+// output ops), in its two thread shapes: job_of_wg in front of
+// upsample_420_run / upsample_any_pixel.  The job stays in memory: its
+// components and destinations are indexed at run time.  No LDS, no atomics,
 // nothing shared between workgroups.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t job_of_wg(const uint32_t *__restrict__ first, uint32_t njobs, uint32_t wg) {
-    uint32_t lo = 0, hi = njobs;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (first[mid] <= wg) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// k_mct_inv_dcshift_pixels' body on a job: NC components read, NCH channels stored
-template <typename T, int NC, int OP>
-__device__ __forceinline__ void store_job_pixels_ops(const StoreJob &J, uint32_t y, uint32_t t, const ShiftArr &shift,
-                                                     const ShiftArr &minv, const ShiftArr &maxv, int32_t mct,
-                                                     int32_t irrev, const OutOps &ops) {
-    constexpr int N = NarrowRun<T>::N;
-    constexpr int NCH = OP == OP_CMYK ? NC - 1 : NC;
-    T *const drow = (T *)J.dst[0] + (size_t)y * J.dstride;
-    uint32_t x0;
-    const int n = run_of<N>((uintptr_t)drow, NCH * sizeof(T), t, J.w, x0);
-    if (n <= 0) return;
-    const size_t si = (size_t)y * J.sstride + x0;
-    int32_t v[NC][N];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) load_run<N>(J.src[k] + si, n, v[k]);
-    if (mct) inv_mct_run<N>(v[0], v[1], v[2], irrev, shift, minv, maxv);
-#pragma unroll
-    for (int k = 0; k < NC; ++k)
-        if (!mct || k >= 3) inv_plain_run<N>(v[k], (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-    if constexpr (op_ycc(OP)) ycc_run<OP, N>(v[0], v[1], v[2], ops);
-    if constexpr (OP == OP_CMYK) cmyk_run<N>(v[0], v[1], v[2], v[3], ops);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) prec_run<N>(v[chan_comp(OP, c)], ops.pc[c]);
-    int32_t px[N * NCH];
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) px[i * NCH + c] = v[chan_comp(OP, c)][i];
-    store_samples<T, N * NCH>(drow + (size_t)x0 * NCH, px, n * NCH);
-}
-
-// launch_mct_inv_dcshift_ops for a table: OP_SYCC / OP_EYCC jobs have three
-// components, OP_CMYK jobs four
-template <typename T, bool IL, int OP>
-__global__ void __launch_bounds__(256) k_store_jobs_ops(const StoreJob *__restrict__ jobs,
-                                                        const uint32_t *__restrict__ first, uint32_t njobs,
-                                                        const OutOps *__restrict__ opstab) {
-    constexpr int N = NarrowRun<T>::N;
-    const uint32_t wg = blockIdx.x;
-    const uint32_t lo = job_of_wg(first, njobs, wg);
-    const StoreJob J = jobs[lo];
-    const OutOps &ops = opstab[J.ops];
-    const uint32_t ncomp = op_ycc(OP) ? 3u : (OP == OP_CMYK ? 4u : J.ncomp), tw = J.w, th = J.h;
-    const int32_t mct = J.mct && ncomp >= 3, irrev = (int32_t)J.irrev;
-    ShiftArr shift{}, minv{}, maxv{};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { shift.v[k] = J.shift[k]; minv.v[k] = J.mn[k]; maxv.v[k] = J.mx[k]; }
-    const uint32_t rpr = store_job_row_threads(tw, ncomp, (uint32_t)sizeof(T), IL);
-    const uint32_t g = (wg - first[lo]) * 256u + threadIdx.x;
-    const uint32_t y = g / rpr, t = g - y * rpr;
-    if (y >= th) return;
-    if constexpr (IL) {
-        if constexpr (op_ycc(OP)) { store_job_pixels_ops<T, 3, OP>(J, y, t, shift, minv, maxv, mct, irrev, ops); return; }
-        if constexpr (OP == OP_CMYK) { store_job_pixels_ops<T, 4, OP>(J, y, t, shift, minv, maxv, mct, irrev, ops); return; }
-        if constexpr (OP == OP_PREC) {
-            if (ncomp == 3) { store_job_pixels_ops<T, 3, OP>(J, y, t, shift, minv, maxv, mct, irrev, ops); return; }
-            if (ncomp == 4) { store_job_pixels_ops<T, 4, OP>(J, y, t, shift, minv, maxv, mct, irrev, ops); return; }
-            if (ncomp == 2) {  // a thread per pixel, a store per sample
-                const size_t si = (size_t)y * J.sstride + t;
-                T *const d = (T *)J.dst[0] + (size_t)y * J.dstride + (size_t)t * 2;
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    int32_t a[1] = {J.src[k][si]};
-                    inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-                    prec_run<1>(a, ops.pc[k]);
-                    __builtin_nontemporal_store((T)a[0], d + k);
-                }
-                return;
-            }
-        }
-    }
-    // planar (one interleaved component is a plane): k_mct_inv_dcshift_planar's body
-    const size_t drow = (size_t)y * J.dstride;
-    uint32_t x0;
-    const int n = run_of<N>((uintptr_t)((T *)J.dst[0] + drow), sizeof(T), t, tw, x0);
-    if (n <= 0) return;
-    const size_t si = (size_t)y * J.sstride + x0, di = drow + x0;
-    if constexpr (OP == OP_CMYK) {
-        PlanePtrs sp{};
-        DstPlanes dp{};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { sp.p[k] = const_cast<int32_t *>(J.src[k]); dp.p[k] = J.dst[k]; }
-        cmyk_planar_run<T>(sp, si, dp, di, n, shift, minv, maxv, mct, irrev, ops);
-        return;
-    }
-    if (op_ycc(OP) || mct) {
-        int32_t a[N], b[N], c[N];
-        load_run<N>(J.src[0] + si, n, a);
-        load_run<N>(J.src[1] + si, n, b);
-        load_run<N>(J.src[2] + si, n, c);
-        if (!op_ycc(OP) || mct) {
-            inv_mct_run<N>(a, b, c, irrev, shift, minv, maxv);
-        } else {
-            inv_plain_run<N>(a, irrev & 1, shift.v[0], minv.v[0], maxv.v[0]);
-            inv_plain_run<N>(b, (irrev >> 1) & 1, shift.v[1], minv.v[1], maxv.v[1]);
-            inv_plain_run<N>(c, (irrev >> 2) & 1, shift.v[2], minv.v[2], maxv.v[2]);
-        }
-        if constexpr (op_ycc(OP)) ycc_run<OP, N>(a, b, c, ops);
-        prec_run<N>(a, ops.pc[0]);
-        prec_run<N>(b, ops.pc[1]);
-        prec_run<N>(c, ops.pc[2]);
-        store_samples<T, N>((T *)J.dst[0] + di, a, n);
-        store_samples<T, N>((T *)J.dst[1] + di, b, n);
-        store_samples<T, N>((T *)J.dst[2] + di, c, n);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if ((uint32_t)k >= ncomp || ((op_ycc(OP) || mct) && k < 3)) continue;
-        int32_t a[N];
-        load_run<N>(J.src[k] + si, n, a);
-        inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-        prec_run<N>(a, ops.pc[k]);
-        store_samples<T, N>((T *)J.dst[k] + di, a, n);
-    }
-}
-
-hipError_t launch_store_jobs_ops(const StoreJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg,
-                                 const OutOps *ops, int32_t fmt, bool interleaved, int op, hipStream_t s) {
-    if (!njobs || !nwg) return hipSuccess;
-    if (op < OP_PREC || op > OP_CMYK) return hipErrorInvalidValue;
-    if (op != OP_PREC && fmt != SMP_I32 && fmt != SMP_U8 && fmt != SMP_U16) return hipErrorInvalidValue;
-#define GRK_JO(T, IL, OP) \
-    hipLaunchKernelGGL((k_store_jobs_ops<T, IL, OP>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs, ops)
-#define GRK_JP(T)                                                          \
-    do {                                                                   \
-        if (interleaved) GRK_JO(T, true, OP_PREC); else GRK_JO(T, false, OP_PREC); \
-    } while (0)
-#define GRK_JC(T)                                                                          \
-    do {                                                                                   \
-        if (op == OP_PREC) GRK_JP(T);                                                      \
-        else if (op == OP_SYCC) { if (interleaved) GRK_JO(T, true, OP_SYCC); else GRK_JO(T, false, OP_SYCC); } \
-        else if (op == OP_EYCC) { if (interleaved) GRK_JO(T, true, OP_EYCC); else GRK_JO(T, false, OP_EYCC); } \
-        else { if (interleaved) GRK_JO(T, true, OP_CMYK); else GRK_JO(T, false, OP_CMYK); }  \
-    } while (0)
-    switch (fmt) {
-        case SMP_I32: GRK_JC(int32_t); break;
-        case SMP_U8: GRK_JC(uint8_t); break;
-        case SMP_I8: GRK_JP(int8_t); break;
-        case SMP_U16: GRK_JC(uint16_t); break;
-        case SMP_I16: GRK_JP(int16_t); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_JC
-#undef GRK_JP
-#undef GRK_JO
-    return hipGetLastError();
-}
-
-// launch_upsample_ops for a table, in its two thread shapes.  The job stays
-// in memory: its components and destinations are indexed at run time.
 template <typename T, bool IL, int OP>
 __global__ void __launch_bounds__(256) k_conv_jobs_420(const ConvJob *__restrict__ jobs,
                                                        const uint32_t *__restrict__ first, uint32_t njobs,
@@ -3101,29 +2933,25 @@ __global__ void __launch_bounds__(256) k_conv_jobs_any(const ConvJob *__restrict
 hipError_t launch_conv_jobs(const ConvJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg,
                             const OutOps *ops, int32_t fmt, bool interleaved, bool fast, bool sycc, hipStream_t s) {
     if (!njobs || !nwg) return hipSuccess;
-    if (fast && fmt != SMP_I32 && fmt != SMP_U8 && fmt != SMP_U16) return hipErrorInvalidValue;
-#define GRK_C420(T, IL, OP) \
-    hipLaunchKernelGGL((k_conv_jobs_420<T, IL, OP>), dim3(nwg), dim3(256), 0, s, jobs, first, njobs, ops)
-#define GRK_CANY(T) \
-    hipLaunchKernelGGL(k_conv_jobs_any<T>, dim3(nwg), dim3(256), 0, s, jobs, first, njobs, ops, interleaved ? 1 : 0)
-#define GRK_CJ(T)                                                                                        \
-    do {                                                                                                 \
-        if (!fast) GRK_CANY(T);                                                                          \
-        else if (interleaved) { if (sycc) GRK_C420(T, true, OP_SYCC); else GRK_C420(T, true, OP_PREC); } \
-        else { if (sycc) GRK_C420(T, false, OP_SYCC); else GRK_C420(T, false, OP_PREC); }                \
-    } while (0)
-    switch (fmt) {
-        case SMP_I32: GRK_CJ(int32_t); break;
-        case SMP_U8: GRK_CJ(uint8_t); break;
-        case SMP_I8: GRK_CANY(int8_t); break;
-        case SMP_U16: GRK_CJ(uint16_t); break;
-        case SMP_I16: GRK_CANY(int16_t); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GRK_CJ
-#undef GRK_CANY
-#undef GRK_C420
-    return hipGetLastError();
+    if (fast && !colour_fmt_of(fmt)) return hipErrorInvalidValue;
+    return with_sample_type(fmt, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (colour_fmt<T>) {
+            if (fast) {
+                const auto run = [&](auto il, auto op) {
+                    hipLaunchKernelGGL((k_conv_jobs_420<T, decltype(il)::value != 0, decltype(op)::value>), dim3(nwg),
+                                       dim3(256), 0, s, jobs, first, njobs, ops);
+                };
+                if (interleaved && sycc) run(Const<1>{}, Const<OP_SYCC>{});
+                else if (interleaved) run(Const<1>{}, Const<OP_PREC>{});
+                else if (sycc) run(Const<0>{}, Const<OP_SYCC>{});
+                else run(Const<0>{}, Const<OP_PREC>{});
+                return;
+            }
+        }
+        hipLaunchKernelGGL(k_conv_jobs_any<T>, dim3(nwg), dim3(256), 0, s, jobs, first, njobs, ops,
+                           interleaved ? 1 : 0);
+    });
 }
 
 // MQ encoder: 64 blocks (lanes) per wavefront.  The coder is a serial chain

@@ -109,8 +109,9 @@ def test_mixed_formats_in_one_batch(codec):
 def _store_jobs(rng, T, layout, ncomp, mct, irrev, widths, heights, odd):
     """Jobs over random planes, one per (w, h): (job dict, guard-extended destination)."""
     import torch
-    prec, sgnd, tdt = {np.uint8: (8, False, torch.uint8), np.uint16: (12, False, torch.uint16),
-                       np.int16: (12, True, torch.int16), np.int32: (16, True, torch.int32)}[T]
+    prec, sgnd, tdt = {np.uint8: (8, False, torch.uint8), np.int8: (8, True, torch.int8),
+                       np.uint16: (12, False, torch.uint16), np.int16: (12, True, torch.int16),
+                       np.int32: (16, True, torch.int32)}[T]
     jobs = []
     for w in widths:
         for h in heights:
@@ -149,7 +150,7 @@ def _run_store_jobs(jobs, layout):
         assert torch.equal(x, y), ("job %d of %d" % (i, len(jobs)), jobs[i]["w"], jobs[i]["src"].shape)
 
 
-@pytest.mark.parametrize("T", [np.uint8, np.uint16, np.int16, np.int32])
+@pytest.mark.parametrize("T", [np.uint8, np.int8, np.uint16, np.int16, np.int32])
 @pytest.mark.parametrize("layout", ["chw", "hwc"])
 def test_store_jobs_edges(T, layout):
     """k_store_jobs through the stage call: widths around the type's run

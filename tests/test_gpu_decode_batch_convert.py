@@ -219,6 +219,45 @@ def test_convert_jobs_table(T, layout):
     _run(jobs, layout)
 
 
+@pytest.mark.parametrize("T", [np.int8, np.int16])
+@pytest.mark.parametrize("layout", ["chw", "hwc"])
+def test_convert_jobs_signed_one_grid(T, layout):
+    """Signed raw sources on one grid with a precision op -- the job kernel's
+    int8 / int16 stores with ops -- against grk.convert_to on the same int32
+    planes (a signed component has no DC shift, so its raw samples are its
+    finished ones; both clamp to the component's range first): 1 .. 4
+    components of 12 bits, scaled and clipped to the output precision, widths
+    1, N - 1, N, N + 1 around the run length N = 16 / sizeof(T), heights 1 and
+    3, destinations at odd offsets with padded rows, guards around them."""
+    grk, torch = _grk_torch()
+    rng = np.random.default_rng(13)
+    il = layout == "hwc"
+    N = 16 // np.dtype(T).itemsize
+    half = 1 << 11
+    jobs, alts = [], []
+    for nc in (1, 2, 3, 4):
+        for w in (1, N - 1, N, N + 1):
+            for h in (1, 3):
+                n = len(jobs)
+                out_prec, mode = (8 if T == np.int8 else (16, 10)[n % 2]), ("scale", "clip")[(n // 2) % 2]
+                x0, y0, off, pad = 3 + (n & 1), 2, n % 4, n % 3
+                src = torch.from_numpy(rng.integers(-half - 20, half + 20, (nc, h, w + 3)).astype(np.int32)).cuda()
+                row = (nc * w if il else w) + pad
+                size = off + (h if il else nc * h) * row + 16
+                base, alt = (torch.from_numpy(np.full(size, 0x5A, dtype=T)).cuda() for _ in range(2))
+                comps = [dict(src=src[k], prec=12, sgnd=True, dx=1, dy=1, origin=(x0, y0), raw=True) for k in range(nc)]
+                jobs.append(dict(rect=(x0, y0, x0 + w, y0 + h), comps=comps, dst=base[off:], dst_stride=row,
+                                 out_prec=out_prec, prec_mode=mode))
+                grk.convert_to([src[k][:, :w] for k in range(nc)], alt[off:], (x0, y0, x0 + w, y0 + h), [(1, 1)] * nc, 12,
+                               True, layout=layout, dst_stride=row, out_prec=out_prec, prec_mode=mode)
+                alts.append((base, alt, (nc, w, h, out_prec, mode, off, pad)))
+    grk.convert_jobs_to(jobs, layout=layout)
+    torch.cuda.synchronize()
+    for base, alt, what in alts:
+        assert not bool((alt == 0x5A).all()), what  # (the reference call stored something)
+        assert torch.equal(base, alt), what
+
+
 def test_convert_jobs_refusals():
     grk, torch = _grk_torch()
     rng = np.random.default_rng(12)
