@@ -1664,6 +1664,19 @@ __device__ __forceinline__ void t1_tables_init(uint8_t *zc, uint8_t *sc, uint32_
     __syncthreads();
 }
 
+// v_writelane_b32: lane `lane` of `old` replaced by the wave-uniform v.  A
+// compiler that has the builtin takes it; the clang of ROCm 7.2.0 (AMD clang
+// 22.0.0git, roc-7.2.0) has none, and there the declaration below binds the
+// LLVM intrinsic by its name (checked on that version: one v_writelane_b32 per
+// call, the hazard wait states placed by the compiler).
+#if __has_builtin(__builtin_amdgcn_writelane)
+__device__ __forceinline__ uint32_t wave_writelane(uint32_t v, uint32_t lane, uint32_t old) {
+    return (uint32_t)__builtin_amdgcn_writelane((int)v, (int)lane, (int)old);
+}
+#else
+extern "C" __device__ uint32_t wave_writelane(uint32_t v, uint32_t lane, uint32_t old) __asm("llvm.amdgcn.writelane.i32");
+#endif
+
 // One wavefront per block, lane = row.  Workgroup b runs on XCD b % 8 (the
 // dispatcher deals workgroups round-robin), so the 64 blocks of group g are
 // given to workgroups of one XCD, back to back: their row words, 8 bytes per
@@ -1678,7 +1691,7 @@ __global__ __launch_bounds__(64) void k_t1_prep(const EncBlock *__restrict__ blo
     const EncBlock b = blocks[i];
     const int32_t *src = coef + b.coef_off;
     uint32_t m[64];
-    uint64_t negrow = 0;
+    uint32_t neg_lo = 0, neg_hi = 0;
     uint32_t orv = 0;
 #pragma unroll
     for (int y = 0; y < 64; ++y) {
@@ -1686,8 +1699,10 @@ __global__ __launch_bounds__(64) void k_t1_prep(const EncBlock *__restrict__ blo
         if ((uint32_t)y < b.h && x < b.w) mv = quant_mag(src[(size_t)y * b.stride + x], b.qmfbid, b.inv_step, &ng);
         m[y] = mv;
         orv |= mv;
-        uint64_t bal = __ballot(ng);
-        if (x == (uint32_t)y) negrow = bal;
+        const uint64_t bal = __ballot(ng);
+        // lane y keeps row y's ballot (a wave-uniform pair of words)
+        neg_lo = wave_writelane((uint32_t)bal, y, neg_lo);
+        neg_hi = wave_writelane((uint32_t)(bal >> 32), y, neg_hi);
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) orv |= __shfl_xor(orv, off);
@@ -1698,19 +1713,29 @@ __global__ __launch_bounds__(64) void k_t1_prep(const EncBlock *__restrict__ blo
     }
     const EncScratch E = enc_scratch(scr, n, maxdepth);
     uint64_t *G = E.group(i >> 6) + (i & 63);  // row R of this block: G[R * 64]
-    G[(T1E_NEG + x + 1) * 64] = x < b.h ? negrow : 0;
+    G[(T1E_NEG + x + 1) * 64] = x < b.h ? (uint64_t)neg_hi << 32 | neg_lo : 0;
     if (x == 0) G[T1E_NEG * 64] = 0;
     if (x == 63) G[(T1E_NEG + 65) * 64] = 0;
     const uint32_t nd = numbps < maxdepth ? numbps : maxdepth;  // numbps > maxdepth: refused (res.pad)
+    // the top plane's bit (bit numbps + 5, the highest set in the block) to
+    // bit 31: each plane is then the ballot of the sign bits, and one shift
+    // per (row, plane) moves the next plane up
+    if (nd) {
+        const uint32_t up = (uint32_t)__clz(orv);
+#pragma unroll
+        for (int y = 0; y < 64; ++y) m[y] <<= up;
+    }
     uint64_t acc = 0;  // significance before plane p = OR of the planes above
     for (uint32_t d = 0; d < nd; ++d) {
-        const uint32_t p = numbps - 1 - d;
-        uint64_t mine = 0;
+        uint32_t lo = 0, hi = 0;
 #pragma unroll
         for (int y = 0; y < 64; ++y) {
-            uint64_t bal = __ballot((m[y] >> (p + 6)) & 1u);
-            if (x == (uint32_t)y) mine = bal;
+            const uint64_t bal = __ballot((int32_t)m[y] < 0);
+            m[y] <<= 1;
+            lo = wave_writelane((uint32_t)bal, y, lo);
+            hi = wave_writelane((uint32_t)(bal >> 32), y, hi);
         }
+        const uint64_t mine = (uint64_t)hi << 32 | lo;
         if (x < b.h) {
             G[(t1e_depth_row(d) + T1E_BITS + x) * 64] = mine;
             G[(t1e_depth_row(d) + T1E_ABOVE + x) * 64] = acc;
@@ -2173,84 +2198,137 @@ __global__ __launch_bounds__(LANES * WAVES) __attribute__((amdgpu_waves_per_eu(W
                  cxw, pa, pb, ring, 6);
 }
 
-// Rebuild of the decoded values from the lane-interleaved bit-plane rows:
-// one workgroup of 4 wavefronts per (64-block group, RB_ROWS rows).  For
-// each row, lane l of every wavefront stages its block's plane words of that
-// row into LDS (wavefront w takes the planes q = w mod 4; one 512-byte run
-// per plane); then wavefront w takes blocks b = w mod 4, and lane x forms
-// coefficient (y, x) from the LDS words (broadcast reads; the block's
-// parameters by readlane) and the row is stored coalesced.  Then
-// T1Part1::postDecode scaling (5/3: v/2, 9/7: float(v) * step).  roi (null:
-// none): per-block ROI up-shift -- T1Part1::post_decode (T1Part1.cpp:230-250)
-// shifts magnitudes >= 2^roishift down by roishift (and zeroes the block for
-// a shift >= 31) before the scaling.
-constexpr uint32_t RB_ROWS = 8;
-__global__ __launch_bounds__(256) void k_t1_rebuild(const DecBlock *__restrict__ blocks, uint32_t n,
-                                                    const T1Scratch *__restrict__ scr, int32_t *__restrict__ tiles,
-                                                    const uint8_t *__restrict__ roi) {
-    __shared__ uint64_t s_sig[32][64];  // [plane][block]
-    __shared__ uint64_t s_ref[32][64];
-    __shared__ uint64_t s_neg[64];
-    const uint32_t g = blockIdx.x, l = threadIdx.x & 63;
-    const int32_t w = (int32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t y0 = blockIdx.y * RB_ROWS;
-    const uint64_t *gb = t1_group_base(const_cast<T1Scratch *>(scr), g, sizeof(T1Scratch));
-    const uint32_t nb = n - g * 64 < 64 ? n - g * 64 : 64;
-    // this lane's block (lane l < nb)
-    DecBlock mb{};
-    DecodedPlanes dp{-1, 0, 32};
-    uint32_t rs = 0;
-    if (l < nb) {
-        mb = blocks[g * 64 + l];
-        dp = decoded_planes(mb.len && mb.numbps <= T1_MAX_DEC_BPS ? mb.numpasses : 0, mb.numbps);
-        rs = roi ? roi[g * 64 + l] : 0u;
+// Rebuild of the decoded values from the lane-interleaved bit-plane rows, on
+// the scalar side.  A wavefront takes an octet -- 8 adjacent blocks of a
+// group, 64 bytes of every plane row (row R of block b of a group is word
+// R * 64 + b) -- for RB_ROWS rows; lane x forms the coefficients of column x.
+// Every 64-bit row mask is wave-uniform: one 64-byte scalar load brings the
+// octet's words of a (plane, row), the magnitude bit-plane
+//   M_q = (S_q & ~above) | (R_q & above),   above = S_{q+1} | S_{q+2} | ..
+// (S sigafter, R refbit: the first significant plane's bit is 1, the planes
+// under it carry their refinement bits) is formed per block in SGPRs, and the
+// lane takes its bit with a select on that mask and a shift-or: 2 VALU per
+// (block, plane), no LDS, no barrier.  The value is t1_rebuild's (t1_lane.h):
+// with m the magnitude bits at their planes, 2 * m + min(m, 1 << qlow).
+// The blocks of an octet differ in their planes and shapes: a plane outside a
+// block's [low, top] (sigafter) or [qlow, top - 1] (refbit) is replaced by 0
+// by a scalar select on the block's plane sets, and the rows read are those
+// of the union over the octet's blocks that have the row -- what the decoder
+// wrote.  A 64-byte load also brings the words of the octet's blocks that
+// lack that plane or row and of the lanes past the last block: words the
+// decoder may not have written (they lie inside the scratch, whose groups are
+// whole -- t1_scratch_records), read and then dropped -- the plane-set select
+// replaces them by 0, and a block without the row is skipped before its
+// accumulator is used.  The refbit words R likewise keep the row's last
+// loaded plane (0 at first) where no block has a refinement row: every
+// rf[b] select is then 0.
+// Then T1Part1::postDecode scaling (5/3: v/2, 9/7: float(v) * step).
+// roi (null: none): per-block ROI up-shift -- T1Part1::post_decode
+// (T1Part1.cpp:230-250) shifts magnitudes >= 2^roishift down by roishift (and
+// zeroes the block for a shift >= 31) before the scaling.
+constexpr uint32_t RB_ROWS = 8, RB_WAVES = 4;
+typedef uint64_t rb_octet __attribute__((ext_vector_type(8)));
+// one plane of the octet; ALL: every block has the plane in both sets
+template <bool ALL>
+__device__ __forceinline__ void rb_plane(const rb_octet &S, const rb_octet &R, const uint32_t (&in)[8],
+                                         const uint32_t (&rf)[8], uint32_t q, uint32_t sh, uint64_t (&above)[8],
+                                         uint32_t (&acc)[8]) {
+#pragma unroll
+    for (uint32_t b = 0; b < 8; ++b) {
+        const uint64_t s = ALL || ((in[b] >> q) & 1u) ? S[b] : 0, r = ALL || ((rf[b] >> q) & 1u) ? R[b] : 0;
+        const uint64_t m = (s & ~above[b]) | (r & above[b]);
+        above[b] |= s;
+        acc[b] = (acc[b] << sh) | (__builtin_amdgcn_inverse_ballot_w64(m) ? 1u : 0u);
     }
-    // packed per-block parameters for the readlane broadcasts
-    const uint32_t pk = (uint32_t)(dp.top & 0xff) | ((uint32_t)dp.low & 0xff) << 8 | ((uint32_t)dp.qlow & 0xff) << 16 |
-                        (rs & 0xff) << 24;
-    const uint32_t wh = mb.w | mb.h << 8 | (mb.irrev ? 1u << 16 : 0u);
-    const uint64_t *pa = gb + (size_t)T1R_PA * 64 + l, *pb = gb + (size_t)T1R_PB * 64 + l;
-    const uint64_t *ng = gb + (size_t)T1R_NEG * 64 + l;
-    for (uint32_t y = y0; y < y0 + RB_ROWS; ++y) {
-        if (y < mb.h && dp.top >= 0) {
-            for (int32_t q = dp.low + ((w - dp.low) & 3); q <= dp.top; q += 4)
-                s_sig[q][l] = pa[(size_t)((uint32_t)q * 64 + y) * 64];
-            for (int32_t q = dp.qlow + ((w - dp.qlow) & 3); q < dp.top; q += 4)
-                s_ref[q][l] = pb[(size_t)((uint32_t)q * 64 + y) * 64];
-            if (w == 0) s_neg[l] = ng[(size_t)(y + 1) * 64];
+}
+__global__ __launch_bounds__(64 * RB_WAVES) void k_t1_rebuild(const DecBlock *__restrict__ blocks, uint32_t n,
+                                                              const T1Scratch *__restrict__ scr,
+                                                              int32_t *__restrict__ tiles,
+                                                              const uint8_t *__restrict__ roi) {
+    const uint32_t l = threadIdx.x & 63;
+    const uint32_t i0 = (blockIdx.x * RB_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * 8;
+    if (i0 >= n) return;
+    const uint32_t nb = n - i0 < 8 ? n - i0 : 8;
+    const uint32_t y0 = blockIdx.y * RB_ROWS;
+    // lane b < nb holds block b's parameters: the plane sets of its sigafter
+    // and refbit rows stay in SGPRs, what forms and stores the value is
+    // read from the lane once per row
+    DecBlock mb{};
+    uint32_t in_l = 0, rf_l = 0, pk = 0;
+    if (l < nb) {
+        mb = blocks[i0 + l];
+        const DecodedPlanes dp = decoded_planes(mb.len && mb.numbps <= T1_MAX_DEC_BPS ? mb.numpasses : 0, mb.numbps);
+        if (dp.top >= 0) {
+            in_l = ((2u << dp.top) - 1) & ~((1u << dp.low) - 1);
+            if (dp.qlow < 32) rf_l = ((1u << dp.top) - 1) & ~((1u << dp.qlow) - 1);
         }
-        __syncthreads();
-        for (uint32_t b = (uint32_t)w; b < nb; b += 4) {
-            const uint32_t bwh = __builtin_amdgcn_readlane(wh, b);
-            const uint32_t bh = (bwh >> 8) & 0xff, bw = bwh & 0xff;
-            if (y >= bh) continue;  // uniform
-            const uint32_t bpk = __builtin_amdgcn_readlane(pk, b);
-            const int32_t top = (int8_t)(bpk & 0xff), low = (int32_t)((bpk >> 8) & 0xff);
-            const int32_t qlow = (int32_t)((bpk >> 16) & 0xff);
-            const uint32_t brs = bpk >> 24;
-            int32_t v = 0;
-            if (top >= 0) {
-                uint32_t cs = 0;  // bit (q - low): significant after plane q
-                for (int32_t q = top; q >= low; --q) cs = (cs << 1) | (uint32_t)((s_sig[q][b] >> l) & 1u);
-                if (cs) {
-                    const int32_t p = low + 31 - (int32_t)__clz(cs);
-                    const int32_t ql = p < qlow ? p : qlow;
-                    uint32_t cr = 0;  // bit (q - ql): refinement bit at plane q, q in [ql, p)
-                    for (int32_t q = p - 1; q >= ql; --q) cr = (cr << 1) | (uint32_t)((s_ref[q][b] >> l) & 1u);
-                    const uint32_t bits = (1u << (p - ql)) | cr;
-                    int32_t mag = (int32_t)((bits << (ql + 1)) | (1u << ql));
-                    if (brs) mag = brs >= 31 ? 0 : (mag >= (1 << brs) ? mag >> brs : mag);
-                    v = ((s_neg[b] >> l) & 1u) ? -mag : mag;
+        // the half-LSB term's bound 1 << qlow (qlow = 32: none, m < 2^30), the width, 9/7, the ROI shift
+        pk = (dp.qlow < 30 ? (uint32_t)dp.qlow : 30u) | mb.w << 8 | (mb.irrev ? 1u << 16 : 0u) |
+             (roi ? (uint32_t)roi[i0 + l] << 24 : 0u);
+    }
+    uint32_t in[8], rf[8], bh[8], hmax = 0, hmin = 64;
+    // over the octet's blocks: the planes some block has, and those all of them have in both sets
+    uint32_t uin0 = 0, urf0 = 0, all0 = ~0u;
+#pragma unroll
+    for (uint32_t b = 0; b < 8; ++b) {
+        in[b] = __builtin_amdgcn_readlane(in_l, b);
+        rf[b] = __builtin_amdgcn_readlane(rf_l, b);
+        bh[b] = __builtin_amdgcn_readlane(mb.h, b);
+        hmax = bh[b] > hmax ? bh[b] : hmax;
+        if (bh[b]) {
+            hmin = bh[b] < hmin ? bh[b] : hmin;
+            uin0 |= in[b];
+            urf0 |= rf[b];
+            all0 &= in[b] & rf[b];
+        }
+    }
+    const uint64_t *gb = t1_group_base(const_cast<T1Scratch *>(scr), i0 >> 6, sizeof(T1Scratch)) + (i0 & 56);
+    const uint32_t y1 = y0 + RB_ROWS < hmax ? y0 + RB_ROWS : hmax;
+    for (uint32_t y = y0; y < y1; ++y) {
+        // the same over the blocks that have this row
+        uint32_t uin = uin0, urf = urf0, all = all0;
+        if (y >= hmin) {
+            uin = urf = 0;
+            all = ~0u;
+#pragma unroll
+            for (uint32_t b = 0; b < 8; ++b)
+                if (y < bh[b]) {
+                    uin |= in[b];
+                    urf |= rf[b];
+                    all &= in[b] & rf[b];
                 }
-            }
+        }
+        uint32_t acc[8];
+        uint64_t above[8];
+        rb_octet S, R = 0, N = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 8; ++b) { acc[b] = 0; above[b] = 0; }
+        uint32_t ql = uin ? 31u - (uint32_t)__builtin_clz(uin) : 0;  // the last plane taken
+        for (uint32_t rem = uin; rem;) {
+            const uint32_t q = 31u - (uint32_t)__builtin_clz(rem), sh = ql - q;  // planes no block has are skipped
+            ql = q;
+            rem &= ~(1u << q);
+            S = *(const rb_octet *)(gb + (size_t)(T1R_PA + q * 64 + y) * 64);
+            if ((urf >> q) & 1u) R = *(const rb_octet *)(gb + (size_t)(T1R_PB + q * 64 + y) * 64);
+            if ((all >> q) & 1u) rb_plane<true>(S, R, in, rf, q, sh, above, acc);
+            else rb_plane<false>(S, R, in, rf, q, sh, above, acc);
+        }
+        if (uin) N = *(const rb_octet *)(gb + (size_t)(T1R_NEG + y + 1) * 64);
+#pragma unroll
+        for (uint32_t b = 0; b < 8; ++b) {
+            if (y >= bh[b]) continue;  // uniform
+            const uint32_t bpk = __builtin_amdgcn_readlane(pk, b);
+            const uint32_t m = acc[b] << ql, hb = 1u << (bpk & 0xff), brs = bpk >> 24;
+            int32_t mag = (int32_t)(2 * m + (m < hb ? m : hb));
+            if (brs) mag = brs >= 31 ? 0 : (mag >= (1 << brs) ? mag >> brs : mag);
+            const int32_t v = __builtin_amdgcn_inverse_ballot_w64(N[b]) ? -mag : mag;
             const float step = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mb.step), b));
-            const int32_t o = (bwh >> 16) ? __float_as_int(__fmul_rn((float)v, step)) : v / 2;
+            const int32_t o = (bpk >> 16) & 1u ? __float_as_int(__fmul_rn((float)v, step)) : v / 2;
             const uint32_t off_lo = __builtin_amdgcn_readlane((uint32_t)mb.dst_off, b);
             const uint32_t off_hi = __builtin_amdgcn_readlane((uint32_t)(mb.dst_off >> 32), b);
             const uint32_t stride = __builtin_amdgcn_readlane(mb.dstride, b);
-            if (l < bw) tiles[(((uint64_t)off_hi << 32) | off_lo) + (size_t)y * stride + l] = o;
+            if (l < ((bpk >> 8) & 0xff)) tiles[(((uint64_t)off_hi << 32) | off_lo) + (size_t)y * stride + l] = o;
         }
-        __syncthreads();
     }
 }
 
@@ -3180,8 +3258,8 @@ hipError_t launch_t1_decode(const DecBlock *blocks, uint32_t n, const uint8_t *d
         hipLaunchKernelGGL((k_t1_decode_ub<DEC_LANES, false, DEC_WAVES, DEC_WAVES>), dim3(nwg),
                            dim3(DEC_LANES * DEC_WAVES), 0, s, blocks, n, (const uint32_t *)ubuf, fixed_words, scratch,
                            segs, seg_first, cblksty, nullptr, bpw);
-    hipLaunchKernelGGL(k_t1_rebuild, dim3((n + 63) / 64, 64 / RB_ROWS), dim3(256), 0, s, blocks, n, scratch, tiles,
-                       roi);
+    hipLaunchKernelGGL(k_t1_rebuild, dim3((n + 8 * RB_WAVES - 1) / (8 * RB_WAVES), 64 / RB_ROWS), dim3(64 * RB_WAVES), 0,
+                       s, blocks, n, scratch, tiles, roi);
     return hipGetLastError();
 }
 
