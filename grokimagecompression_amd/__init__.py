@@ -253,6 +253,17 @@ class StoreJob(ctypes.Structure):
                 ("max", ctypes.c_int32 * 4)]
 
 
+class PaletteJob(ctypes.Structure):
+    """grkgpu_palette_job: one tile of grkgpu_palette_jobs_to (StoreJob's fields, then the channel map)."""
+    _fields_ = [("src", ctypes.c_void_p * 4), ("dst", ctypes.c_void_p * 4), ("src_stride", ctypes.c_uint32),
+                ("dst_stride", ctypes.c_uint32), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32),
+                ("numcomps", ctypes.c_uint32), ("mct", ctypes.c_int32), ("wavelet_mask", ctypes.c_uint32),
+                ("ops_", ctypes.c_uint32), ("shift", ctypes.c_int32 * 4), ("min", ctypes.c_int32 * 4),
+                ("max", ctypes.c_int32 * 4), ("chan_comp", ctypes.c_uint8 * MAXC), ("chan_pcol", ctypes.c_int8 * MAXC),
+                ("numchannels", ctypes.c_uint32), ("ne", ctypes.c_uint32), ("npc", ctypes.c_uint32),
+                ("used_", ctypes.c_uint32), ("zero", ctypes.c_int32), ("table_off", ctypes.c_uint32)]
+
+
 class CBatchItem(ctypes.Structure):
     """grkgpu_cbatch_item: one image of grkgpu_compress_batch / grkgpu_compress_batch_plan."""
     _fields_ = [("img", ImageDesc), ("p", ctypes.POINTER(CParams)), ("in_", Planes), ("cs", ctypes.c_void_p),
@@ -529,6 +540,11 @@ def lib():
                                                  P(ctypes.c_size_t)]
             L.grkgpu_palette_to.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), U32, P(U32), P(I32), P(U32), VP,
                                             U32, U32, P(OutPlanes), U32, VP]
+        if hasattr(L, "grkgpu_jp2_decompress_batch"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_jp2_decompress_batch.argtypes = [VP, P(BatchItem), P(OutOps), U32, P(DParams), P(BatchInfo),
+                                                      P(Jp2Info)]
+            L.grkgpu_jp2_batch_plan.argtypes = [P(BatchItem), P(OutOps), U32, P(DParams), P(BatchInfo), P(Jp2Info)]
+            L.grkgpu_palette_jobs_to.argtypes = [P(PaletteJob), U32, VP, U32, U32, U32, VP]
         L.grkgpu_dcshift_mct_fwd.argtypes = [P(VP), U32, U32, U32, U32, P(I32), I32, I32, VP]
         L.grkgpu_mct_inv_dcshift.argtypes = [P(VP), U32, U32, U32, U32, P(U32), P(I32), I32, I32, VP]
         L.grkgpu_dwt_fwd.argtypes = [VP, VP, U32, U32, U32, U32, U32, I32, VP]
@@ -797,6 +813,68 @@ def plan_batch_convert(bufs, dtype=None, layout="chw", reduce=0, layers=0, upsam
     dp = DParams(cp_reduce=reduce, cp_layer=layers)
     rc = lib().grkgpu_batch_convert_plan(items, arr, n, ctypes.byref(dp), ctypes.byref(info))
     return _plan_result(rc, info, items, n)
+
+
+_JP2_COLOURS = {"auto": COLOUR_AUTO, "auto_rgb": COLOUR_AUTO_RGB, None: COLOUR_NONE}
+
+
+def _jp2_batch_ops(n, colour, out_prec, prec_mode, force_rgb):
+    """The grkgpu_out_ops array of a batch of JP2 files -- one entry per file,
+    as decompress_jp2 always passes its ops -- and the per-item colour /
+    out_prec / force_rgb lists; each argument one value or a list.  (An OutOps
+    in a colour slot goes to the library as it is, for its refusals.)"""
+    colours, precs = _per_item(colour, n, "colour", "file"), _per_item(out_prec, n, "out_prec", "file")
+    modes, forces = _per_item(prec_mode, n, "prec_mode", "file"), _per_item(force_rgb, n, "force_rgb", "file")
+    arr = (OutOps * max(n, 1))()
+    for i in range(n):
+        if isinstance(colours[i], OutOps):
+            arr[i], colours[i] = colours[i], None
+            continue
+        if colours[i] not in _JP2_COLOURS:
+            raise GrkGpuError("colour must be 'auto', 'auto_rgb' or None (got %r)" % (colours[i],))
+        _out_ops(None, precs[i], modes[i])  # (argument checks)
+        arr[i] = OutOps(colour=_JP2_COLOURS[colours[i]] | (COLOUR_FORCE_RGB if forces[i] else 0),
+                        prec=int(precs[i] or 0), prec_mode=_PREC_MODES[modes[i]])
+    return arr, colours, precs, forces
+
+
+def _jp2_conversion(colour, colour_space):
+    """The conversion colour='auto' / 'auto_rgb' / None resolves to for a file of that colour space
+    (decompress's colour names; grkgpu_jp2_decompress's rule)."""
+    if colour in ("auto", "auto_rgb") and colour_space == "sycc":
+        return "sycc"
+    return colour_space if colour == "auto_rgb" and colour_space in ("eycc", "cmyk") else None
+
+
+def plan_jp2_batch(bufs, dtype=None, layout="chw", colour="auto", out_prec=None, prec_mode="clip", force_rgb=False,
+                   reduce=0, layers=0, ops=None):
+    """grkgpu_jp2_batch_plan: the host half of Codec.decompress_jp2_batch -- no
+    device call.  The arguments are one value or a list with one entry per
+    file; ops (a list of OutOps or None entries) stands in for colour /
+    out_prec / prec_mode / force_rgb where a test needs values the keywords
+    refuse.  Returns plan_batch's dict plus "infos": one Jp2Info per file."""
+    bufs = list(bufs)
+    n = len(bufs)
+    items, keep = _batch_items(bufs)
+    if ops is not None:
+        arr = (OutOps * max(n, 1))()
+        for i, o in enumerate(ops):
+            if o is not None:
+                arr[i] = o
+    else:
+        arr = _jp2_batch_ops(n, colour, out_prec, prec_mode, force_rgb)[0]
+    dtypes, layouts = _per_item(dtype, n, "dtype", "file"), _per_item(layout, n, "layout", "file")
+    for i in range(n):
+        _layout_shape((1, 1, 1), layouts[i])
+        items[i].out.sample_fmt = _out_format(dtypes[i])[1]
+        items[i].out.layout = _LAYOUTS[layouts[i]]
+    info = BatchInfo()
+    infos = (Jp2Info * max(n, 1))()
+    dp = DParams(cp_reduce=reduce, cp_layer=layers)
+    rc = lib().grkgpu_jp2_batch_plan(items, arr, n, ctypes.byref(dp), ctypes.byref(info), infos)
+    res = _plan_result(rc, info, items, n)
+    res["infos"] = [Jp2Info.from_buffer_copy(infos[i]) for i in range(n)]
+    return res
 
 
 def convert_jobs_to(jobs, layout="chw"):
@@ -1530,20 +1608,27 @@ class Codec:
         return out
 
     def _decompress_batch(self, convert, bufs, dtype, layout, device_out, out, reduce, layers, stack, errors,
-                          upsample=False, colour=None, out_prec=None, prec_mode="clip"):
+                          upsample=False, colour=None, out_prec=None, prec_mode="clip", jp2=False, force_rgb=False):
         """decompress_batch (convert=False: grkgpu_decompress_batch, a
-        subsampled stream gets no destination and the call refuses it) and
+        subsampled stream gets no destination and the call refuses it),
         decompress_batch_convert (grkgpu_decompress_batch_convert with its
         ops, LAYOUT_UPSAMPLE and the shapes colour / out_prec leave; a
-        subsampled stream that is not upsampled gets host planes), from the
-        argument checks to the list or stacked tensor they return."""
+        subsampled stream that is not upsampled gets host planes) and
+        decompress_jp2_batch (jp2=True: grkgpu_jp2_decompress_batch; the
+        geometry is the file's channels, colour is resolved by its colour
+        space and the result is (outs, infos)), from the argument checks to
+        the list or stacked tensor they return."""
         if errors not in ("raise", "return"):
             raise GrkGpuError("errors must be 'raise' or 'return'")
         bufs = list(bufs)
         n = len(bufs)
         dtypes, layouts = _per_item(dtype, n, "dtype"), _per_item(layout, n, "layout")
         devs, ups = _per_item(device_out, n, "device_out"), _per_item(upsample, n, "upsample")
-        ops, colours, precs = _batch_ops(n, colour, out_prec, prec_mode) if convert else (None, [None] * n, [None] * n)
+        forces, infos = [False] * n, [None] * n
+        if jp2:
+            ops, colours, precs, forces = _jp2_batch_ops(n, colour, out_prec, prec_mode, force_rgb)
+        else:
+            ops, colours, precs = _batch_ops(n, colour, out_prec, prec_mode) if convert else (None, [None] * n, [None] * n)
         outs = [None] * n if out is None else _per_item(list(out), n, "out")
         if layers < 0 or reduce < 0:
             raise GrkGpuError("reduce and layers must be >= 0")
@@ -1557,8 +1642,15 @@ class Codec:
             # geometry from the main header alone, by decompress's rules (the
             # library checks everything else); a stream whose header does not
             # read gets no destination and fails inside the call with its own code
-            d = ImageDesc()
-            hdr_ok = lib().grkgpu_read_header(ctypes.c_void_p(items[i].cs), items[i].len, ctypes.byref(d)) == 0
+            d, col = ImageDesc(), colours[i]
+            if jp2:  # the output channels (a file whose boxes do not read fails inside the call, like a bad header)
+                try:
+                    _, d, infos[i] = _jp2_read(buf)
+                    hdr_ok, col = True, _jp2_conversion(col, infos[i]["colour_space"])
+                except GrkGpuError:
+                    hdr_ok = False
+            else:
+                hdr_ok = lib().grkgpu_read_header(ctypes.c_void_p(items[i].cs), items[i].len, ctypes.byref(d)) == 0
             dt, fmt = _out_format(dtypes[i])
             o = outs[i]
             if o is not None and _out_dtype(o) is not None:
@@ -1575,12 +1667,12 @@ class Codec:
             subsampled = any(g != (1, 1) for g in grid)
             if subsampled and not convert:
                 continue  # refused by the call
-            chans = _out_channels(colours[i], False, [d.prec[k] for k in range(c)], [d.sgnd[k] for k in range(c)],
+            chans = _out_channels(col, bool(forces[i]), [d.prec[k] for k in range(c)], [d.sgnd[k] for k in range(c)],
                                   precs[i])
             if len(chans) != c:  # (CMYK: the black ink's plane goes; one grid either way)
                 grid = [grid[0]] * len(chans)
             c = len(chans)
-            up = (bool(ups[i]) or colours[i] == "sycc") and subsampled
+            up = (bool(ups[i]) or col == "sycc") and subsampled
             extent = lambda a0, a1, s: cd(cd(a1, s) - cd(a0, s), R)  # noqa: E731
             if subsampled and not up:  # a list of host planes, each on its grid
                 if o is not None or devs[i] or stack or (layouts[i] != "chw" and all(g == grid[0] for g in grid)):
@@ -1627,7 +1719,9 @@ class Codec:
             lib().grkgpu_set_stream(self._ctx, _stream_handle(self.device))
         info = BatchInfo()
         dp = DParams(cp_reduce=reduce, cp_layer=layers)
-        if convert:
+        if jp2:
+            rc = lib().grkgpu_jp2_decompress_batch(self._ctx, items, ops, n, ctypes.byref(dp), ctypes.byref(info), None)
+        elif convert:
             rc = lib().grkgpu_decompress_batch_convert(self._ctx, items, ops, n, ctypes.byref(dp), ctypes.byref(info))
         else:
             rc = lib().grkgpu_decompress_batch(self._ctx, items, n, ctypes.byref(dp), ctypes.byref(info))
@@ -1637,11 +1731,11 @@ class Codec:
         if rc and (errors == "raise" or not failed):
             raise GrkGpuError("grkgpu error %d: %s" % (rc, msg))
         if stacked is not None:
-            return stacked
+            return (stacked, infos) if jp2 else stacked
         for i in failed:
             outs[i] = GrkGpuError("grkgpu error %d: item %d failed%s" % (items[i].status, i,
                                                                          msg[msg.index(":"):] if failed[0] == i else ""))
-        return outs
+        return (outs, infos) if jp2 else outs
 
     def decompress_batch(self, bufs, dtype=None, layout="chw", device_out=False, out=None, reduce=0, layers=0,
                          stack=False, errors="raise"):
@@ -1680,6 +1774,25 @@ class Codec:
         return self._decompress_batch(True, bufs, dtype, layout, device_out, out, reduce, layers, stack, errors,
                                       upsample, colour, out_prec, prec_mode)
 
+    def decompress_jp2_batch(self, bufs, dtype=None, layout="chw", colour="auto", out_prec=None, prec_mode="clip",
+                             force_rgb=False, reduce=0, layers=0, device_out=False, out=None, stack=False,
+                             errors="raise"):
+        """Decode a list of .jp2 files in one launch set
+        (grkgpu_jp2_decompress_batch) -> (outs, infos): item i is what
+        decompress_jp2(buf, dtype=, layout=, colour=, out_prec=, prec_mode=,
+        force_rgb=, reduce=, layers=, device_out=) returns, array and info, bit
+        for bit -- palettes, channel swaps and force-RGB included, stored by
+        job tables of the palette kernels, so 64 copies of a palette file take
+        the launches of one.  dtype, layout, colour, out_prec, prec_mode,
+        force_rgb and device_out are one value for all files or a list with one
+        entry per file; out is None or a list of outputs.  A subsampled file
+        that is not converted gets a list of host planes.  stack=True: one
+        (n, ...) array or tensor.  errors and self.batch_info as
+        decompress_batch (errors="return": the GrkGpuError in the failing
+        item's slot of outs; its info is None when the boxes did not read)."""
+        return self._decompress_batch(True, bufs, dtype, layout, device_out, out, reduce, layers, stack, errors, False,
+                                      colour, out_prec, prec_mode, True, force_rgb)
+
     def decompress_jp2(self, buf, dtype=None, layout="chw", colour="auto", out_prec=None, prec_mode="clip",
                        window=None, reduce=0, layers=0, device_out=False, force_rgb=False):
         """Decode a .jp2 file (grkgpu_jp2_decompress) -> (array, info): the
@@ -1704,8 +1817,8 @@ class Codec:
             raise GrkGpuError("colour must be 'auto', 'auto_rgb' or None (got %r)" % (colour,))
         ji, d, info = _jp2_read(buf)
         c = d.numcomps
-        sycc = colour in ("auto", "auto_rgb") and info["colour_space"] == "sycc"
-        conv = info["colour_space"] if colour == "auto_rgb" and info["colour_space"] in ("eycc", "cmyk") else None
+        sycc = _jp2_conversion(colour, info["colour_space"]) == "sycc"
+        conv = None if sycc else _jp2_conversion(colour, info["colour_space"])
         if any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c)) and not sycc:
             mv = memoryview(buf)[ji.cs_offset:ji.cs_offset + ji.cs_length]
             return self.decompress(np.frombuffer(mv, dtype=np.uint8), dtype=dtype, layout=layout, out_prec=out_prec,
@@ -2212,3 +2325,66 @@ def palette_to(src, dst, w, prec, sgnd, chan_comp, chan_pcol, chan_prec, table=N
     _check(lib().grkgpu_palette_to(ptrs, c, w, h, sstride, pr, sg, nch, cc, cpc, cpr, tp, ne, npc, ctypes.byref(op),
                                    stride, _stream_handle(src.device)))
     return dst
+
+
+def palette_jobs_to(jobs, table=None, layout="chw"):
+    """grkgpu_palette_jobs_to: the palette stores of Codec.decompress_jp2_batch
+    for a list of tiles in one launch per table size class.  jobs: dicts with
+      src        (c <= 4, h, src_stride) int32 cuda tensor, or None with
+                 zero=True: (h given) the components count as zero samples
+      dst        flat cuda tensor, every job's of one dtype; planar: channel
+                 k's plane at k * h * dst_stride
+      w, prec, sgnd (per component), chan_comp, chan_pcol (None: the sample
+      itself), and optionally dst_stride, mct, ne, npc, table_off (the job's
+      table in `table`, in entries, even), zero, h, numcomps.
+    table: flat 16-bit cuda tensor, the merged table (None: no job looks up).
+    Returns the dsts."""
+    _layout_shape((1, 1, 1), layout)
+    il = layout == "hwc"
+    if not jobs:
+        return []
+    dt, fmt = _out_format(_out_dtype(jobs[0]["dst"]))
+    if table is not None and (table.dim() != 1 or table.element_size() != 2 or not table.is_contiguous()
+                              or not table.is_cuda):
+        raise GrkGpuError("palette_jobs_to: table: a flat cuda tensor of 16-bit entries")
+    arr = (PaletteJob * len(jobs))()
+    for i, q in enumerate(jobs):
+        src, dst, w = q.get("src"), q["dst"], int(q["w"])
+        zero = bool(q.get("zero"))
+        if src is None:
+            c, h, sstride = int(q["numcomps"]), int(q["h"]), 0
+        else:
+            c, h, sstride = src.shape
+        nch = len(q["chan_comp"])
+        row = w * nch if il else w
+        stride = row if q.get("dst_stride") is None else int(q["dst_stride"])
+        need = (h - 1) * stride + row if il else (nch * h - 1) * stride + row
+        bad = (dst.dim() != 1 or not dst.is_contiguous() or not dst.is_cuda or stride < row or (h and dst.numel() < need)
+               or _out_dtype(dst) != dt or c > 4 or not 1 <= nch <= 4 or len(q["chan_pcol"]) != nch
+               or (table is not None and table.device != dst.device) or (src is None and not zero))
+        if src is not None:
+            bad = bad or (src.dtype != _torch_dtype(np.int32) or not src.is_contiguous() or src.device != dst.device
+                          or w > sstride)
+        if bad:
+            raise GrkGpuError("palette_jobs_to: job %d: src (c <= 4,h,stride >= w) int32 (or None with zero), 1 .. 4 "
+                              "channels, dst flat %s, %d samples, on one device" % (i, dt.name, need))
+        j = arr[i]
+        prec, sgnd = _per_comp(q["prec"], c), _per_comp(q["sgnd"], c)
+        for k in range(c):
+            j.src[k] = None if src is None else src[k].data_ptr()
+            j.shift[k] = 0 if sgnd[k] else 1 << (prec[k] - 1)
+            j.min[k] = -(1 << (prec[k] - 1)) if sgnd[k] else 0
+            j.max[k] = (1 << (prec[k] - 1)) - 1 if sgnd[k] else (1 << prec[k]) - 1
+        for k in range(1 if il else nch):
+            j.dst[k] = dst.data_ptr() + k * h * stride * dt.itemsize
+        j.src_stride, j.dst_stride, j.w, j.h, j.numcomps = sstride, stride, w, h, c
+        j.mct = int(q.get("mct", 0))
+        for k in range(nch):
+            j.chan_comp[k] = int(q["chan_comp"][k])
+            j.chan_pcol[k] = -1 if q["chan_pcol"][k] is None else int(q["chan_pcol"][k])
+        j.numchannels, j.ne, j.npc = nch, int(q.get("ne", 0)), int(q.get("npc", 0))
+        j.zero, j.table_off = 1 if zero else 0, int(q.get("table_off", 0))
+    _check(lib().grkgpu_palette_jobs_to(arr, len(jobs), None if table is None else table.data_ptr(),
+                                        0 if table is None else table.numel(), fmt, _LAYOUTS[layout],
+                                        _stream_handle(jobs[0]["dst"].device)))
+    return [q["dst"] for q in jobs]

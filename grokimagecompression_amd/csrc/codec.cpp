@@ -21,6 +21,7 @@
 #include <atomic>
 #include <array>
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -4396,6 +4397,15 @@ struct TileConv {
     OutOps o;
     bool conv;
 };
+// ... and of launch_palette (a mapped item's tile or fill that the PalJob table does not take): the ops when
+// conv, the item's table `table_off` entries into the launch set's merged table (not read when map.ne = 0)
+struct TilePal {
+    TileStore ts;
+    PalMap map;
+    uint32_t table_off;
+    bool conv;
+    OutOps o;
+};
 // a tile as a record (nc <= 4) and back
 static StoreJob store_job_of(const TileStore &ts) {
     StoreJob j{};
@@ -4423,18 +4433,40 @@ static TileStore tile_store_of(const StoreJob &j, int32_t fmt, bool il) {
 // The last store of a launch set (grkgpu_decompress_batch / _convert and the
 // two stage calls): plain StoreJobs, StoreJobs with ops, ConvJobs, the OutOps
 // the jobs index, and the per-tile launches.  One device buffer holds the
-// tables: the records of the three (sizes multiples of 8, from a 16-byte
+// tables: the records of each (sizes multiples of 8, from a 16-byte
 // boundary), the OutOps, then every first array.
-static_assert(sizeof(StoreJob) % 8 == 0 && sizeof(ConvJob) % 8 == 0 && sizeof(OutOps) % 8 == 0, "table records stay aligned");
+//
+// The stores through a channel map (a JP2 item with a palette, a channel swap
+// or force-RGB) are PalJobs in two tables of their own: pal_fill, the zero jobs
+// over samples nothing decoded, and pal, the tiles.  A fill that stands for a
+// reduced decode's margin covers its item's whole output, tiles included, so
+// every fill launches before every tile store: the fills are the earlier
+// phase, and same-stream order carries the dependency.  A group's key: the
+// sample format, mode = pal_job_shape, cls = the table's LDS class
+// (pal_lds_class) + 4 with ops.  pal_table: the merged table on the device.
+static_assert(sizeof(StoreJob) % 8 == 0 && sizeof(ConvJob) % 8 == 0 && sizeof(OutOps) % 8 == 0 && sizeof(PalJob) % 8 == 0,
+              "table records stay aligned");
 struct StorePlan {
     JobTable<StoreJob> plain, conv;
     JobTable<ConvJob> up;
+    JobTable<PalJob> pal_fill, pal;
     std::vector<OutOps> ops;
     std::vector<TileStore> singles;
     std::vector<TileOpsStore> conv_singles;
     std::vector<TileConv> up_singles;
+    std::vector<TilePal> pal_singles;  // (the fills among them have map.zero set)
+    const uint16_t *pal_table = nullptr;
 
-    uint32_t njobs() const { return plain.njobs + conv.njobs + up.njobs; }
+    uint32_t njobs() const { return plain.njobs + conv.njobs + up.njobs + pal_fill.njobs + pal.njobs; }
+    // a store through a channel map: o = its ops (entry ops_index) or null; false: not tabled (the caller keeps
+    // it as a TilePal)
+    bool add_pal(int32_t fmt, bool il, const OutOps *o, PalJob j, uint32_t ops_index) {
+        if (j.s.ncomp > 4 || j.map.nch > 4) return false;
+        j.s.ops = ops_index;
+        const int shape = pal_job_shape(j.map.nch, il);
+        const JobKey key{fmt, shape, pal_lds_class(j.map.ne, j.map.npc) + (o ? 4 : 0)};
+        return (j.map.zero ? pal_fill : pal).add(key, j, pal_job_wgs(j, sample_bytes(fmt), shape));
+    }
     bool add_store(int32_t fmt, bool il, const StoreJob &j) {
         return plain.add({fmt, il, 0}, j, store_job_wgs(j, sample_bytes(fmt), il));
     }
@@ -4450,17 +4482,22 @@ struct StorePlan {
         return up.add({fmt, il, (fast ? 1 : 0) | (fast && o.sycc ? 2 : 0)}, j, conv_job_wgs(j, sample_bytes(fmt), fast));
     }
 
-    // the buffer: the three tables' records at rec[], the OutOps, the first arrays at fst[]
-    struct Places { size_t rec[3], ops, fst[3], end; };
+    // the buffer: the five tables' records at rec[] (plain, conv, up, pal_fill, pal), the OutOps, the first
+    // arrays at fst[]
+    struct Places { size_t rec[5], ops, fst[5], end; };
     Places places() const {
         Places p{};
         p.rec[1] = plain.rec_bytes();
         p.rec[2] = p.rec[1] + conv.rec_bytes();
-        p.ops = p.rec[2] + up.rec_bytes();
+        p.rec[3] = p.rec[2] + up.rec_bytes();
+        p.rec[4] = p.rec[3] + pal_fill.rec_bytes();
+        p.ops = p.rec[4] + pal.rec_bytes();
         p.fst[0] = p.ops + ops.size() * sizeof(OutOps);
         p.fst[1] = p.fst[0] + plain.first_bytes();
         p.fst[2] = p.fst[1] + conv.first_bytes();
-        p.end = p.fst[2] + up.first_bytes();
+        p.fst[3] = p.fst[2] + up.first_bytes();
+        p.fst[4] = p.fst[3] + pal_fill.first_bytes();
+        p.end = p.fst[4] + pal.first_bytes();
         return p;
     }
     size_t bytes() const { return places().end; }
@@ -4468,7 +4505,8 @@ struct StorePlan {
         const Places p = places();
         if (!ops.empty()) memcpy(stage + p.ops, ops.data(), ops.size() * sizeof(OutOps));
         const size_t filled = plain.fill(stage, p.rec[0], p.fst[0]) + conv.fill(stage, p.rec[1], p.fst[1]) +
-                              up.fill(stage, p.rec[2], p.fst[2]) + ops.size() * sizeof(OutOps);
+                              up.fill(stage, p.rec[2], p.fst[2]) + pal_fill.fill(stage, p.rec[3], p.fst[3]) +
+                              pal.fill(stage, p.rec[4], p.fst[4]) + ops.size() * sizeof(OutOps);
         return upload_tables(stage, dev, filled, p.end, s);
     }
     // Phase 1, the stores on the components' own grids, then phase 2, the
@@ -4510,6 +4548,27 @@ struct StorePlan {
                        : launch_upsample_to(t.pl, t.nc, t.r.x0, t.r.y0, t.r.w(), t.r.h(), t.dst, t.fmt, t.il, t.dstride, s);
             if (e == hipSuccess && nl) ++*nl;
         }
+        // the stores through a channel map (other items' outputs than the launches above write): the fills,
+        // tabled and per rectangle, then the tiles
+        const auto pal_launch = [&](const PalJob *j, const uint32_t *first, uint32_t n, uint32_t nwg, const JobKey &k) {
+            return launch_palette_jobs(j, first, n, nwg, k.fmt, k.mode, (k.cls & 4) ? 1 : 0, (k.cls & 4) ? dops : nullptr,
+                                       pal_table, pal_lds_bytes(k.cls & 3), s);
+        };
+        const auto pal_tiles = [&](bool zero) {
+            for (size_t i = 0; e == hipSuccess && i < pal_singles.size(); ++i) {
+                const TilePal &t = pal_singles[i];
+                if ((t.map.zero != 0) != zero) continue;
+                const TileStore &ts = t.ts;
+                e = launch_palette(ts.src, ts.sstride, ts.w, ts.h, ts.dst, ts.fmt, ts.il, ts.dstride, ts.nc, ts.sh, ts.mn,
+                                   ts.mx, ts.mct, ts.wmask, t.map, t.map.ne ? pal_table + t.table_off : nullptr,
+                                   t.conv ? &t.o : nullptr, s);
+                if (e == hipSuccess && nl) ++*nl;
+            }
+        };
+        if (e == hipSuccess) e = pal_fill.launch(dev, p.rec[3], p.fst[3], nl, pal_launch);
+        pal_tiles(true);
+        if (e == hipSuccess) e = pal.launch(dev, p.rec[4], p.fst[4], nl, pal_launch);
+        pal_tiles(false);
         return e;
     }
 
@@ -4536,6 +4595,7 @@ struct ItemBases {
     uintptr_t work0, img0;
     const size_t *roff, *stoff;
     bool host_only;
+    uint32_t pal_off = 0;  // a mapped item's table in the merged table, in entries
     uintptr_t dst(const DecHost &h, uint32_t k) const {
         if (host_only) return 0;
         return h.planes_on_device ? (uintptr_t)h.planes[k] : img0 + roff[k];
@@ -4566,6 +4626,11 @@ static void plan_conv(StorePlan &P, const DecHost &h, uint32_t &ops_at, const Up
 // the components' own grids -- with an ops index where that store converts
 // (DecHost::grid_ops) --, a ConvJob per tile of an upsampled item and per
 // rectangle of converted zeros, and per-tile launches for what no table takes.
+// An item with a channel map (h.cm: every component at (1,1), no colour
+// conversion): a PalJob per decoded tile, where decompress_impl launches the
+// palette store, and a zero PalJob where it calls fill_mapped -- the whole
+// output when it extends past the decoded samples (opad), else the tiles the
+// stream never reached; StorePlan launches the fills ahead of the tiles.
 static void plan_item_stores(StorePlan &P, const DecHost &h, const ItemBases &B) {
     const uint32_t nc = h.nc, no = h.no, nout = h.nout(), ow = h.orect[0].w();
     const size_t eb = h.il ? (size_t)no * h.sb : h.sb;
@@ -4585,6 +4650,45 @@ static void plan_item_stores(StorePlan &P, const DecHost &h, const ItemBases &B)
         if (!tabled && o) P.conv_singles.push_back(TileOpsStore{ts, *o});
         else if (!tabled) P.singles.push_back(ts);
     };
+    PalMap pmap{};
+    if (h.cm) {
+        pmap.nch = no;
+        pmap.ne = h.cm->table ? h.cm->ne : 0;
+        pmap.npc = h.cm->table ? h.cm->npc : 0;
+        for (uint32_t ch = 0; ch < no; ++ch) {
+            pmap.comp[ch] = (uint8_t)h.cm->comp[ch];
+            pmap.pcol[ch] = (int8_t)h.cm->pcol[ch];
+        }
+        set_pal_used(pmap);
+    }
+    auto pal_store = [&](const TileStore &ts, bool zero) {
+        PalJob j{};
+        j.s = store_job_of(ts);
+        j.map = pmap;
+        j.map.zero = zero ? 1 : 0;
+        j.table_off = pmap.ne ? B.pal_off : 0;
+        if (h.conv && nc <= 4 && no <= 4 && ops_at == 0xffffffffu) { ops_at = (uint32_t)P.ops.size(); P.ops.push_back(h.dops); }
+        if (!P.add_pal(ts.fmt, ts.il, h.conv ? &h.dops : nullptr, j, h.conv ? ops_at : 0))
+            P.pal_singles.push_back(TilePal{ts, j.map, j.table_off, h.conv, h.dops});
+    };
+    auto pal_fill = [&](const Rect &o) {
+        if (o.empty()) return;
+        TileStore ts{};
+        for (uint32_t k = 0; k < nout; ++k)
+            ts.dst.p[k] = (void *)(B.dst(h, k) + ((uint64_t)(o.y0 - h.orect[0].y0) * ow + (o.x0 - h.orect[0].x0)) * eb);
+        ts.w = o.w(); ts.h = o.h(); ts.dstride = h.il ? ow * no : ow; ts.nc = nc; ts.fmt = h.od.fmt; ts.il = h.il;
+        pal_store(ts, true);
+    };
+    if (h.cm && h.opad) {
+        pal_fill(h.orect[0]);
+    } else if (h.cm && h.missing) {
+        for (uint32_t t = h.tb; t < h.te; ++t) {
+            if (h.walk.decoded[t] || h.wskip[t]) continue;
+            const Rect cr = tile_rect(h.cp, t);
+            pal_fill(intersect({ceil_pow2(cr.x0, h.reduce), ceil_pow2(cr.y0, h.reduce), ceil_pow2(cr.x1, h.reduce),
+                                ceil_pow2(cr.y1, h.reduce)}, h.orect[0]));
+        }
+    }
     for (uint32_t lt = 0; lt < h.nsh; ++lt) {
         const Tile &tile = h.tiles[lt];
         if (!tile.comps.empty() && h.mixed) {  // each tile-component on its own grid, no MCT
@@ -4629,7 +4733,10 @@ static void plan_item_stores(StorePlan &P, const DecHost &h, const ItemBases &B)
                 ts.sstride = tr.w(); ts.w = out.w(); ts.h = out.h();
                 ts.dstride = pil ? ow * no : ow;  // (h.il: ow * no fits 32 bits, checked by begin())
                 ts.nc = nc; ts.fmt = gops ? h.od.fmt : gfmt; ts.il = pil; ts.mct = h.tmct[lt]; ts.wmask = wmask;
-                if (gops) {
+                if (h.cm) {
+                    ts.fmt = h.od.fmt;
+                    pal_store(ts, false);
+                } else if (gops) {
                     if (nc <= 4 && ops_at == 0xffffffffu) { ops_at = (uint32_t)P.ops.size(); P.ops.push_back(h.dops); }
                     store(ts, &h.dops, ops_at);
                 } else {
@@ -4680,10 +4787,28 @@ static void plan_item_stores(StorePlan &P, const DecHost &h, const ItemBases &B)
     }
 }
 
-// ops / convert: grkgpu_decompress_batch_convert (ops null: no item converts)
+// What grkgpu_jp2_decompress_batch knows of item i beyond its bytes, filled by
+// the entry point's `prep` on the host pool: the jp2c payload inside the file,
+// the ops with GRKGPU_COLOUR_AUTO / _AUTO_RGB resolved (o; has_ops: the caller
+// gave ops), the channel map of a file with a palette or a channel swap, and
+// whether the file says sRGB.  chan and the table it points at live until the
+// call returns.
+struct Jp2Item {
+    const uint8_t *cs = nullptr;
+    size_t len = 0;
+    grkgpu_out_ops o{};
+    bool has_ops = false;
+    const ChanMap *chan = nullptr;
+    bool is_rgb = false;
+};
+using Jp2Prep = std::function<int(size_t, Jp2Item &)>;
+
+// ops / convert: grkgpu_decompress_batch_convert (ops null: no item converts).
+// jp2 (grkgpu_jp2_decompress_batch; implies convert): items[i].cs / len are a
+// JP2 file, parsed by (*jp2)(i, ...); force-RGB is taken.
 static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
                       grkgpu_batch_info *info, bool host_only, bool convert = false,
-                      const grkgpu_out_ops *ops = nullptr) {
+                      const grkgpu_out_ops *ops = nullptr, const Jp2Prep *jp2 = nullptr) {
     if (info) *info = grkgpu_batch_info{};
     if ((!c && !host_only) || (n && !items)) return set_err(GRKGPU_EINVAL, "null argument");
     if (p && (p->DA_x0 || p->DA_y0 || p->DA_x1 || p->DA_y1))
@@ -4694,6 +4819,7 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
     const uint32_t reduce = p ? p->cp_reduce : 0, layers = p ? p->cp_layer : 0;
     std::vector<DecHost> H(n);
     std::vector<std::string> emsg(n);
+    std::vector<Jp2Item> J(jp2 ? n : 0);
     // (called on the thread whose check failed: the message is thread-local)
     auto fail = [&](size_t i, int rc) { items[i].status = rc; emsg[i] = g_err; };
     host_parallel_for(n, 1, [&](size_t a, size_t b) {
@@ -4702,18 +4828,22 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
             it.status = GRKGPU_OK;
             it.img = grkgpu_image_desc{};
             DecHost &h = H[i];
-            int rc = it.cs ? check_out_planes(&it.out) : set_err(GRKGPU_EINVAL, "null argument");
+            int rc = it.cs ? GRKGPU_OK : set_err(GRKGPU_EINVAL, "null argument");
+            if (!rc && jp2) rc = (*jp2)(i, J[i]);  // (the boxes first, as grkgpu_jp2_decompress reads them)
+            if (!rc) rc = check_out_planes(&it.out);
             if (!rc && !convert && (it.out.layout & GRKGPU_LAYOUT_UPSAMPLE))
                 rc = set_err(GRKGPU_EUNSUPPORTED, "upsampled output is not supported in a batch");
-            const grkgpu_out_ops *const o = convert && ops && out_ops_active(&ops[i]) ? &ops[i] : nullptr;
-            if (!rc && convert && ops) rc = check_out_ops(&ops[i], it.out.sample_fmt);
-            if (!rc && o && (o->colour & GRKGPU_COLOUR_FORCE_RGB))
+            const grkgpu_out_ops *const given = jp2 ? (J[i].has_ops ? &J[i].o : nullptr) : (convert && ops ? &ops[i] : nullptr);
+            const grkgpu_out_ops *const o = out_ops_active(given) ? given : nullptr;
+            if (!rc && given) rc = check_out_ops(given, it.out.sample_fmt);
+            if (!rc && !jp2 && o && (o->colour & GRKGPU_COLOUR_FORCE_RGB))
                 rc = set_err(GRKGPU_EUNSUPPORTED, "force-RGB is not supported in a batch");
             if (!rc) {
-                h.csb = it.cs; h.len = it.len; h.img = &it.img;
+                h.csb = jp2 ? J[i].cs : it.cs; h.len = jp2 ? J[i].len : it.len; h.img = &it.img;
                 h.od = DecodeOut{it.out.planes, (int32_t)it.out.sample_fmt,
                                  (it.out.layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED,
-                                 it.out.on_device, (it.out.layout & GRKGPU_LAYOUT_UPSAMPLE) != 0, o, 0, nullptr, 0};
+                                 it.out.on_device, (it.out.layout & GRKGPU_LAYOUT_UPSAMPLE) != 0, o, 0,
+                                 jp2 ? J[i].chan : nullptr, jp2 && J[i].is_rgb ? 1 : 0};
                 h.reduce = reduce; h.max_layers = layers; h.host_only = host_only; h.batch = !convert;
                 rc = h.begin();
             }
@@ -4760,6 +4890,21 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
         any_roi = any_roi || !h.droi.empty();
         ++n_ok;
     }
+    // the items' palettes: one merged table of uint16 entries behind the
+    // streams in the same pinned buffer and device buffer, so it reaches the
+    // device in the streams' copy; each item's table (copies of one file
+    // included) at an even entry
+    std::vector<uint32_t> pal_off(n, 0);
+    const uint64_t pal_base = cs_total;  // (a multiple of 16)
+    uint64_t pal_entries = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const DecHost &h = H[i];
+        if (items[i].status || !h.cm || !h.cm->table || !h.cm->ne) continue;
+        pal_off[i] = (uint32_t)pal_entries;
+        pal_entries = (pal_entries + (uint64_t)h.cm->ne * h.cm->npc + 1) & ~(uint64_t)1;
+    }
+    if (pal_entries > 0x7fffffffull) return set_err(GRKGPU_EUNSUPPORTED, "batch too large for one call");
+    cs_total = (cs_total + pal_entries * 2 + 15) & ~(uint64_t)15;
     uint64_t uwords = 0;
     for (uint32_t i = 0; i < n; ++i)
         for (size_t q = 0; !items[i].status && q < H[i].dsegs.size(); ++q)
@@ -4852,7 +4997,7 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
     StorePlan stores;
     auto bases = [&](uint32_t i) {
         return ItemBases{host_only ? 0 : (uintptr_t)c->work.p, host_only ? 0 : (uintptr_t)c->img.p, roff[i].data(),
-                         stoff[i].data(), host_only};
+                         stoff[i].data(), host_only, pal_off[i]};
     };
     for (uint32_t i = 0; i < n; ++i)
         if (!items[i].status) plan_item_stores(stores, H[i], bases(i));
@@ -4883,8 +5028,11 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
                 uint8_t *d = c->h_cs.as<uint8_t>() + cs_off[i];
                 memcpy(d, H[i].csb, H[i].len);
                 if (!H[i].extra.empty()) memcpy(d + H[i].len, H[i].extra.data(), H[i].extra.size());
+                if (const ChanMap *cm = H[i].cm; cm && cm->table && cm->ne)
+                    memcpy(c->h_cs.as<uint8_t>() + pal_base + (size_t)pal_off[i] * 2, cm->table, (size_t)cm->ne * cm->npc * 2);
             }
         });
+        stores.pal_table = (const uint16_t *)(c->cs.as<uint8_t>() + pal_base);
 
         HIPCHK(hipEventRecord(c->ev[0], s));
         HIPCHK(hipMemcpyAsync(c->cs.p, c->h_cs.p, cs_total, hipMemcpyHostToDevice, s));
@@ -4920,6 +5068,7 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
             if (items[i].status) continue;
             const DecHost &h = H[i];
             if (h.converted_zeros()) continue;  // (ConvJobs over null sources)
+            if (h.cm && (h.opad || h.missing)) continue;  // (zero PalJobs: entry 0 of the looked-up channels)
             void *dst[GRKGPU_MAX_COMPS];
             for (uint32_t k = 0; k < h.nout(); ++k) dst[k] = (void *)bases(i).dst(h, k);
             HIPCHK(dec_zero_fills(h, dst, s, &nl));
@@ -5473,14 +5622,14 @@ extern "C" int grkgpu_jp2_read_palette(const uint8_t *file, size_t len, uint16_t
     return GRKGPU_OK;
 }
 
-extern "C" int grkgpu_jp2_decompress(grkgpu_ctx *c, const uint8_t *file, size_t len, const grkgpu_dparams *dp,
-                                     uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
-                                     const grkgpu_out_planes *out, const grkgpu_out_ops *ops, grkgpu_jp2_info *info) {
-    if (!c || !file || !out) return set_err(GRKGPU_EINVAL, "null argument");
-    Jp2Parsed j;
-    int rc = jp2_parse(file, len, j, info, nullptr);
-    if (rc) return rc;
-    grkgpu_out_ops o{};
+// What a decode of the parsed file j hands the codec, for grkgpu_jp2_decompress
+// and every item of grkgpu_jp2_decompress_batch: the caller's ops with
+// GRKGPU_COLOUR_AUTO / _AUTO_RGB resolved by the file's colour space (o; ops
+// null: untouched), the refusal of force-RGB on a file with a profile, and the
+// channel map of a file with a palette or a channel swap (mapped; cm.table
+// points into j).
+static int jp2_resolve(const Jp2Parsed &j, const grkgpu_out_ops *ops, grkgpu_out_ops &o, ChanMap &cm, bool &mapped) {
+    o = grkgpu_out_ops{};
     if (ops) {
         o = *ops;
         const uint32_t force = o.colour & GRKGPU_COLOUR_FORCE_RGB, col = o.colour & ~GRKGPU_COLOUR_FORCE_RGB;
@@ -5496,13 +5645,9 @@ extern "C" int grkgpu_jp2_decompress(grkgpu_ctx *c, const uint8_t *file, size_t 
         if (force && (j.boxes.icc_len || space == JP2_CS_ICC))
             return set_err(GRKGPU_EUNSUPPORTED, "JP2: force-RGB on a file with an ICC profile");
     }
-    const bool is_rgb = j.ch.colour_space == JP2_CS_SRGB;
-    const uint8_t *cs = file + j.boxes.cs_off;
-    const size_t cslen = (size_t)j.boxes.cs_len;
-    if (!j.ch.mapped)
-        return decompress_to_impl(c, cs, cslen, dp, tile_begin, tile_end, img, out, ops ? &o : nullptr, false, nullptr,
-                                  is_rgb);
-    ChanMap cm{};
+    mapped = j.ch.mapped;
+    cm = ChanMap{};
+    if (!mapped) return GRKGPU_OK;
     cm.nch = (uint32_t)j.ch.ch.size();
     for (uint32_t i = 0; i < cm.nch; ++i) {
         cm.comp[i] = j.ch.ch[i].comp;
@@ -5515,7 +5660,59 @@ extern "C" int grkgpu_jp2_decompress(grkgpu_ctx *c, const uint8_t *file, size_t 
         cm.npc = j.boxes.npc;
         cm.table = j.table.data();
     }
-    return decompress_to_impl(c, cs, cslen, dp, tile_begin, tile_end, img, out, ops ? &o : nullptr, false, &cm, is_rgb);
+    return GRKGPU_OK;
+}
+
+extern "C" int grkgpu_jp2_decompress(grkgpu_ctx *c, const uint8_t *file, size_t len, const grkgpu_dparams *dp,
+                                     uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                                     const grkgpu_out_planes *out, const grkgpu_out_ops *ops, grkgpu_jp2_info *info) {
+    if (!c || !file || !out) return set_err(GRKGPU_EINVAL, "null argument");
+    Jp2Parsed j;
+    int rc = jp2_parse(file, len, j, info, nullptr);
+    if (rc) return rc;
+    grkgpu_out_ops o{};
+    ChanMap cm{};
+    bool mapped = false;
+    rc = jp2_resolve(j, ops, o, cm, mapped);
+    if (rc) return rc;
+    return decompress_to_impl(c, file + j.boxes.cs_off, (size_t)j.boxes.cs_len, dp, tile_begin, tile_end, img, out,
+                              ops ? &o : nullptr, false, mapped ? &cm : nullptr, j.ch.colour_space == JP2_CS_SRGB);
+}
+
+// grkgpu_jp2_decompress_batch / grkgpu_jp2_batch_plan: batch_impl with the box
+// layer per item (parsed on the host pool, each item's Jp2Parsed and ChanMap
+// its own and alive until the call returns)
+static int jp2_batch(grkgpu_ctx *c, grkgpu_batch_item *items, const grkgpu_out_ops *ops, uint32_t n,
+                     const grkgpu_dparams *p, grkgpu_batch_info *info, grkgpu_jp2_info *infos, bool host_only) {
+    std::vector<Jp2Parsed> parsed(items ? n : 0);
+    std::vector<ChanMap> maps(items ? n : 0);
+    const Jp2Prep prep = [&](size_t i, Jp2Item &it) -> int {
+        if (infos) memset(&infos[i], 0, sizeof(infos[i]));
+        Jp2Parsed &j = parsed[i];
+        int rc = jp2_parse(items[i].cs, items[i].len, j, infos ? &infos[i] : nullptr, nullptr);
+        if (rc) return rc;
+        bool mapped = false;
+        rc = jp2_resolve(j, ops ? &ops[i] : nullptr, it.o, maps[i], mapped);
+        if (rc) return rc;
+        it.cs = items[i].cs + j.boxes.cs_off;
+        it.len = (size_t)j.boxes.cs_len;
+        it.has_ops = ops != nullptr;
+        it.chan = mapped ? &maps[i] : nullptr;
+        it.is_rgb = j.ch.colour_space == JP2_CS_SRGB;
+        return GRKGPU_OK;
+    };
+    return batch_impl(c, items, n, p, info, host_only, true, nullptr, &prep);
+}
+
+extern "C" int grkgpu_jp2_decompress_batch(grkgpu_ctx *c, grkgpu_batch_item *items, const grkgpu_out_ops *ops,
+                                           uint32_t n, const grkgpu_dparams *p, grkgpu_batch_info *info,
+                                           grkgpu_jp2_info *infos) {
+    return jp2_batch(c, items, ops, n, p, info, infos, false);
+}
+
+extern "C" int grkgpu_jp2_batch_plan(grkgpu_batch_item *items, const grkgpu_out_ops *ops, uint32_t n,
+                                     const grkgpu_dparams *p, grkgpu_batch_info *info, grkgpu_jp2_info *infos) {
+    return jp2_batch(nullptr, items, ops, n, p, info, infos, true);
 }
 
 static int jp2_wparams_of(const grkgpu_image_desc *img, const grkgpu_jp2_wparams *wp, Jp2WriteParams &w) {
@@ -5704,6 +5901,84 @@ extern "C" int grkgpu_mct_inv_dcshift_jobs_to(const grkgpu_store_job *jobs, uint
         }
         if (int rc = bind_dst(q.dst, il ? 1u : nc, fmt)) return rc;
         if (!stores.add_store(fmt, il, j)) stores.singles.push_back(tile_store_of(j, fmt, il));
+    }
+    int rc = check_device(-1);
+    if (rc) return rc;
+    return stores.run_alone((hipStream_t)stream);
+}
+
+static_assert(sizeof(grkgpu_palette_job) == sizeof(PalJob) && offsetof(grkgpu_palette_job, ops_) == offsetof(PalJob, s.ops) &&
+                  offsetof(grkgpu_palette_job, max) == offsetof(PalJob, s.mx) &&
+                  offsetof(grkgpu_palette_job, chan_comp) == offsetof(PalJob, map.comp) &&
+                  offsetof(grkgpu_palette_job, chan_pcol) == offsetof(PalJob, map.pcol) &&
+                  offsetof(grkgpu_palette_job, numchannels) == offsetof(PalJob, map.nch) &&
+                  offsetof(grkgpu_palette_job, ne) == offsetof(PalJob, map.ne) &&
+                  offsetof(grkgpu_palette_job, npc) == offsetof(PalJob, map.npc) &&
+                  offsetof(grkgpu_palette_job, used_) == offsetof(PalJob, map.used) &&
+                  offsetof(grkgpu_palette_job, zero) == offsetof(PalJob, map.zero) &&
+                  offsetof(grkgpu_palette_job, table_off) == offsetof(PalJob, table_off),
+              "grkgpu_palette_job is PalJob");
+
+extern "C" int grkgpu_palette_jobs_to(const grkgpu_palette_job *jobs, uint32_t n, const uint16_t *table,
+                                      uint32_t table_entries, uint32_t sample_fmt, uint32_t layout, void *stream) {
+    if (sample_fmt > GRKGPU_SAMPLE_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if (layout > GRKGPU_LAYOUT_INTERLEAVED) return set_err(GRKGPU_EINVAL, "unknown layout");
+    if (!n) return GRKGPU_OK;
+    if (!jobs) return set_err(GRKGPU_EINVAL, "null argument");
+    if (table && (uintptr_t)table % 4) return set_err(GRKGPU_EINVAL, "misaligned palette table");
+    const int32_t fmt = (int32_t)sample_fmt;
+    const bool il = layout == GRKGPU_LAYOUT_INTERLEAVED;
+    const uint32_t sb = sample_bytes(fmt);
+    const bool sg = fmt == SMP_I8 || fmt == SMP_I16;
+    const int64_t lo = fmt == SMP_I32 ? INT32_MIN : (sg ? -((int64_t)1 << (8 * sb - 1)) : 0);
+    const int64_t hi = fmt == SMP_I32 ? INT32_MAX : (sg ? ((int64_t)1 << (8 * sb - 1)) - 1 : ((int64_t)1 << (8 * sb)) - 1);
+    StorePlan stores;
+    stores.pal_table = table;
+    for (uint32_t i = 0; i < n; ++i) {
+        const grkgpu_palette_job &q = jobs[i];
+        const uint32_t nc = q.numcomps, nch = q.numchannels;
+        if (nc < 1 || nc > 4 || nch < 1 || nch > 4 || (!q.zero && q.src_stride < q.w) ||
+            (uint64_t)q.dst_stride < (uint64_t)q.w * (il ? nch : 1))
+            return set_err(GRKGPU_EINVAL, "bad arguments (1 .. 4 components and channels, strides must hold a row)");
+        if (q.wavelet_mask >> nc) return set_err(GRKGPU_EINVAL, "wavelet mask names a component the job does not have");
+        if (q.ne > 1024 || q.npc > 16 || (q.ne != 0) != (q.npc != 0))
+            return set_err(GRKGPU_EINVAL, "palette of 1 .. 1024 x 1 .. 16 entries");
+        // every entry the kernel reads lies inside the merged table
+        if (q.ne && (!table || (q.table_off & 1) || (uint64_t)q.table_off + (uint64_t)q.ne * q.npc > table_entries))
+            return set_err(GRKGPU_EINVAL, "palette table outside the merged table (table_off must be even)");
+        PalJob j;
+        memcpy(&j, &q, sizeof(j));
+        j.s.ops = 0;
+        j.map.zero = q.zero ? 1 : 0;
+        for (uint32_t k = q.zero ? 0 : nc; k < 4; ++k) j.s.src[k] = nullptr;
+        for (uint32_t k = il ? 1u : nch; k < 4; ++k) j.s.dst[k] = nullptr;
+        bool looks_up = false;
+        for (uint32_t ch = 0; ch < nch; ++ch) {
+            const uint32_t k = q.chan_comp[ch];
+            if (k >= nc || q.chan_pcol[ch] >= (int32_t)q.npc)
+                return set_err(GRKGPU_EINVAL, "channel map outside the components / the palette");
+            if (q.chan_pcol[ch] < 0) {
+                j.map.pcol[ch] = -1;
+                if (q.min[k] > q.max[k] || q.min[k] < lo || q.max[k] > hi)
+                    return set_err(GRKGPU_EINVAL, "sample format does not hold the component's range");
+            } else {
+                looks_up = true;
+            }
+        }
+        if (looks_up != (q.ne != 0)) return set_err(GRKGPU_EINVAL, "a table exactly when a channel looks up");
+        set_pal_used(j.map);
+        for (uint32_t k = 0; !q.zero && k < nc; ++k)
+            if (((j.map.used >> k) & 1 || (q.mct && nc >= 3 && k < 3)) && (!q.src[k] || (uintptr_t)q.src[k] % 4))
+                return set_err(GRKGPU_EINVAL, "null or misaligned source plane");
+        if (int rc = bind_dst(q.dst, il ? 1u : nch, fmt)) return rc;
+        if (!stores.add_pal(fmt, il, nullptr, j, 0)) {
+            TilePal t{};
+            t.ts = tile_store_of(j.s, fmt, il);
+            for (uint32_t k = 0; k < (il ? 1u : nch); ++k) t.ts.dst.p[k] = q.dst[k];
+            t.map = j.map;
+            t.table_off = j.table_off;
+            stores.pal_singles.push_back(t);
+        }
     }
     int rc = check_device(-1);
     if (rc) return rc;

@@ -321,6 +321,49 @@ hipError_t launch_palette(const PlanePtrs &src, uint32_t sstride, uint32_t tw, u
                           int32_t fmt, bool interleaved, uint32_t dstride, uint32_t ncomp, const ShiftArr &shift,
                           const ShiftArr &mn, const ShiftArr &mx, int32_t mct, int32_t irrev, const PalMap &map,
                           const uint16_t *table, const OutOps *ops, hipStream_t s);
+// launch_palette for a table of tiles in one launch (the batch decode of JP2
+// files, grkgpu_palette_jobs_to): a StoreJob's arguments -- dst, dstride and
+// the ops index describing the map's nch <= 4 channels --, the tile's PalMap
+// and where its table starts in the launch's merged table of uint16 entries
+// (table_off, even, so that the LDS fill keeps its dword path; not read when
+// ne = 0).  map.zero: the sources are null and not read.
+// grkgpu_palette_job's layout (static_assert in codec.cpp).
+struct PalJob {
+    StoreJob s;
+    PalMap map;
+    uint32_t table_off;
+};
+// The job kernel's shape: 0 planar (one interleaved channel is a plane), 3 / 4
+// interleaved runs on the destination's 16-byte grid, 2 interleaved with a
+// thread per pixel
+__host__ __device__ inline int pal_job_shape(uint32_t nch, bool interleaved) { return interleaved && nch > 1 ? (int)nch : 0; }
+constexpr uint32_t PAL_JOB_ROWS = 8;  // rows a workgroup keeps its table for (PAL_ROWS of kernels.hip)
+// threads along a row of a job and its workgroups: bands of PAL_JOB_ROWS rows
+// by chunks of 256 row threads
+__host__ __device__ inline uint32_t pal_job_row_threads(uint32_t w, uint32_t sb, int shape) {
+    if (shape == 2) return w;
+    const uint32_t n = 16 / sb;
+    return (uint32_t)(((uint64_t)w + n - 1) / n + 1);
+}
+inline uint64_t pal_job_wgs(const PalJob &j, uint32_t sb, int shape) {
+    if (!j.s.w || !j.s.h) return 0;
+    return (uint64_t)((pal_job_row_threads(j.s.w, sb, shape) + 255) / 256) * ((j.s.h + PAL_JOB_ROWS - 1) / PAL_JOB_ROWS);
+}
+// The LDS a launch reserves for its jobs' tables, in three classes, so that a
+// 16-entry palette does not take 32 KB because another item's has 700 entries:
+// 0 no table (direct maps, force-RGB), 1 up to 4 KB, 2 up to 32 KB (the largest
+// table: 1024 x 16 entries).
+inline int pal_lds_class(uint32_t ne, uint32_t npc) {
+    const uint32_t bytes = ne * npc * 2;
+    return !bytes ? 0 : (bytes <= 4096 ? 1 : 2);
+}
+inline uint32_t pal_lds_bytes(int cls) { return cls == 0 ? 0u : (cls == 1 ? 4096u : 32768u); }
+// first: njobs + 1 first-workgroup numbers (prefix sums of pal_job_wgs), nwg = first[njobs].  Every job of a
+// launch has the sample format, the shape and the op class (op = 0, or 1 = OP_PREC with the OutOps table ops)
+// given, and a table of at most lds_bytes.
+hipError_t launch_palette_jobs(const PalJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg, int32_t fmt,
+                               int shape, int op, const OutOps *ops, const uint16_t *table, uint32_t lds_bytes,
+                               hipStream_t s);
 // One DWT level of one tile-component (dwt.hip).  A launch runs one level of
 // every job in a table (grid.y = job).
 struct DwtJob {

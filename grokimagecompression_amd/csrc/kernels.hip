@@ -1027,12 +1027,15 @@ __device__ __forceinline__ void pal_load(const int32_t *p, int n, int32_t (&v)[N
 }
 
 // The finished runs of the components that feed a channel, one after the
-// other, each handed to emit(component, run): the MCT triple first
-template <int N, typename F>
+// other, each handed to emit(component, run): the MCT triple first.  KMAX as
+// in the store bodies above: GRK_MAX_COMPS for kernel arguments, indexed at run
+// time, or 4 for a PalJob's, which sit in scalar registers (static indices
+// behind uniform guards).
+template <int N, int KMAX = GRK_MAX_COMPS, typename F>
 __device__ __forceinline__ void palette_components(const PlanePtrs &src, size_t si, int n, uint32_t ncomp,
                                                    const ShiftArr &shift, const ShiftArr &minv, const ShiftArr &maxv,
                                                    int32_t mct, int32_t irrev, const PalMap &map, F emit) {
-    uint32_t k = 0;
+    uint32_t k0 = 0;
     if (mct && ncomp >= 3) {
         int32_t a[N], b[N], c[N];
         if (!map.zero) {
@@ -1051,10 +1054,10 @@ __device__ __forceinline__ void palette_components(const PlanePtrs &src, size_t 
         emit(1u, b, row);
         palette_rows<N>(c, map, row);
         emit(2u, c, row);
-        k = 3;
+        k0 = 3;
     }
-    for (; k < ncomp; ++k) {
-        if (!((map.used >> k) & 1)) continue;  // feeds no channel
+    const auto plain = [&](uint32_t k) {
+        if (!((map.used >> k) & 1)) return;  // feeds no channel
         int32_t a[N];
         if (!map.zero) {
             pal_load<N>(src.p[k] + si, n, a);
@@ -1066,9 +1069,120 @@ __device__ __forceinline__ void palette_components(const PlanePtrs &src, size_t 
         uint32_t row[N];
         palette_rows<N>(a, map, row);
         emit(k, a, row);
+    };
+    if constexpr (KMAX > 4) {
+        for (uint32_t k = k0; k < ncomp; ++k) plain(k);
+    } else {
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if ((uint32_t)k >= k0 && (uint32_t)k < ncomp) plain((uint32_t)k);
     }
 }
 
+// f(c) for every channel c < nch: a run-time loop, or (KMAX = 4) unrolled behind uniform guards
+template <int KMAX, typename F>
+__device__ __forceinline__ void palette_channels(uint32_t nch, F f) {
+    if constexpr (KMAX > 4) {
+        for (uint32_t c = 0; c < nch; ++c) f(c);
+    } else {
+#pragma unroll
+        for (int c = 0; c < KMAX; ++c)
+            if ((uint32_t)c < nch) f((uint32_t)c);
+    }
+}
+
+// The bodies of the palette stores, shared by the per-tile kernels and the
+// job-table kernel k_palette_jobs below: thread t of row y finishes its run
+// (or pixel), looks it up in the workgroup's LDS table `lut` and stores it.
+// Every argument but t is uniform over the workgroup; ops: null exactly when
+// OP = 0; KMAX as in palette_components.
+//
+// planar: dst.p[c] = plane of channel c
+template <typename T, int OP, int KMAX = GRK_MAX_COMPS>
+__device__ __forceinline__ void palette_planar_row(const PlanePtrs &src, uint32_t sstride, uint32_t tw,
+                                                   const DstPlanes &dst, uint32_t dstride, uint32_t ncomp, uint32_t y,
+                                                   uint32_t t, const ShiftArr &shift, const ShiftArr &minv,
+                                                   const ShiftArr &maxv, int32_t mct, int32_t irrev, const PalMap &map,
+                                                   const uint16_t *lut, [[maybe_unused]] const OutOps *ops) {
+    constexpr int N = NarrowRun<T>::N;
+    const size_t drow = (size_t)y * dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)((T *)dst.p[0] + drow), sizeof(T), t, tw, x0);
+    if (n <= 0) return;
+    const size_t si = (size_t)y * sstride + x0, di = drow + x0;
+    palette_components<N, KMAX>(src, si, n, ncomp, shift, minv, maxv, mct, irrev, map,
+                                [&](uint32_t k, const int32_t (&a)[N], const uint32_t (&row)[N]) {
+                                    palette_channels<KMAX>(map.nch, [&](uint32_t c) {
+                                        if (map.comp[c] != k) return;
+                                        int32_t v[N];
+                                        palette_run<N>(a, row, map.pcol[c], lut, v);
+                                        if constexpr (OP != 0) prec_run<N>(v, ops->pc[c]);
+                                        store_samples<T, N>((T *)dst.p[c] + di, v, n);
+                                    });
+                                });
+}
+
+// interleaved, NCH = 3 / 4 channels: channel c of pixel (y, x) at
+// dst0[y * dstride + x * NCH + c], runs on the destination's 16-byte grid
+template <typename T, int NCH, int OP, int KMAX = GRK_MAX_COMPS>
+__device__ __forceinline__ void palette_pixels_row(const PlanePtrs &src, uint32_t sstride, uint32_t tw, void *dst0,
+                                                   uint32_t dstride, uint32_t ncomp, uint32_t y, uint32_t t,
+                                                   const ShiftArr &shift, const ShiftArr &minv, const ShiftArr &maxv,
+                                                   int32_t mct, int32_t irrev, const PalMap &map, const uint16_t *lut,
+                                                   [[maybe_unused]] const OutOps *ops) {
+    constexpr int N = NarrowRun<T>::N;
+    T *const drow = (T *)dst0 + (size_t)y * dstride;
+    uint32_t x0;
+    const int n = run_of<N>((uintptr_t)drow, NCH * sizeof(T), t, tw, x0);
+    if (n <= 0) return;
+    const size_t si = (size_t)y * sstride + x0;
+    int32_t v[NCH][N];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[c][i] = 0;
+    palette_components<N, KMAX>(src, si, n, ncomp, shift, minv, maxv, mct, irrev, map,
+                                [&](uint32_t k, const int32_t (&a)[N], const uint32_t (&row)[N]) {
+#pragma unroll
+                                    for (int c = 0; c < NCH; ++c)
+                                        if (map.comp[c] == k) palette_run<N>(a, row, map.pcol[c], lut, v[c]);
+                                });
+    if constexpr (OP != 0) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) prec_run<N>(v[c], ops->pc[c]);
+    }
+    int32_t px[N * NCH];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) px[i * NCH + c] = v[c][i];
+    store_samples<T, N * NCH>(drow + (size_t)x0 * NCH, px, n * NCH);
+}
+
+// interleaved, any other channel count: pixel x of row y, one store per sample
+template <typename T, int OP, int KMAX = GRK_MAX_COMPS>
+__device__ __forceinline__ void palette_pixel_any(const PlanePtrs &src, uint32_t sstride, uint32_t tw, void *dst0,
+                                                  uint32_t dstride, uint32_t ncomp, uint32_t y, uint32_t x,
+                                                  const ShiftArr &shift, const ShiftArr &minv, const ShiftArr &maxv,
+                                                  int32_t mct, int32_t irrev, const PalMap &map, const uint16_t *lut,
+                                                  [[maybe_unused]] const OutOps *ops) {
+    if (x >= tw) return;
+    const size_t si = (size_t)y * sstride + x;
+    T *const d = (T *)dst0 + (size_t)y * dstride + (size_t)x * map.nch;
+    palette_components<1, KMAX>(src, si, 1, ncomp, shift, minv, maxv, mct, irrev, map,
+                                [&](uint32_t k, const int32_t (&a)[1], const uint32_t (&row)[1]) {
+                                    palette_channels<KMAX>(map.nch, [&](uint32_t c) {
+                                        if (map.comp[c] != k) return;
+                                        int32_t v[1];
+                                        palette_run<1>(a, row, map.pcol[c], lut, v);
+                                        if constexpr (OP != 0) prec_run<1>(v, ops->pc[c]);
+                                        __builtin_nontemporal_store((T)v[0], d + c);
+                                    });
+                                });
+}
+
+// The per-tile kernels: a (row threads, bands of PAL_ROWS rows) grid in front
+// of those bodies.
 // planar: dst.p[c] = plane of channel c
 template <typename T, int OP = 0, typename... O>
 __global__ void __launch_bounds__(256) k_palette_planar(PlanePtrs src, uint32_t sstride, uint32_t tw, uint32_t th,
@@ -1077,29 +1191,14 @@ __global__ void __launch_bounds__(256) k_palette_planar(PlanePtrs src, uint32_t 
                                                         int32_t irrev, PalMap map, const uint16_t *table, O... o) {
     static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
     static_assert(OP == 0 || OP == OP_PREC, "no colour conversion behind a palette");
-    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
+    const OutOps *const ops = ops_ptr(o...);
     extern __shared__ uint16_t pal_lut[];
     palette_load(pal_lut, table, map.ne * map.npc);
-    constexpr int N = NarrowRun<T>::N;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t yb = blockIdx.y * PAL_ROWS, ye = yb + PAL_ROWS < th ? yb + PAL_ROWS : th;
-    for (uint32_t y = yb; y < ye; ++y) {
-        const size_t drow = (size_t)y * dstride;
-        uint32_t x0;
-        const int n = run_of<N>((uintptr_t)((T *)dst.p[0] + drow), sizeof(T), t, tw, x0);
-        if (n <= 0) continue;
-        const size_t si = (size_t)y * sstride + x0, di = drow + x0;
-        palette_components<N>(src, si, n, ncomp, shift, minv, maxv, mct, irrev, map,
-                              [&](uint32_t k, const int32_t (&a)[N], const uint32_t (&row)[N]) {
-                                  for (uint32_t c = 0; c < map.nch; ++c) {
-                                      if (map.comp[c] != k) continue;
-                                      int32_t v[N];
-                                      palette_run<N>(a, row, map.pcol[c], pal_lut, v);
-                                      if constexpr (OP != 0) prec_run<N>(v, ops->pc[c]);
-                                      store_samples<T, N>((T *)dst.p[c] + di, v, n);
-                                  }
-                              });
-    }
+    for (uint32_t y = yb; y < ye; ++y)
+        palette_planar_row<T, OP>(src, sstride, tw, dst, dstride, ncomp, y, t, shift, minv, maxv, mct, irrev, map,
+                                  pal_lut, ops);
 }
 
 // interleaved: channel c of pixel (y, x) at dst.p[0][y * dstride + x * nch + c].
@@ -1112,55 +1211,18 @@ __global__ void __launch_bounds__(256) k_palette_pixels(PlanePtrs src, uint32_t 
                                                         int32_t irrev, PalMap map, const uint16_t *table, O... o) {
     static_assert(sizeof...(O) == (OP != 0), "one OutOps exactly when OP != 0");
     static_assert(OP == 0 || OP == OP_PREC, "no colour conversion behind a palette");
-    [[maybe_unused]] const OutOps *const ops = ops_ptr(o...);
+    const OutOps *const ops = ops_ptr(o...);
     extern __shared__ uint16_t pal_lut[];
     palette_load(pal_lut, table, map.ne * map.npc);
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t yb = blockIdx.y * PAL_ROWS, ye = yb + PAL_ROWS < th ? yb + PAL_ROWS : th;
     for (uint32_t y = yb; y < ye; ++y) {
-        T *const drow = (T *)dst.p[0] + (size_t)y * dstride;
-        if constexpr (NCH != 0) {
-            constexpr int N = NarrowRun<T>::N;
-            uint32_t x0;
-            const int n = run_of<N>((uintptr_t)drow, NCH * sizeof(T), t, tw, x0);
-            if (n <= 0) continue;
-            const size_t si = (size_t)y * sstride + x0;
-            int32_t v[NCH][N];
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int i = 0; i < N; ++i) v[c][i] = 0;
-            palette_components<N>(src, si, n, ncomp, shift, minv, maxv, mct, irrev, map,
-                                  [&](uint32_t k, const int32_t (&a)[N], const uint32_t (&row)[N]) {
-#pragma unroll
-                                      for (int c = 0; c < NCH; ++c)
-                                          if (map.comp[c] == k) palette_run<N>(a, row, map.pcol[c], pal_lut, v[c]);
-                                  });
-            if constexpr (OP != 0) {
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) prec_run<N>(v[c], ops->pc[c]);
-            }
-            int32_t px[N * NCH];
-#pragma unroll
-            for (int i = 0; i < N; ++i)
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) px[i * NCH + c] = v[c][i];
-            store_samples<T, N * NCH>(drow + (size_t)x0 * NCH, px, n * NCH);
-        } else {
-            if (t >= tw) continue;
-            const size_t si = (size_t)y * sstride + t;
-            T *const d = drow + (size_t)t * map.nch;
-            palette_components<1>(src, si, 1, ncomp, shift, minv, maxv, mct, irrev, map,
-                                  [&](uint32_t k, const int32_t (&a)[1], const uint32_t (&row)[1]) {
-                                      for (uint32_t c = 0; c < map.nch; ++c) {
-                                          if (map.comp[c] != k) continue;
-                                          int32_t v[1];
-                                          palette_run<1>(a, row, map.pcol[c], pal_lut, v);
-                                          if constexpr (OP != 0) prec_run<1>(v, ops->pc[c]);
-                                          __builtin_nontemporal_store((T)v[0], d + c);
-                                      }
-                                  });
-        }
+        if constexpr (NCH != 0)
+            palette_pixels_row<T, NCH, OP>(src, sstride, tw, dst.p[0], dstride, ncomp, y, t, shift, minv, maxv, mct,
+                                           irrev, map, pal_lut, ops);
+        else
+            palette_pixel_any<T, OP>(src, sstride, tw, dst.p[0], dstride, ncomp, y, t, shift, minv, maxv, mct, irrev, map,
+                                     pal_lut, ops);
     }
 }
 
@@ -2970,6 +3032,94 @@ hipError_t launch_palette(const PlanePtrs &src, uint32_t sstride, uint32_t tw, u
                                    map, table, s);
         else launch_pal<T, OP_PREC>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift, mn, mx, mct, irrev,
                                     map, table, s, *ops);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// The palette store for a table of tiles (PalJob, grk_device.h) in one launch:
+// the batch decode of JP2 files.  Workgroup wg finds its job with job_of_wg;
+// the search depends on blockIdx alone, so it, the record's fields and the
+// job's OutOps are uniform over the workgroup: scalar loads before the first
+// store, the StoreJob part kept in scalar registers as in k_store_jobs, the
+// map indexed where it lies.  Within its job a workgroup owns one band of
+// PAL_ROWS rows by one chunk of 256 row threads (pal_job_row_threads: the runs
+// of the destination's 16-byte grid, or SHAPE 2's pixels), so the LDS fill is
+// amortised exactly as in the per-tile kernels: ne * npc entries from table +
+// table_off, once, and only when the job looks up (ne != 0; a direct or
+// force-RGB map has no table).  The rows are palette_planar_row /
+// palette_pixels_row / palette_pixel_any, the per-tile kernels' bodies.
+// map.zero: null sources, entry 0 of each looked-up channel (the tiles a cut
+// stream never reached, the margin of a reduced decode).
+//
+// SHAPE (pal_job_shape): 0 planar, 3 / 4 interleaved runs, 2 interleaved with
+// a thread per pixel.  OP = 0 or OP_PREC with the OutOps table, as
+// k_store_jobs.  Dynamic LDS is per launch: the host groups the jobs by the
+// size class of their table (pal_lds_class: none, <= 4 KB, <= 32 KB).  No
+// atomics, nothing shared between workgroups.
+// ---------------------------------------------------------------------------
+template <typename T, int SHAPE, int OP = 0, typename... O>
+__global__ void __launch_bounds__(256) k_palette_jobs(const PalJob *__restrict__ jobs,
+                                                      const uint32_t *__restrict__ first, uint32_t njobs,
+                                                      const uint16_t *__restrict__ table, O... opstab) {
+    static_assert(sizeof...(O) == (OP != 0), "the OutOps table exactly when OP != 0");
+    static_assert(OP == 0 || OP == OP_PREC, "no colour conversion behind a palette");
+    extern __shared__ uint16_t pal_lut[];
+    const uint32_t wg = blockIdx.x;
+    const uint32_t lo = job_of_wg(first, njobs, wg);
+    const StoreJob J = jobs[lo].s;
+    const PalMap &map = jobs[lo].map;
+    const OutOps *const ops = job_ops(J.ops, opstab...);
+    if (map.ne) palette_load(pal_lut, table + jobs[lo].table_off, map.ne * map.npc);  // (uniform: every thread or none)
+    const uint32_t ncomp = J.ncomp, tw = J.w, th = J.h;
+    const int32_t mct = J.mct && ncomp >= 3, irrev = (int32_t)J.irrev;
+    PlanePtrs src{};
+    DstPlanes dst{};
+    ShiftArr shift{}, minv{}, maxv{};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        src.p[k] = const_cast<int32_t *>(J.src[k]); dst.p[k] = J.dst[k];
+        shift.v[k] = J.shift[k]; minv.v[k] = J.mn[k]; maxv.v[k] = J.mx[k];
+    }
+    const uint32_t chunks = (pal_job_row_threads(tw, (uint32_t)sizeof(T), SHAPE) + 255u) / 256u;
+    const uint32_t b = wg - first[lo], band = b / chunks;
+    const uint32_t t = (b - band * chunks) * 256u + threadIdx.x;
+    const uint32_t yb = band * PAL_ROWS, ye = yb + PAL_ROWS < th ? yb + PAL_ROWS : th;
+    for (uint32_t y = yb; y < ye; ++y) {
+        if constexpr (SHAPE == 3 || SHAPE == 4)
+            palette_pixels_row<T, SHAPE, OP, 4>(src, J.sstride, tw, J.dst[0], J.dstride, ncomp, y, t, shift, minv, maxv,
+                                                mct, irrev, map, pal_lut, ops);
+        else if constexpr (SHAPE == 2)
+            palette_pixel_any<T, OP, 4>(src, J.sstride, tw, J.dst[0], J.dstride, ncomp, y, t, shift, minv, maxv, mct, irrev,
+                                        map, pal_lut, ops);
+        else
+            palette_planar_row<T, OP, 4>(src, J.sstride, tw, dst, J.dstride, ncomp, y, t, shift, minv, maxv, mct, irrev,
+                                         map, pal_lut, ops);
+    }
+}
+
+static_assert(PAL_JOB_ROWS == (uint32_t)PAL_ROWS, "pal_job_wgs counts the kernels' bands");
+hipError_t launch_palette_jobs(const PalJob *jobs, const uint32_t *first, uint32_t njobs, uint32_t nwg, int32_t fmt,
+                               int shape, int op, const OutOps *ops, const uint16_t *table, uint32_t lds_bytes,
+                               hipStream_t s) {
+    if (!njobs || !nwg) return hipSuccess;
+    if ((op != 0 && op != OP_PREC) || (op != 0) != (ops != nullptr) || shape < 0 || shape > 4 || shape == 1 ||
+        lds_bytes > 32768 || (lds_bytes && (!table || ((uintptr_t)table & 3))))
+        return hipErrorInvalidValue;
+    return with_sample_type(fmt, [&](auto t) {
+        using T = decltype(t);
+        const auto launch = [&](auto sh) {
+            constexpr int SHAPE = decltype(sh)::value;
+            if (op == 0)
+                hipLaunchKernelGGL((k_palette_jobs<T, SHAPE>), dim3(nwg), dim3(256), lds_bytes, s, jobs, first, njobs,
+                                   table);
+            else
+                hipLaunchKernelGGL((k_palette_jobs<T, SHAPE, OP_PREC, OpsTable>), dim3(nwg), dim3(256), lds_bytes, s, jobs,
+                                   first, njobs, table, ops);
+        };
+        if (shape == 0) launch(Const<0>{});
+        else if (shape == 2) launch(Const<2>{});
+        else if (shape == 3) launch(Const<3>{});
+        else launch(Const<4>{});
     });
 }
 

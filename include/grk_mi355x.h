@@ -981,6 +981,37 @@ int grkgpu_jp2_read_palette(const uint8_t *file, size_t len, uint16_t *entries, 
 int grkgpu_jp2_decompress(grkgpu_ctx *ctx, const uint8_t *file, size_t len, const grkgpu_dparams *p,
                           uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
                           const grkgpu_out_planes *out, const grkgpu_out_ops *ops, grkgpu_jp2_info *info);
+/* A batch of JP2 files in one launch set: grkgpu_decompress_batch_convert with
+ * the box layer per item.  items[i].cs / len are the FILE (only its jp2c
+ * payload is uploaded); item i is grkgpu_jp2_decompress(ctx, file, len, p, 0,
+ * 0xffffffff, &img, &out, &ops[i], &infos[i]) and receives that call's samples
+ * and img bit for bit.  ops is NULL or has n entries, in which
+ * GRKGPU_COLOUR_AUTO, _AUTO_RGB and _FORCE_RGB are valid per item; infos is
+ * NULL or has n entries (as grkgpu_jp2_read_info fills them; zeroed for a file
+ * whose boxes do not parse).  A file without a palette or a channel swap
+ * contributes exactly the records grkgpu_decompress_batch_convert makes for
+ * its payload with the resolved ops.  A file with a palette, a channel swap
+ * or force-RGB on one or two channels is stored through job tables of the
+ * palette store (grkgpu_palette_jobs_to's kernel): the items' tables packed
+ * into one merged table that rides behind the codestreams in their one H2D
+ * copy, one launch per (sample format, layout shape, table size class, with or
+ * without precision ops) present, the fills over samples nothing decoded in
+ * launches ahead of the tiles' -- so 64 copies of a palette file take the
+ * launches of one.  Items of more than four components or channels keep the
+ * single call's per-tile launches.  The boxes are parsed and every check runs
+ * on the host before the first device call; a failing item gets the single
+ * call's code in `status` (a raw codestream: GRKGPU_ECORRUPT; force-RGB on a
+ * file with an ICC profile: GRKGPU_EUNSUPPORTED), its destination is left
+ * untouched and the others decode.  The call-level rules (decode area, n = 0,
+ * NULL arguments, "batch too large for one call", the return code and
+ * "item <i>: ..." message) and info are grkgpu_decompress_batch's;
+ * n_store_jobs counts the records of every table.  With no mapped item and no
+ * force-RGB the call is grkgpu_decompress_batch_convert on the payloads,
+ * launch for launch.  grkgpu_jp2_batch_plan is the host half alone. */
+int grkgpu_jp2_decompress_batch(grkgpu_ctx *ctx, grkgpu_batch_item *items, const grkgpu_out_ops *ops, uint32_t n,
+                                const grkgpu_dparams *p, grkgpu_batch_info *info, grkgpu_jp2_info *infos);
+int grkgpu_jp2_batch_plan(grkgpu_batch_item *items, const grkgpu_out_ops *ops, uint32_t n, const grkgpu_dparams *p,
+                          grkgpu_batch_info *info, grkgpu_jp2_info *infos);
 /* Writer: jp, ftyp (brand 'jp2 ', MinV 0, CL 'jp2 '), jp2h { ihdr, bpcc only
  * when the depths differ (BPC 255), colr, cdef only for exactly one alpha
  * channel behind the colour channels (jp2_setup_encoder, jp2.cpp:2264-2343) },
@@ -1121,6 +1152,39 @@ int grkgpu_palette_to(const int32_t *const *src, uint32_t numcomps, uint32_t w, 
                       const uint32_t *prec, const int32_t *sgnd, uint32_t numchannels, const uint32_t *chan_comp,
                       const int32_t *chan_pcol, const uint32_t *chan_prec, const uint16_t *table, uint32_t ne,
                       uint32_t npc, const grkgpu_out_planes *dst, uint32_t dst_stride, void *stream);
+/* grkgpu_palette_to for a table of n tiles in one launch per table size class
+ * (the last kernel of grkgpu_jp2_decompress_batch on its own; the palette
+ * mirror of grkgpu_mct_inv_dcshift_jobs_to): jobs is a host array whose src /
+ * dst are device pointers.  The first fields are grkgpu_store_job's, dst and
+ * dst_stride describing the numchannels (1 .. 4) output channels; channel c
+ * takes component chan_comp[c]'s finished sample (chan_pcol[c] < 0, which
+ * [min, max] must fit into the format) or entry
+ * table[table_off + clamp(sample, 0, ne - 1) * npc + chan_pcol[c]], narrowed
+ * to the format.  table: one merged device table of table_entries uint16
+ * entries, 4-byte aligned (may be NULL when no job looks up); table_off even,
+ * ne 0 .. 1024, npc 0 .. 16, ne = 0 exactly when no channel of the job looks
+ * up.  zero != 0: src is not read (may be NULL), every component counts as
+ * finished zero samples -- the fill of samples nothing decoded.  Interleaved
+ * jobs of 3 / 4 channels store runs on the destination's 16-byte grid, of 2 a
+ * pixel per thread; one channel is a plane.  Jobs of w = 0 or h = 0 store
+ * nothing.  ops_ and used_ are set by the call.  The job table is copied to the
+ * device and freed after the launch, so the call synchronises `stream`. */
+typedef struct {
+    const int32_t *src[4];
+    void *dst[4];
+    uint32_t src_stride, dst_stride, w, h;
+    uint32_t numcomps;
+    int32_t mct;
+    uint32_t wavelet_mask, ops_;
+    int32_t shift[4], min[4], max[4];
+    uint8_t chan_comp[GRKGPU_MAX_COMPS];
+    int8_t chan_pcol[GRKGPU_MAX_COMPS];
+    uint32_t numchannels, ne, npc, used_;
+    int32_t zero;
+    uint32_t table_off;
+} grkgpu_palette_job;
+int grkgpu_palette_jobs_to(const grkgpu_palette_job *jobs, uint32_t n, const uint16_t *table, uint32_t table_entries,
+                           uint32_t sample_fmt, uint32_t layout, void *stream);
 /* The upsampling store of grkgpu_decompress_to (GRKGPU_LAYOUT_UPSAMPLE) on its
  * own -- the kernels the decode runs, fed finished samples: src[k] = device
  * plane of component k on its own grid, [ceil(x0 / dx[k]), ceil(x1 / dx[k])) x
