@@ -185,6 +185,11 @@ _NP_FMT = {np.dtype(np.int32): SAMPLE_I32, np.dtype(np.uint8): SAMPLE_U8, np.dty
            np.dtype(np.uint16): SAMPLE_U16, np.dtype(np.int16): SAMPLE_I16}
 
 
+# decode output of the float entry points only (Codec.decompress_float / decompress_batch_float)
+SAMPLE_F32, SAMPLE_F16, SAMPLE_BF16 = 16, 17, 18
+_FLOAT_FMT = {"float32": SAMPLE_F32, "float16": SAMPLE_F16, "bfloat16": SAMPLE_BF16}
+
+
 class Planes(ctypes.Structure):
     """grkgpu_planes: the image planes of grkgpu_compress_ex (sample_fmt = a
     SAMPLE_* width | SAMPLE_INTERLEAVED | SAMPLE_BIG_ENDIAN)."""
@@ -300,6 +305,12 @@ class OutOps(ctypes.Structure):
     apply in their store."""
     _fields_ = [("colour", ctypes.c_uint32), ("prec", ctypes.c_uint32), ("prec_mode", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
+
+
+class OutNorm(ctypes.Structure):
+    """grkgpu_out_norm: scale and bias per output channel of a float decode
+    (the sample stored is float32(v) * scale + bias, each step rounded)."""
+    _fields_ = [("scale", ctypes.c_float * MAXC), ("bias", ctypes.c_float * MAXC)]
 
 
 def _out_channels(colour, force_rgb, prec, sgnd, out_prec=None):
@@ -508,6 +519,12 @@ def lib():
             L.grkgpu_decompress_batch_convert.argtypes = [VP, P(BatchItem), P(OutOps), U32, P(DParams), P(BatchInfo)]
             L.grkgpu_batch_convert_plan.argtypes = [P(BatchItem), P(OutOps), U32, P(DParams), P(BatchInfo)]
             L.grkgpu_convert_jobs_to.argtypes = [P(ConvertJob), U32, U32, U32, VP]
+        if hasattr(L, "grkgpu_decompress_float"):  # not in an older library given by GRKGPU_LIB (A/B runs)
+            L.grkgpu_decompress_float.argtypes = [VP, VP, ctypes.c_size_t, P(DParams), U32, U32, P(ImageDesc),
+                                                  P(OutPlanes), P(OutOps), P(OutNorm)]
+            L.grkgpu_decompress_batch_float.argtypes = [VP, P(BatchItem), P(OutOps), P(OutNorm), U32, P(DParams),
+                                                        P(BatchInfo)]
+            L.grkgpu_batch_float_plan.argtypes = [P(BatchItem), P(OutOps), P(OutNorm), U32, P(DParams), P(BatchInfo)]
         if hasattr(L, "grkgpu_compress_batch"):  # not in an older library given by GRKGPU_LIB (A/B runs)
             L.grkgpu_compress_batch.argtypes = [VP, P(CBatchItem), U32, P(CBatchInfo)]
             L.grkgpu_compress_batch_plan.argtypes = [P(CBatchItem), U32, P(CBatchInfo)]
@@ -1150,6 +1167,123 @@ def _check_out(out, shape, device, dtype=np.int32, layout="chw"):
     return True
 
 
+def _float_format(dtype):
+    """(name, GRKGPU_SAMPLE_F*) of a float decode's dtype: np.float32 /
+    np.float16, "float32" / "float16" / "bfloat16", or the torch dtypes."""
+    name = dtype if isinstance(dtype, str) else None
+    if name is None and str(dtype).startswith("torch."):
+        name = str(dtype)[6:]
+    if name is None:
+        try:
+            name = np.dtype(dtype).name
+        except TypeError:
+            name = None
+    if name not in _FLOAT_FMT:
+        raise GrkGpuError("dtype must be float32, float16 or bfloat16 (got %s)" % (dtype,))
+    return name, _FLOAT_FMT[name]
+
+
+def _float_empty(shape, name, device):
+    """An output of a float decode: a cuda tensor (device = its index), or on
+    the host (device None) a numpy array -- a torch CPU tensor for bfloat16,
+    which numpy does not have."""
+    if device is None and name != "bfloat16":
+        return np.empty(shape, dtype=name)
+    torch = _torch()
+    return torch.empty(tuple(shape), dtype=getattr(torch, name), device="cpu" if device is None else "cuda:%d" % device)
+
+
+def _check_out_float(out, shape, device, name, layout="chw"):
+    """_check_out for a float decode's `out`: a numpy array (float32 /
+    float16), a torch CPU tensor (bfloat16 only: the host form of that dtype)
+    or a tensor on the codec's device.  Returns whether it lives on the device."""
+    shape = tuple(_layout_shape(shape, layout))
+    if isinstance(out, np.ndarray):
+        if name == "bfloat16":
+            raise GrkGpuError("numpy has no bfloat16: out must be a torch tensor")
+        if out.shape != shape or out.dtype != np.dtype(name) or not out.flags.c_contiguous:
+            raise GrkGpuError("out must be a C-contiguous %s array of shape %s (got %s %s)"
+                              % (name, shape, out.shape, out.dtype))
+        return False
+    torch = _torch()
+    if not isinstance(out, torch.Tensor):
+        raise GrkGpuError("out must be a numpy array or a torch tensor")
+    if tuple(out.shape) != shape or out.dtype != getattr(torch, name) or not out.is_contiguous():
+        raise GrkGpuError("out must be a contiguous %s tensor of shape %s (got %s %s)"
+                          % (name, shape, tuple(out.shape), out.dtype))
+    if not out.is_cuda:
+        if name != "bfloat16":
+            raise GrkGpuError("a host out of %s samples must be a numpy array" % name)
+        return False
+    if out.device.index != device:
+        raise GrkGpuError("out must live on cuda:%d (got %s)" % (device, out.device))
+    return True
+
+
+def _out_norm(scale, bias, c=None, norm=None):
+    """grkgpu_out_norm of scale / bias: each a scalar or one value per output
+    channel, rounded to float32.  c: the channel count the values are checked
+    against (None, the plan call: not known here -- a scalar fills every
+    entry, a sequence its own length, the entries behind it 1 and 0)."""
+    norm = OutNorm() if norm is None else norm
+    for name, v, dst, rest in (("scale", scale, norm.scale, 1.0), ("bias", bias, norm.bias, 0.0)):
+        a = np.asarray(v, dtype=np.float64).reshape(-1)
+        if a.size < 1 or a.size > MAXC or (c is not None and a.size not in (1, c)):
+            raise GrkGpuError("%s: a scalar or one value per output channel (got %d for %s)"
+                              % (name, a.size, MAXC if c is None else c))
+        for k in range(MAXC):
+            dst[k] = np.float32(a[0] if a.size == 1 else (a[k] if k < a.size else rest))
+    return norm
+
+
+def norm_scale_bias(prec, mean, std, sgnd=False):
+    """(scale, bias) as float32 arrays for Codec.decompress_float, by the
+    ToTensor + Normalize convention: x / (2^prec - 1) first, then (x - mean) /
+    std, so scale = 1 / ((2^prec - 1) * std) and bias = -mean / std, each
+    computed in float64 and rounded once.  mean / std: a scalar or one value
+    per channel.  sgnd=True: the samples are signed; the same formula, mean
+    and std then speak of x / (2^prec - 1) in [-0.5, 0.5]."""
+    mean, std = np.atleast_1d(np.asarray(mean, np.float64)), np.atleast_1d(np.asarray(std, np.float64))
+    mean, std = np.broadcast_arrays(mean, std)
+    if prec < 1 or prec > 31 or not np.all(np.isfinite(mean)) or not np.all(np.isfinite(std)) or np.any(std == 0):
+        raise GrkGpuError("norm_scale_bias: prec 1 .. 31, finite mean and a finite non-zero std")
+    full = np.float64((1 << prec) - 1)
+    return (1.0 / (full * std)).astype(np.float32), (-mean / std).astype(np.float32)
+
+
+def plan_batch_float(bufs, dtype="float32", scale=1.0, bias=0.0, layout="chw", reduce=0, layers=0, upsample=False,
+                     colour=None, out_prec=None, prec_mode="clip", ops=None, sample_fmt=None):
+    """grkgpu_batch_float_plan: the host half of Codec.decompress_batch_float --
+    no device call.  The keywords are that call's, one value or a list with one
+    entry per stream; ops as in plan_batch_convert; sample_fmt (a list of raw
+    GRKGPU_SAMPLE_* values or None entries) stands in for dtype where a test
+    needs a format the keyword refuses.  Returns plan_batch's dict."""
+    bufs = list(bufs)
+    n = len(bufs)
+    items, keep = _batch_items(bufs)
+    if ops is not None:
+        arr = (OutOps * max(n, 1))()
+        for i, o in enumerate(ops):
+            if o is not None:
+                arr[i] = o
+    else:
+        arr, _, _ = _batch_ops(n, colour, out_prec, prec_mode)
+    dtypes, layouts = _per_item(dtype, n, "dtype"), _per_item(layout, n, "layout")
+    ups = _per_item(upsample, n, "upsample")
+    scales, biases = _per_item(scale, n, "scale", seq=(list,)), _per_item(bias, n, "bias", seq=(list,))
+    norms = (OutNorm * max(n, 1))()
+    for i in range(n):
+        _layout_shape((1, 1, 1), layouts[i])
+        items[i].out.sample_fmt = _float_format(dtypes[i])[1] if sample_fmt is None or sample_fmt[i] is None \
+            else sample_fmt[i]
+        items[i].out.layout = _LAYOUTS[layouts[i]] | (LAYOUT_UPSAMPLE if ups[i] else 0)
+        _out_norm(scales[i], biases[i], None, norms[i])
+    info = BatchInfo()
+    dp = DParams(cp_reduce=reduce, cp_layer=layers)
+    rc = lib().grkgpu_batch_float_plan(items, arr, norms, n, ctypes.byref(dp), ctypes.byref(info))
+    return _plan_result(rc, info, items, n)
+
+
 def _stream_handle(device):
     torch = _torch()
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
@@ -1403,7 +1537,8 @@ class Codec:
         """grkgpu_out_planes of a checked output: a (c,h,w) / (h,w,c) array or
         tensor, or a list of host planes."""
         op = OutPlanes(sample_fmt=fmt, layout=_LAYOUTS[layout], on_device=1 if on_dev else 0)
-        ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.ctypes.data)
+        # (a tensor on the host: the bfloat16 result of a float decode)
+        ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
         if layout == "hwc":
             op.planes[0] = ptr(out)
         else:
@@ -1607,8 +1742,81 @@ class Codec:
             _check(lib().grkgpu_decompress(self._ctx, bp, bn, None, ptrs, 1 if on_dev else 0))
         return out
 
+    def decompress_float(self, buf, dtype="float32", scale=1.0, bias=0.0, layout="chw", device_out=False, out=None,
+                         reduce=0, window=None, layers=0, upsample=False, colour=None, out_prec=None,
+                         prec_mode="clip"):
+        """Decode a .j2k codestream straight to normalised float samples
+        (grkgpu_decompress_float): with v the int32 value decompress(buf,
+        reduce=, window=, layers=, upsample=, colour=, out_prec=, prec_mode=)
+        gives for output channel ch, the sample is
+            np.float32(v) * np.float32(scale[ch]) + np.float32(bias[ch])
+        -- the product and the sum each rounded in float32, no FMA -- stored
+        as float32, or rounded to nearest even to float16 / bfloat16, by the
+        last decode kernel: no integer image, no follow-up passes.  dtype:
+        np.float32 / np.float16, "float32" / "float16" / "bfloat16" or the
+        torch dtypes.  scale / bias: a scalar or one value per output channel
+        (norm_scale_bias gives the ToTensor + Normalize pair).  Host results
+        are numpy arrays, bfloat16 ones torch CPU tensors; device_out / out
+        as decompress (a host `out` of bfloat16 samples is a torch CPU
+        tensor).  Samples nothing decoded come out as bias[ch] (with a colour
+        step: the normalised conversion of zeros).  Subsampled components
+        that are not upsampled come back as a list of host planes.  Not
+        here: force_rgb, custom_mct, JP2 files."""
+        name, fmt = _float_format(dtype)
+        ops = _out_ops(colour, out_prec, prec_mode)
+        d = read_header(buf)
+        if window is not None:  # the window (reference grid) clipped to the image
+            wx0, wy0, wx1, wy1 = window
+            d.x0, d.y0, d.x1, d.y1 = max(d.x0, wx0), max(d.y0, wy0), min(d.x1, wx1), min(d.y1, wy1)
+            if d.x1 <= d.x0 or d.y1 <= d.y0:
+                raise GrkGpuError("decode window outside the image")
+        if layers < 0:
+            raise GrkGpuError("layers must be >= 0")
+        cd = lambda v, s: -(-v // s)  # noqa: E731
+        R = 1 << reduce
+
+        def extent(a0, a1, s):  # (decompress's rule)
+            if window is not None:
+                return cd(cd(a1, s), R) - cd(cd(a0, s), R)
+            return cd(cd(a1, s) - cd(a0, s), R)
+        c = d.numcomps
+        subsampled = any(d.dx[k] != 1 or d.dy[k] != 1 for k in range(c))
+        chans = _out_channels(colour, False, [d.prec[k] for k in range(c)], [d.sgnd[k] for k in range(c)], out_prec)
+        grid = [(d.dx[k], d.dy[k]) for k in range(c)]
+        if len(chans) != c:  # (CMYK: the black ink's plane goes; one grid either way)
+            grid = [grid[0]] * len(chans)
+        c = len(chans)
+        norm = _out_norm(scale, bias, c)
+        dp = DParams(cp_reduce=reduce, cp_layer=layers)
+        if window is not None:
+            dp.DA_x0, dp.DA_y0, dp.DA_x1, dp.DA_y1 = [int(v) for v in window]
+        up = (bool(upsample) or colour == "sycc") and subsampled
+        if subsampled and not up:  # a list of host planes, each on its grid
+            if out is not None or device_out or (layout != "chw" and all(g == grid[0] for g in grid)):
+                raise GrkGpuError("subsampled components decode to host planes only")
+            out = [_float_empty((extent(d.y0, d.y1, g[1]), extent(d.x0, d.x1, g[0])), name, None) for g in grid]
+            op = self._out_planes(out, c, fmt, "chw", False)
+            op.layout = _LAYOUTS[layout]
+        else:
+            shp = (c, extent(d.y0, d.y1, 1), extent(d.x0, d.x1, 1))
+            if out is not None:
+                on_dev = _check_out_float(out, shp, self.device, name, layout)
+            else:
+                on_dev = bool(device_out)
+                out = _float_empty(_layout_shape(shp, layout), name, self.device if on_dev else None)
+            if on_dev:
+                lib().grkgpu_set_stream(self._ctx, _stream_handle(out.device))
+            op = self._out_planes(out, c, fmt, layout, on_dev)
+            if up:
+                op.layout |= LAYOUT_UPSAMPLE
+        bp, bn, keep = _buf_ptr(buf)
+        _check(lib().grkgpu_decompress_float(self._ctx, bp, bn, ctypes.byref(dp), 0, 0xFFFFFFFF, None, ctypes.byref(op),
+                                             None if ops is None else ctypes.byref(ops), ctypes.byref(norm)))
+        return out
+
     def _decompress_batch(self, convert, bufs, dtype, layout, device_out, out, reduce, layers, stack, errors,
-                          upsample=False, colour=None, out_prec=None, prec_mode="clip", jp2=False, force_rgb=False):
+                          upsample=False, colour=None, out_prec=None, prec_mode="clip", jp2=False, force_rgb=False,
+                          norm=None):
         """decompress_batch (convert=False: grkgpu_decompress_batch, a
         subsampled stream gets no destination and the call refuses it),
         decompress_batch_convert (grkgpu_decompress_batch_convert with its
@@ -1617,7 +1825,9 @@ class Codec:
         decompress_jp2_batch (jp2=True: grkgpu_jp2_decompress_batch; the
         geometry is the file's channels, colour is resolved by its colour
         space and the result is (outs, infos)), from the argument checks to
-        the list or stacked tensor they return."""
+        the list or stacked tensor they return.  norm = (scale, bias):
+        decompress_batch_float (grkgpu_decompress_batch_float; dtype names a
+        float format, the outputs are _float_empty's)."""
         if errors not in ("raise", "return"):
             raise GrkGpuError("errors must be 'raise' or 'return'")
         bufs = list(bufs)
@@ -1630,6 +1840,12 @@ class Codec:
         else:
             ops, colours, precs = _batch_ops(n, colour, out_prec, prec_mode) if convert else (None, [None] * n, [None] * n)
         outs = [None] * n if out is None else _per_item(list(out), n, "out")
+        floats = norm is not None
+        if floats:  # (a list: one entry per stream; anything else: one value, or one per channel, for all)
+            scales, biases = _per_item(norm[0], n, "scale", seq=(list,)), _per_item(norm[1], n, "bias", seq=(list,))
+            norms = (OutNorm * max(n, 1))()
+        # the formats and outputs of the integer calls, or of the float call (dt: a float format's name)
+        fmt_of = _float_format if floats else _out_format
         if layers < 0 or reduce < 0:
             raise GrkGpuError("reduce and layers must be >= 0")
         if stack and out is not None:
@@ -1651,9 +1867,9 @@ class Codec:
                     hdr_ok = False
             else:
                 hdr_ok = lib().grkgpu_read_header(ctypes.c_void_p(items[i].cs), items[i].len, ctypes.byref(d)) == 0
-            dt, fmt = _out_format(dtypes[i])
+            dt, fmt = fmt_of(dtypes[i])
             o = outs[i]
-            if o is not None and _out_dtype(o) is not None:
+            if o is not None and not floats and _out_dtype(o) is not None:
                 if dtypes[i] is not None and _out_dtype(o) != dt:
                     raise GrkGpuError("item %d: out holds %s samples, dtype asks for %s"
                                       % (i, _out_dtype(o).name, dt.name))
@@ -1672,12 +1888,15 @@ class Codec:
             if len(chans) != c:  # (CMYK: the black ink's plane goes; one grid either way)
                 grid = [grid[0]] * len(chans)
             c = len(chans)
+            if floats:
+                _out_norm(scales[i], biases[i], c, norms[i])
             up = (bool(ups[i]) or col == "sycc") and subsampled
             extent = lambda a0, a1, s: cd(cd(a1, s) - cd(a0, s), R)  # noqa: E731
             if subsampled and not up:  # a list of host planes, each on its grid
                 if o is not None or devs[i] or stack or (layouts[i] != "chw" and all(g == grid[0] for g in grid)):
                     raise GrkGpuError("item %d: subsampled components decode to host planes only" % i)
-                o = [np.empty((extent(d.y0, d.y1, g[1]), extent(d.x0, d.x1, g[0])), dtype=dt) for g in grid]
+                pshapes = [(extent(d.y0, d.y1, g[1]), extent(d.x0, d.x1, g[0])) for g in grid]
+                o = [_float_empty(ps, dt, None) if floats else np.empty(ps, dtype=dt) for ps in pshapes]
                 outs[i] = o
                 items[i].out = self._out_planes(o, c, fmt, "chw", False)
                 items[i].out.layout = _LAYOUTS[layouts[i]]
@@ -1687,10 +1906,12 @@ class Codec:
             if stack:
                 continue
             if o is not None:
-                on_dev = _check_out(o, shp, self.device, dt, layouts[i])
+                on_dev = (_check_out_float if floats else _check_out)(o, shp, self.device, dt, layouts[i])
             else:
                 on_dev = bool(devs[i])
-                if on_dev:
+                if floats:
+                    o = _float_empty(shapes[i][0], dt, self.device if on_dev else None)
+                elif on_dev:
                     o = _torch().empty(shapes[i][0], dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
                 else:
                     o = np.empty(shapes[i][0], dtype=dt)
@@ -1705,14 +1926,16 @@ class Codec:
                 raise GrkGpuError("stack=True needs streams of one shape, dtype, layout and destination")
             shp, dt, _ = shapes[0]
             any_dev = bool(devs[0])
-            if any_dev:
+            if floats:
+                stacked = _float_empty((n,) + tuple(shp), dt, self.device if any_dev else None)
+            elif any_dev:
                 stacked = _torch().empty((n,) + tuple(shp), dtype=_torch_dtype(dt), device="cuda:%d" % self.device)
             else:
                 stacked = np.empty((n,) + tuple(shp), dtype=dt)
             c = shp[0] if layouts[0] == "chw" else shp[2]
             for i in range(n):
                 outs[i] = stacked[i]
-                items[i].out = self._out_planes(stacked[i], c, _out_format(dt)[1], layouts[i], any_dev)
+                items[i].out = self._out_planes(stacked[i], c, fmt_of(dt)[1], layouts[i], any_dev)
                 if shapes[i][2]:
                     items[i].out.layout |= LAYOUT_UPSAMPLE
         if any_dev:
@@ -1721,6 +1944,8 @@ class Codec:
         dp = DParams(cp_reduce=reduce, cp_layer=layers)
         if jp2:
             rc = lib().grkgpu_jp2_decompress_batch(self._ctx, items, ops, n, ctypes.byref(dp), ctypes.byref(info), None)
+        elif floats:
+            rc = lib().grkgpu_decompress_batch_float(self._ctx, items, ops, norms, n, ctypes.byref(dp), ctypes.byref(info))
         elif convert:
             rc = lib().grkgpu_decompress_batch_convert(self._ctx, items, ops, n, ctypes.byref(dp), ctypes.byref(info))
         else:
@@ -1773,6 +1998,22 @@ class Codec:
         stack=True gives the (n, h, w, 3) tensor a loader wants."""
         return self._decompress_batch(True, bufs, dtype, layout, device_out, out, reduce, layers, stack, errors,
                                       upsample, colour, out_prec, prec_mode)
+
+    def decompress_batch_float(self, bufs, dtype="float32", scale=1.0, bias=0.0, layout="chw", device_out=False,
+                               out=None, reduce=0, layers=0, upsample=False, colour=None, out_prec=None,
+                               prec_mode="clip", stack=False, errors="raise"):
+        """decompress_batch_convert to normalised float samples
+        (grkgpu_decompress_batch_float): item i is what decompress_float(buf,
+        dtype=, scale=, bias=, layout=, ...) returns, bit for bit, and 64
+        copies of a stream still take the launches of one.  Every keyword is
+        one value for all streams or a list with one entry per stream; for
+        scale and bias a list means one entry per stream, each a scalar or
+        one value per output channel (a tuple or an array: one value per
+        channel, for every stream).  stack=True with device_out gives the (n,
+        h, w, 3) float16 tensor a model takes.  errors and self.batch_info as
+        decompress_batch."""
+        return self._decompress_batch(True, bufs, dtype, layout, device_out, out, reduce, layers, stack, errors,
+                                      upsample, colour, out_prec, prec_mode, norm=(scale, bias))
 
     def decompress_jp2_batch(self, bufs, dtype=None, layout="chw", colour="auto", out_prec=None, prec_mode="clip",
                              force_rgb=False, reduce=0, layers=0, device_out=False, out=None, stack=False,

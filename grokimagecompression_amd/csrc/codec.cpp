@@ -13,6 +13,7 @@
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -2768,7 +2769,15 @@ struct DecodeOut {
     int custom_mct;  // grkgpu_decompress_mct: a COD with MCT = 2 (Part 2 array-based) is decoded, not refused
     const struct ChanMap *chan;  // grkgpu_jp2_decompress: the output channels where they are not the components in order
     int is_rgb;  // grkgpu_jp2_decompress: the file says sRGB (GRKGPU_COLOUR_FORCE_RGB leaves 3+ channels alone)
+    // grkgpu_decompress_float: fmt is SMP_F32 / _F16 / _BF16 (refused everywhere else), the samples leave as
+    // v * scale + bias per output channel (null: 1, 0).  Such a decode always converts: ops is never null.
+    int fl;
+    const grkgpu_out_norm *norm;
 };
+// the formats a decode stores: the integer ones, or (the float entry points) the float ones
+static bool out_fmt_ok(const DecodeOut &od) {
+    return od.fl ? float_fmt(od.fmt) : (od.fmt >= SMP_I32 && od.fmt <= SMP_I16);
+}
 // The output channels of a JP2 file with a palette or a channel swap
 // (jp2_resolve_channels): channel c takes component comp[c]'s sample, or entry
 // [sample][pcol[c]] of the ne x npc table (host memory), and leaves with prec[c]
@@ -2797,7 +2806,7 @@ static int check_out_ops(const grkgpu_out_ops *o, uint32_t fmt) {
     if (o->prec > 16) return set_err(GRKGPU_EINVAL, "output precision must be 1 .. 16 (0: the component's own)");
     if (o->prec && o->prec_mode > GRKGPU_PREC_SCALE) return set_err(GRKGPU_EINVAL, "unknown precision mode");
     if (o->reserved) return set_err(GRKGPU_EINVAL, "reserved field of the output ops must be 0");
-    if (o->prec && fmt != SMP_I32 && o->prec > 8 * sample_bytes((int32_t)fmt))
+    if (o->prec && fmt != SMP_I32 && !float_fmt((int32_t)fmt) && o->prec > 8 * sample_bytes((int32_t)fmt))
         return set_err(GRKGPU_EINVAL, "sample format does not hold the output precision");
     return GRKGPU_OK;
 }
@@ -2899,6 +2908,14 @@ static int32_t holding_fmt(uint32_t nc, const uint32_t *prec, const int32_t *sgn
     if ((any_s && any_u) || mp > 16) return SMP_I32;
     return mp <= 8 ? (any_s ? SMP_I8 : SMP_U8) : (any_s ? SMP_I16 : SMP_U16);
 }
+// channel k's part of an image's ops, as the ops of a one-component store (a plane converted on its own grid)
+static OutOps plane_ops(const OutOps &o, uint32_t k) {
+    OutOps ok{};
+    ok.pc[0] = o.pc[k];
+    ok.scale[0] = o.scale[k];
+    ok.bias[0] = o.bias[k];
+    return ok;
+}
 
 // reduce > 0 (whole-image decode only): the image at resolution
 // numres - 1 - reduce (grk_decompress -r, cp_reduce, grok.h:698-702): every
@@ -2968,6 +2985,7 @@ struct DecHost {
     Rect wr{};
     uint32_t ix0 = 0, iy0 = 0, ix1 = 0, iy1 = 0, ox1 = 0, oy1 = 0, nc = 0, ntiles = 0, iw = 0;
     bool whole = true, subs = false, mixed = false, conv = false, sycc = false, colconv = false;
+    bool fl = false;  // a float destination: conv holds, dops carries scale / bias, no fill is a memset
     uint32_t colour = 0;
     OutOps dops{};
     uint32_t oprec[GRKGPU_MAX_COMPS];
@@ -3045,7 +3063,8 @@ struct DecHost {
     // plane's own grid); else the ops, if any, run in the upsampling store
     bool grid_ops() const { return conv && !up; }
     // samples nothing decoded leave as the colour conversion of zeros, by a converting store over null sources
-    bool converted_zeros() const { return colconv && !up && !cm && (opad || missing); }
+    // (a float destination: always -- the normalised zero is no memset; on each plane's own grid when mixed)
+    bool converted_zeros() const { return (colconv || fl) && !up && !cm && (opad || missing); }
     // the clamped, shifted tile at the decoded resolution: where component k's samples of tile lt lie in
     // its tile buffer (tr) and the part of them inside the output (out)
     Rect tile_res(uint32_t lt, uint32_t k) const {
@@ -3088,7 +3107,8 @@ int DecHost::begin() {
     planes = od.planes;
     planes_on_device = od.on_device;
     if (!csb || (!planes && !host_only)) return set_err(GRKGPU_EINVAL, "null argument");
-    if (od.fmt < SMP_I32 || od.fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if (!out_fmt_ok(od)) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    fl = od.fl != 0;
     sb = sample_bytes(od.fmt);  // bytes per output sample
     il = od.interleaved != 0;
     size_t pos = 0;
@@ -3142,7 +3162,9 @@ int DecHost::begin() {
     // grk_decompress in the store of the last kernel -- dops their device
     // form, oprec the precision the samples leave with.  sYCC needs every
     // component of the pixel, so it implies the upsampled output.
-    conv = out_ops_active(od.ops);
+    // A float destination (od.fl) converts whatever the ops say: its scale and
+    // bias ride in dops, so every store of it is a store with ops.
+    conv = out_ops_active(od.ops) || fl;
     colour = conv ? colour_of(od.ops) : GRKGPU_COLOUR_NONE;
     sycc = colour == GRKGPU_COLOUR_SYCC;
     // eYCC / CMYK -> RGB sit where sYCC sits, on components of one grid (they
@@ -3216,6 +3238,14 @@ int DecHost::begin() {
         int rc = resolve_out_ops(od.ops, nc, cp.prec, cp.sgnd, cp.dx, cp.dy, dops, no, oprec, osgnd);
         if (rc) return rc;
     }
+    if (fl) {  // the output channels' scale and bias; entries beyond them are not read
+        for (uint32_t k = 0; k < no; ++k) {
+            dops.scale[k] = od.norm ? od.norm->scale[k] : 1.0f;
+            dops.bias[k] = od.norm ? od.norm->bias[k] : 0.0f;
+            if (!std::isfinite(dops.scale[k]) || !std::isfinite(dops.bias[k]))
+                return set_err(GRKGPU_EINVAL, "scale and bias of every output channel must be finite");
+        }
+    }
     up = (od.upsample || sycc) && subs;
     if (up && reduce)  // grk_decompress refuses -u with -r
         return set_err(GRKGPU_EINVAL, "upsampled output of a reduced decode is not supported");
@@ -3230,7 +3260,7 @@ int DecHost::begin() {
             if (no != nc && k >= 3) { img->dx[k] = img->dx[k + 1]; img->dy[k] = img->dy[k + 1]; }
         }
     }
-    for (uint32_t k = 0; od.fmt != SMP_I32 && k < no; ++k) {
+    for (uint32_t k = 0; od.fmt != SMP_I32 && !fl && k < no; ++k) {  // (a float format holds every precision and sign)
         const bool sg = od.fmt == SMP_I8 || od.fmt == SMP_I16;
         if ((osgnd[k] != 0) != sg || oprec[k] > 8 * sb)
             return set_err(GRKGPU_EINVAL, "sample format does not hold the component's precision / signedness");
@@ -3792,7 +3822,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                            uint32_t reduce = 0, const Rect *win = nullptr, uint32_t max_layers = 0,
                            bool host_only = false, std::vector<uint8_t> *decoded_out = nullptr) {
     if ((!c && !host_only) || !csb || (!od.planes && !host_only)) return set_err(GRKGPU_EINVAL, "null argument");
-    if (od.fmt < SMP_I32 || od.fmt > SMP_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if (!out_fmt_ok(od)) return set_err(GRKGPU_EINVAL, "unknown sample format");
     ActiveCall active;
     double t_start = now_ms();
     DecHost H;
@@ -3966,7 +3996,34 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
         return launch_palette(PlanePtrs{}, 0, o.w(), o.h(), fdst, od.fmt, il, il ? ow * no : ow, nc, ShiftArr{},
                               ShiftArr{}, ShiftArr{}, 0, 0, z, ptable, conv ? &dops : nullptr, s);
     };
-    if (cm && opad) {
+    // A float destination has no zero to memset: samples nothing decoded
+    // leave as the normalised precision op of zero (bias, where no colour step
+    // runs) -- the same converting store over null sources, on each plane's
+    // own grid where the grids differ (planar output, no colour step there).
+    const bool fl = H.fl;
+    auto fill_plane = [&](uint32_t k, const Rect &o) -> hipError_t {
+        UpPlan zero{};
+        zero.c[0].dx = zero.c[0].dy = 1;
+        DstPlanes fdst{};
+        fdst.p[0] = at(k, (uint64_t)(o.y0 - orect[k].y0) * orect[k].w() + (o.x0 - orect[k].x0));
+        return launch_upsample_ops(zero, 1, o.x0, o.y0, o.w(), o.h(), fdst, od.fmt, false, orect[k].w(),
+                                   plane_ops(dops, k), s);
+    };
+    if (fl && mixed && !up && (opad || missing)) {
+        for (uint32_t k = 0; k < nc; ++k) {
+            if (opad) {
+                HIPCHK(fill_plane(k, orect[k]));
+                continue;
+            }
+            for (uint32_t t = tb; t < te; ++t) {
+                if (walk.decoded[t] || wskip[t]) continue;
+                const Rect cr = comp_rect(tile_rect(cp, t), cp.dx[k], cp.dy[k]);
+                const Rect o = intersect({ceil_pow2(cr.x0, reduce), ceil_pow2(cr.y0, reduce), ceil_pow2(cr.x1, reduce),
+                                          ceil_pow2(cr.y1, reduce)}, orect[k]);
+                if (!o.empty()) HIPCHK(fill_plane(k, o));
+            }
+        }
+    } else if (cm && opad) {
         HIPCHK(fill_mapped(orect[0]));
     } else if (cm && missing) {
         for (uint32_t t = tb; t < te; ++t) {
@@ -3976,9 +4033,9 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                                       ceil_pow2(cr.y1, reduce)}, orect[0]);
             if (!o.empty()) HIPCHK(fill_mapped(o));
         }
-    } else if (colconv && !up && opad) {
+    } else if ((colconv || fl) && !up && opad) {
         HIPCHK(fill_converted(orect[0]));
-    } else if (colconv && !up && missing) {
+    } else if ((colconv || fl) && !up && missing) {
         for (uint32_t t = tb; t < te; ++t) {
             if (walk.decoded[t] || wskip[t]) continue;
             const Rect cr = comp_rect(tile_rect(cp, t), cp.dx[0], cp.dy[0]);  // (one grid; sYCC: the image's)
@@ -3986,7 +4043,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                                       ceil_pow2(cr.y1, reduce)}, orect[0]);
             if (!o.empty()) HIPCHK(fill_converted(o));
         }
-    } else {
+    } else if (!fl) {  // (float, upsampled: the upsampling launch writes such pixels itself)
         HIPCHK(dec_zero_fills(H, dst.p, s, &nl));
     }
     ShiftArr sh{}, mn{}, mx{};
@@ -4017,8 +4074,7 @@ static int decompress_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, grkgpu
                 mnk.v[0] = mn.v[k];
                 mxk.v[0] = mx.v[k];
                 if (conv && !up) {  // each plane on its own grid, converted
-                    OutOps ok{};
-                    ok.pc[0] = dops.pc[k];
+                    const OutOps ok = plane_ops(dops, k);
                     HIPCHK(launch_mct_inv_dcshift_ops(tsrc, tr.w(), out.w(), out.h(), tdst, od.fmt, false,
                                                       orect[k].w(), 1, sk, mnk, mxk, 0, tc.irrev, ok, s));
                     continue;
@@ -4224,9 +4280,13 @@ extern "C" int grkgpu_decompress_tiles(grkgpu_ctx *c, const uint8_t *csb, size_t
 }
 
 // grkgpu_out_planes' own rules, checked before anything touches a device
-static int check_out_planes(const grkgpu_out_planes *out) {
+// (floats: the float entry points, which take the float formats and only those)
+static const grkgpu_out_ops g_no_ops{};
+static int check_out_planes(const grkgpu_out_planes *out, bool floats = false) {
     if (!out) return set_err(GRKGPU_EINVAL, "null argument");
-    if (out->sample_fmt > GRKGPU_SAMPLE_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
+    if (floats && !float_fmt((int32_t)out->sample_fmt))
+        return set_err(GRKGPU_EINVAL, "a float decode needs GRKGPU_SAMPLE_F32 / _F16 / _BF16");
+    if (!floats && out->sample_fmt > GRKGPU_SAMPLE_I16) return set_err(GRKGPU_EINVAL, "unknown sample format");
     if ((out->layout & ~GRKGPU_LAYOUT_UPSAMPLE) > GRKGPU_LAYOUT_INTERLEAVED)
         return set_err(GRKGPU_EINVAL, "unknown layout");
     return GRKGPU_OK;
@@ -4235,15 +4295,19 @@ static int check_out_planes(const grkgpu_out_planes *out) {
 static int decompress_to_impl(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
                               uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
                               const grkgpu_out_planes *out, const grkgpu_out_ops *ops, bool custom_mct = false,
-                              const ChanMap *chan = nullptr, bool is_rgb = false) {
-    int rc = check_out_planes(out);
+                              const ChanMap *chan = nullptr, bool is_rgb = false, bool floats = false,
+                              const grkgpu_out_norm *norm = nullptr) {
+    int rc = check_out_planes(out, floats);
     if (rc) return rc;
     rc = check_out_ops(ops, out->sample_fmt);
     if (rc) return rc;
+    if (floats && ops && (ops->colour & GRKGPU_COLOUR_FORCE_RGB))
+        return set_err(GRKGPU_EUNSUPPORTED, "force-RGB is not supported with a float destination");
     const DecodeOut od{out->planes, (int32_t)out->sample_fmt,
                        (out->layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED, out->on_device,
-                       (out->layout & GRKGPU_LAYOUT_UPSAMPLE) != 0, out_ops_active(ops) ? ops : nullptr,
-                       custom_mct ? 1 : 0, chan, is_rgb ? 1 : 0};
+                       (out->layout & GRKGPU_LAYOUT_UPSAMPLE) != 0,
+                       out_ops_active(ops) ? ops : (floats ? &g_no_ops : nullptr),
+                       custom_mct ? 1 : 0, chan, is_rgb ? 1 : 0, floats ? 1 : 0, floats ? norm : nullptr};
     if (!dp) return decompress_impl(c, csb, len, img, od, tile_begin, tile_end);
     const bool win = dp->DA_x0 || dp->DA_y0 || dp->DA_x1 || dp->DA_y1;
     const Rect w{dp->DA_x0, dp->DA_y0, dp->DA_x1, dp->DA_y1};
@@ -4262,6 +4326,13 @@ extern "C" int grkgpu_decompress_convert(grkgpu_ctx *c, const uint8_t *csb, size
                                          uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
                                          const grkgpu_out_planes *out, const grkgpu_out_ops *ops) {
     return decompress_to_impl(c, csb, len, dp, tile_begin, tile_end, img, out, ops);
+}
+
+extern "C" int grkgpu_decompress_float(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
+                                       uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                                       const grkgpu_out_planes *out, const grkgpu_out_ops *ops,
+                                       const grkgpu_out_norm *norm) {
+    return decompress_to_impl(c, csb, len, dp, tile_begin, tile_end, img, out, ops, false, nullptr, false, true, norm);
 }
 
 extern "C" int grkgpu_decompress_mct(grkgpu_ctx *c, const uint8_t *csb, size_t len, const grkgpu_dparams *dp,
@@ -4704,8 +4775,7 @@ static void plan_item_stores(StorePlan &P, const DecHost &h, const ItemBases &B)
                 ts.sstride = tr.w(); ts.dstride = h.orect[k].w(); ts.w = out.w(); ts.h = out.h();
                 ts.nc = 1; ts.wmask = tc.irrev; ts.fmt = gops ? h.od.fmt : gfmt;
                 if (gops) {  // each plane on its own grid, converted
-                    OutOps ok{};
-                    ok.pc[0] = h.dops.pc[k];
+                    const OutOps ok = plane_ops(h.dops, k);
                     if (kops_at[k] == 0xffffffffu) { kops_at[k] = (uint32_t)P.ops.size(); P.ops.push_back(ok); }
                     store(ts, &ok, kops_at[k]);
                 } else {
@@ -4764,19 +4834,47 @@ static void plan_item_stores(StorePlan &P, const DecHost &h, const ItemBases &B)
     // decoded rectangle cwin[0]) and on the tiles the stream never reached,
     // which no other job writes, so the order among the jobs is free.
     if (!h.converted_zeros()) return;
-    std::vector<Rect> zr;
-    const Rect &o0 = h.orect[0], &cw = h.cwin[0];
-    if (h.opad) {
-        zr.push_back({std::max(cw.x1, o0.x0), o0.y0, o0.x1, o0.y1});
-        zr.push_back({o0.x0, std::max(cw.y1, o0.y0), std::min(cw.x1, o0.x1), o0.y1});
+    // the rectangles nothing decoded on component g's grid
+    auto zero_rects = [&](uint32_t g) {
+        std::vector<Rect> zr;
+        const Rect &o0 = h.orect[g], &cw = h.cwin[g];
+        if (h.opad) {
+            zr.push_back({std::max(cw.x1, o0.x0), o0.y0, o0.x1, o0.y1});
+            zr.push_back({o0.x0, std::max(cw.y1, o0.y0), std::min(cw.x1, o0.x1), o0.y1});
+        }
+        for (uint32_t t = h.tb; h.missing && t < h.te; ++t) {
+            if (h.walk.decoded[t] || h.wskip[t]) continue;
+            const Rect cr = comp_rect(tile_rect(h.cp, t), h.cp.dx[g], h.cp.dy[g]);  // (one grid; sYCC: the image's)
+            zr.push_back(intersect({ceil_pow2(cr.x0, h.reduce), ceil_pow2(cr.y0, h.reduce), ceil_pow2(cr.x1, h.reduce),
+                                    ceil_pow2(cr.y1, h.reduce)}, o0));
+        }
+        return zr;
+    };
+    if (h.mixed) {
+        // (a float destination only) each plane on its own grid: one-component jobs with the plane's own ops
+        for (uint32_t k = 0; k < nc; ++k) {
+            const Rect &ok_ = h.orect[k];
+            const OutOps ok = plane_ops(h.dops, k);
+            for (const Rect &o : zero_rects(k)) {
+                if (o.empty()) continue;
+                ConvJob j{};
+                j.c[0].dx = j.c[0].dy = 1;
+                j.dst[0] = (void *)(B.dst(h, k) + ((uint64_t)(o.y0 - ok_.y0) * ok_.w() + (o.x0 - ok_.x0)) * h.sb);
+                j.X0 = o.x0; j.Y0 = o.y0; j.x1 = o.x1; j.y1 = o.y1;
+                j.dstride = ok_.w(); j.ncomp = 1;
+                if (kops_at[k] == 0xffffffffu) { kops_at[k] = (uint32_t)P.ops.size(); P.ops.push_back(ok); }
+                if (P.add_up(h.od.fmt, false, ok, j, kops_at[k])) continue;
+                UpPlan zero{};
+                zero.c[0] = j.c[0];
+                DstPlanes fdst{};
+                fdst.p[0] = j.dst[0];
+                P.up_singles.push_back(TileConv{zero, 1, o, fdst, h.od.fmt, false, j.dstride, ok, true});
+            }
+        }
+        return;
     }
-    for (uint32_t t = h.tb; h.missing && t < h.te; ++t) {
-        if (h.walk.decoded[t] || h.wskip[t]) continue;
-        const Rect cr = comp_rect(tile_rect(h.cp, t), h.cp.dx[0], h.cp.dy[0]);  // (one grid; sYCC: the image's)
-        zr.push_back(intersect({ceil_pow2(cr.x0, h.reduce), ceil_pow2(cr.y0, h.reduce), ceil_pow2(cr.x1, h.reduce),
-                                ceil_pow2(cr.y1, h.reduce)}, o0));
-    }
-    for (const Rect &o : zr) {
+    const Rect &o0 = h.orect[0];
+    for (const Rect &o : zero_rects(0)) {
         if (o.empty()) continue;
         UpPlan zero{};
         for (uint32_t k = 0; k < nc; ++k) zero.c[k].dx = zero.c[k].dy = 1;
@@ -4808,7 +4906,8 @@ using Jp2Prep = std::function<int(size_t, Jp2Item &)>;
 // JP2 file, parsed by (*jp2)(i, ...); force-RGB is taken.
 static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const grkgpu_dparams *p,
                       grkgpu_batch_info *info, bool host_only, bool convert = false,
-                      const grkgpu_out_ops *ops = nullptr, const Jp2Prep *jp2 = nullptr) {
+                      const grkgpu_out_ops *ops = nullptr, const Jp2Prep *jp2 = nullptr, bool floats = false,
+                      const grkgpu_out_norm *norms = nullptr) {
     if (info) *info = grkgpu_batch_info{};
     if ((!c && !host_only) || (n && !items)) return set_err(GRKGPU_EINVAL, "null argument");
     if (p && (p->DA_x0 || p->DA_y0 || p->DA_x1 || p->DA_y1))
@@ -4830,11 +4929,12 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
             DecHost &h = H[i];
             int rc = it.cs ? GRKGPU_OK : set_err(GRKGPU_EINVAL, "null argument");
             if (!rc && jp2) rc = (*jp2)(i, J[i]);  // (the boxes first, as grkgpu_jp2_decompress reads them)
-            if (!rc) rc = check_out_planes(&it.out);
+            if (!rc) rc = check_out_planes(&it.out, floats);
             if (!rc && !convert && (it.out.layout & GRKGPU_LAYOUT_UPSAMPLE))
                 rc = set_err(GRKGPU_EUNSUPPORTED, "upsampled output is not supported in a batch");
             const grkgpu_out_ops *const given = jp2 ? (J[i].has_ops ? &J[i].o : nullptr) : (convert && ops ? &ops[i] : nullptr);
-            const grkgpu_out_ops *const o = out_ops_active(given) ? given : nullptr;
+            // (a float item always converts: its ops are never null)
+            const grkgpu_out_ops *const o = out_ops_active(given) ? given : (floats ? &g_no_ops : nullptr);
             if (!rc && given) rc = check_out_ops(given, it.out.sample_fmt);
             if (!rc && !jp2 && o && (o->colour & GRKGPU_COLOUR_FORCE_RGB))
                 rc = set_err(GRKGPU_EUNSUPPORTED, "force-RGB is not supported in a batch");
@@ -4843,7 +4943,8 @@ static int batch_impl(grkgpu_ctx *c, grkgpu_batch_item *items, uint32_t n, const
                 h.od = DecodeOut{it.out.planes, (int32_t)it.out.sample_fmt,
                                  (it.out.layout & ~GRKGPU_LAYOUT_UPSAMPLE) == GRKGPU_LAYOUT_INTERLEAVED,
                                  it.out.on_device, (it.out.layout & GRKGPU_LAYOUT_UPSAMPLE) != 0, o, 0,
-                                 jp2 ? J[i].chan : nullptr, jp2 && J[i].is_rgb ? 1 : 0};
+                                 jp2 ? J[i].chan : nullptr, jp2 && J[i].is_rgb ? 1 : 0, floats ? 1 : 0,
+                                 floats && norms ? &norms[i] : nullptr};
                 h.reduce = reduce; h.max_layers = layers; h.host_only = host_only; h.batch = !convert;
                 rc = h.begin();
             }
@@ -5119,6 +5220,18 @@ extern "C" int grkgpu_decompress_batch_convert(grkgpu_ctx *c, grkgpu_batch_item 
 extern "C" int grkgpu_batch_convert_plan(grkgpu_batch_item *items, const grkgpu_out_ops *ops, uint32_t n,
                                          const grkgpu_dparams *p, grkgpu_batch_info *info) {
     return batch_impl(nullptr, items, n, p, info, true, true, ops);
+}
+
+extern "C" int grkgpu_decompress_batch_float(grkgpu_ctx *c, grkgpu_batch_item *items, const grkgpu_out_ops *ops,
+                                             const grkgpu_out_norm *norms, uint32_t n, const grkgpu_dparams *p,
+                                             grkgpu_batch_info *info) {
+    return batch_impl(c, items, n, p, info, false, true, ops, nullptr, true, norms);
+}
+
+extern "C" int grkgpu_batch_float_plan(grkgpu_batch_item *items, const grkgpu_out_ops *ops,
+                                       const grkgpu_out_norm *norms, uint32_t n, const grkgpu_dparams *p,
+                                       grkgpu_batch_info *info) {
+    return batch_impl(nullptr, items, n, p, info, true, true, ops, nullptr, true, norms);
 }
 
 // ---------------------------------------------------------------------------

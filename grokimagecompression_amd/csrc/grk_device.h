@@ -16,13 +16,17 @@ struct PlanePtrs { int32_t *p[GRK_MAX_COMPS]; };
 // to int32 by the kernel that first reads them (DC shift + MCT, or the fused
 // DWT level 0) -- an 8K 12-bit frame crosses PCIe as 2 B/sample.
 struct SrcPlanes { const void *p[GRK_MAX_COMPS]; };
-enum SampleFmt : int32_t { SMP_I32 = 0, SMP_U8 = 1, SMP_I8 = 2, SMP_U16 = 3, SMP_I16 = 4 };
+enum SampleFmt : int32_t { SMP_I32 = 0, SMP_U8 = 1, SMP_I8 = 2, SMP_U16 = 3, SMP_I16 = 4,
+                           // decode output of the float entry points only (GRKGPU_SAMPLE_F32 / _F16 / _BF16):
+                           // the finished int32 value v leaves as v * scale + bias (OutOps, below)
+                           SMP_F32 = 16, SMP_F16 = 17, SMP_BF16 = 18 };
+constexpr bool float_fmt(int32_t fmt) { return fmt >= SMP_F32 && fmt <= SMP_BF16; }
 // flags on a source format (GRKGPU_SAMPLE_INTERLEAVED / _BIG_ENDIAN): pixels
 // in p[0], sample (y, x, c) at p[0][y * stride + x * ncomp + c]; 16-bit
 // samples stored most-significant byte first
 constexpr int32_t SMP_INTERLEAVED = 0x100, SMP_BIG_ENDIAN = 0x200;
 constexpr uint32_t sample_bytes(int32_t fmt) {
-    return (fmt & 0xff) == SMP_I32 ? 4u : ((fmt & 0xff) <= SMP_I8 ? 1u : 2u);
+    return (fmt & 0xff) == SMP_I32 || (fmt & 0xff) == SMP_F32 ? 4u : ((fmt & 0xff) <= SMP_I8 ? 1u : 2u);
 }
 struct ShiftArr { int32_t v[GRK_MAX_COMPS]; };
 
@@ -230,6 +234,10 @@ struct OutOps {
     PrecOp pc[GRK_MAX_COMPS];
     int32_t col, coff[2];
     float sc[4];
+    // a float destination (SMP_F32 / _F16 / _BF16) only: channel c's value v -- after everything above --
+    // leaves as fadd(fmul((float)v, scale[c]), bias[c]), each rounded on its own in float32 (no FMA), then
+    // rounded to nearest even to the destination's format.  Not read by any other format's kernels.
+    float scale[GRK_MAX_COMPS], bias[GRK_MAX_COMPS];
 };
 // launch_mct_inv_dcshift_to / launch_upsample_to with the conversions in their
 // stores (the same kernels, instantiated with the ops; int32 planes run
@@ -263,7 +271,7 @@ struct ConvJob {
 // the two thread shapes, by launch_upsample_ops' rule: the 16-byte runs of
 // k_upsample_420 (fast) or k_upsample_any's thread per pixel
 __host__ __device__ inline bool conv_job_fast(const UpComp *c, uint32_t ncomp, int32_t fmt, int32_t col) {
-    return (fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16) && !col && ncomp == 3 && c[0].dx == 1 &&
+    return (fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16 || float_fmt(fmt)) && !col && ncomp == 3 && c[0].dx == 1 &&
            c[0].dy == 1 && c[1].dx == 2 && c[2].dx == 2 && c[1].dy == c[2].dy && (c[1].dy == 1 || c[1].dy == 2);
 }
 // threads along a row of a job (sb = bytes of a destination sample) and its workgroups of 256 threads

@@ -175,10 +175,68 @@ __global__ void k_mct_inv_dcshift(PlanePtrs src, uint32_t sstride, uint32_t tw, 
 template <typename T>
 struct NarrowRun { static constexpr int N = 16 / (int)sizeof(T); };
 
+// Float destinations (SMP_F32 / _F16 / _BF16, the float decode entry points
+// only): tag types of the destination's sample size, so that everything sized
+// by sizeof(T) -- the run length, run_of, the row threads -- works as for the
+// integer formats.  A float store always has OutOps (OP != 0): behind the
+// precision op, norm_run replaces a run's finished int32 values by the bit
+// patterns of their float32 images v * scale + bias; pack_word / store_sample
+// then round those to the destination's format, to nearest even (gfx950:
+// v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32; denormals are kept, overflow is inf).
+struct SmpF32 { uint32_t bits; };
+struct SmpF16 { uint16_t bits; };
+struct SmpBF16 { uint16_t bits; };
+template <typename T>
+constexpr bool float_tag = std::is_same<T, SmpF32>::value || std::is_same<T, SmpF16>::value || std::is_same<T, SmpBF16>::value;
+
+// channel ch's values -> float32 bit patterns: the product and the sum each
+// rounded on their own (no FMA, as in inv_mct_run); nothing for an integer T
+template <typename T, int N>
+__device__ __forceinline__ void norm_run([[maybe_unused]] int32_t (&v)[N], [[maybe_unused]] const OutOps &o,
+                                         [[maybe_unused]] uint32_t ch) {
+    if constexpr (float_tag<T>) {
+#pragma clang fp contract(off)
+        const float s = o.scale[ch], b = o.bias[ch];
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = __float_as_int(__fadd_rn(__fmul_rn((float)v[i], s), b));
+    }
+}
+// Two float32 bit patterns as one word of two 16-bit floats, low address
+// first: gfx950's packed conversions, which round to nearest even under the
+// kernels' mode (what the compiler selects for a <2 x float> truncation).
+// Spelled as the instruction: written as a vector conversion of two adjacent
+// elements of a run, the run's array is promoted to one 32-wide vector value
+// that is copied at every element write -- k_mct_inv_dcshift_pixels<SmpF16, 4,
+// OP_PREC> then takes 128 VGPRs and 1320 bytes of scratch where its uint16 form
+// takes 45 VGPRs and none.
+template <typename T>
+__device__ __forceinline__ uint32_t pack_floats(int32_t a, int32_t b) {
+    uint32_t r;
+    if constexpr (std::is_same<T, SmpF16>::value)
+        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    else
+        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// one finished value to its sample at p (a float T: v is norm_run's bit pattern)
+template <typename T>
+__device__ __forceinline__ void store_sample(int32_t v, T *p) {
+    if constexpr (std::is_same<T, SmpF32>::value)
+        __builtin_nontemporal_store((uint32_t)v, (uint32_t *)p);
+    else if constexpr (std::is_same<T, SmpF16>::value)
+        __builtin_nontemporal_store(__builtin_bit_cast(uint16_t, (_Float16)__int_as_float(v)), (uint16_t *)p);
+    else if constexpr (std::is_same<T, SmpBF16>::value)
+        __builtin_nontemporal_store(__builtin_bit_cast(uint16_t, (__bf16)__int_as_float(v)), (uint16_t *)p);
+    else
+        __builtin_nontemporal_store((T)v, p);
+}
+
 // one word of a run: samples [j * 4 / sizeof(T), ...) of v, low address first
 template <typename T>
 __device__ __forceinline__ uint32_t pack_word(const int32_t *v, int j) {
-    if constexpr (sizeof(T) == 1)
+    if constexpr (float_tag<T> && sizeof(T) == 2)
+        return pack_floats<T>(v[2 * j], v[2 * j + 1]);
+    else if constexpr (sizeof(T) == 1)
         return ((uint32_t)v[4 * j] & 0xffu) | (((uint32_t)v[4 * j + 1] & 0xffu) << 8) |
                (((uint32_t)v[4 * j + 2] & 0xffu) << 16) | ((uint32_t)v[4 * j + 3] << 24);
     else if constexpr (sizeof(T) == 2)
@@ -208,7 +266,7 @@ __device__ __forceinline__ void store_samples(T *p, const int32_t (&v)[NS], int 
     } else {
 #pragma unroll
         for (int i = 0; i < NS; ++i)
-            if (i < n) __builtin_nontemporal_store((T)v[i], p + i);
+            if (i < n) store_sample<T>(v[i], p + i);
     }
 }
 
@@ -454,6 +512,7 @@ __device__ __forceinline__ void cmyk_planar_run(const PlanePtrs &src, size_t si,
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             prec_run<4>(v[j], ops.pc[j]);
+            norm_run<T, 4>(v[j], ops, j);
             push_packed<T>(pk[j], v[j]);
         }
     }
@@ -481,7 +540,10 @@ __device__ __forceinline__ void store_plain_run(const PlanePtrs &src, size_t si,
     int32_t a[N];
     load_run<N>(src.p[k] + si, n, a);
     inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-    if constexpr (OP != 0) prec_run<N>(a, ops->pc[ch]);
+    if constexpr (OP != 0) {
+        prec_run<N>(a, ops->pc[ch]);
+        norm_run<T, N>(a, *ops, ch);
+    }
     store_samples<T, N>((T *)dst.p[ch] + di, a, n);
 }
 
@@ -524,6 +586,9 @@ __device__ __forceinline__ void store_planar_run(const PlanePtrs &src, uint32_t 
             prec_run<N>(a, ops->pc[0]);
             prec_run<N>(b, ops->pc[1]);
             prec_run<N>(c, ops->pc[2]);
+            norm_run<T, N>(a, *ops, 0);
+            norm_run<T, N>(b, *ops, 1);
+            norm_run<T, N>(c, *ops, 2);
         }
         store_samples<T, N>((T *)dst.p[0] + di, a, n);
         store_samples<T, N>((T *)dst.p[1] + di, b, n);
@@ -537,7 +602,10 @@ __device__ __forceinline__ void store_planar_run(const PlanePtrs &src, uint32_t 
             int32_t a[N];
             load_run<N>(src.p[k] + si, n, a);
             inv_plain_run<N>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-            if constexpr (OP != 0) prec_run<N>(a, ops->pc[k]);
+            if constexpr (OP != 0) {
+                prec_run<N>(a, ops->pc[k]);
+                norm_run<T, N>(a, *ops, k);
+            }
             store_samples<T, N>((T *)dst.p[k] + di, a, n);
         }
     } else {
@@ -578,7 +646,10 @@ __device__ __forceinline__ void store_pixels_run(const PlanePtrs &src, uint32_t 
     if constexpr (OP == OP_CMYK) cmyk_run<N>(v[0], v[1], v[2], v[3], *ops);
     if constexpr (OP != 0) {
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) prec_run<N>(v[chan_comp(OP, c)], ops->pc[c]);
+        for (int c = 0; c < NCH; ++c) {
+            prec_run<N>(v[chan_comp(OP, c)], ops->pc[c]);
+            norm_run<T, N>(v[chan_comp(OP, c)], *ops, c);
+        }
     }
     int32_t px[N * NCH];
 #pragma unroll
@@ -595,8 +666,11 @@ __device__ __forceinline__ void store_plain_sample(const PlanePtrs &src, size_t 
                                                    const ShiftArr &maxv, [[maybe_unused]] const OutOps *ops) {
     int32_t a[1] = {src.p[k][si]};
     inv_plain_run<1>(a, (irrev >> k) & 1, shift.v[k], minv.v[k], maxv.v[k]);
-    if constexpr (OP != 0) prec_run<1>(a, ops->pc[ch]);
-    __builtin_nontemporal_store((T)a[0], d + ch);
+    if constexpr (OP != 0) {
+        prec_run<1>(a, ops->pc[ch]);
+        norm_run<T, 1>(a, *ops, ch);
+    }
+    store_sample<T>(a[0], d + ch);
 }
 
 // interleaved, any other component count: pixel x of row y, one store per
@@ -620,7 +694,8 @@ __device__ __forceinline__ void store_pixel_any(const PlanePtrs &src, uint32_t s
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             prec_run<1>(v[j], ops->pc[j]);
-            __builtin_nontemporal_store((T)v[j][0], d + j);
+            norm_run<T, 1>(v[j], *ops, j);
+            store_sample<T>(v[j][0], d + j);
         }
         if constexpr (KMAX > 4)
             for (uint32_t k = 4; k < ncomp; ++k)
@@ -636,10 +711,13 @@ __device__ __forceinline__ void store_pixel_any(const PlanePtrs &src, uint32_t s
             prec_run<1>(a, ops->pc[0]);
             prec_run<1>(b, ops->pc[1]);
             prec_run<1>(c, ops->pc[2]);
+            norm_run<T, 1>(a, *ops, 0);
+            norm_run<T, 1>(b, *ops, 1);
+            norm_run<T, 1>(c, *ops, 2);
         }
-        __builtin_nontemporal_store((T)a[0], d);
-        __builtin_nontemporal_store((T)b[0], d + 1);
-        __builtin_nontemporal_store((T)c[0], d + 2);
+        store_sample<T>(a[0], d);
+        store_sample<T>(b[0], d + 1);
+        store_sample<T>(c[0], d + 2);
         c0 = 3;
     }
     if constexpr (KMAX > 4) {
@@ -693,7 +771,10 @@ __global__ void k_mct_inv_dcshift_pixels(PlanePtrs src, uint32_t sstride, uint32
     if constexpr (OP == OP_CMYK) cmyk_run<N>(v[0], v[1], v[2], v[3], *ops);
     if constexpr (OP != 0) {
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) prec_run<N>(v[chan_comp(OP, c)], ops->pc[c]);
+        for (int c = 0; c < NCH; ++c) {
+            prec_run<N>(v[chan_comp(OP, c)], ops->pc[c]);
+            norm_run<T, N>(v[chan_comp(OP, c)], *ops, c);
+        }
     }
     int32_t px[N * NCH];
 #pragma unroll
@@ -774,7 +855,12 @@ __device__ __forceinline__ void store_packed(T *p, const uint32_t (&w)[4], int n
     } else {
 #pragma unroll
         for (int i = 0; i < G; ++i)
-            if (i < n) __builtin_nontemporal_store((T)(w[i * SB / 4] >> (8 * (i * SB % 4))), p + i);
+            if (i < n) {
+                const uint32_t u = w[i * SB / 4] >> (8 * (i * SB % 4));
+                if constexpr (!float_tag<T>) __builtin_nontemporal_store((T)u, p + i);
+                else if constexpr (SB == 4) __builtin_nontemporal_store(u, (uint32_t *)p + i);
+                else __builtin_nontemporal_store((uint16_t)u, (uint16_t *)p + i);  // (packed: already converted)
+            }
     }
 }
 
@@ -1374,7 +1460,10 @@ __device__ __forceinline__ void upsample_420_run(const UpComp *pc, uint32_t X0, 
     }
     if constexpr (OP != 0) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) prec_run<N>(v[k], ops->pc[k]);
+        for (int k = 0; k < 3; ++k) {
+            prec_run<N>(v[k], ops->pc[k]);
+            norm_run<T, N>(v[k], *ops, k);
+        }
     }
     if constexpr (IL) {
         int32_t px[N * 3];
@@ -1423,8 +1512,9 @@ __device__ __forceinline__ void upsample_any_pixel(const UpComp *pc, uint32_t nc
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 prec_run<1>(v[k], ops->pc[k]);
+                norm_run<T, 1>(v[k], *ops, k);
                 T *const d = il ? (T *)dstp[0] + drow + (size_t)x * 3 + k : (T *)dstp[k] + drow + x;
-                __builtin_nontemporal_store((T)v[k][0], d);
+                store_sample<T>(v[k][0], d);
             }
             return;
         }
@@ -1437,8 +1527,9 @@ __device__ __forceinline__ void upsample_any_pixel(const UpComp *pc, uint32_t nc
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 prec_run<1>(v[k], ops->pc[k]);
+                norm_run<T, 1>(v[k], *ops, k);
                 T *const d = il ? (T *)dstp[0] + drow + (size_t)x * 3 + k : (T *)dstp[k] + drow + x;
-                __builtin_nontemporal_store((T)v[k][0], d);
+                store_sample<T>(v[k][0], d);
             }
             return;
         }
@@ -1457,8 +1548,9 @@ __device__ __forceinline__ void upsample_any_pixel(const UpComp *pc, uint32_t nc
                     a[0] = up_sample<T, OP>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy));
                 }
                 prec_run<1>(a, ops->pc[ch]);
+                norm_run<T, 1>(a, *ops, ch);
                 T *const d = il ? (T *)dstp[0] + drow + (size_t)x * (ncomp - 1) + ch : (T *)dstp[ch] + drow + x;
-                __builtin_nontemporal_store((T)a[0], d);
+                store_sample<T>(a[0], d);
             }
             return;
         }
@@ -1472,8 +1564,9 @@ __device__ __forceinline__ void upsample_any_pixel(const UpComp *pc, uint32_t nc
         } else {
             int32_t v[1] = {up_sample<T, OP>(c, (int32_t)(X / c.dx), (int32_t)(Y / c.dy))};
             prec_run<1>(v, ops->pc[k]);
+            norm_run<T, 1>(v, *ops, k);
             T *const d = il ? (T *)dstp[0] + drow + (size_t)x * ncomp + k : (T *)dstp[k] + drow + x;
-            __builtin_nontemporal_store((T)v[0], d);
+            store_sample<T>(v[0], d);
         }
     }
 }
@@ -2435,9 +2528,27 @@ static hipError_t with_sample_type(int32_t fmt, F &&f) {
 // The formats with a colour conversion (sYCC / eYCC / CMYK output is unsigned)
 // and with the 4:2:0 run kernel: U8 / U16 / I32.  The signed narrow formats
 // have the OP = 0 and OP_PREC instantiations only.
+// The float formats hold every precision and sign: colour formats too.
 template <typename T>
-constexpr bool colour_fmt = std::is_unsigned<T>::value || sizeof(T) == 4;
-constexpr bool colour_fmt_of(int32_t fmt) { return fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16; }
+constexpr bool colour_fmt = std::is_unsigned<T>::value || sizeof(T) == 4 || float_tag<T>;
+constexpr bool colour_fmt_of(int32_t fmt) { return fmt == SMP_I32 || fmt == SMP_U8 || fmt == SMP_U16 || float_fmt(fmt); }
+// with_sample_type for the float formats: the launchers with ops take them
+// (OP != 0 instantiations only), every other launcher refuses them as unknown
+template <typename F>
+static hipError_t with_float_type(int32_t fmt, F &&f) {
+    switch (fmt) {
+        case SMP_F32: f(SmpF32{}); break;
+        case SMP_F16: f(SmpF16{}); break;
+        case SMP_BF16: f(SmpBF16{}); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+// ... and for any output format of a launcher with ops
+template <typename F>
+static hipError_t with_out_type(int32_t fmt, F &&f) {
+    return float_fmt(fmt) ? with_float_type(fmt, f) : with_sample_type(fmt, f);
+}
 // a compile-time OP / flag handed to a generic lambda
 template <int V>
 using Const = std::integral_constant<int, V>;
@@ -2703,7 +2814,8 @@ hipError_t launch_store_jobs(const StoreJob *jobs, const uint32_t *first, uint32
     if (!njobs || !nwg) return hipSuccess;
     if (op < 0 || op > OP_CMYK || (op != 0) != (ops != nullptr)) return hipErrorInvalidValue;
     if (op > OP_PREC && !colour_fmt_of(fmt)) return hipErrorInvalidValue;
-    return with_sample_type(fmt, [&](auto t) {
+    if (op == 0 && float_fmt(fmt)) return hipErrorInvalidValue;  // a float store always has its OutOps
+    return with_out_type(fmt, [&](auto t) {
         using T = decltype(t);
         // (the table's type is spelled out: deduced from `ops` it would lose its __restrict__)
         const auto launch = [&](auto c, auto il) {
@@ -2719,7 +2831,9 @@ hipError_t launch_store_jobs(const StoreJob *jobs, const uint32_t *first, uint32
             if (interleaved) launch(c, Const<1>{});
             else launch(c, Const<0>{});
         };
-        if (op == 0) return layouts(Const<0>{});
+        if constexpr (!float_tag<T>) {
+            if (op == 0) return layouts(Const<0>{});
+        }
         if constexpr (colour_fmt<T>) {
             if (op == OP_SYCC) return layouts(Const<OP_SYCC>{});
             if (op == OP_EYCC) return layouts(Const<OP_EYCC>{});
@@ -2918,7 +3032,7 @@ hipError_t launch_mct_inv_dcshift_ops(const PlanePtrs &src, uint32_t sstride, ui
     if (ncomp < 1 || ncomp > (uint32_t)GRK_MAX_COMPS || !sycc_launchable(ops, ncomp, fmt))
         return hipErrorInvalidValue;
     if (!tw || !th) return hipSuccess;
-    return with_sample_type(fmt, [&](auto t) {
+    return with_out_type(fmt, [&](auto t) {
         using T = decltype(t);
         with_op<T>(ops, [&](auto op) {
             launch_inv<T, decltype(op)::value, OutOps>(src, sstride, tw, th, dst, interleaved, dstride, ncomp, shift,
@@ -2937,7 +3051,7 @@ hipError_t launch_upsample_ops(const UpPlan &src, uint32_t ncomp, uint32_t X0, u
     if (!w || !h) return hipSuccess;
     // (eYCC / CMYK need one grid, which the fast shape is not: k_upsample_any's)
     const bool fast = conv_job_fast(src.c, ncomp, fmt, ops.col);
-    return with_sample_type(fmt, [&](auto t) {
+    return with_out_type(fmt, [&](auto t) {
         using T = decltype(t);
         if constexpr (colour_fmt<T>) {
             if (fast && ops.sycc)
@@ -3162,7 +3276,7 @@ hipError_t launch_conv_jobs(const ConvJob *jobs, const uint32_t *first, uint32_t
                             const OutOps *ops, int32_t fmt, bool interleaved, bool fast, bool sycc, hipStream_t s) {
     if (!njobs || !nwg) return hipSuccess;
     if (fast && !colour_fmt_of(fmt)) return hipErrorInvalidValue;
-    return with_sample_type(fmt, [&](auto t) {
+    return with_out_type(fmt, [&](auto t) {
         using T = decltype(t);
         if constexpr (colour_fmt<T>) {
             if (fast) {

@@ -813,6 +813,64 @@ int grkgpu_decompress_batch_convert(grkgpu_ctx *ctx, grkgpu_batch_item *items, c
                                     uint32_t n, const grkgpu_dparams *p, grkgpu_batch_info *info);
 int grkgpu_batch_convert_plan(grkgpu_batch_item *items, const grkgpu_out_ops *ops, uint32_t n,
                               const grkgpu_dparams *p, grkgpu_batch_info *info);
+/* Decode straight to normalised float32 / float16 / bfloat16 samples: what a
+ * network takes, written once by the store of the last decode kernel instead of
+ * an integer image followed by x.to(float) * scale + bias passes over it.
+ *
+ * grkgpu_decompress_float is grkgpu_decompress_convert with one of the float
+ * formats below in out->sample_fmt -- valid in these calls only; every other
+ * entry point keeps refusing a sample_fmt above GRKGPU_SAMPLE_I16.  Let v be
+ * the int32 value grkgpu_decompress_convert delivers for output channel ch
+ * with the same ops and GRKGPU_SAMPLE_I32 (after inverse MCT, DC shift, clamp,
+ * upsampling, colour step and precision op).  The sample stored is
+ *     f = fadd(fmul((float)v, norm->scale[ch]), norm->bias[ch])
+ * in float32: (float)v rounds to nearest even (exact below 2^24), the product
+ * and the sum are each rounded on their own (no FMA), nothing is flushed to
+ * zero.  F32 stores f; F16 / BF16 store f rounded to nearest even, overflow
+ * going to +-inf, float16 subnormals kept.  In numpy:
+ *     (v.astype(float32) * float32(s) + float32(b)).astype(float16)
+ * Samples nothing decoded (the zero margin of a reduced decode at an odd
+ * origin, an upsampled stream's zero lead-in, tiles a cut stream never
+ * reached) are normalised like any other: bias[ch] without a colour step, the
+ * normalised conversion of zeros with one.
+ *
+ * ops may be NULL; norm == NULL is scale 1, bias 0.  Everything
+ * grkgpu_decompress_convert takes on a raw codestream is taken: both layouts
+ * and GRKGPU_LAYOUT_UPSAMPLE, SYCC / EYCC / CMYK and the precision op, window,
+ * cp_reduce, cp_layer and a tile range under that call's rules, host or device
+ * planes (aligned to the sample size).  A float format holds every precision
+ * and sign, so the "format holds the precision" rule does not apply; img is
+ * what grkgpu_decompress_convert reports -- the channels' integer precision
+ * and sign, from which the caller chooses scale.  GRKGPU_EINVAL before any
+ * device call: an integer sample_fmt, a non-finite scale or bias among the
+ * output channels (entries beyond them are not read), and everything
+ * grkgpu_decompress_convert refuses so.  GRKGPU_EUNSUPPORTED:
+ * GRKGPU_COLOUR_FORCE_RGB (it stores through the palette kernels) and a
+ * custom-MCT stream.
+ *
+ * grkgpu_decompress_batch_float is grkgpu_decompress_batch_convert in the same
+ * way: item i is grkgpu_decompress_float on that item bit for bit, with
+ * norms[i] (norms NULL: scale 1, bias 0 for every item).  Items may differ in
+ * float format, layout, ops and norm; an item with an integer format gets
+ * GRKGPU_EINVAL in its status and the others decode.  The call-level rules,
+ * the untouched destinations of failed items and info are unchanged, and the
+ * launch count does not depend on the number of items.
+ * grkgpu_batch_float_plan is the host half alone.
+ *
+ * Out of scope (integer formats only): JP2 files and the palette store
+ * (grkgpu_jp2_*), the custom-MCT store (grkgpu_decompress_mct) and force-RGB,
+ * the stage calls (grkgpu_*_to, grkgpu_*_jobs_to), grkgpu_decompress_multi,
+ * the grk_* API and the plugin, and float input to the encoder. */
+enum { GRKGPU_SAMPLE_F32 = 16, GRKGPU_SAMPLE_F16 = 17, GRKGPU_SAMPLE_BF16 = 18 }; /* decode output only */
+typedef struct { float scale[GRKGPU_MAX_COMPS], bias[GRKGPU_MAX_COMPS]; } grkgpu_out_norm; /* per output channel */
+int grkgpu_decompress_float(grkgpu_ctx *ctx, const uint8_t *cs, size_t len, const grkgpu_dparams *p,
+                            uint32_t tile_begin, uint32_t tile_end, grkgpu_image_desc *img,
+                            const grkgpu_out_planes *out, const grkgpu_out_ops *ops, const grkgpu_out_norm *norm);
+int grkgpu_decompress_batch_float(grkgpu_ctx *ctx, grkgpu_batch_item *items, const grkgpu_out_ops *ops,
+                                  const grkgpu_out_norm *norms, uint32_t n, const grkgpu_dparams *p,
+                                  grkgpu_batch_info *info);
+int grkgpu_batch_float_plan(grkgpu_batch_item *items, const grkgpu_out_ops *ops, const grkgpu_out_norm *norms,
+                            uint32_t n, const grkgpu_dparams *p, grkgpu_batch_info *info);
 /* Encode a batch of images in one launch set: item i is the whole-image encode
  * grkgpu_compress_ex(ctx, &img, p, &in, 0, 0xffffffff, GRKGPU_PART_ALL, ...)
  * and receives that call's codestream byte for byte, but the n items share
